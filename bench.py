@@ -10,7 +10,22 @@ seed, experiments/experiment_1.py:53-58), resident in HBM before timing.
 One step = SolveBoxQP forward + x.backward(ones) (experiment_1.py:69-78) on
 one batch, plus -- for N > 1 -- the single all-gather of x.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--full adds everything else the benchmark measures: the first-use step time,
+the reference's per-phase protocol, per-kernel times and rooflines, the other
+configurations and workloads, and the CPU baseline (--no-cpu-baseline and
+--no-other-configs trim it).
+
+--dump-outputs DIR writes what the last timed step computed, as rank 0's
+caller receives it: DIR/x.npy (DIR/x_local.npy and DIR/x_all.npy for N > 1),
+DIR/dp.npy and DIR/dQ.npy, in the dtype of the layer (float32 here).  An array
+of more than SAMPLE_MAX elements is written as the fixed sample
+sample_index(numel) of its flattened entries (dQ: 128 x 500 x 500 -> 3 M).
+The equality row fixes sum x = 1, so the gradients of x.backward(ones),
+d(sum x)/dp and d(sum x)/dQ, are zero but for rounding (~1e-7): compare them
+with an absolute tolerance.
 
 With N > 1 and no torchrun environment this process touches no GPU: it starts
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
@@ -47,10 +62,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=B_PER_GPU, help="QPs per GPU")
     ap.add_argument("--n", type=int, default=N_X)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--linsolve", choices=["auto", "lu", "spd"], default="auto",
                     help="x-update of the forward solve (control['linsolve']); lu = the reference's cached pivoted LU")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the extras (configs 2 and 4, LU step, sync step)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the extras (configs 2 and 4, LU step, sync step)")
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--strong", action="store_true",
@@ -62,6 +77,11 @@ def parse():
     ap.add_argument("--sync", action="store_true",
                     help="time the layer with its default control (calls wait for the GPU and raise at the call, like the "
                          "reference); default here: control['sync']=False, the pipelined training-loop mode")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline: first-use steps, the reference's protocol, per-kernel "
+                         "times and rooflines, other configs and workloads, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write x, dp and dQ of the last timed step as DIR/<name>.npy (large arrays as a fixed sample)")
     return ap.parse_args()
 
 
@@ -204,6 +224,33 @@ def median(v):
     return s[k // 2] if k % 2 else 0.5 * (s[k // 2 - 1] + s[k // 2])
 
 
+SAMPLE_MAX = 3 * 2 ** 20      # elements per dumped array (12 MiB in float32): at most four arrays stay under 64 MB
+
+
+def sample_index(numel):
+    """The flat indices --dump-outputs keeps of an array of `numel` elements: all of them up to SAMPLE_MAX, otherwise
+    SAMPLE_MAX drawn by a CPU generator seeded with 0 (the same on every run and machine), sorted."""
+    import torch
+    if numel <= SAMPLE_MAX:
+        return torch.arange(numel)
+    g = torch.Generator().manual_seed(0)
+    return torch.randint(numel, (SAMPLE_MAX,), generator=g).sort().values
+
+
+def dump_outputs(directory, last_step, world):
+    """What the caller of one step receives -- the layer's output, p.grad and Q.grad of `last_step` = (out, Q, p) -- as
+    directory/<name>.npy, float32 / float64 as computed"""
+    import numpy as np
+    out, Q, p = last_step
+    arrays = {"x_local": out[0], "x_all": out[1]} if world > 1 else {"x": out}
+    arrays.update(dp=p.grad, dQ=Q.grad)
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        a = flat[sample_index(flat.numel()).to(flat.device)].cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), a.reshape(t.shape) if a.size == flat.numel() else a)
+
+
 def main():
     args = parse()
     if args.cpu_baseline_worker:
@@ -263,15 +310,13 @@ def main():
 
     control, layer = make_layer(args.linsolve, args.sync)
 
-    def forward(i, lay=None):
+    def step(i, lay=None):
         Q, p, A, b, lb, ub = data[i % len(data)]
         Q = Q.detach().requires_grad_(True)          # experiment_1 differentiates w.r.t. Q and p
         p = p.detach().requires_grad_(True)
         out = (lay or layer)(Q, p, A, b, lb, ub)
-        return out[0] if world > 1 else out
-
-    def step(i, lay=None):
-        forward(i, lay).backward(ones)
+        (out[0] if world > 1 else out).backward(ones)
+        return out, Q, p
 
     def sync():
         torch.cuda.synchronize(dev)
@@ -279,49 +324,84 @@ def main():
             torch.distributed.barrier()
             torch.cuda.synchronize(dev)
 
-    def timed(k_steps, lay=None, first=0):
+    def timed(k_steps, lay=None, first=0, keep=None):
+        """wall time of k_steps steps; `keep` (a list) receives the last step's (out, Q, p)"""
         sync()
         t0 = time.perf_counter()
         for i in range(k_steps):
-            step(first + i, lay)
+            if keep is not None and i == k_steps - 1:
+                keep.append(step(first + i, lay))
+            else:
+                step(first + i, lay)
         sync()
         return time.perf_counter() - t0
 
     # ---- the first pass over the ten synthetic batches, untimed: library / workspace start-up rides on the very first
-    #      step; the other nine are what a step on never-seen tensors costs (config.first_use_ms_per_step).  Nothing about
-    #      a tensor is remembered between calls: whether any bound is finite (reference :33-38, a host decision there) is
-    #      found by the setup kernel from the data of every call. ----
+    #      step; the other nine are what a step on never-seen tensors costs (config.first_use_ms_per_step, --full).  Nothing
+    #      about a tensor is remembered between calls: whether any bound is finite (reference :33-38, a host decision there)
+    #      is found by the setup kernel from the data of every call. ----
     for _ in range(30):                   # (batch 0 alone: clocks, allocator and the pinned report pool of a fresh process --
         step(0)                           #  tools/gpu_first_use.py: with ONE such step the nine first-use steps below are 6-8 %
     sync()                                #  slower than the steady state, with thirty they equal it)
-    # nine steps are 6.6 ms: one hiccup of the box is 5 % of that.  Three rounds, each on FRESHLY ALLOCATED copies of batches
-    # 2..10 (never seen by the layer; the copies are made outside the clock), the median round is reported.
-    rounds = []
-    n_fresh = len(data) - 1
-    for _r in range(1 if args.config5 else 3):
-        fresh = [[t.clone() for t in data[i]] for i in range(1, len(data))]
-        sync()
-        t_first = time.perf_counter()
-        for d_ in fresh:
-            Q_, p_ = d_[0].requires_grad_(True), d_[1].requires_grad_(True)
-            out_ = layer(Q_, p_, *d_[2:])
-            (out_[0] if world > 1 else out_).backward(ones)
-        sync()
-        rounds.append((time.perf_counter() - t_first) / n_fresh * 1e3)
-        del fresh, d_, Q_, p_, out_
-    first_use_ms = sorted(rounds)[len(rounds) // 2]
+    if args.full:
+        # nine steps are 6.6 ms: one hiccup of the box is 5 % of that.  Three rounds, each on FRESHLY ALLOCATED copies of
+        # batches 2..10 (never seen by the layer; the copies are made outside the clock), the median round is reported.
+        rounds = []
+        n_fresh = len(data) - 1
+        for _r in range(1 if args.config5 else 3):
+            fresh = [[t.clone() for t in data[i]] for i in range(1, len(data))]
+            sync()
+            t_first = time.perf_counter()
+            for d_ in fresh:
+                Q_, p_ = d_[0].requires_grad_(True), d_[1].requires_grad_(True)
+                out_ = layer(Q_, p_, *d_[2:])
+                (out_[0] if world > 1 else out_).backward(ones)
+            sync()
+            rounds.append((time.perf_counter() - t_first) / n_fresh * 1e3)
+            del fresh, d_, Q_, p_, out_
+        first_use_ms = sorted(rounds)[len(rounds) // 2]
     for i in range(args.warmup):
         step(i)
     # ---- timed region: exactly K steps, nothing else on the stream ----
-    dt = timed(args.steps, first=args.warmup)
+    kept = []
+    dt = timed(args.steps, first=args.warmup, keep=kept)
     L.synchronize()                       # surface any deferred error of the un-synchronised layer calls
     st_timed = last_forward_status(dev)   # iteration count / checks of the LAST timed forward, read from the device
+    if args.dump_outputs and rank == 0 and kept:
+        dump_outputs(args.dump_outputs, kept[0], world)
+    del kept
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t[0])
     ms_per_step = dt / args.steps * 1e3
     value = B_total / (dt / args.steps)
+
+    workload = (f"BASELINE configs[4]: batch={B_total} dz={n} m={m} sharded over {world} GPU(s), {B}/GPU" if args.config5 else
+                f"BASELINE configs[2], strong scaling: ONE batch={B_total} dz={n} m={m} split over {world} GPU(s), {B} on rank 0"
+                if args.strong else f"BASELINE configs[2]: batch={B}/GPU dz={n} m={m}")
+    out = {"metric": "QPs/sec forward+backward, batch=128 dz=500 tol=1e-5", "value": round(value, 1),
+           "unit": "QPs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": workload + " box+equality QP, ADMM forward + fixed-point backward, eps 1e-5, "
+                                  "scale+adaptive_rho defaults",
+                      "global_batch": B_total, "shard_sizes": shard_sizes,
+                      "seeds": f"{len(data)} batches, seeds 0..{len(data) - 1}" + (" (one batch, cut)" if args.strong else " per rank") + ", cycled",
+                      "iters": st_timed["iters"], "checks": st_timed["n_check"], "launch_mode": st_timed["mode_used"],
+                      "stats_source": "device status block of the last timed forward",
+                      "sync": bool(args.sync), "linsolve": {1: "lu", 2: "spd"}[st_timed["linsolve_used"]],
+                      "loop_workgroups_per_qp": st_timed["loop_workgroups_per_qp"],
+                      "parallelism": f"batch-sharded x{world}", "rccl_world_size": world}}
+
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+
+    if not args.full:
+        return finish(out)
 
     # ---- the reference's protocol (experiment_1.py:53-94, SURVEY 8d): one simulation per seed 0..9, forward and
     #      backward timed separately (device events on the launch stream), medians over the simulations ----
@@ -446,32 +526,17 @@ def main():
                                                           round(twin["traffic_bytes_per_step"] / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4))
     roofline["whole_step_traffic_source"] = None if twin is None else twin["source"]
 
-    workload = (f"BASELINE configs[4]: batch={B_total} dz={n} m={m} sharded over {world} GPU(s), {B}/GPU" if args.config5 else
-                f"BASELINE configs[2], strong scaling: ONE batch={B_total} dz={n} m={m} split over {world} GPU(s), {B} on rank 0"
-                if args.strong else f"BASELINE configs[2]: batch={B}/GPU dz={n} m={m}")
-    out = {"metric": "QPs/sec forward+backward, batch=128 dz=500 tol=1e-5", "value": round(value, 1),
-           "unit": "QPs/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong" if args.strong else "weak",
-           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": workload + " box+equality QP, ADMM forward + fixed-point backward, eps 1e-5, "
-                                  "scale+adaptive_rho defaults",
-                      "global_batch": B_total, "shard_sizes": shard_sizes,
-                      "seeds": f"{len(data)} batches, seeds 0..{len(data) - 1}" + (" (one batch, cut)" if args.strong else " per rank") + ", cycled",
-                      "first_use_ms_per_step": round(first_use_ms, 4),
-                      "first_use": "step time over freshly allocated copies of batches 2..10 on their FIRST pass through the layer (median of three such rounds of nine steps, after thirty warm-up steps on batch 1 alone; nothing is cached per tensor: the bound flags of :33-38 are found on the device in every call)",
-                      "iters": iters, "checks": st_timed["n_check"], "launch_mode": st_timed["mode_used"],
-                      "stats_source": "device status block of the last timed forward",
-                      "sync": bool(args.sync), "linsolve": {1: "lu", 2: "spd"}[ls],
-                      "loop_workgroups_per_qp": st_timed["loop_workgroups_per_qp"],
-                      "parallelism": f"batch-sharded x{world}", "rccl_world_size": world},
-           "metric_keys": {"value": "B x K / wall time of the K timed steps (pipelined calls, control['sync']=False)",
-                           "sec_8d_metric": "experiment_1_protocol.QPs_per_sec_median",
-                           "unchanged_reference_harness": "step_sync_default (the layer's default control: every call waits "
-                                                          "for its solve and raises at the call, as experiments/experiment_1.py "
-                                                          "gets it without setting any extension key)"},
-           "experiment_1_protocol": protocol,
-           "roofline": roofline, "roofline_loop": roof_loop, "roofline_factorisation": roof_factor,
-           "kernel_ms_per_step": breakdown, "profiled_pass_ms_per_step": round(dt_prof / args.steps * 1e3, 4)}
+    out["config"].update(
+        first_use_ms_per_step=round(first_use_ms, 4),
+        first_use="step time over freshly allocated copies of batches 2..10 on their FIRST pass through the layer (median of three such rounds of nine steps, after thirty warm-up steps on batch 1 alone; nothing is cached per tensor: the bound flags of :33-38 are found on the device in every call)")
+    out.update({"metric_keys": {"value": "B x K / wall time of the K timed steps (pipelined calls, control['sync']=False)",
+                                "sec_8d_metric": "experiment_1_protocol.QPs_per_sec_median",
+                                "unchanged_reference_harness": "step_sync_default (the layer's default control: every call waits "
+                                                               "for its solve and raises at the call, as experiments/experiment_1.py "
+                                                               "gets it without setting any extension key)"},
+                "experiment_1_protocol": protocol,
+                "roofline": roofline, "roofline_loop": roof_loop, "roofline_factorisation": roof_factor,
+                "kernel_ms_per_step": breakdown, "profiled_pass_ms_per_step": round(dt_prof / args.steps * 1e3, 4)})
 
     if world == 1 and not args.no_other_configs and B == B_PER_GPU and n == N_X and not args.strong:
         # ---- the same step on the north-star-named algorithm (cached pivoted LU) and with the layer's default
@@ -645,9 +710,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(args)
         elif not args.no_cpu_baseline:
             out["cpu_baseline"] = None
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

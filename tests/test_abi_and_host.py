@@ -161,6 +161,35 @@ def test_bench_spawns_its_own_ranks_without_touching_the_gpu(tmp_path, monkeypat
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: x (x_local / x_all with N ranks), dp and dQ of the last step as .npy in the computed dtype;
+    an array above SAMPLE_MAX elements as the seeded, sorted sample_index of its flat entries, the same in every run."""
+    import importlib.util
+    import numpy as np
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    B, n = 128, 500
+    idx = bench.sample_index(B * n * n)
+    assert idx.numel() == bench.SAMPLE_MAX and torch.equal(idx, bench.sample_index(B * n * n))
+    assert bool((idx[1:] >= idx[:-1]).all()) and 0 <= int(idx[0]) and int(idx[-1]) < B * n * n
+    assert torch.equal(bench.sample_index(1000), torch.arange(1000))
+    assert 4 * bench.SAMPLE_MAX * 4 <= 64 * 10 ** 6
+    g = torch.Generator().manual_seed(5)
+    x, Q, p = torch.randn(B, n, 1, generator=g), torch.randn(B, n, n), torch.randn(B, n, 1)
+    Q.grad, p.grad = torch.randn(B, n, n, generator=g), torch.randn(B, n, 1, generator=g)
+    bench.dump_outputs(str(tmp_path / "one"), (x, Q, p), 1)
+    got = {f[:-4]: np.load(tmp_path / "one" / f) for f in os.listdir(tmp_path / "one")}
+    assert sorted(got) == ["dQ", "dp", "x"] and all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["x"], x.numpy()) and np.array_equal(got["dp"], p.grad.numpy())
+    assert np.array_equal(got["dQ"], Q.grad.reshape(-1)[idx].numpy())
+    bench.dump_outputs(str(tmp_path / "two"), ((x[:64], x.double()), Q, p), 2)
+    got = {f[:-4]: np.load(tmp_path / "two" / f) for f in os.listdir(tmp_path / "two")}
+    assert sorted(got) == ["dQ", "dp", "x_all", "x_local"] and got["x_all"].dtype == np.float64
+    assert np.array_equal(got["x_local"], x[:64].numpy()) and np.array_equal(got["x_all"], x.double().numpy())
+
+
 def _kernel_resources():
     """{demangled kernel name: (vgprs, spilled vgprs, scratch bytes)} from the code-object metadata of the built library
     (every translation unit of the split build carries its own code object)."""

@@ -1801,13 +1801,13 @@ def test_g20_n3000_above_2048_rows(dev):
 
 # ---------------------------------------------------------------- bench.py contract
 def test_bench_json_contract(dev):
-    """bench.py prints ONE JSON line with the keys the driver reads, the roofline objects and (on request) the CPU
+    """bench.py --full prints ONE JSON line with the keys the driver reads, the roofline objects and (on request) the CPU
     baseline; values are sane for a short run."""
     import json
     import subprocess
     import sys as _sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([_sys.executable, os.path.join(repo, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([_sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=400)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -1830,6 +1830,50 @@ def test_bench_json_contract(dev):
     assert d["config"]["iters"] == 60 and d["config"]["checks"] == 4 and d["config"]["launch_mode"] == 3
     e1 = d["experiment_1_protocol"]
     assert e1["simulations"] == 10 and e1["QPs_per_sec_median"] > 1000
+
+
+def test_bench_plain_run_dumps_its_last_step(dev, tmp_path):
+    """A plain bench.py run prints the headline line alone, and --dump-outputs writes what its last timed step computed:
+    x, dp and dQ (a fixed sample) of batch (warmup + steps - 1) mod 10, as the layer computes them in this process."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys as _sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 3, 2
+    out = subprocess.run([_sys.executable, os.path.join(repo, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=400)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["warmup"] == warmup and d["unit"] == "QPs/sec" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and abs(d["value"] - 128 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    for k in ("roofline", "experiment_1_protocol", "kernel_ms_per_step", "cpu_baseline", "other_workloads_fwd_bwd"):
+        assert k not in d, k
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["dQ.npy", "dp.npy", "x.npy"], files
+    assert sum(os.path.getsize(os.path.join(tmp_path, f)) for f in files) <= 64 * 10 ** 6
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(repo, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    from lqp_py_amd.synthetic import create_qp_data
+    Q, p, A, b, lb, ub = (t.to(dev) for t in create_qp_data(500, 128, seed=(warmup + steps - 1) % 10))
+    control = L.box_qp_control(eps_rel=1e-5, eps_abs=1e-5, verbose=False, reduce='max')
+    control['sync'] = False
+    Qg, pg = Q.requires_grad_(True), p.requires_grad_(True)
+    x = L.SolveBoxQP(control=control)(Qg, pg, A, b, lb, ub)
+    x.backward(torch.ones_like(x))
+    L.synchronize()
+    assert got["x"].shape == (128, 500, 1) and got["dp"].shape == (128, 500, 1) and got["dQ"].shape == (bench.SAMPLE_MAX,)
+    dQ = Qg.grad.reshape(-1)[bench.sample_index(Qg.grad.numel()).to(dev)]
+    assert err(torch.from_numpy(got["x"]), x) < X_TOL * max(1.0, float(x.detach().abs().max()))
+    # (the equality row fixes sum x = 1, so both gradients of sum x are zero but for rounding, ~1e-7)
+    for name, ref in (("dp", pg.grad), ("dQ", dQ)):
+        assert err(torch.from_numpy(got[name]), ref) < G_RTOL * max(1.0, float(ref.abs().max())), name
 
 
 @pytest.mark.parametrize("seed", range(6))
