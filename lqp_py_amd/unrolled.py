@@ -15,6 +15,13 @@ epoch by epoch in the library on the pivoted LU of each epoch's KKT matrix (``lq
 a few norms of the iterates of ONE check per event -- is differentiated by autograd on its own small graph
 (``_backward_with_rho_events``): no torch op per iteration there either.  What is left (no finite bound: rho = 0, one solve)
 takes the eager path below: the loop as torch ops with ``TorchLU`` (HIP LU factor / cached solves) as the taped solve.
+
+Two conventions where the tape is not differentiable, the same on every path (tests/unroll_table.py):
+  * an exact tie x_k + u_k == bound is treated as free by the kernels (torch.maximum would split the gradient in two).  At an entry
+    with lb == ub every path returns the same dlb + dub; the kernels give the whole of it to the side the iterate came from, the
+    taped loop (``torch.minimum`` on the tie max(., lb) == ub) half to each.
+  * an infinite bound never binds and carries no gradient: with ``scale=True`` the chain through lbs = lb / D must not hand D the
+    0 * inf = NaN of autograd's division rule (``_scale_bound``; k_unroll_scale_vectors takes 0 * inf as 0 too).
 """
 import ctypes
 import os
@@ -41,6 +48,13 @@ def _floor_nonpositive(norms):
 
 def _inf_norm(v):
     return torch.linalg.norm(v, ord=_INF, dim=1, keepdim=True)
+
+
+def _scale_bound(v, D):
+    """v / D (:189) with no gradient through an infinite entry: plain ``v / D`` hands D the gradient 0 * inf = NaN there, and so
+    does the untaken branch of a single ``where`` -- the numerator is masked first.  Values unchanged."""
+    fin = torch.isfinite(v)
+    return torch.where(fin, torch.where(fin, v, torch.zeros_like(v)) / D, v.detach())
 
 
 def _scaled_problem(Q, p, A, b, lb, ub, r, has_box, colmax=None, fro=None):
@@ -74,7 +88,7 @@ def _scaled_problem(Q, p, A, b, lb, ub, r, has_box, colmax=None, fro=None):
             b = E * b
         D = d.unsqueeze(2)
         if has_box:
-            lb, ub = lb / D, ub / D
+            lb, ub = _scale_bound(lb, D), _scale_bound(ub, D)
     if rho is None:
         rho = torch.clamp((torch.linalg.matrix_norm(Q, keepdim=True) if fro is None else fro) / n ** 0.5, min=r['rho_min'], max=r['rho_max'])
     return (Q if colmax is None and fro is None else d), p, A, b, lb, ub, D, E, rho

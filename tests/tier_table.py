@@ -215,8 +215,10 @@ NOT_A_TIER = {
     "LQP_EPI_SLABS": "transport: row slabs of the backward epilogue (each row is computed whole either way)",
     "LQP_BWD_EARLY": "transport: which launch reports the backward's info words",
     "LQP_SPD_PTASKS": "transport: tile tasks handed between the workgroups of the multi-launch sweep",
-    "LQP_UNROLL_EVENTS": "unroll=True only: the unroll tape is not a tier of the forward / backward this table covers",
-    "LQP_UNROLL_SPLIT": "unroll=True only: the unroll tape is not a tier of the forward / backward this table covers",
+    "LQP_UNROLL_EVENTS": "unroll=True only: tests/unroll_table.py holds its rows (tests/test_unroll_table.py requires one per value)",
+    "LQP_UNROLL_SPLIT": "unroll=True only: tests/unroll_table.py holds its rows (tests/test_unroll_table.py requires one per value)",
+    "LQP_UNROLL_NATIVE": "unroll=True only: tests/unroll_table.py holds its rows (tests/test_unroll_table.py requires one per value)",
+    "LQP_UNROLL_SCALE_NATIVE": "unroll=True only: tests/unroll_table.py holds its rows (tests/test_unroll_table.py requires one per value)",
 }
 
 # size thresholds of the selection code: (what, row predicate of the lower side, of the upper side)
@@ -247,7 +249,8 @@ def sample(B):
 
 
 def seed_of(r):
-    return sum(ord(c) * (i + 1) for i, c in enumerate(r["name"])) % 100003
+    """(`j`: the offset a row of tests/unroll_table.py found by its seed search; the rows of this table have none)"""
+    return sum(ord(c) * (i + 1) for i, c in enumerate(r["name"])) % 100003 + r.get("j", 0)
 
 
 def _problem(r, i, qcache=None):
