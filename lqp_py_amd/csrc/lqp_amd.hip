@@ -91,6 +91,16 @@ template <typename F> bool blocks_per_cu(int* per_cu, F fn, int nt, int lds, int
     return true;
 }
 
+struct Device { int dev = 0, cus = 0; };      // the current device and its CU count (current_device_cus)
+// `workgroups` of (fn, nt threads, lds bytes) resident at once: kernels whose workgroups wait for each other inside the launch need
+// every one of them on the chip -- ask the occupancy calculator for THIS kernel (block size, registers, LDS), not just the CU
+// count.  (workgroups = 0: the kernel can run at all; more than 160 KB of LDS: ensure_lds refuses.)
+template <typename F> bool fits(const Device& d, F fn, const int nt, const int lds, const long long workgroups) {
+    int per_cu = 0;
+    return ensure_lds((const void*)fn, lds) == LQP_OK && blocks_per_cu(&per_cu, fn, nt, lds, d.dev) && per_cu >= 1 &&
+           workgroups <= (long long)d.cus * per_cu;
+}
+
 // ---- optional per-kernel-class timing with HIP events on the launch stream ----
 enum { PC_SETUP = 0, PC_LU, PC_PACK, PC_LOOP, PC_RHO, PC_EPILOGUE, PC_BWD_BUILD, PC_SOLVE, PC_BWD_EPILOGUE,
        PC_MISC, PC_LOOP_TAIL, PC_SPD_INV, PC_EQ_CORR, PC_BWD_CHOL, PC_UNROLL, PC_UNROLL_SCALE, PC_COUNT };
@@ -136,120 +146,74 @@ int env_int(const char* name, int dflt) {
 
 // Every LQP_* environment switch that steers a schedule, read ONCE per process (tests that flip one run in a fresh process
 // or set LQP_ENV_NOCACHE=1, which re-reads them at every use).  -1: not set, the library decides.
+// X(field of struct Knobs, environment variable, default): the one list struct Knobs and read_knobs are generated from;
+// docs/KNOBS.md documents every entry (tests/test_tier_table.py holds the two together).
+#define LQP_KNOBS(X) \
+    X(bwd_chol, "LQP_BWD_CHOL", 1) \
+    X(bwd_early, "LQP_BWD_EARLY", 1) \
+    X(bwd_full, "LQP_BWD_FULL", 0) \
+    X(bwd_lookahead, "LQP_BWD_LOOKAHEAD", 1) \
+    X(inv_xcd, "LQP_INV_XCD", 1)                      /* the inverse's column tiles of one problem on one XCD (0: grid order) */ \
+    X(dbg_lu2_absent, "LQP_DBG_LU2_ABSENT", 0)        /* tests only -- the partner workgroups of the two-workgroup LU are not launched */ \
+    X(dbg_loop_absent, "LQP_DBG_LOOP_ABSENT", 0)      /* tests only -- bit 0 ... of the two-workgroup loop, bit 1 ... of the resident sweep, bit 2 ... of the unroll sweep, bit 3 ... of the two-workgroup streaming loop */ \
+    X(bwd_refine, "LQP_BWD_REFINE", 1) \
+    X(dbg_qpass, "LQP_DBG_QPASS", 0) \
+    X(dbg_setup, "LQP_DBG_SETUP", 0) \
+    X(epi_slabs, "LQP_EPI_SLABS", -1) \
+    X(eq_in_loop, "LQP_EQ_IN_LOOP", 1) \
+    X(launch_mode, "LQP_LAUNCH_MODE", 2) \
+    X(linsolve, "LQP_LINSOLVE", 0) \
+    X(loop512, "LQP_LOOP512", 0) \
+    X(loop_dense, "LQP_LOOP_DENSE", 1) \
+    X(loop_dense_w, "LQP_LOOP_DENSE_W", 1) \
+    X(loop_small, "LQP_LOOP_SMALL", 1) \
+    X(loop_split, "LQP_LOOP_SPLIT", 1) \
+    X(loop_split4, "LQP_LOOP_SPLIT4", 1) \
+    X(loop_np2, "LQP_LOOP_NP2", 1) \
+    X(spd_big_fuse, "LQP_SPD_BIG_FUSE", 1) \
+    X(spd_big_f16, "LQP_SPD_BIG_F16", 1) \
+    X(loop_split_seg, "LQP_LOOP_SPLIT_SEG", 1) \
+    X(lu2, "LQP_LU2", 1) \
+    X(lu_wide, "LQP_LU_WIDE", 1) \
+    X(unroll_split, "LQP_UNROLL_SPLIT", 1) \
+    X(lu_wide_min, "LQP_LU_WIDE_MIN", 1024)           /* the wide LU above this many rows (experiments; default 1024) */ \
+    X(lu_mfma, "LQP_LU_MFMA", 1) \
+    X(lu_nt, "LQP_LU_NT", 0) \
+    X(lu_pb, "LQP_LU_PB", 0) \
+    X(nosync_max_events, "LQP_NOSYNC_MAX_EVENTS", 12) \
+    X(prep_fused, "LQP_PREP_FUSED", 1) \
+    X(prep_one, "LQP_PREP_ONE", 1) \
+    X(qpass, "LQP_QPASS", 1) \
+    X(qs_lazy, "LQP_QS_LAZY", 1) \
+    X(resident, "LQP_RESIDENT", 1) \
+    X(rho_late, "LQP_RHO_LATE", 1) \
+    X(spd_big, "LQP_SPD_BIG", 1) \
+    X(spd_ptasks, "LQP_SPD_PTASKS", 48) \
+    X(spd_resident, "LQP_SPD_RESIDENT", 1) \
+    X(spd_resident4, "LQP_SPD_RESIDENT4", 1) \
+    X(hot_past, "LQP_HOT_PAST", 1)                    /* the persistent two-workgroup loop runs on past rho events that change nothing */ \
+    X(hot_rounds, "LQP_HOT_ROUNDS", 2)                /* with a GIVEN rho, rounds of {rho update, gated refactorisation, hot loop again} enqueued behind the first hot launch */ \
+    X(bwd_equil, "LQP_BWD_EQUIL", 1)                  /* power-of-two symmetric equilibration of the Cholesky backward's free-set block */ \
+    X(bwd_f16, "LQP_BWD_F16", 1)                      /* the backward's look-ahead Cholesky with its tile products on the float16 pipe (with LQP_SPD_F16) */ \
+    X(spd_turns, "LQP_SPD_TURNS", 1)                  /* more matrices than half the CUs -> the resident sweep anyway, its pairs taking turns on the chip */ \
+    X(spd_f16, "LQP_SPD_F16", 1)                      /* the resident sweep's panel products on the float16 matrix pipe (two-half operands); 0: float32 matrix instructions */ \
+    X(spd_split, "LQP_SPD_SPLIT", -1) \
+    X(spec_launches, "LQP_SPEC_LAUNCHES", 6) \
+    X(split2, "LQP_SPLIT2", 1) \
+    X(sym512, "LQP_SYM512", 0) \
+    X(sync_plan, "LQP_SYNC_PLAN", 1) \
+    X(tail_epilogue, "LQP_TAIL_EPILOGUE", 1) \
+    X(xcd_local, "LQP_XCD_LOCAL", 1)
 struct Knobs {
-    int bwd_chol;              // LQP_BWD_CHOL
-    int bwd_early;             // LQP_BWD_EARLY
-    int bwd_full;              // LQP_BWD_FULL
-    int bwd_lookahead;         // LQP_BWD_LOOKAHEAD
-    int inv_xcd;               // LQP_INV_XCD: the inverse's column tiles of one problem on one XCD (0: grid order)
-    int dbg_lu2_absent;        // LQP_DBG_LU2_ABSENT: tests only -- the partner workgroups of the two-workgroup LU are not launched
-    int dbg_loop_absent;       // LQP_DBG_LOOP_ABSENT: tests only -- bit 0 ... of the two-workgroup loop, bit 1 ... of the resident sweep, bit 2 ... of the unroll sweep, bit 3 ... of the two-workgroup streaming loop
-    int bwd_refine;            // LQP_BWD_REFINE
-    int dbg_qpass;             // LQP_DBG_QPASS
-    int dbg_setup;             // LQP_DBG_SETUP
-    int epi_slabs;             // LQP_EPI_SLABS
-    int eq_in_loop;            // LQP_EQ_IN_LOOP
-    int launch_mode;           // LQP_LAUNCH_MODE
-    int linsolve;              // LQP_LINSOLVE
-    int loop512;               // LQP_LOOP512
-    int loop_dense;            // LQP_LOOP_DENSE
-    int loop_dense_w;          // LQP_LOOP_DENSE_W
-    int loop_small;            // LQP_LOOP_SMALL
-    int loop_split;            // LQP_LOOP_SPLIT
-    int loop_split4;           // LQP_LOOP_SPLIT4
-    int loop_np2;              // LQP_LOOP_NP2
-    int spd_big_fuse;          // LQP_SPD_BIG_FUSE
-    int spd_big_f16;           // LQP_SPD_BIG_F16
-    int loop_split_seg;        // LQP_LOOP_SPLIT_SEG
-    int lu2;                   // LQP_LU2
-    int lu_wide;               // LQP_LU_WIDE
-    int unroll_split;          // LQP_UNROLL_SPLIT
-    int lu_wide_min;           // LQP_LU_WIDE_MIN: the wide LU above this many rows (experiments; default 1024)
-    int lu_mfma;               // LQP_LU_MFMA
-    int lu_nt;                 // LQP_LU_NT
-    int lu_pb;                 // LQP_LU_PB
-    int nosync_max_events;     // LQP_NOSYNC_MAX_EVENTS
-    int prep_fused;            // LQP_PREP_FUSED
-    int prep_one;              // LQP_PREP_ONE
-    int qpass;                 // LQP_QPASS
-    int qs_lazy;               // LQP_QS_LAZY
-    int resident;              // LQP_RESIDENT
-    int rho_late;              // LQP_RHO_LATE
-    int spd_big;               // LQP_SPD_BIG
-    int spd_ptasks;            // LQP_SPD_PTASKS
-    int spd_resident;          // LQP_SPD_RESIDENT
-    int spd_resident4;         // LQP_SPD_RESIDENT4
-    int hot_past;              // LQP_HOT_PAST: the persistent two-workgroup loop runs on past rho events that change nothing
-    int hot_rounds;            // LQP_HOT_ROUNDS: with a GIVEN rho, rounds of {rho update, gated refactorisation, hot loop again} enqueued behind the first hot launch
-    int bwd_equil;             // LQP_BWD_EQUIL: power-of-two symmetric equilibration of the Cholesky backward's free-set block
-    int bwd_f16;               // LQP_BWD_F16: the backward's look-ahead Cholesky with its tile products on the float16 pipe (with LQP_SPD_F16)
-    int spd_turns;             // LQP_SPD_TURNS: more matrices than half the CUs -> the resident sweep anyway, its pairs taking turns on the chip
-    int spd_f16;               // LQP_SPD_F16: the resident sweep's panel products on the float16 matrix pipe (two-half operands); 0: float32 matrix instructions
-    int spd_split;             // LQP_SPD_SPLIT
-    int spec_launches;         // LQP_SPEC_LAUNCHES
-    int split2;                // LQP_SPLIT2
-    int sym512;                // LQP_SYM512
-    int sync_plan;             // LQP_SYNC_PLAN
-    int tail_epilogue;         // LQP_TAIL_EPILOGUE
-    int xcd_local;             // LQP_XCD_LOCAL
+#define LQP_KNOB_FIELD(field, env, dflt) int field;
+    LQP_KNOBS(LQP_KNOB_FIELD)
+#undef LQP_KNOB_FIELD
 };
 Knobs read_knobs() {
     Knobs k;
-    k.bwd_chol = env_int("LQP_BWD_CHOL", 1);
-    k.bwd_early = env_int("LQP_BWD_EARLY", 1);
-    k.bwd_full = env_int("LQP_BWD_FULL", 0);
-    k.bwd_lookahead = env_int("LQP_BWD_LOOKAHEAD", 1);
-    k.inv_xcd = env_int("LQP_INV_XCD", 1);
-    k.dbg_lu2_absent = env_int("LQP_DBG_LU2_ABSENT", 0);
-    k.dbg_loop_absent = env_int("LQP_DBG_LOOP_ABSENT", 0);
-    k.bwd_refine = env_int("LQP_BWD_REFINE", 1);
-    k.dbg_qpass = env_int("LQP_DBG_QPASS", 0);
-    k.dbg_setup = env_int("LQP_DBG_SETUP", 0);
-    k.epi_slabs = env_int("LQP_EPI_SLABS", -1);
-    k.eq_in_loop = env_int("LQP_EQ_IN_LOOP", 1);
-    k.launch_mode = env_int("LQP_LAUNCH_MODE", 2);
-    k.linsolve = env_int("LQP_LINSOLVE", 0);
-    k.loop512 = env_int("LQP_LOOP512", 0);
-    k.loop_dense = env_int("LQP_LOOP_DENSE", 1);
-    k.loop_dense_w = env_int("LQP_LOOP_DENSE_W", 1);
-    k.loop_small = env_int("LQP_LOOP_SMALL", 1);
-    k.loop_split = env_int("LQP_LOOP_SPLIT", 1);
-    k.loop_split4 = env_int("LQP_LOOP_SPLIT4", 1);
-    k.loop_np2 = env_int("LQP_LOOP_NP2", 1);
-    k.spd_big_fuse = env_int("LQP_SPD_BIG_FUSE", 1);
-    k.spd_big_f16 = env_int("LQP_SPD_BIG_F16", 1);
-    k.loop_split_seg = env_int("LQP_LOOP_SPLIT_SEG", 1);
-    k.lu2 = env_int("LQP_LU2", 1);
-    k.lu_wide = env_int("LQP_LU_WIDE", 1);
-    k.unroll_split = env_int("LQP_UNROLL_SPLIT", 1);
-    k.lu_wide_min = env_int("LQP_LU_WIDE_MIN", 1024);
-    k.lu_mfma = env_int("LQP_LU_MFMA", 1);
-    k.lu_nt = env_int("LQP_LU_NT", 0);
-    k.lu_pb = env_int("LQP_LU_PB", 0);
-    k.nosync_max_events = env_int("LQP_NOSYNC_MAX_EVENTS", 12);
-    k.prep_fused = env_int("LQP_PREP_FUSED", 1);
-    k.prep_one = env_int("LQP_PREP_ONE", 1);
-    k.qpass = env_int("LQP_QPASS", 1);
-    k.qs_lazy = env_int("LQP_QS_LAZY", 1);
-    k.resident = env_int("LQP_RESIDENT", 1);
-    k.rho_late = env_int("LQP_RHO_LATE", 1);
-    k.spd_big = env_int("LQP_SPD_BIG", 1);
-    k.spd_ptasks = env_int("LQP_SPD_PTASKS", 48);
-    k.spd_resident = env_int("LQP_SPD_RESIDENT", 1);
-    k.spd_resident4 = env_int("LQP_SPD_RESIDENT4", 1);
-    k.spd_f16 = env_int("LQP_SPD_F16", 1);
-    k.spd_turns = env_int("LQP_SPD_TURNS", 1);
-    k.bwd_f16 = env_int("LQP_BWD_F16", 1);
-    k.bwd_equil = env_int("LQP_BWD_EQUIL", 1);
-    k.hot_past = env_int("LQP_HOT_PAST", 1);
-    k.hot_rounds = env_int("LQP_HOT_ROUNDS", 2);
-    k.spd_split = env_int("LQP_SPD_SPLIT", -1);
-    k.spec_launches = env_int("LQP_SPEC_LAUNCHES", 6);
-    k.split2 = env_int("LQP_SPLIT2", 1);
-    k.sym512 = env_int("LQP_SYM512", 0);
-    k.sync_plan = env_int("LQP_SYNC_PLAN", 1);
-    k.tail_epilogue = env_int("LQP_TAIL_EPILOGUE", 1);
-    k.xcd_local = env_int("LQP_XCD_LOCAL", 1);
+#define LQP_KNOB_READ(field, env, dflt) k.field = env_int(env, dflt);
+    LQP_KNOBS(LQP_KNOB_READ)
+#undef LQP_KNOB_READ
     return k;
 }
 const Knobs& knobs() {
@@ -309,12 +273,10 @@ int launch_lu2(hipStream_t st, T* M, int B, int N, int ld, size_t mstride, int* 
                const int* gate, const int* nvec, unsigned long long* scr, size_t scr_stride) {
     constexpr int PB = lu2_panel_width<T>();
     if (!scr || scr_stride < (size_t)LU2_SCR_WORDS || N > 512 || N < 3 * PB || knobs().lu2 == 0 || t_single_wg_lu) return -1;
-    int dev = 0, cus = 0, per_cu = 0;
+    Device d;
     auto fn = k_lu_factor2<T, PB>;
     const int lds = Lu2Lds<T, PB>(round_up(N, 64)).total;
-    if (!current_device_cus(&dev, &cus) || ensure_lds((const void*)fn, lds) != LQP_OK ||
-        !blocks_per_cu(&per_cu, fn, LU2_NT, lds, dev) || per_cu < 1 || shared_grid(B, 2) > cus * per_cu)
-        return -1;
+    if (!current_device_cus(&d.dev, &d.cus) || !fits(d, fn, LU2_NT, lds, shared_grid(B, 2))) return -1;
     const unsigned int epoch = g_lu2_epoch.fetch_add(1u) + 1u;
     { ProfScope ps(st, PC_LU);
       // (LQP_DBG_LU2_ABSENT: the hand-offs of workgroups b time out, info = -7, the caller repeats on one workgroup per matrix)
@@ -352,50 +314,40 @@ int launch_lu_wide(hipStream_t st, T* M, int B, int N, int ld, size_t mstride, i
     return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
 }
 
-int launch_lu(hipStream_t st, float* M, int B, int N, int ld, size_t mstride, int* piv, int pstride, int* info,
+template <typename T>
+int launch_lu(hipStream_t st, T* M, int B, int N, int ld, size_t mstride, int* piv, int pstride, int* info,
               const int* gate, const int* nvec = nullptr, unsigned long long* scr = nullptr, size_t scr_stride = 0) {
     if (N > 512) {
-        const int rw = launch_lu_wide<float>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec, scr, scr_stride);
+        const int rw = launch_lu_wide<T>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec, scr, scr_stride);
         if (rw >= 0) return rw;
     }
-    if (N > 1024) return launch_lu_big<float>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec);
-    { const int r2 = launch_lu2<float>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec, scr, scr_stride);
+    if (N > 1024) return launch_lu_big<T>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec);
+    { const int r2 = launch_lu2<T>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec, scr, scr_stride);
       if (r2 >= 0) return r2; }
-    int nt = lu_threads<float>(N);
-    int pb = lu_panel_width<float>(N);
-    const int want_nt = knobs().lu_nt;
-    if (want_nt == 1024) { nt = 1024; pb = std::min(pb, 16); }
-    const int want = knobs().lu_pb;
-    if ((want == 8 || want == 16 || (want == 32 && nt == 512)) && 2 * want * round_up(N, 64) * 4 <= 128 * 1024) pb = want;
-    const bool mfma = knobs().lu_mfma != 0;
-#define LQP_LU_CASE(PBV, MF, NTV) return launch_lu_impl<float, PBV, MF, NTV>(st, B, M, N, ld, mstride, piv, pstride, info, gate, nvec)
-    if (nt == 512) {
-        if (pb == 32) { if (mfma) LQP_LU_CASE(32, true, 512); LQP_LU_CASE(32, false, 512); }
-        if (pb == 16) { if (mfma) LQP_LU_CASE(16, true, 512); LQP_LU_CASE(16, false, 512); }
-        LQP_LU_CASE(8, false, 512);
+    int nt = lu_threads<T>(N);
+    int pb = lu_panel_width<T>(N);
+#define LQP_LU_CASE(PBV, MF, NTV) return launch_lu_impl<T, PBV, MF, NTV>(st, B, M, N, ld, mstride, piv, pstride, info, gate, nvec)
+    if constexpr (sizeof(T) == 4) {
+        const int want_nt = knobs().lu_nt;
+        if (want_nt == 1024) { nt = 1024; pb = std::min(pb, 16); }
+        const int want = knobs().lu_pb;
+        if ((want == 8 || want == 16 || (want == 32 && nt == 512)) && 2 * want * round_up(N, 64) * 4 <= 128 * 1024) pb = want;
+        const bool mfma = knobs().lu_mfma != 0;
+        if (nt == 512) {
+            if (pb == 32) { if (mfma) LQP_LU_CASE(32, true, 512); LQP_LU_CASE(32, false, 512); }
+            if (pb == 16) { if (mfma) LQP_LU_CASE(16, true, 512); LQP_LU_CASE(16, false, 512); }
+            LQP_LU_CASE(8, false, 512);
+        }
+        if (pb == 16) { if (mfma) LQP_LU_CASE(16, true, 1024); LQP_LU_CASE(16, false, 1024); }
+        LQP_LU_CASE(8, false, 1024);
+    } else {
+        if (nt == 512) {
+            if (pb == 16) LQP_LU_CASE(16, true, 512);
+            LQP_LU_CASE(8, true, 512);
+        }
+        if (pb == 16) LQP_LU_CASE(16, true, 1024);
+        LQP_LU_CASE(8, true, 1024);
     }
-    if (pb == 16) { if (mfma) LQP_LU_CASE(16, true, 1024); LQP_LU_CASE(16, false, 1024); }
-    LQP_LU_CASE(8, false, 1024);
-#undef LQP_LU_CASE
-}
-int launch_lu(hipStream_t st, double* M, int B, int N, int ld, size_t mstride, int* piv, int pstride, int* info,
-              const int* gate, const int* nvec = nullptr, unsigned long long* scr = nullptr, size_t scr_stride = 0) {
-    if (N > 512) {
-        const int rw = launch_lu_wide<double>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec, scr, scr_stride);
-        if (rw >= 0) return rw;
-    }
-    if (N > 1024) return launch_lu_big<double>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec);
-    { const int r2 = launch_lu2<double>(st, M, B, N, ld, mstride, piv, pstride, info, gate, nvec, scr, scr_stride);
-      if (r2 >= 0) return r2; }
-    const int nt = lu_threads<double>(N);
-    const int pb = lu_panel_width<double>(N);
-#define LQP_LU_CASE(PBV, NTV) return launch_lu_impl<double, PBV, true, NTV>(st, B, M, N, ld, mstride, piv, pstride, info, gate, nvec)
-    if (nt == 512) {
-        if (pb == 16) LQP_LU_CASE(16, 512);
-        LQP_LU_CASE(8, 512);
-    }
-    if (pb == 16) LQP_LU_CASE(16, 1024);
-    LQP_LU_CASE(8, 1024);
 #undef LQP_LU_CASE
 }
 
@@ -528,6 +480,17 @@ int wait_report(hipStream_t st, const int* host_report, int words) {
 // with n_launch / linsolve_used / factor_launches / loop_workgroups of the enqueue and keeps them.
 // LQP_RETRY_LU (internal): the matrix left the symmetric x-update -- repeat the solve with linsolve = 1.
 constexpr int LQP_RETRY_LU = 100;
+// the solve's own figures, from the status block it left (`rv`: a host copy, or the words in pinned host memory)
+inline void solve_stats(lqp_boxqp_stats* stats, const volatile int* rv, const int max_iters, const int check) {
+    const int final_iter = rv[ST_DONE] ? rv[ST_FINAL_ITER] : max_iters - 1;
+    stats->iters = final_iter;
+    stats->n_factor = 1 + rv[ST_NFACTOR];
+    stats->n_solve = final_iter + 1;
+    stats->n_check = final_iter / check + 1;
+    stats->rho_updated = rv[ST_RHO_UPDATED];
+    stats->fail_index = -1;
+    stats->any_lb = rv[ST_ANY_LB]; stats->any_ub = rv[ST_ANY_UB];
+}
 inline bool flags_timeout_loop(const int* rep) { return ((const volatile int*)rep)[ST_TIMEOUT] != 0; }
 int collect_report(hipStream_t st, const int* rep, const bool polled, const int B, const int max_iters, const int check,
                    lqp_boxqp_stats* stats) {
@@ -551,15 +514,8 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
         return LQP_ERR_SINGULAR;
     }
     if (rv[ST_TIMEOUT] || (flags_or & RP_TIMEOUT)) return LQP_ERR_TIMEOUT;
-    const int final_iter = rv[ST_DONE] ? rv[ST_FINAL_ITER] : max_iters - 1;
-    stats->iters = final_iter;
-    stats->n_factor = 1 + rv[ST_NFACTOR];
-    stats->n_solve = final_iter + 1;
-    stats->n_check = final_iter / check + 1;
-    stats->rho_updated = rv[ST_RHO_UPDATED];
-    stats->fail_index = -1;
+    solve_stats(stats, rv, max_iters, check);
     stats->mode_used = 2;
-    stats->any_lb = rv[ST_ANY_LB]; stats->any_ub = rv[ST_ANY_UB];
     return LQP_OK;
 }
 
@@ -609,81 +565,127 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     return L;
 }
 
+// ---- the tier plan: what one attempt at a forward solve will launch, decided before its first launch ----
+// Ks -> the instance of the resident sweep on NP workgroups per matrix (four: Ks = 7, 8 only) and of the two-workgroup loop
+inline int spd_prep_lds_bytes(const int Ks) { return (2 * 64 * SPD_LS + 2 * LQP_NW + 64 * Ks) * 4; }      // (k_spd_prep)
+typedef void (*SweepFn)(const FwdParams<float>, const int*);
+typedef void (*SplitFn)(const FwdParams<float>, const int, const int, const int);
+template <int NP> SweepFn spd_resident_fn(const int Ks, const bool f16) {
+#if LQP_PIV_MFMA
+#define LQP_KS_CASE(KS) case KS: return f16 ? k_spd_resident<KS, NP, true> : k_spd_resident<KS, NP, false>
+#else
+#define LQP_KS_CASE(KS) case KS: return k_spd_resident<KS, NP, false>
+#endif
+    if constexpr (NP == 2) switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
+    switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
+#undef LQP_KS_CASE
+}
+template <int NP> SplitFn loop_split_fn(const int Ks, const bool dbg) {
+#define LQP_KS_CASE(KS) case KS: return k_admm_loop_split<KS, 512, false, NP>
+    if constexpr (NP == 2) {
+        switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
+        if (Ks != 7 && dbg) return k_admm_loop_split<8, 512, true, 2>;
+    }
+    switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
+#undef LQP_KS_CASE
+}
+
+// the kernel of the first (hot) launch of the persistent mode
+enum LoopKind {
+    LOOP_ONE,           // k_admm_loop: one workgroup per problem
+    LOOP_SPLIT,         // k_admm_loop_split: two (four) workgroups per problem, the matrix in their registers
+    LOOP_SMALL,         // k_admm_loop_small: n <= 128, 256 threads per problem
+    LOOP_NP2,           // k_admm_loop_np2: above 512 rows, the streaming loop on two workgroups per problem
+    LOOP_DENSE,         // k_admm_loop_dense: LU tier, n <= 256, the explicit inverse in the registers of two workgroups
+    LOOP_DENSE_W        // k_admm_loop_dense_w: LU tier, W workgroups per problem
+};
+constexpr int kMaxChecksPerLaunch = kRing / 4;
+
+template <typename T> struct FwdPlan {
+    typedef void (*LoopFn)(const FwdParams<T>, int, int, int, int, int);
+    int retry = 0;                      // forward_impl's retry bits of this attempt
+    bool solo = false;                  // (retry bit 2: nothing shared between workgroups)
+    int dbg_loop_absent = 0;            // LQP_DBG_LOOP_ABSENT
+    // x-update: the symmetric inverse (lqp_spd.hpp) or the pivoted LU of the KKT matrix
+    bool spd = false;
+    bool spd_split = false;             // SPD_NP workgroups per matrix
+    bool spd_turns = false;             // ... more matrices than half the CUs: the pairs of the resident sweep take turns
+    bool spd_big_split = false;         // above 512 rows: two workgroups per matrix, a launch per phase of a pivot step
+    bool spd_resident = false;          // all pivot steps in one launch, the matrix in the registers of its rs_np workgroups
+    int rs_np = SPD_NP;
+    SweepFn rs_fn = nullptr;
+    int spd_pivot_tasks = 0;
+    bool rho_late_big = false;          // k_spd_rho_big turns the sums k_spd_begin leaves into rho
+    bool fuse2 = false;                 // k_spd_big_step: two pivot steps per pass over the tiles
+    int f16 = 0;                        // ... its flag bit for the float16 pipe (32 or 0)
+    // the loop
+    LoopKind kind = LOOP_ONE;
+    int kind_lds = 0;                   // LDS of LOOP_SMALL / LOOP_DENSE / LOOP_DENSE_W
+    int kind_wg = 1;                    // workgroups per problem of the hot launch
+    int densew_tpr = 0;
+    bool loop_split_seg = false;        // mode 1: k_admm_loop_split per check segment, its pairs taking turns on the chip
+    LoopFn loop_fn = nullptr; int loop_nt = 1024, loop_lds = 0;     // hot launch of LOOP_ONE, every launch of mode 1
+    LoopFn tail_fn = nullptr; int tail_lds = 0;                     // continuation launches (LQP_NT threads)
+    SplitFn split_fn = nullptr; int split_nt = 512, split_lds = 0;  // LOOP_SPLIT and loop_split_seg
+    int mode = 0;                       // 2: persistent loop kernel, 1: one launch per check segment
+    bool inkernel_refactor = false;     // the continuation kernel refactorises at its adaptive-rho events itself
+    // the scheduler
+    bool up_front = false;              // run_planned: the whole schedule enqueued before anything is waited for
+    bool hot_past = false;
+    int hot_rounds = 0;
+    bool tail_epilogue = false;
+    int spec_launches = 0;
+    // what lqp_boxqp_stats reports of it
+    int factor_launches = 0, loop_workgroups = 1;
+};
+
+// Every decision of an attempt and every ensure_lds / occupancy query; launches nothing.  Writes the fields of P that are decisions.
+// retry: bit 0 -- the symmetric x-update gave the solve up (not symmetric / not positive definite in f32): pivoted LU;
+//        bit 1 -- a pair of the turn-taking two-workgroup loop (split_seg) waited for its partner in vain: the one-workgroup loop
+//        bit 2 -- a kernel that shares its problems between workgroups gave up waiting (bounded spins: something else holds the
+//                 CUs -- another stream, another process, RCCL): nothing shared this time -- one workgroup per matrix in every
+//                 factorisation, host-launched check segments instead of the persistent loop with its grid barrier
 template <typename T>
-int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
-                 const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
-                 void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
-                 const int retry = 0) {
-    // retry: bit 0 -- the symmetric x-update gave the solve up (not symmetric / not positive definite in f32): pivoted LU;
-    //        bit 1 -- a pair of the turn-taking two-workgroup loop (split_seg) waited for its partner in vain: the one-workgroup loop
-    //        bit 2 -- a kernel that shares its problems between workgroups gave up waiting (bounded spins: something else holds the
-    //                 CUs -- another stream, another process, RCCL): nothing shared this time -- one workgroup per matrix in every
-    //                 factorisation, host-launched check segments instead of the persistent loop with its grid barrier
+int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
+    const int B = P.B, n = P.n, m = P.m;
     const bool force_lu = (retry & 1) != 0;
     const bool solo = (retry & 4) != 0;
-    struct SoloScope { bool on; explicit SoloScope(bool o) : on(o && !t_single_wg_lu) { if (on) t_single_wg_lu = true; }
-                       ~SoloScope() { if (on) t_single_wg_lu = false; } } solo_scope(solo);
-    FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    if (ws_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-    FwdParams<T>& P = L.P;
-    P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
-    P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in; P.beta_in = (const T*)ctl->beta_in;
-    P.x = (T*)x; P.z = (T*)z; P.u = (T*)u; P.lams = (T*)lams; P.nus = (T*)nus; P.rho_out = (T*)rho_out;
-    P.scale = ctl->scale; P.bound_flags_in = (const int*)ctl->bound_flags_in;
-    if (ctl->reserved2 & 4) {           // verbose: the largest primal / dual error of the batch at every check (lqp_boxqp_check_trace)
-        P.vtrace = L.vtrace_area;
-        HIP_OK(hipMemsetAsync(P.vtrace, 0, sizeof(unsigned int) * 2 * kRing, st));
-    }
-    P.host_report = (int*)ctl->host_report;
-    if (P.host_report) report_reset(P.host_report, ST_WORDS + 2 * B);      // (before the first launch: see wait_report)
-    P.xcd_local = knobs().xcd_local != 0 ? 1 : 0;
-    P.dbg_qpass = knobs().dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
-    P.zero_words = (int)(((char*)(P.counters + (size_t)kRing * CT_WORDS) - (char*)P.status) / sizeof(int));
+    plan = FwdPlan<T>();
+    plan.retry = retry; plan.solo = solo;
+    plan.dbg_loop_absent = k.dbg_loop_absent;
+    P.xcd_local = k.xcd_local != 0 ? 1 : 0;
+    P.dbg_qpass = k.dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
     P.dbg = g_lu_dbg;
     P.dbg_setup = nullptr;
-    if (g_lu_dbg && knobs().dbg_setup) { P.dbg_setup = g_lu_dbg; P.dbg = nullptr; }
-    P.rho_mode = ctl->rho_mode; P.beta_mode = ctl->beta_mode;
-    P.check_solved = ctl->check_solved < 1 ? 1 : ctl->check_solved;
-    P.adaptive_rho = ctl->adaptive_rho;
-    P.eps_abs = (T)ctl->eps_abs; P.eps_rel = (T)ctl->eps_rel; P.rho_value = (T)ctl->rho_value;
-    P.rho_min = (T)ctl->rho_min; P.rho_max = (T)ctl->rho_max;
-    P.ar_tol = (T)ctl->adaptive_rho_tol; P.ar_inv_tol = (T)(1.0 / ctl->adaptive_rho_tol);
-    P.ar_thr = (T)ctl->adaptive_rho_threshold; P.beta_value = (T)ctl->beta_value;
-
+    if (g_lu_dbg && k.dbg_setup) { P.dbg_setup = g_lu_dbg; P.dbg = nullptr; }
     const int check = P.check_solved;
     const int max_iters = ctl->max_iters;
-    const int ar_iter = ctl->adaptive_rho_iter < 1 ? 1 : ctl->adaptive_rho_iter;
-    int n_launch = 0;
+    const int ar_iter = P.ar_iter;
 
     // ---- x-update linear algebra: pivoted LU of the KKT matrix, or the symmetric inverse (lqp_spd.hpp) ----
     bool spd = false;
     if constexpr (sizeof(T) == 4) {
         int want = ctl->linsolve;
-        if (want == 0) want = knobs().linsolve;
+        if (want == 0) want = k.linsolve;
         const bool rho_pos = !(ctl->rho_mode == 1 && !(ctl->rho_value > 0.0));
         // (512 < n <= 1024: the sweep parks its panel in the M area, see wg_spd_sweep_big)
         spd = !force_lu && want != 1 && rho_pos && P.Ks <= SPD_BIGK && m <= SPD_MAXM &&
-              (P.Ks <= SPD_MAXK || ((size_t)P.Np * P.Np >= (size_t)P.Ks * LQP_BLK && knobs().spd_big));
+              (P.Ks <= SPD_MAXK || ((size_t)P.Np * P.Np >= (size_t)P.Ks * LQP_BLK && k.spd_big));
         // the equality correction (G, T: 2 m rows of 64 Ks floats next to the product's scratch) and the loop's vectors must
         // fit the 160 KB of LDS: large n with many equality rows (n > 960 at m >= 8, ...) stays on the LU path
         spd = spd && spd_factor_lds_bytes(m, P.Ks) <= 160 * 1024 && sym_loop_lds_bytes(n, m, P.Ks, 0) <= 160 * 1024;
     }
+    plan.spd = spd;
     P.spd = spd ? 1 : 0;
     // (the LU path too: its refactorisations form (D Q) D again from Q and the scaling vector -- assemble_kkt_rows -- instead of
     //  reading a stored copy the setup kernel would have to write: 128 MB per batch at n = 500)
-    P.qs_lazy = knobs().qs_lazy ? 1 : 0;
-    P.ar_iter = ar_iter; P.ar_max = ctl->adaptive_rho_max_iter; P.ring = kRing;
+    P.qs_lazy = k.qs_lazy ? 1 : 0;
 
     // symmetric path with fewer problems than half the CUs: share each matrix between SPD_NP workgroups
-    bool spd_split = false;
-    const int spd_pivot_tasks = knobs().spd_ptasks;
-    if (spd && P.Ks >= 3 && P.Ks <= SPD_MAXK) {
-        int dev_ = 0, cus_ = 0;
-        if (current_device_cus(&dev_, &cus_)) spd_split = B * SPD_NP <= cus_;
-        spd_split = (knobs().spd_split < 0 ? (spd_split ? 1 : 0) : knobs().spd_split) != 0;
-        spd_split = spd_split && (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS;     // room for W, W^T in the M area
-        spd_split = spd_split && !solo;
-    }
+    const bool share = (k.spd_split < 0 ? (B * SPD_NP <= d.cus ? 1 : 0) : k.spd_split) != 0 && !solo;
+    plan.spd_pivot_tasks = k.spd_ptasks;
+    bool spd_split = spd && P.Ks >= 3 && P.Ks <= SPD_MAXK && share &&
+                     (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS;     // room for W, W^T in the M area
     // More matrices than half the CUs (BASELINE configs[4]: 1024 per GPU): the resident sweep all the same, its pairs taking turns
     // on the chip as the loop's do (FwdParams::split_seg) -- partners are neighbours in dispatch order on one XCD (shared_map), so a
     // workgroup that waits for its partner waits for a CU that a COMPLETE earlier pair is about to leave.  Round 4 measured this
@@ -691,581 +693,549 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
     // turn is 0.28 ms and needs no pass over Q in front (k_spd_prep: 0.44 ms at B = 1024).
     bool spd_turns = false;
 #if LQP_PIV_MFMA
-    if (spd && !spd_split && !solo && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && knobs().spd_turns != 0 &&
-        knobs().spd_resident != 0 && knobs().spd_f16 != 0 && knobs().spd_split != 0 &&
-        (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) && (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS) {
-        int dev_ = 0, cus_ = 0;
-        if (current_device_cus(&dev_, &cus_) && B * SPD_NP > cus_) { spd_turns = true; spd_split = true; }
+    if (spd && !spd_split && !solo && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && k.spd_turns != 0 &&
+        k.spd_resident != 0 && k.spd_f16 != 0 && k.spd_split != 0 &&
+        (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) && (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS && B * SPD_NP > d.cus) {
+        spd_turns = true; spd_split = true;
     }
 #endif
-    bool spd_big_split = false;
-    if (spd && P.Ks > SPD_MAXK) {
-        int dev_ = 0, cus_ = 0;
-        if (current_device_cus(&dev_, &cus_)) spd_big_split = B * SPD_NP <= cus_;
-        spd_big_split = (knobs().spd_split < 0 ? (spd_big_split ? 1 : 0) : knobs().spd_split) != 0 && !solo;
-    }
+    const bool spd_big_split = spd && P.Ks > SPD_MAXK && share;
     // ... and, with the exchange buffer in the M area and the step flags behind the loop's granules, in ONE launch
-    // (More matrices than half the CUs: the register-resident sweep with its pairs taking turns on the chip, as the loop does it
-    //  -- FwdParams::split_seg -- was built and measured in round 4: the one-workgroup sweep streams every tile through L2 / HBM
-    //  in every pivot step, 9.7 GB per factorisation at B = 1024, n = 500, and still is as fast: 2.91 ms against 8 turns x 0.36
-    //  ms + the equality correction in a launch of its own = 3.13 ms; B = 256: 0.73 against 0.80.  Not kept.)
     bool spd_resident = spd_split && P.xchg && P.Ks >= SPLIT_MINK &&
                         (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) &&
-                        knobs().spd_resident != 0;
-    int rs_np = SPD_NP;                 // workgroups per matrix of the resident sweep: 2, or 4 for batches up to a quarter of the CUs
-    void (*rs_fn)(const FwdParams<float>, const int*) = nullptr;
-    if (spd_resident) {
-        // its workgroups per matrix wait for each other inside the launch: every one of them must be resident -- ask the
-        // occupancy calculator for THIS kernel (block size, registers, LDS), not just the CU count
-        int dev_ = 0, cus_ = 0, per_cu = 0;
-        const int rlds = rs_q_lds_bytes(P.Ks);     // (the look-ahead sweep's counters behind the flags, the scaling vector behind them)
-        bool ok = false;
+                        k.spd_resident != 0;
+    if constexpr (sizeof(T) == 4) {
+        if (spd_resident) {
+            // workgroups per matrix of the resident sweep: 2, or 4 for batches up to a quarter of the CUs
+            const int rlds = rs_q_lds_bytes(P.Ks);     // (the look-ahead sweep's counters behind the flags, the scaling vector behind them)
+            const bool f16 = k.spd_f16 != 0;
+            bool ok = false;
 #if LQP_PIV_MFMA
-        if (P.Ks >= 7 && current_device_cus(&dev_, &cus_) && 4 * B <= cus_ && knobs().spd_resident4 != 0) {
-            rs_fn = P.Ks == 7 ? k_spd_resident<7, 4> : k_spd_resident<8, 4>;
-            if (knobs().spd_f16 != 0) rs_fn = P.Ks == 7 ? k_spd_resident<7, 4, true> : k_spd_resident<8, 4, true>;
-            ok = ensure_lds((const void*)rs_fn, rlds) == LQP_OK && blocks_per_cu(&per_cu, rs_fn, RS_NT, rlds, dev_) &&
-                 per_cu >= 1 && shared_grid(B, 4) <= cus_ * per_cu;
-            if (ok) rs_np = 4;
-        }
+            if (P.Ks >= 7 && 4 * B <= d.cus && k.spd_resident4 != 0) {
+                plan.rs_fn = spd_resident_fn<4>(P.Ks, f16);
+                ok = fits(d, plan.rs_fn, RS_NT, rlds, shared_grid(B, 4));
+                if (ok) plan.rs_np = 4;
+            }
 #endif
-        if (!ok) {
-            rs_fn = P.Ks == 3 ? k_spd_resident<3> : P.Ks == 4 ? k_spd_resident<4> : P.Ks == 5 ? k_spd_resident<5> : P.Ks == 6 ? k_spd_resident<6>
-                  : P.Ks == 7 ? k_spd_resident<7> : k_spd_resident<8>;
-#if LQP_PIV_MFMA
-            if (knobs().spd_f16 != 0)
-                rs_fn = P.Ks == 3 ? k_spd_resident<3, 2, true> : P.Ks == 4 ? k_spd_resident<4, 2, true> : P.Ks == 5 ? k_spd_resident<5, 2, true>
-                      : P.Ks == 6 ? k_spd_resident<6, 2, true> : P.Ks == 7 ? k_spd_resident<7, 2, true> : k_spd_resident<8, 2, true>;
-#endif
-            ok = ensure_lds((const void*)rs_fn, rlds) == LQP_OK && current_device_cus(&dev_, &cus_) &&
-                 blocks_per_cu(&per_cu, rs_fn, RS_NT, rlds, dev_) && per_cu >= 1 && (spd_turns || shared_grid(B, SPD_NP) <= cus_ * per_cu);
+            if (!ok) {
+                plan.rs_fn = spd_resident_fn<2>(P.Ks, f16);
+                ok = fits(d, plan.rs_fn, RS_NT, rlds, spd_turns ? 0 : shared_grid(B, SPD_NP));
+            }
+            spd_resident = ok;
         }
-        spd_resident = ok;
     }
     if (spd_turns && !spd_resident) { spd_turns = false; spd_split = false; }      // (the one-workgroup sweep after all)
+    plan.spd_split = spd_split; plan.spd_turns = spd_turns; plan.spd_big_split = spd_big_split; plan.spd_resident = spd_resident;
     // rho = ||Qs||_F / sqrt(n): the norm is summed by k_spd_begin, which reads all of Q anyway, and rho is added to the
     // diagonal by the resident sweep -- the setup kernel then makes one pass over Q instead of two
-    P.rho_late = (spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && knobs().rho_late) ? 1 : 0;
+    P.rho_late = (spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late) ? 1 : 0;
     // ... and above 512 rows on two workgroups per matrix: the sums k_spd_begin leaves are turned into rho by k_spd_rho_big
-    const bool rho_late_big = spd_big_split && !spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && knobs().rho_late != 0 &&
-                              (size_t)P.Np * P.Np >= (size_t)(2 * P.Ks + 1) * LQP_BLK;
-    if (rho_late_big) P.rho_late = 1;
+    plan.rho_late_big = spd_big_split && !spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late != 0 &&
+                        (size_t)P.Np * P.Np >= (size_t)(2 * P.Ks + 1) * LQP_BLK;
+    if (plan.rho_late_big) P.rho_late = 1;
+    // two pivot steps per pass over the tiles (wg_spd_sweep_big, phases bits 2 .. 4): pivot + Y of step k | its update on
+    // block column k + 1 alone | pivot + Y' of step k + 1 | ONE read-modify-write of every other tile with both products
+    plan.fuse2 = k.spd_big_fuse != 0 && (size_t)P.Np * P.Np >= (size_t)(2 * P.Ks + 1) * LQP_BLK;
+    // ... its panel blocks as two-half operands, the update products on the float16 pipe (lqp_f16x2.hpp)
+    plan.f16 = (plan.fuse2 && k.spd_big_f16 != 0) ? 32 : 0;
     // auto-scaling on: ONE pass over Q for the column maxima, the symmetry verdict and the (unscaled) blocks, in front of
     // the setup kernel (k_spd_prep); the resident sweep scales its tiles as it loads them and sums ||Qs||_F itself
     P.prep_fused = 0;
 #if LQP_PIV_MFMA
     if constexpr (sizeof(T) == 4) {
-        P.prep_fused = (spd_resident && P.scale && P.qs_lazy && (ctl->rho_mode != 0 || P.rho_late) && knobs().prep_fused) ? 1 : 0;
+        P.prep_fused = (spd_resident && P.scale && P.qs_lazy && (ctl->rho_mode != 0 || P.rho_late) && k.prep_fused) ? 1 : 0;
         // ... and the one-workgroup tier (more problems than half the CUs, n <= 512): k_spd_inverse scales the prepared
         // blocks, sums ||Qs||_F and adds rho itself (wg_spd_factor)
         if (!P.prep_fused && spd && !spd_split && !spd_big_split && P.Ks <= SPD_MAXK && P.scale && P.qs_lazy &&
             ctl->rho_mode != 2 && (size_t)n * P.ldq >= (size_t)SPD_NP * P.Ks * LQP_NB + 8 &&      // (k_spd_prep's scratch per
-            knobs().prep_one)                                                             //  problem lives in its Qs area)
+            k.prep_one)                                                                   //  problem lives in its Qs area)
             P.prep_fused = 2;
     }
-#endif
-#if LQP_PIV_MFMA
     // ... or no pass in front at all: the resident sweep reads Q itself, straight into the registers that keep it
-    if (P.prep_fused == 1 && (size_t)n * P.ldq >= (size_t)rs_np * (64 * P.Ks + 2) && knobs().qpass) P.prep_fused = 3;
+    if (P.prep_fused == 1 && (size_t)n * P.ldq >= (size_t)plan.rs_np * (64 * P.Ks + 2) && k.qpass) P.prep_fused = 3;
 #endif
+    // the LDS opt-ins of the prologue's and the factorisation's kernels (launch_lu and launch_pack see to their own)
+    int rc = ensure_lds((const void*)k_fwd_setup<T>, setup_lds_bytes<T>(n));
     if constexpr (sizeof(T) == 4) {
-        if (P.prep_fused == 1 || P.prep_fused == 2) {
-            const int lds = (2 * 64 * SPD_LS + 2 * LQP_NW + 64 * P.Ks) * 4;
-            const int r3 = ensure_lds((const void*)k_spd_prep<>, lds);
-            if (r3) return r3;
-            ProfScope ps(st, PC_SPD_INV);
-            hipLaunchKernelGGL(k_spd_prep<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P);
-            ++n_launch;
+        if (!rc && (P.prep_fused == 1 || P.prep_fused == 2)) rc = ensure_lds((const void*)k_spd_prep<>, spd_prep_lds_bytes(P.Ks));
+        if (spd) {
+            const int lds = spd_factor_lds_bytes(m, P.Ks);
+            if (!rc) rc = ensure_lds((const void*)(P.Ks > SPD_MAXK ? k_spd_inverse<2> : k_spd_inverse<1>), lds);
+            if (!rc && (spd_big_split || spd_split)) rc = ensure_lds((const void*)k_spd_begin<>, lds);
+            if (!rc && spd_big_split) rc = ensure_lds((const void*)k_spd_big_step<>, lds);
+            if (!rc && spd_split && !spd_big_split) rc = ensure_lds((const void*)k_spd_step<>, lds);
+            if (!rc && (spd_big_split || spd_split)) rc = ensure_lds((const void*)k_spd_end<>, lds);
         }
     }
+    if (rc) return rc;
 
-    // ---- setup (its workgroup 0 zeroes status + counter ring), factor, pack ----
-    {
-        const int lds = setup_lds_bytes<T>(n);
-        auto fn = k_fwd_setup<T>;
-        int rc = ensure_lds((const void*)fn, lds);
-        if (rc) return rc;
-        ProfScope ps(st, PC_SETUP);
-        hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, st, P);
-        ++n_launch;
-    }
-    // factorise (gate == nullptr) or refactorise under the device-side gate of k_rho_update
-    auto factor_step = [&](const int* gate) -> int {
-        if constexpr (sizeof(T) == 4) {
-            if (spd) {
-                const int lds = spd_factor_lds_bytes(m, P.Ks);
-                auto inv_fn = P.Ks > SPD_MAXK ? k_spd_inverse<2> : k_spd_inverse<1>;
-                const int r2 = ensure_lds((const void*)inv_fn, lds);
-                if (r2) return r2;
-                ProfScope ps(st, PC_SPD_INV);
-                if (spd_big_split) {
-                    // 512 < n <= 1024, few problems: two workgroups per matrix, a launch per phase of a pivot step
-                    int r3 = ensure_lds((const void*)k_spd_begin<>, lds);
-                    if (!r3) r3 = ensure_lds((const void*)k_spd_big_step<>, lds);
-                    if (!r3) r3 = ensure_lds((const void*)k_spd_end<>, lds);
-                    if (r3) return r3;
-                    hipLaunchKernelGGL(k_spd_begin<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P, gate);
-                    if (rho_late_big && gate == nullptr) {
-                        hipLaunchKernelGGL(k_spd_rho_big<>, dim3(B), dim3(LQP_NT), 0, st, P);
-                        ++n_launch;
-                    }
-                    // two pivot steps per pass over the tiles (wg_spd_sweep_big, phases bits 2 .. 4): pivot + Y of step k | its update on
-                    // block column k + 1 alone | pivot + Y' of step k + 1 | ONE read-modify-write of every other tile with both products
-                    const bool fuse2 = knobs().spd_big_fuse != 0 && (size_t)P.Np * P.Np >= (size_t)(2 * P.Ks + 1) * LQP_BLK;
-                    // ... its panel blocks as two-half operands, the update products on the float16 pipe (lqp_f16x2.hpp)
-                    const int f16 = (fuse2 && knobs().spd_big_f16 != 0) ? 32 : 0;
-                    for (int k = 0; k < P.Ks; ++k) {
-                        const dim3 grd(shared_grid(B, SPD_NP)), blk(LQP_NT);
-                        if (fuse2 && k + 1 < P.Ks) {
-                            hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 1 | f16);
-                            hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 4 | f16);
-                            hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k + 1, 1 | 16 | f16);
-                            hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 8 | f16);
-                            ++k;
-                            continue;
-                        }
-                        hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 1);
-                        hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 2);
-                    }
-                    hipLaunchKernelGGL(k_spd_end<>, dim3(B), dim3(LQP_NT), lds, st, P, gate);
-                    n_launch += 2 * P.Ks + 2;
-                    return LQP_OK;
-                }
-                if (spd_split) {
-                    // few problems: SPD_NP workgroups per matrix, one launch per pivot step (k_spd_begin/step/end)
-                    int r3 = ensure_lds((const void*)k_spd_begin<>, lds);
-                    if (!r3) r3 = ensure_lds((const void*)k_spd_step<>, lds);
-                    if (!r3) r3 = ensure_lds((const void*)k_spd_end<>, lds);
-                    if (r3) return r3;
-                    if (!(gate == nullptr && P.prep_fused))      // (the first factorisation's blocks: k_spd_prep built them)
-                        hipLaunchKernelGGL(k_spd_begin<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P, gate);
-                    if (spd_resident) {
-                        // all pivot steps in one launch, the matrix in the registers of its two workgroups
-                        const int rlds = rs_q_lds_bytes(P.Ks);
-                        r3 = ensure_lds((const void*)rs_fn, rlds);
-                        if (r3) return r3;
-                        hipLaunchKernelGGL(rs_fn, dim3((knobs().dbg_loop_absent & 2) ? B : shared_grid(B, rs_np)), dim3(RS_NT), rlds, st, P, gate);
-                        n_launch += 1;
-                    } else {
-                        for (int k = 0; k < P.Ks; ++k)
-                            hipLaunchKernelGGL(k_spd_step<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P, gate, k, spd_pivot_tasks);
-                        n_launch += P.Ks;
-                    }
-                    if (!(gate == nullptr && P.eq_in_loop)) hipLaunchKernelGGL(k_spd_end<>, dim3(B), dim3(LQP_NT), lds, st, P, gate);
-                    n_launch += 2;
-                    return LQP_OK;
-                }
-                hipLaunchKernelGGL(inv_fn, dim3(B), dim3(LQP_NT), lds, st, P, gate);
-                ++n_launch;
-                return LQP_OK;
-            }
-        }
-        // (scratch of the two-workgroup LU: the head of each problem's packed area -- the pack kernel fills it afterwards)
-        const size_t pk_words = packed_blocks(P.K) * LQP_BLK * sizeof(T) / 8;
-        int r2 = launch_lu(st, P.M, B, P.N, P.Np, (size_t)P.Np * P.Np, P.piv, P.Np, P.info, gate, nullptr,
-                           (unsigned long long*)P.packed, pk_words);
-        if (r2) return r2;
-        r2 = launch_pack<T>(st, B, P.M, P.N, P.Np, (size_t)P.Np * P.Np, P.piv, P.Np, P.packed, P.dest, gate);
-        n_launch += 2;
-        return r2;
-    };
-    int rc = LQP_OK;
-
-    // ---- launch mode ----
+    // ---- the loop kernels ----
     // hot (first) launch: optional 512-thread build (256 VGPRs per thread: 16 register-resident blocks instead
     // of 8).  Measured SLOWER at B=128 n=500 (2.03 ms vs 1.54 ms; 1.76 ms with a 6-deep ring and 4 spills):
     // 8 waves hide the per-block dependent chain worse than 16, which costs more than the 8 extra resident
     // blocks save.  Kept selectable (LQP_LOOP512=1) for re-measurement; continuation launches always use 1024.
-    const bool res_env = knobs().resident != 0;
-    const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && res_env &&
+    const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && k.resident != 0 &&
                           loop_lds_bytes<T>(n, m, P.Np, true) <= 160 * 1024;
-    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && knobs().loop512 != 0;
-    int loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident);
-    int loop_nt = hot512 ? 512 : 1024;
-    auto loop_fn = k_admm_loop<T, false, false, 1024>;
-    auto tail_fn = k_admm_loop<T, false, true, 1024>;        // same code, own name: continuation launches
+    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0;
+    plan.loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident);
+    plan.loop_nt = hot512 ? 512 : 1024;
+    plan.loop_fn = k_admm_loop<T, false, false, 1024>;
+    plan.tail_fn = k_admm_loop<T, false, true, 1024>;        // same code, own name: continuation launches
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
-    int tail_lds = 0;
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
     //  separate gated kernels, and the continuation kernel's LDS does not have to hold an LU panel)
     // (float64 too since round 5: the pipelined schedule enqueues every possible event up front -- nine at the defaults -- and with
     //  separate gated kernels each one cost four launches that do nothing when the solve is over: rho update, LU, pack, tail)
-    bool inkernel_refactor = P.N <= 1024;
+    plan.inkernel_refactor = P.N <= 1024;
     if constexpr (sizeof(T) == 4) {
-        if (resident) { loop_fn = k_admm_loop<T, true, false, 1024>; tail_fn = k_admm_loop<T, true, true, 1024>; }
-        if (hot512) loop_fn = k_admm_loop<T, true, false, 512>;
+        if (resident) { plan.loop_fn = k_admm_loop<T, true, false, 1024>; plan.tail_fn = k_admm_loop<T, true, true, 1024>; }
+        if (hot512) plan.loop_fn = k_admm_loop<T, true, false, 512>;
         if (spd) {
             P.sym_rl = sym_resident_lds_blocks(n, m, P.Ks);
-            loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl);
-            tail_lds = std::max(loop_lds, spd_factor_lds_bytes(m, P.Ks));      // the tail refactorises in-kernel
-            loop_nt = 1024;
-            loop_fn = k_admm_loop<T, true, false, 1024, true>;
-            tail_fn = k_admm_loop<T, true, true, 1024, true>;
+            plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl);
+            plan.tail_lds = std::max(plan.loop_lds, spd_factor_lds_bytes(m, P.Ks));      // the tail refactorises in-kernel
+            plan.loop_nt = 1024;
+            plan.loop_fn = k_admm_loop<T, true, false, 1024, true>;
+            plan.tail_fn = k_admm_loop<T, true, true, 1024, true>;
             // optional 512-thread first launch (8 elements per thread, 12 register-resident blocks).  Measured at
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
             // blocks show, the product is bound by the un-overlapped sum of its resident and streamed phases.
-            if (knobs().sym512) {
+            if (k.sym512) {
                 P.sym_rl_hot = sym_resident_lds_blocks(n, m, P.Ks, resident_regs<512>(), 8);
-                loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl_hot, 8);
-                loop_nt = 512;
-                loop_fn = k_admm_loop<T, true, false, 512, true>;
+                plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl_hot, 8);
+                plan.loop_nt = 512;
+                plan.loop_fn = k_admm_loop<T, true, false, 512, true>;
             }
         }
     }
-    rc = ensure_lds((const void*)loop_fn, loop_lds);
+    rc = ensure_lds((const void*)plan.loop_fn, plan.loop_lds);
     if (rc) return rc;
     if (!spd) {
-        tail_lds = loop_lds;
+        plan.tail_lds = plan.loop_lds;
         if (P.N <= 1024) {
-            tail_lds = std::max(tail_lds, LuLds<T, (sizeof(T) == 4 ? 16 : 8)>(round_up(P.N, 64)).total);
-            tail_lds = std::max(tail_lds, (int)pack_lds_bytes<T>());
+            plan.tail_lds = std::max(plan.tail_lds, LuLds<T, (sizeof(T) == 4 ? 16 : 8)>(round_up(P.N, 64)).total);
+            plan.tail_lds = std::max(plan.tail_lds, (int)pack_lds_bytes<T>());
         }
     }
-    rc = ensure_lds((const void*)tail_fn, tail_lds);
+    rc = ensure_lds((const void*)plan.tail_fn, plan.tail_lds);
     if (rc) return rc;
+
+    // ---- launch mode ----
     int mode = ctl->launch_mode;
-    if (mode == 0) mode = knobs().launch_mode;     // auto: persistent when every workgroup is resident
-    if (ctl->check_hook || solo) mode = 1;                   // the hook sits between the check segments | no grid barrier
+    if (mode == 0) mode = k.launch_mode;            // auto: persistent when every workgroup is resident
+    if (ctl->check_hook || solo) mode = 1;          // the hook sits between the check segments | no grid barrier
     if (mode == 2) {
         // the grid barrier needs EVERY workgroup resident -- of the hot kernel and of the continuation kernel
         // (own block size and LDS footprint): take the smaller of the two answers
-        int dev = 0, cus = 0, per_cu = 0, per_cu_tail = 0;
-        if (!current_device_cus(&dev, &cus) || !blocks_per_cu(&per_cu, loop_fn, loop_nt, loop_lds, dev) ||
-            !blocks_per_cu(&per_cu_tail, tail_fn, LQP_NT, tail_lds, dev))
+        int per_cu = 0, per_cu_tail = 0;
+        if (!blocks_per_cu(&per_cu, plan.loop_fn, plan.loop_nt, plan.loop_lds, d.dev) ||
+            !blocks_per_cu(&per_cu_tail, plan.tail_fn, LQP_NT, plan.tail_lds, d.dev))
             return LQP_ERR_HIP;
         per_cu = std::min(per_cu, per_cu_tail);
-        if (per_cu < 1 || B > cus * per_cu) mode = 1;     // not every workgroup resident: no grid barrier
+        if (per_cu < 1 || B > d.cus * per_cu) mode = 1;     // not every workgroup resident: no grid barrier
         // More problems than half the CUs but all resident (128 < B <= 256 here): the persistent one-workgroup kernel streams
         // two thirds of its matrix per iteration, while pairs of the two-workgroup kernel, taking turns, hold theirs in
         // registers (split_seg below) -- one launch per check segment then beats the persistent launch (B = 256, n = 500: loop
         // 0.82 -> 0.42 ms, step 1.87 -> 1.60 ms; B = 192: 1.63 -> 1.51).  Only when the caller left the mode to the library.
         if constexpr (sizeof(T) == 4) {
-            if (mode == 2 && ctl->launch_mode == 0 && knobs().launch_mode == 2 && spd && P.xchg && 2 * B > cus &&
-                P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && knobs().loop_split != 0 &&
-                knobs().loop_split_seg != 0 && !ctl->check_hook)
+            if (mode == 2 && ctl->launch_mode == 0 && k.launch_mode == 2 && spd && P.xchg && 2 * B > d.cus &&
+                P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && k.loop_split != 0 &&
+                k.loop_split_seg != 0 && !ctl->check_hook)
                 mode = 1;
         }
     }
-    const int max_checks_per_launch = kRing / 4;
-    // two workgroups per QP for the first (hot) launch: symmetric path, persistent mode, 2 B workgroups resident
-    bool loop_split = false;
-    int split_lds = 0, split_nt = 512, loop_np = 1;
-    void (*split_fn)(const FwdParams<float>, const int, const int, const int) = nullptr;
+    plan.mode = mode;
     if constexpr (sizeof(T) == 4) {
-        if (spd && mode == 2 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && knobs().loop_split != 0) {
+        // two workgroups per QP for the first (hot) launch: symmetric path, persistent mode, 2 B workgroups resident
+        if (spd && mode == 2 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && k.loop_split != 0) {
             // 512 threads x 256 VGPRs: every block of the workgroup's half lives in registers.  (The 1024-thread
             // build -- 12 blocks in 128 VGPRs, 6 in LDS, 16 waves -- spills ~60 VGPRs into the hot loop and measured
             // 0.38 ms against 0.28 ms at B = 128, n = 500; the template still takes NT = 1024.)
-            split_nt = 512;
-            int dev = 0, cus = 0, per_cu = 0;
-            if (!current_device_cus(&dev, &cus)) return LQP_ERR_HIP;
+            int loop_np = 1;
             // four workgroups per QP (one column pair each) when the batch leaves room for them: B <= #CUs / 4
-            if (P.Ks >= 7 && 4 * B <= cus && knobs().loop_split4 != 0) {
-                split_lds = split_loop_lds_bytes<512, 4>(P.Ks, m);
-                split_fn = P.Ks == 7 ? k_admm_loop_split<7, 512, false, 4> : k_admm_loop_split<8, 512, false, 4>;
-                if (split_lds <= 160 * 1024 && ensure_lds((const void*)split_fn, split_lds) == LQP_OK &&
-                    blocks_per_cu(&per_cu, split_fn, split_nt, split_lds, dev) && per_cu >= 1 && shared_grid(B, 4) <= cus * per_cu)
-                    loop_np = 4;
+            if (P.Ks >= 7 && 4 * B <= d.cus && k.loop_split4 != 0) {
+                plan.split_lds = split_loop_lds_bytes<512, 4>(P.Ks, m);
+                plan.split_fn = loop_split_fn<4>(P.Ks, false);
+                if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 4))) loop_np = 4;
             }
             if (loop_np != 4) {
-                split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-                split_fn = P.Ks == 3 ? k_admm_loop_split<3, 512> : P.Ks == 4 ? k_admm_loop_split<4, 512> : P.Ks == 5 ? k_admm_loop_split<5, 512> : P.Ks == 6 ? k_admm_loop_split<6, 512>
-                         : P.Ks == 7 ? k_admm_loop_split<7, 512> : (g_lu_dbg ? k_admm_loop_split<8, 512, true> : k_admm_loop_split<8, 512>);
-                if (split_lds <= 160 * 1024 && ensure_lds((const void*)split_fn, split_lds) == LQP_OK &&
-                    blocks_per_cu(&per_cu, split_fn, split_nt, split_lds, dev) && per_cu >= 1 && shared_grid(B, 2) <= cus * per_cu)
-                    loop_np = 2;
+                plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
+                plan.split_fn = loop_split_fn<2>(P.Ks, g_lu_dbg != nullptr);
+                if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 2))) loop_np = 2;
             }
-            loop_split = loop_np > 1;
+            if (loop_np > 1) { plan.kind = LOOP_SPLIT; plan.kind_wg = loop_np; }
         }
-    }
-    // above 512 rows (BASELINE configs[3]: n = 1000): the streaming loop of the symmetric path with TWO workgroups per problem, each
-    // streaming one range of whole block columns of H (admm_loop_body_from, NP == 2): twice the registers and LDS under the same
-    // matrix (16 % -> 32 % of it on chip), half the stream per CU -- one CU alone pulls 58 GB/s, 29 us per iteration at n = 1000
-    bool loop_np2 = false;
-    if constexpr (sizeof(T) == 4) {
-        if (spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && loop_nt == 1024 && knobs().loop_np2 != 0 && !solo &&
-            !(retry & 2)) {
-            int dev = 0, cus = 0, per_cu = 0;
-            if (current_device_cus(&dev, &cus) && ensure_lds((const void*)k_admm_loop_np2<>, loop_lds) == LQP_OK &&
-                blocks_per_cu(&per_cu, k_admm_loop_np2<>, 1024, loop_lds, dev) && per_cu >= 1 && shared_grid(B, 2) <= cus * per_cu)
-                loop_np2 = true;
+        // above 512 rows (BASELINE configs[3]: n = 1000): the streaming loop of the symmetric path with TWO workgroups per problem, each
+        // streaming one range of whole block columns of H (admm_loop_body_from, NP == 2): twice the registers and LDS under the same
+        // matrix (16 % -> 32 % of it on chip), half the stream per CU -- one CU alone pulls 58 GB/s, 29 us per iteration at n = 1000
+        if (spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && plan.loop_nt == 1024 && k.loop_np2 != 0 && !solo &&
+            !(retry & 2) && fits(d, k_admm_loop_np2<>, 1024, plan.loop_lds, shared_grid(B, 2))) {
+            plan.kind = LOOP_NP2; plan.kind_wg = 2;
         }
-    }
-    // ... and for batches LARGER than half the CUs (BASELINE configs[4]: 1024 per GPU), where the loop runs one launch per
-    // check segment anyway: the same kernel, its pairs taking turns on the chip (FwdParams::split_seg) -- a pair holds its
-    // whole matrix in registers for the 15 iterations of a segment where the one-workgroup kernel streams two thirds of it
-    // per iteration (B = 1024, n = 500: loop 3.35 -> 8 turns x 4 segments)
-    bool loop_split_seg = false;
-    if constexpr (sizeof(T) == 4) {
-        if (spd && mode == 1 && !loop_split && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 &&
-            knobs().loop_split != 0 && knobs().loop_split_seg != 0 && !(retry & 2) && !solo) {
-            int dev = 0, cus = 0, per_cu = 0;
-            split_nt = 512;
-            split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-            split_fn = P.Ks == 3 ? k_admm_loop_split<3, 512> : P.Ks == 4 ? k_admm_loop_split<4, 512> : P.Ks == 5 ? k_admm_loop_split<5, 512> : P.Ks == 6 ? k_admm_loop_split<6, 512>
-                     : P.Ks == 7 ? k_admm_loop_split<7, 512> : k_admm_loop_split<8, 512>;
-            if (current_device_cus(&dev, &cus) && 2 * B > cus && split_lds <= 160 * 1024 &&
-                ensure_lds((const void*)split_fn, split_lds) == LQP_OK &&
-                blocks_per_cu(&per_cu, split_fn, split_nt, split_lds, dev) && per_cu >= 1)
-                loop_split_seg = true;
+        // ... and for batches LARGER than half the CUs (BASELINE configs[4]: 1024 per GPU), where the loop runs one launch per
+        // check segment anyway: the same kernel, its pairs taking turns on the chip (FwdParams::split_seg) -- a pair holds its
+        // whole matrix in registers for the 15 iterations of a segment where the one-workgroup kernel streams two thirds of it
+        // per iteration (B = 1024, n = 500: loop 3.35 -> 8 turns x 4 segments)
+        if (spd && mode == 1 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 &&
+            k.loop_split != 0 && k.loop_split_seg != 0 && !(retry & 2) && !solo && 2 * B > d.cus) {
+            plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
+            plan.split_fn = loop_split_fn<2>(P.Ks, false);
+            plan.loop_split_seg = fits(d, plan.split_fn, plan.split_nt, plan.split_lds, 0);
         }
     }
     // LU tier, persistent mode, n <= 256, 2 B workgroups resident: the explicit inverse of the KKT matrix in the registers of two
     // workgroups per problem (lqp_dense.hpp) -- float64, many equality rows, non-symmetric Q, control['linsolve'] = 'lu'
-    bool loop_dense = false;
-    int dense_lds = 0;
-    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && knobs().loop_dense != 0) {
-        int dev = 0, cus = 0, per_cu = 0;
-        dense_lds = dense_loop_lds_bytes<T>(m);
-        auto fnd = k_admm_loop_dense<T>;
-        if (dense_lds <= 160 * 1024 && lu_inverse_lds_bytes<T>(P.Np) <= 160 * 1024 && current_device_cus(&dev, &cus) &&
-            ensure_lds((const void*)fnd, dense_lds) == LQP_OK && blocks_per_cu(&per_cu, fnd, DENSE_NT, dense_lds, dev) &&
-            per_cu >= 1 && shared_grid(B, 2) <= cus * per_cu)
-            loop_dense = true;
+    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0) {
+        const int dense_lds = dense_loop_lds_bytes<T>(m);
+        if (lu_inverse_lds_bytes<T>(P.Np) <= 160 * 1024 && fits(d, k_admm_loop_dense<T>, DENSE_NT, dense_lds, shared_grid(B, 2))) {
+            plan.kind = LOOP_DENSE; plan.kind_lds = dense_lds; plan.kind_wg = 2;
+        }
     }
     // ... and for batches that leave most of the chip idle, any n the inverse kernel takes: W workgroups per problem, each with its
     // rows of the inverse in registers (k_admm_loop_dense_w): a matrix-vector product spreads over CUs, triangular solves do not
-    bool loop_dense_w = false;
-    int densew_lds = 0, densew_tprv = 0, densew_W = 0;
-    if (!spd && mode == 2 && P.dnx && !loop_dense && n > DENSE_NMAX && knobs().loop_dense_w != 0 && lu_inverse_fits<T>(P.Np) &&
+    if (!spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && lu_inverse_fits<T>(P.Np) &&
         (size_t)P.dnx_words >= densew_xchg_words<T>(n)) {
-        int dev = 0, cus = 0, per_cu = 0;
-        densew_lds = densew_lds_bytes<T>(n, m);
-        densew_tprv = densew_tpr(n, densew_cpt<T>());
-        densew_W = (n + DENSEW_NT / densew_tprv - 1) / (DENSEW_NT / densew_tprv);
-        auto fnw = k_admm_loop_dense_w<T>;
-        if (densew_tprv <= 32 && densew_W >= 2 && densew_lds <= 160 * 1024 && current_device_cus(&dev, &cus) &&
-            ensure_lds((const void*)fnw, densew_lds) == LQP_OK && blocks_per_cu(&per_cu, fnw, DENSEW_NT, densew_lds, dev) &&
-            per_cu >= 1 && densew_W * B <= cus * per_cu)
-            loop_dense_w = true;
-    }
-    // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
-    bool loop_small = false;
-    int small_lds = 0;
-    if constexpr (sizeof(T) == 4) {
-        if (spd && mode == 2 && !loop_split && P.Ks <= 2 && knobs().loop_small != 0) {
-            int dev = 0, cus = 0, per_cu = 0;
-            small_lds = small_loop_lds_bytes(m);
-            if (current_device_cus(&dev, &cus) && blocks_per_cu(&per_cu, k_admm_loop_small<>, 256, small_lds, dev) &&
-                per_cu >= 1 && B <= cus * per_cu)
-                loop_small = true;
+        const int densew_lds = densew_lds_bytes<T>(n, m);
+        const int tpr = densew_tpr(n, densew_cpt<T>());
+        const int W = (n + DENSEW_NT / tpr - 1) / (DENSEW_NT / tpr);
+        if (tpr <= 32 && W >= 2 && fits(d, k_admm_loop_dense_w<T>, DENSEW_NT, densew_lds, (long long)W * B)) {
+            plan.kind = LOOP_DENSE_W; plan.kind_lds = densew_lds; plan.kind_wg = W; plan.densew_tpr = tpr;
         }
     }
-    // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
-    // (ctrl.reserved2 bit 0: the caller will read the corrected H from the workspace afterwards -- lqp_boxqp_unroll_backward --
-    //  so the correction must reach global memory: k_spd_end runs)
-    if constexpr (sizeof(T) == 4)
-    {
+    if constexpr (sizeof(T) == 4) {
+        // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
+        if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
+            const int small_lds = small_loop_lds_bytes(m);
+            if (fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
+        }
+        // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
+        // (ctrl.reserved2 bit 0: the caller will read the corrected H from the workspace afterwards -- lqp_boxqp_unroll_backward --
+        //  so the correction must reach global memory: k_spd_end runs)
         // (one launch per check segment, pairs taking turns: the FIRST segment's launch applies it and writes the corrected blocks
         //  back -- from two turns of the chip on; below that k_spd_end on every CU at once is faster: B = 256 1.39 against 1.53 ms
         //  per step, B = 512 2.69 against 2.59)
-        int dev_ = 0, cus_ = 0;
-        const bool seg_eq = loop_split_seg && current_device_cus(&dev_, &cus_) && B >= 2 * cus_;
-        P.eq_in_loop = ((loop_split || seg_eq) && spd_resident && m > 0 && !(ctl->reserved2 & 1) && knobs().eq_in_loop) ? 1 : 0;
+        const bool seg_eq = plan.loop_split_seg && B >= 2 * d.cus;
+        P.eq_in_loop = ((plan.kind == LOOP_SPLIT || seg_eq) && spd_resident && m > 0 && !(ctl->reserved2 & 1) && k.eq_in_loop) ? 1 : 0;
     }
-    rc = factor_step(nullptr);
+
+    // ---- the scheduler ----
+    // no-host-sync plan (ctrl.reserved == 1, persistent launches): enqueue the WHOLE schedule.
+    // Every kernel exits at once when the device-side DONE flag is up, the refactor chains are
+    // gated on device, so nothing needs the host; errors are read later by the caller
+    // (lqp_boxqp_forward_layout).  Only taken when the number of adaptive-rho events is small.
+    // A synchronous call (the default: the reference's semantics) enqueues the same schedule and then waits for the report
+    // the last kernel stores into the caller's pinned memory (wait_report) -- not for the stream.
+    int n_events = 0;
+    if (ctl->adaptive_rho)
+        for (int a = ar_iter; a < max_iters && a < ctl->adaptive_rho_max_iter; a += ar_iter) ++n_events;
+    plan.up_front = (ctl->reserved >= 1 || k.sync_plan != 0) && mode == 2 && n_events <= k.nosync_max_events;
+    // (round 6) the two-workgroup loop does not stop at the first iteration at which rho MAY be adapted: it looks at the
+    // counters of the check before and only hands over to the continuation kernel when the event changes something
+    // (FwdParams::hot_past).  Its range is the whole solve; the continuation launch is enqueued from the first event
+    // iteration on and finds its real starting point in status[ST_RESUME].
+    plan.hot_past = plan.up_front && plan.kind == LOOP_SPLIT && spd && plan.inkernel_refactor && ctl->adaptive_rho && k.hot_past != 0 &&
+                    ar_iter < ctl->adaptive_rho_max_iter && ar_iter < max_iters;
+    P.hot_past = plan.hot_past ? 1 : 0;
+    // A GIVEN rho is the case in which the adaptation does fire (`rho = 0.01`: three factorisations, 281 iterations,
+    // 4.5 ms with everything behind iteration 100 on the continuation kernel).  Enqueue a few rounds of {the event
+    // on the gated kernels of the refactorisation, the hot loop again from where it stopped}: each costs a solve that
+    // is over ~5 launches that leave at once -- which is why the automatic rho (it practically never adapts) gets none.
+    plan.hot_rounds = ctl->rho_mode != 0 ? k.hot_rounds : 0;
+    plan.tail_epilogue = k.tail_epilogue != 0;
+    plan.spec_launches = k.spec_launches;
+    plan.factor_launches = spd ? (spd_big_split ? 2 * P.Ks + 2 : spd_split ? (spd_resident ? 3 : P.Ks + 2) : 1) : 2;
+    plan.loop_workgroups = plan.loop_split_seg ? 2 : plan.kind_wg;      // (what the loop's launches put on a problem)
+    return LQP_OK;
+}
+
+// ---- launch steps: they read the plan and decide nothing ----
+// factorise (gate == nullptr) or refactorise under the device-side gate of k_rho_update
+template <typename T>
+int enqueue_factor(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, const int* gate, int& n_launch) {
+    const int B = P.B;
+    if constexpr (sizeof(T) == 4) {
+        if (plan.spd) {
+            const int lds = spd_factor_lds_bytes(P.m, P.Ks);
+            ProfScope ps(st, PC_SPD_INV);
+            if (plan.spd_big_split) {
+                // 512 < n <= 1024, few problems: two workgroups per matrix, a launch per phase of a pivot step
+                hipLaunchKernelGGL(k_spd_begin<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P, gate);
+                if (plan.rho_late_big && gate == nullptr) {
+                    hipLaunchKernelGGL(k_spd_rho_big<>, dim3(B), dim3(LQP_NT), 0, st, P);
+                    ++n_launch;
+                }
+                const int f16 = plan.f16;
+                for (int k = 0; k < P.Ks; ++k) {
+                    const dim3 grd(shared_grid(B, SPD_NP)), blk(LQP_NT);
+                    if (plan.fuse2 && k + 1 < P.Ks) {
+                        hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 1 | f16);
+                        hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 4 | f16);
+                        hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k + 1, 1 | 16 | f16);
+                        hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 8 | f16);
+                        ++k;
+                        continue;
+                    }
+                    hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 1);
+                    hipLaunchKernelGGL(k_spd_big_step<>, grd, blk, lds, st, P, gate, k, 2);
+                }
+                hipLaunchKernelGGL(k_spd_end<>, dim3(B), dim3(LQP_NT), lds, st, P, gate);
+                n_launch += 2 * P.Ks + 2;
+                return LQP_OK;
+            }
+            if (plan.spd_split) {
+                // few problems: SPD_NP workgroups per matrix, one launch per pivot step (k_spd_begin/step/end)
+                if (!(gate == nullptr && P.prep_fused))      // (the first factorisation's blocks: k_spd_prep built them)
+                    hipLaunchKernelGGL(k_spd_begin<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P, gate);
+                if (plan.spd_resident) {
+                    // all pivot steps in one launch, the matrix in the registers of its two workgroups
+                    hipLaunchKernelGGL(plan.rs_fn, dim3((plan.dbg_loop_absent & 2) ? B : shared_grid(B, plan.rs_np)), dim3(RS_NT),
+                                       rs_q_lds_bytes(P.Ks), st, P, gate);
+                    n_launch += 1;
+                } else {
+                    for (int k = 0; k < P.Ks; ++k)
+                        hipLaunchKernelGGL(k_spd_step<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), lds, st, P, gate, k, plan.spd_pivot_tasks);
+                    n_launch += P.Ks;
+                }
+                if (!(gate == nullptr && P.eq_in_loop)) hipLaunchKernelGGL(k_spd_end<>, dim3(B), dim3(LQP_NT), lds, st, P, gate);
+                n_launch += 2;
+                return LQP_OK;
+            }
+            hipLaunchKernelGGL(P.Ks > SPD_MAXK ? k_spd_inverse<2> : k_spd_inverse<1>, dim3(B), dim3(LQP_NT), lds, st, P, gate);
+            ++n_launch;
+            return LQP_OK;
+        }
+    }
+    // (scratch of the two-workgroup LU: the head of each problem's packed area -- the pack kernel fills it afterwards)
+    const size_t pk_words = packed_blocks(P.K) * LQP_BLK * sizeof(T) / 8;
+    int r2 = launch_lu(st, P.M, B, P.N, P.Np, (size_t)P.Np * P.Np, P.piv, P.Np, P.info, gate, nullptr,
+                       (unsigned long long*)P.packed, pk_words);
+    if (r2) return r2;
+    r2 = launch_pack<T>(st, B, P.M, P.N, P.Np, (size_t)P.Np * P.Np, P.piv, P.Np, P.packed, P.dest, gate);
+    n_launch += 2;
+    return r2;
+}
+
+// everything in front of the loop: the pass over Q (k_spd_prep), setup (its workgroup 0 zeroes status + counter ring), the first
+// factorisation, and for the dense tiers X = M^-1
+template <typename T>
+int enqueue_prologue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, int& n_launch) {
+    const int B = P.B;
+    if (P.vtrace) HIP_OK(hipMemsetAsync(P.vtrace, 0, sizeof(unsigned int) * 2 * kRing, st));
+    if (P.host_report) report_reset(P.host_report, ST_WORDS + 2 * B);      // (before the first launch: see wait_report)
+    if constexpr (sizeof(T) == 4) {
+        if (P.prep_fused == 1 || P.prep_fused == 2) {
+            ProfScope ps(st, PC_SPD_INV);
+            hipLaunchKernelGGL(k_spd_prep<>, dim3(shared_grid(B, SPD_NP)), dim3(LQP_NT), spd_prep_lds_bytes(P.Ks), st, P);
+            ++n_launch;
+        }
+    }
+    {
+        ProfScope ps(st, PC_SETUP);
+        hipLaunchKernelGGL(k_fwd_setup<T>, dim3(B), dim3(LQP_NT), setup_lds_bytes<T>(P.n), st, P);
+        ++n_launch;
+    }
+    int rc = enqueue_factor(st, P, plan, nullptr, n_launch);
     if (rc) return rc;
-    if (loop_dense || loop_dense_w) {
+    if (plan.kind == LOOP_DENSE || plan.kind == LOOP_DENSE_W) {
         // X = M^-1 over the LAPACK copy of the factor (the pack kernel has read it; a refactorisation re-assembles M anyway)
         rc = launch_lu_inverse<T>(st, B, P.N, P.packed, packed_blocks(P.K) * LQP_BLK, P.dest, P.Np, P.M, (size_t)P.Np * P.Np, P.Np, nullptr);
         if (rc) return rc;
         ++n_launch;
     }
-    // the first launch of the persistent modes
-    auto launch_hot = [&](const int it, const int e, const int ctr_base, const int prev_slot, const int flags) {
-        ProfScope ps(st, PC_LOOP);
-        if constexpr (sizeof(T) == 4) {
-            if (loop_split && it == 0) {
-                hipLaunchKernelGGL(split_fn, dim3((knobs().dbg_loop_absent & 1) ? B : shared_grid(B, loop_np)), dim3(split_nt), split_lds, st, P, it, e, ctr_base);
-                return;
-            }
-            if (loop_small && it == 0) {
-                hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), small_lds, st, P, it, e, ctr_base);
-                return;
-            }
-            if (loop_np2 && it == 0) {
-                hipLaunchKernelGGL(k_admm_loop_np2<>, dim3((knobs().dbg_loop_absent & 8) ? B : shared_grid(B, 2)), dim3(1024), loop_lds, st, P, it, e, ctr_base, prev_slot, flags);
-                return;
-            }
-        }
-        if (loop_dense && it == 0) {
-            hipLaunchKernelGGL(k_admm_loop_dense<T>, dim3(shared_grid(B, 2)), dim3(DENSE_NT), dense_lds, st, P, it, e, ctr_base);
-            return;
-        }
-        if (loop_dense_w && it == 0) {
-            hipLaunchKernelGGL(k_admm_loop_dense_w<T>, dim3(densew_W * B), dim3(DENSEW_NT), densew_lds, st, P, it, e, ctr_base, densew_tprv);
-            return;
-        }
-        hipLaunchKernelGGL(loop_fn, dim3(B), dim3(loop_nt), loop_lds, st, P, it, e, ctr_base, prev_slot, flags);
-    };
+    return LQP_OK;
+}
 
-    // ---- no-host-sync plan (ctrl.reserved == 1, persistent launches): enqueue the WHOLE schedule.
-    //      Every kernel exits at once when the device-side DONE flag is up, the refactor chains are
-    //      gated on device, so nothing needs the host; errors are read later by the caller
-    //      (lqp_boxqp_forward_layout).  Only taken when the number of adaptive-rho events is small.
-    // A synchronous call (the default: the reference's semantics) enqueues the same schedule and then waits for the report
-    // the last kernel stores into the caller's pinned memory (wait_report) -- not for the stream.
-    if ((ctl->reserved >= 1 || knobs().sync_plan != 0) && mode == 2) {
-        int n_events = 0;
-        if (ctl->adaptive_rho)
-            for (int a = ar_iter; a < max_iters && a < ctl->adaptive_rho_max_iter; a += ar_iter) ++n_events;
-        if (n_events <= knobs().nosync_max_events) {
-            int it = 0;
-            const bool tail_epilogue = knobs().tail_epilogue != 0;
-            bool epilogue_done = false;
-            bool resume_next = false;       // the next continuation launch starts where the hot kernel says it stopped
-            while (it < max_iters) {
-                // the adaptive-rho step of iteration `it` runs as the prologue of the continuation kernel
-                bool event = ctl->adaptive_rho && it > 0 && it % ar_iter == 0 && it < ctl->adaptive_rho_max_iter;
-                if (event && !inkernel_refactor) {      // f64 / symmetric path: separate gated kernels
-                    const int last_slot = ((it - 1) / check) % kRing;
-                    { ProfScope ps(st, PC_RHO);
-                      hipLaunchKernelGGL(k_rho_update<T>, dim3(B), dim3(LQP_NT), 0, st, P, last_slot, 0); }
-                    ++n_launch;
-                    rc = factor_step(P.status + ST_GATE);
-                    if (rc) return rc;
-                    event = false;
-                }
-                int e = max_iters;
-                // (round 6) the two-workgroup loop does not stop at the first iteration at which rho MAY be adapted: it looks at the
-                // counters of the check before and only hands over to the continuation kernel when the event changes something
-                // (FwdParams::hot_past).  Its range is the whole solve; the continuation launch is enqueued from the first event
-                // iteration on and finds its real starting point in status[ST_RESUME].
-                const bool hot_past = it == 0 && loop_split && spd && inkernel_refactor && ctl->adaptive_rho && knobs().hot_past != 0 &&
-                                      ar_iter < ctl->adaptive_rho_max_iter && ar_iter < max_iters;
-                if (ctl->adaptive_rho && !((spd || inkernel_refactor) && it > 0) && !hot_past) {      // (the continuation kernel walks through its events itself)
-                    const int a = (it / ar_iter + 1) * ar_iter;
-                    if (a < ctl->adaptive_rho_max_iter) e = std::min(e, a);
-                }
-                // a launch may hold at most kRing/2 checks (counter ring); longer tails are split
-                e = std::min(e, it + (kRing / 2) * check);
-                const long long c_first = (it + check - 1) / check;
-                const long long c_last = (e - 1) / check;
-                if (c_last >= kRing) {      // these slots were used one ring ago: clear exactly them (stream-ordered)
-                    for (long long c = std::max<long long>(c_first, kRing); c <= c_last; ) {
-                        const int s0 = (int)(c % kRing);
-                        const long long run = std::min<long long>(c_last - c + 1, kRing - s0);
-                        HIP_OK(hipMemsetAsync(P.counters + (size_t)s0 * CT_WORDS, 0,
-                                              sizeof(unsigned int) * CT_WORDS * (size_t)run, st));
-                        c += run;
-                    }
-                }
-                const int prev_slot = it > 0 ? ((it - 1) / check) % kRing : -1;
-                bool last_tail = false;
-                if (it == 0) {
-                    P.hot_past = hot_past ? 1 : 0;
-                    launch_hot(it, e, (int)(c_first % kRing), prev_slot, 1);
-                    resume_next = hot_past;
-                    if (hot_past) {
-                        // A GIVEN rho is the case in which the adaptation does fire (`rho = 0.01`: three factorisations, 281 iterations,
-                        // 4.5 ms with everything behind iteration 100 on the continuation kernel).  Enqueue a few rounds of {the event
-                        // on the gated kernels of the refactorisation, the hot loop again from where it stopped}: each costs a solve that
-                        // is over ~5 launches that leave at once -- which is why the automatic rho (it practically never adapts) gets none.
-                        const int rounds = ctl->rho_mode != 0 ? knobs().hot_rounds : 0;
-                        for (int rd = 0; rd < rounds; ++rd) {
-                            { ProfScope ps(st, PC_RHO);
-                              hipLaunchKernelGGL(k_rho_update<T>, dim3(B), dim3(LQP_NT), 0, st, P, -1, max_iters); }
-                            ++n_launch;
-                            rc = factor_step(P.status + ST_GATE);
-                            if (rc) return rc;
-                            if constexpr (sizeof(T) == 4) {
-                                FwdParams<float> Pr = P;
-                                Pr.hot_resume = 1;
-                                Pr.eq_in_loop = 0;          // (k_spd_end has corrected the new blocks in global memory)
-                                ProfScope ps(st, PC_LOOP);
-                                hipLaunchKernelGGL(split_fn, dim3(shared_grid(B, loop_np)), dim3(split_nt), split_lds, st, Pr, ar_iter, e,
-                                                   (int)(((ar_iter + check - 1) / check) % kRing));
-                                ++n_launch;
-                            }
-                        }
-                        e = ar_iter;          // (the continuation launch below is enqueued for [first event, ...): see above)
-                    }
-                } else {
-                    // the last continuation launch ends with the epilogue (one launch and its boundary less)
-                    last_tail = e >= max_iters && tail_epilogue;
-                    ProfScope ps(st, PC_LOOP_TAIL);
-                    hipLaunchKernelGGL(tail_fn, dim3(B), dim3(LQP_NT), tail_lds, st,
-                                       P, it, e, (int)(c_first % kRing), prev_slot,
-                                       ((event || spd || inkernel_refactor) ? 3 : 1) | (last_tail ? 4 : 0) | (resume_next ? 8 : 0));
-                    resume_next = false;
-                }
-                ++n_launch;
-                it = e;
-                epilogue_done = last_tail;
-            }
-            if (!epilogue_done) {
-                ProfScope ps(st, PC_EPILOGUE);
-                hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
-                ++n_launch;
-            }
-            if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
-            const int factor_launches = spd ? (spd_big_split ? 2 * P.Ks + 2 : spd_split ? (spd_resident ? 3 : P.Ks + 2) : 1) : 2;
-            if (ctl->reserved == 1) {
-                if (stats) {
-                    memset(stats, 0, sizeof(*stats));
-                    stats->iters = stats->n_factor = stats->n_solve = stats->n_check = -1;   // not known on the host
-                    stats->fail_index = -1; stats->n_launch = n_launch; stats->mode_used = 3;
-                    stats->any_lb = stats->any_ub = -1;
-                    stats->linsolve_used = spd ? 2 : 1;
-                    stats->factor_launches = factor_launches;
-                    stats->loop_workgroups = loop_split ? loop_np : ((loop_dense || loop_np2) ? 2 : (loop_dense_w ? densew_W : 1));
-                }
-                return LQP_OK;
-            }
-            if (ctl->reserved == 2 && P.host_report) {
-                // split call: everything is enqueued; the caller does its own host work (output views, bookkeeping) while
-                // the GPU runs and then collects the report with lqp_boxqp_forward_finish
-                if (stats) {
-                    memset(stats, 0, sizeof(*stats));
-                    stats->iters = stats->n_factor = stats->n_solve = stats->n_check = -1;
-                    stats->fail_index = -1; stats->n_launch = n_launch; stats->mode_used = 4;
-                    stats->any_lb = stats->any_ub = -1;
-                    stats->linsolve_used = spd ? 2 : 1;
-                    stats->factor_launches = factor_launches;
-                    stats->loop_workgroups = loop_split ? loop_np : ((loop_dense || loop_np2) ? 2 : (loop_dense_w ? densew_W : 1));
-                }
-                return LQP_OK;
-            }
-            // ---- synchronous call: status block, info and flag words of every problem ----
-            std::vector<int> rep_copy;
-            const int* rep = P.host_report;
-            if (!rep) {                     // (a C caller without pinned memory: three small copies and a stream wait)
-                rep_copy.resize(ST_WORDS + 2 * B);
-                HIP_OK(hipMemcpyAsync(rep_copy.data(), P.status, sizeof(int) * ST_WORDS, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipMemcpyAsync(rep_copy.data() + ST_WORDS, P.info, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipMemcpyAsync(rep_copy.data() + ST_WORDS + B, P.bflags, sizeof(int) * B, hipMemcpyDeviceToHost, st));
-                HIP_OK(hipStreamSynchronize(st));
-                rep = rep_copy.data();
-            }
-            lqp_boxqp_stats local;
-            lqp_boxqp_stats* so = stats ? stats : &local;
-            memset(so, 0, sizeof(*so));
-            so->n_launch = n_launch; so->linsolve_used = spd ? 2 : 1; so->factor_launches = factor_launches;
-            so->loop_workgroups = loop_split ? loop_np : ((loop_dense || loop_np2) ? 2 : (loop_dense_w ? densew_W : 1));
-            rc = collect_report(st, rep, rep == P.host_report, B, max_iters, check, so);
-            if (rc == LQP_ERR_TIMEOUT && !spd && !t_single_wg_lu && !(flags_timeout_loop(rep))) {      // a shared LU timed out: one workgroup per matrix
-                SingleWgLu only;
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats, ws, ws_bytes, retry);
-            }
-            if (rc == LQP_ERR_TIMEOUT && !solo)     // a shared sweep / loop / grid barrier gave up: once more with nothing shared
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats, ws, ws_bytes,
-                                       retry | 4);
-            if (rc == LQP_RETRY_LU)         // Qs + rho I not positive definite in f32 (first factorisation or an
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats,
-                                       ws, ws_bytes, retry | 1);     // adaptive-rho one): the LU path takes the solve
-            return rc;
-        }
+// the first launch of the persistent mode: iterations [0, e), the kernel of plan.kind
+template <typename T>
+void launch_hot(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, const int e, const int ctr_base) {
+    const int B = P.B, absent = plan.dbg_loop_absent;
+    ProfScope ps(st, PC_LOOP);
+    if constexpr (sizeof(T) == 4) switch (plan.kind) {
+        case LOOP_SPLIT:
+            hipLaunchKernelGGL(plan.split_fn, dim3((absent & 1) ? B : shared_grid(B, plan.kind_wg)), dim3(plan.split_nt), plan.split_lds, st, P, 0, e, ctr_base);
+            return;
+        case LOOP_SMALL:
+            hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            return;
+        case LOOP_NP2:
+            hipLaunchKernelGGL(k_admm_loop_np2<>, dim3((absent & 8) ? B : shared_grid(B, 2)), dim3(1024), plan.loop_lds, st, P, 0, e, ctr_base, -1, 1);
+            return;
+        default: break;
     }
+    switch (plan.kind) {
+        case LOOP_DENSE:
+            hipLaunchKernelGGL(k_admm_loop_dense<T>, dim3(shared_grid(B, 2)), dim3(DENSE_NT), plan.kind_lds, st, P, 0, e, ctr_base);
+            return;
+        case LOOP_DENSE_W:
+            hipLaunchKernelGGL(k_admm_loop_dense_w<T>, dim3(plan.kind_wg * B), dim3(DENSEW_NT), plan.kind_lds, st, P, 0, e, ctr_base, plan.densew_tpr);
+            return;
+        default:
+            hipLaunchKernelGGL(plan.loop_fn, dim3(B), dim3(plan.loop_nt), plan.loop_lds, st, P, 0, e, ctr_base, -1, 1);
+    }
+}
 
-    // ---- iterate ----
+// an adaptive-rho event on separate kernels: k_rho_update raises the device-side gate, the refactorisation runs under it
+template <typename T>
+int enqueue_rho_event(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, const int slot, const int resume_end, int& n_launch) {
+    { ProfScope ps(st, PC_RHO);
+      hipLaunchKernelGGL(k_rho_update<T>, dim3(P.B), dim3(LQP_NT), 0, st, P, slot, resume_end); }
+    ++n_launch;
+    return enqueue_factor(st, P, plan, P.status + ST_GATE, n_launch);
+}
+
+// the counter-ring slots of a launch over iterations [it, e): check c counts into slot c % kRing
+struct RingSpan {
+    long long c_first, c_last;      // first check index >= it, last check index <= e - 1
+    int ctr_base, prev_slot;        // slot of c_first; slot of the last check before `it` (-1: none)
+    RingSpan(const int it, const int e, const int check)
+        : c_first((it + check - 1) / check), c_last((e - 1) / check), ctr_base((int)(c_first % kRing)),
+          prev_slot(it > 0 ? ((it - 1) / check) % kRing : -1) {}
+};
+
+// what the enqueue knows; the solve's own figures are not on the host yet (-1) -- collect_report / solve_stats fill them in
+template <typename T>
+void fill_stats(lqp_boxqp_stats* stats, const FwdPlan<T>& plan, const int mode_used, const int n_launch) {
+    memset(stats, 0, sizeof(*stats));
+    stats->iters = stats->n_factor = stats->n_solve = stats->n_check = -1;
+    stats->fail_index = -1; stats->n_launch = n_launch; stats->mode_used = mode_used;
+    stats->any_lb = stats->any_ub = -1;
+    stats->linsolve_used = plan.spd ? 2 : 1;
+    stats->factor_launches = plan.factor_launches;
+    stats->loop_workgroups = plan.loop_workgroups;
+}
+
+// why an attempt gave up, for forward_impl's retry loop
+enum GaveUp {
+    GU_NONE = 0,
+    GU_NOT_SPD,             // Qs + rho I not positive definite in f32 (first factorisation or an adaptive-rho one; on some rank)
+    GU_LU_TIMEOUT,          // a shared LU never met its partner
+    GU_SEG_TIMEOUT,         // a pair of the turn-taking loop (split_seg) waited for its partner in vain
+    GU_SHARED_TIMEOUT       // another shared sweep / loop / grid barrier gave up
+};
+struct Attempt {
+    int status; GaveUp why;
+    Attempt(int s) : status(s), why(GU_NONE) {}
+    Attempt(GaveUp w) : status(LQP_OK), why(w) {}
+};
+
+// ---- the whole schedule up front (plan.up_front) ----
+template <typename T>
+Attempt run_planned(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, const lqp_boxqp_ctrl* ctl, lqp_boxqp_stats* stats,
+                    int n_launch) {
+    const int B = P.B, check = P.check_solved, max_iters = ctl->max_iters, ar_iter = P.ar_iter;
+    const bool spd = plan.spd;
+    int rc = LQP_OK;
+    int it = 0;
+    bool epilogue_done = false;
+    bool resume_next = false;       // the next continuation launch starts where the hot kernel says it stopped
+    while (it < max_iters) {
+        // the adaptive-rho step of iteration `it` runs as the prologue of the continuation kernel
+        bool event = ctl->adaptive_rho && it > 0 && it % ar_iter == 0 && it < ctl->adaptive_rho_max_iter;
+        if (event && !plan.inkernel_refactor) {      // f64 / symmetric path: separate gated kernels
+            rc = enqueue_rho_event(st, P, plan, ((it - 1) / check) % kRing, 0, n_launch);
+            if (rc) return rc;
+            event = false;
+        }
+        int e = max_iters;
+        const bool hot_past = it == 0 && plan.hot_past;
+        if (ctl->adaptive_rho && !((spd || plan.inkernel_refactor) && it > 0) && !hot_past) {      // (the continuation kernel walks through its events itself)
+            const int a = (it / ar_iter + 1) * ar_iter;
+            if (a < ctl->adaptive_rho_max_iter) e = std::min(e, a);
+        }
+        // a launch may hold at most kRing/2 checks (counter ring); longer tails are split
+        e = std::min(e, it + (kRing / 2) * check);
+        const RingSpan s(it, e, check);
+        if (s.c_last >= kRing) {      // these slots were used one ring ago: clear exactly them (stream-ordered)
+            for (long long c = std::max<long long>(s.c_first, kRing); c <= s.c_last; ) {
+                const int s0 = (int)(c % kRing);
+                const long long run = std::min<long long>(s.c_last - c + 1, kRing - s0);
+                HIP_OK(hipMemsetAsync(P.counters + (size_t)s0 * CT_WORDS, 0,
+                                      sizeof(unsigned int) * CT_WORDS * (size_t)run, st));
+                c += run;
+            }
+        }
+        bool last_tail = false;
+        if (it == 0) {
+            launch_hot(st, P, plan, e, s.ctr_base);
+            resume_next = hot_past;
+            if (hot_past) {
+                // rounds of {the event on the gated kernels of the refactorisation, the hot loop again from where it stopped}
+                for (int rd = 0; rd < plan.hot_rounds; ++rd) {
+                    rc = enqueue_rho_event(st, P, plan, -1, max_iters, n_launch);
+                    if (rc) return rc;
+                    if constexpr (sizeof(T) == 4) {
+                        FwdParams<float> Pr = P;
+                        Pr.hot_resume = 1;
+                        Pr.eq_in_loop = 0;          // (k_spd_end has corrected the new blocks in global memory)
+                        ProfScope ps(st, PC_LOOP);
+                        hipLaunchKernelGGL(plan.split_fn, dim3(shared_grid(B, plan.kind_wg)), dim3(plan.split_nt), plan.split_lds, st, Pr,
+                                           ar_iter, e, RingSpan(ar_iter, e, check).ctr_base);
+                        ++n_launch;
+                    }
+                }
+                e = ar_iter;          // (the continuation launch below is enqueued for [first event, ...): see plan.hot_past)
+            }
+        } else {
+            // the last continuation launch ends with the epilogue (one launch and its boundary less)
+            last_tail = e >= max_iters && plan.tail_epilogue;
+            ProfScope ps(st, PC_LOOP_TAIL);
+            hipLaunchKernelGGL(plan.tail_fn, dim3(B), dim3(LQP_NT), plan.tail_lds, st,
+                               P, it, e, s.ctr_base, s.prev_slot,
+                               ((event || spd || plan.inkernel_refactor) ? 3 : 1) | (last_tail ? 4 : 0) | (resume_next ? 8 : 0));
+            resume_next = false;
+        }
+        ++n_launch;
+        it = e;
+        epilogue_done = last_tail;
+    }
+    if (!epilogue_done) {
+        ProfScope ps(st, PC_EPILOGUE);
+        hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
+        ++n_launch;
+    }
+    if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
+    // reserved == 1: nothing is waited for.  reserved == 2 with a host report, the split call: everything is enqueued; the caller
+    // does its own host work (output views, bookkeeping) while the GPU runs and then collects the report with lqp_boxqp_forward_finish
+    if (ctl->reserved == 1 || (ctl->reserved == 2 && P.host_report)) {
+        if (stats) fill_stats(stats, plan, ctl->reserved == 1 ? 3 : 4, n_launch);
+        return LQP_OK;
+    }
+    // ---- synchronous call: status block, info and flag words of every problem ----
+    std::vector<int> rep_copy;
+    const int* rep = P.host_report;
+    if (!rep) {                     // (a C caller without pinned memory: three small copies and a stream wait)
+        rep_copy.resize(ST_WORDS + 2 * B);
+        HIP_OK(hipMemcpyAsync(rep_copy.data(), P.status, sizeof(int) * ST_WORDS, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(rep_copy.data() + ST_WORDS, P.info, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(rep_copy.data() + ST_WORDS + B, P.bflags, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        rep = rep_copy.data();
+    }
+    lqp_boxqp_stats local;
+    lqp_boxqp_stats* so = stats ? stats : &local;
+    fill_stats(so, plan, 2, n_launch);
+    rc = collect_report(st, rep, rep == P.host_report, B, max_iters, check, so);
+    if (rc == LQP_ERR_TIMEOUT && !spd && !t_single_wg_lu && !(flags_timeout_loop(rep))) return GU_LU_TIMEOUT;
+    if (rc == LQP_ERR_TIMEOUT && !plan.solo) return GU_SHARED_TIMEOUT;
+    if (rc == LQP_RETRY_LU) return GU_NOT_SPD;
+    return rc;
+}
+
+// ---- host-driven chunks: check segments (mode 1) or persistent launches (mode 2), the status read back after each chunk ----
+template <typename T>
+Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, const lqp_boxqp_ctrl* ctl, lqp_boxqp_stats* stats,
+                    int n_launch) {
+    const int B = P.B, check = P.check_solved, max_iters = ctl->max_iters, ar_iter = P.ar_iter, mode = plan.mode;
+    const bool spd = plan.spd;
+    int rc = LQP_OK;
     int h_status[ST_WORDS];
     memset(h_status, 0, sizeof(h_status));
     int it = 0;
     long long zeroed_upto = kRing;     // check indices [0, zeroed_upto) have clean slots
     bool done = false, singular_checked = false;
     int nfactor_seen = 0;
-    int chunk_cap = knobs().spec_launches;
+    int chunk_cap = plan.spec_launches;
     int fail_index = -1;
     while (it < max_iters && !done) {
         int in_chunk = 0;
@@ -1274,49 +1244,42 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
             // adaptive-rho event at the start of iteration `it` (:237)
             const bool tail_events = spd && mode == 2;       // symmetric path, persistent: events inside the tail kernel
             if (!tail_events && ctl->adaptive_rho && it > 0 && it % ar_iter == 0 && it < ctl->adaptive_rho_max_iter) {
-                const int last_slot = ((it - 1) / check) % kRing;
-                { ProfScope ps(st, PC_RHO);
-                  hipLaunchKernelGGL(k_rho_update<T>, dim3(B), dim3(LQP_NT), 0, st, P, last_slot, 0); }
-                ++n_launch;
-                rc = factor_step(P.status + ST_GATE);
+                rc = enqueue_rho_event(st, P, plan, ((it - 1) / check) % kRing, 0, n_launch);
                 if (rc) return rc;
             }
             // end of this launch
             int e = max_iters;
             const int next_check = ((it + check - 1) / check) * check;
             if (mode == 1) e = std::min(e, next_check + 1);
-            else e = std::min(e, next_check + 1 + (max_checks_per_launch - 1) * check);
+            else e = std::min(e, next_check + 1 + (kMaxChecksPerLaunch - 1) * check);
             if (ctl->adaptive_rho && !(tail_events && it > 0)) {
                 const int a = (it / ar_iter + 1) * ar_iter;
                 if (a < ctl->adaptive_rho_max_iter) e = std::min(e, a);
             }
             if (e <= it) e = it + 1;
-            // counter slots of the checks inside [it, e)
-            const long long c_first = (it + check - 1) / check;        // first check index >= it
-            const long long c_last = (e - 1) / check;                  // last check index <= e-1
-            while (c_last >= zeroed_upto) {
+            const RingSpan s(it, e, check);
+            while (s.c_last >= zeroed_upto) {
                 const int s0 = (int)(zeroed_upto % kRing);
                 HIP_OK(hipMemsetAsync(P.counters + (size_t)s0 * CT_WORDS, 0, sizeof(unsigned int) * CT_WORDS * (kRing / 2), st));
                 zeroed_upto += kRing / 2;
             }
-            const int ctr_base = (int)(c_first % kRing);
-            const int prev_slot = it > 0 ? ((it - 1) / check) % kRing : -1;
             { const bool first = (mode == 2 && it == 0) || mode == 1;
               if (first && mode == 2) {
-                  launch_hot(it, e, ctr_base, prev_slot, 1);
-              } else if (loop_split_seg) {
+                  launch_hot(st, P, plan, e, s.ctr_base);
+              } else if (plan.loop_split_seg) {
                   if constexpr (sizeof(T) == 4) {
                       FwdParams<float> Ps = P;
                       Ps.split_seg = 1;
-                      Ps.seg_prev_slot = prev_slot;
+                      Ps.seg_prev_slot = s.prev_slot;
                       if (it > 0) Ps.eq_in_loop = 0;
                       ProfScope ps(st, PC_LOOP);
-                      hipLaunchKernelGGL(split_fn, dim3(shared_grid(B, 2)), dim3(split_nt), split_lds, st, Ps, it, e, ctr_base);
+                      hipLaunchKernelGGL(plan.split_fn, dim3(shared_grid(B, 2)), dim3(plan.split_nt), plan.split_lds, st, Ps, it, e, s.ctr_base);
                   }
               } else {
                   ProfScope ps(st, first ? PC_LOOP : PC_LOOP_TAIL);
-                  hipLaunchKernelGGL(first ? loop_fn : tail_fn, dim3(B), dim3(first ? loop_nt : LQP_NT), first ? loop_lds : tail_lds, st, P, it, e,
-                                     ctr_base, prev_slot, mode == 2 ? ((tail_events && !first) ? 3 : 1) : 0);
+                  hipLaunchKernelGGL(first ? plan.loop_fn : plan.tail_fn, dim3(B), dim3(first ? plan.loop_nt : LQP_NT),
+                                     first ? plan.loop_lds : plan.tail_lds, st, P, it, e,
+                                     s.ctr_base, s.prev_slot, mode == 2 ? ((tail_events && !first) ? 3 : 1) : 0);
               } }
             ++n_launch;
             ++in_chunk;
@@ -1353,11 +1316,10 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         // A failed factorisation ends or restarts the solve.  With a check hook (strict global stop over batch shards)
         // that decision must be the same on every rank -- a rank that restarted alone would pair its collectives with
         // other checks of its peers -- so the local verdict goes through the hook (SUM over the ranks) first.
-        // returns LQP_OK, an error, or -1: repeat the solve on the LU path
-        auto after_factorisation = [&]() -> int {
+        auto after_factorisation = [&]() -> Attempt {
             int rcf = first_failure(st, P.info, B, &fail_index, P.host_report ? P.host_report + ST_WORDS : nullptr);      // synchronises
             if (rcf == LQP_OK || rcf == LQP_ERR_SINGULAR) { const int r4 = fetch_status(); if (r4) return r4; }
-            if (rcf == LQP_ERR_TIMEOUT && !spd && !t_single_wg_lu) return -2;
+            if (rcf == LQP_ERR_TIMEOUT && !spd && !t_single_wg_lu) return GU_LU_TIMEOUT;
             if (rcf != LQP_OK && rcf != LQP_ERR_SINGULAR) return rcf;
             bool leave_spd = rcf == LQP_ERR_SINGULAR && spd, singular = rcf == LQP_ERR_SINGULAR && !spd;
             if (ctl->check_hook) {
@@ -1373,32 +1335,14 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
                 if (stats) { memset(stats, 0, sizeof(*stats)); stats->fail_index = fail_index; }
                 return LQP_ERR_SINGULAR;
             }
-            return leave_spd ? -1 : LQP_OK;
+            if (leave_spd) return GU_NOT_SPD;
+            return LQP_OK;
         };
-        if (!singular_checked) {
+        if (singular_checked) { const int r4 = fetch_status(); if (r4) return r4; }
+        if (!singular_checked || h_status[ST_NFACTOR] != nfactor_seen) {      // the first factorisation, or an adaptive-rho one ran in this chunk
             singular_checked = true;
-            rc = after_factorisation();
-            if (rc == -1)       // Qs + rho I not positive definite in f32 (on some rank): the LU path takes it
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats,
-                                       ws, ws_bytes, retry | 1);
-            if (rc == -2) {     // a shared LU timed out: once more, one workgroup per matrix
-                SingleWgLu only;
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats, ws, ws_bytes, retry);
-            }
-            if (rc) return rc;
-        } else {
-            { const int r4 = fetch_status(); if (r4) return r4; }
-            if (h_status[ST_NFACTOR] != nfactor_seen) {      // an adaptive-rho refactorisation ran in this chunk
-                rc = after_factorisation();
-                if (rc == -1)
-                    return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats,
-                                           ws, ws_bytes, retry | 1);
-                if (rc == -2) {
-                    SingleWgLu only;
-                    return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats, ws, ws_bytes, retry);
-                }
-                if (rc) return rc;
-            }
+            const Attempt a = after_factorisation();
+            if (a.why != GU_NONE || a.status) return a;
         }
         nfactor_seen = h_status[ST_NFACTOR];
         if (h_status[ST_TIMEOUT]) {
@@ -1406,35 +1350,80 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
             // blockIdx order onto an otherwise idle chip; when something else holds CUs (another stream, RCCL kernels) a pair can
             // wait for a partner that is not resident.  Its spin is bounded (0.5 s), the kernels drain, and the solve is run again
             // from its setup on the loop that needs nobody (degrade, do not fail).
-            if (loop_split_seg && !(retry & 2))
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats, ws, ws_bytes,
-                                       retry | 2);
-            if (!solo)                      // (the same for every other shared schedule: retry bit 2)
-                return forward_impl<T>(st, B, n, m, Q, p, A, b, lb, ub, ctl, rho_in, x, z, u, lams, nus, rho_out, stats, ws, ws_bytes,
-                                       retry | 4);
+            if (plan.loop_split_seg && !(plan.retry & 2)) return GU_SEG_TIMEOUT;
+            if (!plan.solo) return GU_SHARED_TIMEOUT;      // (the same for every other shared schedule)
             return LQP_ERR_TIMEOUT;
         }
         done = h_status[ST_DONE] != 0;
         chunk_cap = std::min(chunk_cap * 2, 64);
     }
-    const int final_iter = done ? h_status[ST_FINAL_ITER] : max_iters - 1;
-
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
     if (stats) {
-        stats->iters = final_iter;
-        stats->n_factor = 1 + h_status[ST_NFACTOR];
-        stats->n_solve = final_iter + 1;
-        stats->n_check = final_iter / check + 1;
-        stats->rho_updated = h_status[ST_RHO_UPDATED];
-        stats->fail_index = -1;
-        stats->n_launch = n_launch;
-        stats->mode_used = mode;
-        stats->linsolve_used = spd ? 2 : 1;
-        stats->factor_launches = spd ? (spd_big_split ? 2 * P.Ks + 2 : spd_split ? (spd_resident ? 3 : P.Ks + 2) : 1) : 2;
-        stats->loop_workgroups = (loop_split && mode == 2) ? loop_np : (loop_split_seg || (loop_np2 && mode == 2)) ? 2 : 1;
-        stats->any_lb = h_status[ST_ANY_LB]; stats->any_ub = h_status[ST_ANY_UB];
+        fill_stats(stats, plan, mode, n_launch);
+        solve_stats(stats, h_status, max_iters, check);
     }
     return LQP_OK;
+}
+
+// sets t_single_wg_lu from enter() to the end of the scope, unless an enclosing scope has set it already
+struct SoloScope {
+    bool on = false;
+    void enter() { if (!t_single_wg_lu) { on = true; t_single_wg_lu = true; } }
+    ~SoloScope() { if (on) t_single_wg_lu = false; }
+};
+
+// carve, then plan / run / decide until an attempt ends the solve.  A remedy is taken at most once: the run functions name a cause
+// only while its remedy is untried (retry bit clear, t_single_wg_lu clear) and in the order LU before bit 2, bit 1 before bit 2;
+// after that the failure is the status (a singular problem, a time-out with nothing shared left to give up)
+template <typename T>
+int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
+                 const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
+                 void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
+                 int retry = 0) {
+    FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
+    if (ws_bytes < L.bytes) return LQP_ERR_WORKSPACE;
+    {
+        FwdParams<T>& P = L.P;
+        P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
+        P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in; P.beta_in = (const T*)ctl->beta_in;
+        P.x = (T*)x; P.z = (T*)z; P.u = (T*)u; P.lams = (T*)lams; P.nus = (T*)nus; P.rho_out = (T*)rho_out;
+        P.scale = ctl->scale; P.bound_flags_in = (const int*)ctl->bound_flags_in;
+        // verbose: the largest primal / dual error of the batch at every check (lqp_boxqp_check_trace)
+        if (ctl->reserved2 & 4) P.vtrace = L.vtrace_area;
+        P.host_report = (int*)ctl->host_report;
+        P.zero_words = (int)(((char*)(P.counters + (size_t)kRing * CT_WORDS) - (char*)P.status) / sizeof(int));
+        P.rho_mode = ctl->rho_mode; P.beta_mode = ctl->beta_mode;
+        P.check_solved = ctl->check_solved < 1 ? 1 : ctl->check_solved;
+        P.adaptive_rho = ctl->adaptive_rho;
+        P.eps_abs = (T)ctl->eps_abs; P.eps_rel = (T)ctl->eps_rel; P.rho_value = (T)ctl->rho_value;
+        P.rho_min = (T)ctl->rho_min; P.rho_max = (T)ctl->rho_max;
+        P.ar_tol = (T)ctl->adaptive_rho_tol; P.ar_inv_tol = (T)(1.0 / ctl->adaptive_rho_tol);
+        P.ar_thr = (T)ctl->adaptive_rho_threshold; P.beta_value = (T)ctl->beta_value;
+        P.ar_iter = ctl->adaptive_rho_iter < 1 ? 1 : ctl->adaptive_rho_iter;
+        P.ar_max = ctl->adaptive_rho_max_iter; P.ring = kRing;
+    }
+    Device d;
+    if (!current_device_cus(&d.dev, &d.cus)) return LQP_ERR_HIP;
+    SoloScope one_wg_lu;
+    for (;;) {
+        const Knobs k = knobs();            // one snapshot of the switches per attempt (a copy: LQP_ENV_NOCACHE re-reads in place)
+        if (retry & 4) one_wg_lu.enter();
+        FwdParams<T> P = L.P;
+        FwdPlan<T> plan;
+        int rc = plan_forward(P, ctl, retry, k, d, plan);
+        if (rc) return rc;
+        int n_launch = 0;
+        rc = enqueue_prologue(st, P, plan, n_launch);
+        if (rc) return rc;
+        const Attempt a = plan.up_front ? run_planned(st, P, plan, ctl, stats, n_launch) : run_chunked(st, P, plan, ctl, stats, n_launch);
+        switch (a.why) {
+        case GU_NONE: return a.status;
+        case GU_NOT_SPD: retry |= 1; break;             // the LU path takes the solve
+        case GU_LU_TIMEOUT: one_wg_lu.enter(); break;   // once more, one workgroup per matrix
+        case GU_SEG_TIMEOUT: retry |= 2; break;         // the one-workgroup loop
+        case GU_SHARED_TIMEOUT: retry |= 4; break;      // once more with nothing shared
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1464,6 +1453,7 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
                   double rho_value, const void* rho_in, void* dQ, void* dp, void* dA, void* db, void* dlb, void* dub,
                   int32_t* fail_index, void* ws, size_t ws_bytes, int linsolve, void* host_report, const int kkt = 0,
                   int phase = 0) {
+    const Knobs k = knobs();            // one snapshot of the switches per call (a copy: LQP_ENV_NOCACHE re-reads in place)
     BwdParams<T> P;
     memset(&P, 0, sizeof(P));
     P.kkt = kkt ? 1 : 0;
@@ -1474,23 +1464,23 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
     // (the words are set to -1 before the first launch, below -- unless the prefactor call has reported into them and this call
     //  solves on its factor)
     bool reset_pending = P.host_report != nullptr;
-    P.early_report = knobs().bwd_early != 0 ? 1 : 0;
+    P.early_report = k.bwd_early != 0 ? 1 : 0;
     const size_t need = carve_backward<T>(ws, B, n, m, P);
     if (ws_bytes < need) return LQP_ERR_WORKSPACE;
-    if (!knobs().bwd_equil) P.bsc = nullptr;
+    if (!k.bwd_equil) P.bsc = nullptr;
     P.g = (const T*)g; P.x = (const T*)x; P.u = (const T*)u; P.lams = (const T*)lams; P.nus = (const T*)nus;
     P.Q = (const T*)Q; P.A = (const T*)A; P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in;
     P.rho_value = (T)rho_value; P.rho_mode = rho_mode;
     P.dQ = (T*)dQ; P.dp = (T*)dp; P.dA = (T*)dA; P.db = (T*)db; P.dlb = (T*)dlb; P.dub = (T*)dub;
     P.dbg = g_lu_dbg;
     // default: solve on the free set only (see k_bwd_build_reduced); LQP_BWD_FULL=1 keeps the full system
-    P.reduced = (knobs().bwd_full && !kkt) ? 0 : 1;
+    P.reduced = (k.bwd_full && !kkt) ? 0 : 1;
     const int* nvec = P.reduced ? P.nred : nullptr;
     // linsolve 2: the caller vouches for a symmetric Q (the forward's symmetric x-update checked it): the
     // reduced system goes through a blocked Cholesky of Q_FF instead of the pivoted LU of the bordered matrix
     bool chol = false;
     if constexpr (sizeof(T) == 4) {
-        chol = P.reduced && linsolve == 2 && knobs().bwd_chol && round_up(n, LQP_NB) / LQP_NB <= SPD_BIGK &&
+        chol = P.reduced && linsolve == 2 && k.bwd_chol && round_up(n, LQP_NB) / LQP_NB <= SPD_BIGK &&
                m <= SPD_MAXM && bwd_chol_lds_bytes(n, m, m >= 3 ? 4 : 2) <= 160 * 1024;
     }
     // the LU form has the same two phases (ABI 11): 1 = free set, reduced system, its pivoted LU and the packed factor -- none of
@@ -1518,11 +1508,11 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
             const int lds = bwd_chol_lds_bytes(n, m, nr4 ? 4 : 2);
             {
                 const int Kmax = round_up(n, LQP_NB) / LQP_NB;
-                P.la_maxk = !knobs().bwd_lookahead ? 0 : (Kmax < SPD_MAXK ? Kmax : SPD_MAXK - 1);
+                P.la_maxk = !k.bwd_lookahead ? 0 : (Kmax < SPD_MAXK ? Kmax : SPD_MAXK - 1);
             }
             auto chol_fn = nr4 ? k_bwd_chol_solve<4> : k_bwd_chol_solve<0>;
 #if LQP_PIV_MFMA
-            if (knobs().spd_f16 != 0 && knobs().bwd_f16 != 0) chol_fn = nr4 ? k_bwd_chol_solve<4, true> : k_bwd_chol_solve<0, true>;
+            if (k.spd_f16 != 0 && k.bwd_f16 != 0) chol_fn = nr4 ? k_bwd_chol_solve<4, true> : k_bwd_chol_solve<0, true>;
 #endif
             int r2 = ensure_lds((const void*)chol_fn, lds);
             if (r2) return r2;
@@ -1538,7 +1528,7 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
     } else if (P.reduced) {
         const int lds = (round_up(n, 8) + LQP_NW + 8) * 4;
         ProfScope ps(st, PC_BWD_BUILD);
-        const int split = (B <= 128 && knobs().split2) ? 2 : 1;
+        const int split = (B <= 128 && k.split2) ? 2 : 1;
         hipLaunchKernelGGL(k_bwd_build_reduced<T>, dim3(B, split), dim3(LQP_NT), lds, st, P);
     } else {
         ProfScope ps(st, PC_BWD_BUILD);
@@ -1563,11 +1553,11 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
         } else if (P.reported) P.lu_reported = 1;
         rc = launch_solve<T>(st, B, P.packed, P.N, P.dest, P.rhs, 1, (size_t)P.Np, 1, 0, nvec);
         if (rc) return rc;
-        if (P.reduced && !kkt && knobs().bwd_refine) {
+        if (P.reduced && !kkt && k.bwd_refine) {
             // one refinement step: residual with the original entries (double accumulation), correction solve
             const int lds = (round_up(n, 8) + round_up(m > 0 ? m : 1, 8)) * (int)sizeof(T) + round_up(n, 8) * 4;
             { ProfScope ps(st, PC_BWD_BUILD);
-              hipLaunchKernelGGL(k_bwd_residual<T>, dim3(B, (B <= 128 && knobs().split2) ? 2 : 1), dim3(LQP_NT), lds, st, P); }
+              hipLaunchKernelGGL(k_bwd_residual<T>, dim3(B, (B <= 128 && k.split2) ? 2 : 1), dim3(LQP_NT), lds, st, P); }
             rc = launch_solve<T>(st, B, P.packed, P.N, P.dest, P.rhs2, 1, (size_t)P.Np, 1, 0, nvec);
             if (rc) return rc;
             P.refine = 1;
@@ -1579,7 +1569,7 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
         rc = ensure_lds((const void*)fn, lds);
         if (rc) return rc;
         ProfScope ps(st, PC_BWD_EPILOGUE);
-        const int slabs = (knobs().epi_slabs < 0 ? (B <= 128 ? 2 : 1) : knobs().epi_slabs);      // row slabs per problem: fill the chip when the batch is small
+        const int slabs = (k.epi_slabs < 0 ? (B <= 128 ? 2 : 1) : k.epi_slabs);      // row slabs per problem: fill the chip when the batch is small
         hipLaunchKernelGGL(fn, dim3(B, slabs), dim3(LQP_NT), lds, st, P);
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
@@ -1587,7 +1577,7 @@ int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void
         int fi = -1;
         // torch.linalg.solve checks info (and waits) too.  The epilogue stores the info words into the caller's pinned
         // memory as it STARTS: the call returns while the gradients are still being written (stream-ordered results)
-        if (P.host_report && knobs().sync_plan != 0) {
+        if (P.host_report && k.sync_plan != 0) {
             rc = wait_report(st, P.host_report, B);
             if (rc) return rc;
             bool gave_up = false;                    // (-7: a hand-off of a shared LU timed out)
@@ -2031,9 +2021,8 @@ int lqp_boxqp_unroll_backward(void* stream, int B, int n, int m, const void* fwd
             : P.Ks == 7 ? k_unroll_sweep_split<7, SPD_MAXM> : P.Ks == 6 ? k_unroll_sweep_split<6, SPD_MAXM> : k_unroll_sweep_split<5, SPD_MAXM>;
         const int lds2 = P.Ks == 8 ? unroll_split_lds_bytes<8>(m) : P.Ks == 7 ? unroll_split_lds_bytes<7>(m)
                        : P.Ks == 6 ? unroll_split_lds_bytes<6>(m) : unroll_split_lds_bytes<5>(m);
-        int dev = 0, cus = 0, per_cu = 0;
-        if (current_device_cus(&dev, &cus) && ensure_lds((const void*)fn2, lds2) == LQP_OK &&
-            blocks_per_cu(&per_cu, fn2, 512, lds2, dev) && per_cu >= 1 && shared_grid(B, 2) <= cus * per_cu) {
+        Device d;
+        if (current_device_cus(&d.dev, &d.cus) && fits(d, fn2, 512, lds2, shared_grid(B, 2))) {
             static std::atomic<unsigned int> run{1u};
             ProfScope ps(st, PC_UNROLL);
             hipLaunchKernelGGL(fn2, dim3((knobs().dbg_loop_absent & 4) ? B : shared_grid(B, 2)), dim3(512), lds2, st, P, U, run.fetch_add(1u));

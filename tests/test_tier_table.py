@@ -20,6 +20,25 @@ def documented_knobs():
     return {m.group(1): m.group(2).strip() for m in re.finditer(r"^\| `(LQP_\w+)` \| ([^|]+) \|", text, re.M)}
 
 
+# documented in docs/KNOBS.md as "(Python)": read by the Python package, not by the library -- no entry in its knob list
+PYTHON_KNOBS = {"LQP_UNROLL_EVENTS", "LQP_UNROLL_NATIVE", "LQP_UNROLL_SCALE_NATIVE"}
+
+
+def library_knobs():
+    """{name: default} of the LQP_KNOBS list in csrc/lqp_amd.hip, from which struct Knobs and read_knobs are generated."""
+    text = open(os.path.join(_lib.CSRC, "lqp_amd.hip")).read()
+    body = text[text.index("#define LQP_KNOBS(X)"):text.index("struct Knobs {")]
+    return {m.group(2): m.group(3) for m in re.finditer(r'^\s*X\((\w+),\s*"(LQP_\w+)",\s*(-?\d+)\)', body, re.M)}
+
+
+def test_knob_list_and_document_agree():
+    """docs/KNOBS.md says it is generated from the library's knob list: the same names with the same defaults in both."""
+    lib, doc = library_knobs(), documented_knobs()
+    assert len(lib) > 40, "LQP_KNOBS list not parsed"
+    assert PYTHON_KNOBS <= set(doc) and not PYTHON_KNOBS & set(lib)
+    assert {k: v for k, v in doc.items() if k not in PYTHON_KNOBS} == lib
+
+
 def uncovered_knobs(rows):
     knobs = documented_knobs()
     forced = {}

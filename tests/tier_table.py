@@ -1,6 +1,6 @@
 """The schedules of the forward solve and of its backward, as data (no GPU needed to import this module).
 
-Every row names one tier the library can select by itself (forward_impl / backward_impl in csrc/lqp_amd.hip) and says how to
+Every row names one tier the library can select by itself (plan_forward / backward_impl in csrc/lqp_amd.hip) and says how to
 reach it: shape, dtype, batch size -- a symbolic expression of the CU count --, control keys and LQP_* environment overrides.
 It also says what the forward must report having run (`sig`, compared with sol["_stats"]) and how many iterations the solve is
 pinned to (`K`).  tests/test_gpu_tiers.py runs every row on the GPU against the CPU oracle: the truth is the oracle in float64,
@@ -165,6 +165,8 @@ ROWS = [
     row("dense_off_n200_f64", 200, 1, 3, dtype="f64", env={"LQP_LOOP_DENSE": "0"}, sig=sig(LU, lw=1, fl=2, mode=2)),
     row("densew_off_n400_f64", 400, 1, 3, dtype="f64", env={"LQP_LOOP_DENSE_W": "0"}, sig=sig(LU, lw=1, fl=2, mode=2)),
     row("dense_nosync_f64", 120, 2, 3, dtype="f64", ctl=dict(sync=False), sig=sig(LU, lw=2, fl=2, mode=2)),
+    row("dense_chunked_f64", 120, 2, 3, dtype="f64", env={"LQP_SYNC_PLAN": "0"}, sig=sig(LU, lw=2, fl=2, mode=2), same=True,
+        why="host-driven chunks enqueue the same kernels on the same data as the schedule enqueued up front"),
     # above 1024 rows: the wide LU (#CUs / B workgroups per matrix) and the big LU (two panel rows per thread)
     row("wide_n1025_f32", 1025, 0, 2, sig=sig(LU, fl=2, mode=2)),
     row("bigl_n1025_f32", 1025, 0, 2, env={"LQP_LU_WIDE": "0"}, sig=sig(LU, fl=2, mode=2), same=True,
