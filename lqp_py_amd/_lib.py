@@ -258,15 +258,20 @@ _pinned_quarantine = []  # report buffers a kernel that is still queued may writ
 _pinned_lock = threading.Lock()      # (the forward's thread and the autograd thread both allocate and release report buffers)
 
 
+def report_done(report):
+    """A report buffer no kernel writes any more (every word was read, or the stream was waited for) goes back to the pool at
+    once.  One that a queued kernel may still write goes through pinned_release instead."""
+    _pinned_free.setdefault(report.numel(), []).append(report)
+
+
 def pinned_release(report):
     """A report buffer goes back to the pool -- at once when nothing can write it any more (every word has arrived: a kernel
     stores each word exactly once, the library set them to -1 before), otherwise when a later allocation finds it complete."""
     with _pinned_lock:
         if bool((report != -1).all()):
-            _pinned_free.setdefault(report.numel(), []).append(report)
+            report_done(report)
         else:
             _pinned_quarantine.append(report)
-
 
 
 def _pinned(words):
@@ -278,7 +283,7 @@ def _pinned(words):
             done = [r for r in _pinned_quarantine if bool((r != -1).all())]
             _pinned_quarantine[:] = [r for r in _pinned_quarantine if not any(r is d for d in done)]
             for rep in done:
-                _pinned_free.setdefault(rep.numel(), []).append(rep)
+                report_done(rep)
         pool = _pinned_free.setdefault(words, [])
         if not pool:
             stride = (words + 15) // 16 * 16                      # (64-byte aligned slices)
@@ -333,7 +338,7 @@ def poll_errors(block=False):
         info = p.info.numpy()
         if (info == -7).any():              # a workgroup of a shared LU (two per matrix / wide) waited for its partner in vain
             for t in getattr(p, "keep", ()):
-                _pinned_free.setdefault(t.numel(), []).append(t)
+                report_done(t)
             raise RuntimeError(f"lqp_py_amd.{p.what} (reported late: the call did not synchronise): a factorisation shared between "
                                f"workgroups timed out waiting for its partner (batch index {int((info == -7).nonzero()[0][0])}; the "
                                "CUs were held by somebody else); the outputs are not valid.  Repeat with control['sync']=True, which "
@@ -344,7 +349,7 @@ def poll_errors(block=False):
         status5 = (int(p.status[5]) or (flags & RP_TIMEOUT)) if p.status is not None else 0
         seen_words = (int(p.status[12]), int(p.status[13])) if p.status is not None else (1, 1)
         for t in getattr(p, "keep", ()):            # (values are read: the pinned buffers can serve the next call)
-            _pinned_free.setdefault(t.numel(), []).append(t)
+            report_done(t)
         if p.bounds_check is not None and p.status is not None:
             assumed, control, mutate, remember = p.bounds_check
             seen = bool(seen_words[0] or seen_words[1])

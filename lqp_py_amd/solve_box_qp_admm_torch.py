@@ -11,9 +11,11 @@ Everything numeric runs in the HIP library (``lqp_boxqp_forward`` /
 control dict -- including its key-name traps and the caller-dict side effect --
 and moves pointers.  Tensors must be on the GPU; there is no CPU fallback.
 """
+import collections
 import ctypes
 import os
 import threading
+import types
 import weakref
 
 import torch
@@ -102,9 +104,8 @@ class SolveBoxQPLayer(torch.autograd.Function):
         prep, ctx.prepared = ctx.prepared, None
         if prep is not None:
             return _fp_backward_run(prep, dl_dz)
-        grads = _fp_backward(dl_dz, x, u, lams, nus, Q, A, lb, ub, ctx.rho, _wanted(ctx.needs_input_grad, A), sync=ctx.sync,
-                             linsolve=ctx.linsolve)
-        return grads
+        return _fp_backward(dl_dz, x, u, lams, nus, Q, A, lb, ub, ctx.rho, _wanted(ctx.needs_input_grad, A), sync=ctx.sync,
+                            linsolve=ctx.linsolve)
 
 
 def _wanted(need, A):
@@ -181,43 +182,25 @@ def _kkt_backward(dl_dz, x, lams, nus, Q, A, lb, ub, flags=None, linsolve=1, wan
     n = Q.shape[1]
     any_lb, any_ub = flags if flags is not None else _finite_bounds(lb, ub)
     if _KKT_NATIVE:
-        lib = _lib.load()
-        B = Q.shape[0]
-        m = get_ncon(A, dim=1)
-        dt = _lib.dtype_code(x)
-        dev, dty = x.device, x.dtype
+        lib, B, m = _lib.load(), Q.shape[0], get_ncon(A, dim=1)
+        dt, dev, dty = _lib.dtype_code(x), x.device, x.dtype
         want = want or dict(dQ=True, dp=True, dA=m > 0, db=m > 0, dlb=True, dub=True)
         gc, xc, lc, nc, Qc, Ac, lbc, ubc = (_lib.norm(t, dty) for t in (dl_dz, x, lams, nus, Q, A, lb, ub))
-        mk = lambda on, shape: torch.empty(shape, dtype=dty, device=dev) if on else None
-        dQ, dp = mk(want['dQ'], (B, n, n)), mk(want['dp'], (B, n, 1))
-        dA, db = mk(want['dA'] and m > 0, (B, m, n)), mk(want['db'] and m > 0, (B, m, 1))
         # One-sided and unbounded batches run the same kernels (round 5): the reference keeps BOTH halves of G = [-I; I] whenever any
         # bound is finite (:446-452), an infinite bound has an infinite slack, and lam / inf = 0 takes its rows out of the reduced
         # system exactly.  Only the reference's bookkeeping of dl_dh differs (:573-584): lower bounds only -> dlb; upper bounds only
         # -> dub = dl_dh[:n], the LOWER half (all zeros: its quirk, kept); no bounds -> neither.
         only_lb, only_ub = any_lb and not any_ub, any_ub and not any_lb
-        dlb = mk((want['dlb'] and any_lb) or (want['dub'] and only_ub), (B, n, 1))
-        dub = mk(want['dub'] and any_lb and any_ub, (B, n, 1))
+        dQ, dp, dA, db, dlb, dub = _grad_outputs(
+            (want['dQ'], want['dp'], want['dA'], want['db'], (want['dlb'] and any_lb) or (want['dub'] and only_ub),
+             want['dub'] and any_lb and any_ub), B, n, m, dty, dev)
         stream = _lib.current_stream_handle(dev)
         ws = _lib.workspace(dev, lib.lqp_boxqp_backward_fp_workspace_bytes(dt, B, n, m), "bwd", stream)
-        fail = ctypes.c_int32(-1)
-        report = _lib.host_report(B)
-        with _lib.on_device(dev):
-            st = lib.lqp_boxqp_backward_kkt(ctypes.c_void_p(stream), dt, B, n, m, _lib.ptr(gc), _lib.ptr(xc), _lib.ptr(lc),
-                                            _lib.ptr(nc), _lib.ptr(Qc), _lib.ptr(Ac), _lib.ptr(lbc), _lib.ptr(ubc),
-                                            _lib.ptr(dQ), _lib.ptr(dp), _lib.ptr(dA), _lib.ptr(db), _lib.ptr(dlb), _lib.ptr(dub),
-                                            ctypes.byref(fail) if sync else None, _lib.ptr(ws), ws.numel(), int(linsolve),
-                                            ctypes.c_void_p(report.data_ptr()))
-        if st == 3:
-            raise RuntimeError(f"lqp_py_amd.torch_solve_box_qp_grad_kkt: the input matrix is singular (batch index {fail.value})")
-        _lib.check(st, "torch_solve_box_qp_grad_kkt")
-        try:
-            _lib.poll_errors()
-        finally:
-            if not sync:
-                _lib.defer_check("SolveBoxQP.backward", dev, report, B, False)
-            else:
-                _lib._pinned_free.setdefault(report.numel(), []).append(report)
+        fail, report = ctypes.c_int32(-1), _lib.host_report(B)
+        args = (ctypes.c_void_p(stream), dt, B, n, m, _lib.ptr(gc), _lib.ptr(xc), _lib.ptr(lc), _lib.ptr(nc), _lib.ptr(Qc), _lib.ptr(Ac),
+                _lib.ptr(lbc), _lib.ptr(ubc), _lib.ptr(dQ), _lib.ptr(dp), _lib.ptr(dA), _lib.ptr(db), _lib.ptr(dlb), _lib.ptr(dub),
+                ctypes.byref(fail) if sync else None, _lib.ptr(ws), ws.numel(), int(linsolve), ctypes.c_void_p(report.data_ptr()))
+        _backward_call(lib.lqp_boxqp_backward_kkt, args, "torch_solve_box_qp_grad_kkt", fail, report, dev, B, sync)
         if only_ub:
             dlb, dub = None, (-dlb if want['dub'] else None)
         elif only_lb:
@@ -365,17 +348,16 @@ def resolve_control(control, n_x):
     )
 
 
-def _rho_argument(rho, B, like):
-    """-> (mode, scalar value, device tensor or None): 0 auto, 1 scalar, 2 one value per problem"""
-    if rho is None:
+def _per_problem_argument(name, example, value, B, like):
+    """-> (mode, scalar value, device tensor or None): 0 the default rule (rho: auto, beta: the quantile rule), 1 scalar,
+    2 one value per problem (the reference broadcasts a (B,1) beta against D (B,n), :171-175)"""
+    if value is None:
         return 0, 0.0, None
-    if not torch.is_tensor(rho):
-        return 1, float(rho), None
-    if rho.numel() == 1:
-        return 1, float(rho), None
-    if rho.numel() != B:
-        _bad("a rho tensor must hold one value per problem, e.g. shape (B,1,1)")
-    return 2, 0.0, rho.detach().to(device=like.device, dtype=like.dtype).reshape(B).contiguous()
+    if not torch.is_tensor(value) or value.numel() == 1:
+        return 1, float(value), None
+    if value.numel() != B:
+        _bad(f"a {name} tensor must hold one value per problem, e.g. shape {example}")
+    return 2, 0.0, value.detach().to(device=like.device, dtype=like.dtype).reshape(B).contiguous()
 
 
 _LINSOLVE = {'auto': 0, 'lu': 1, 'spd': 2, 0: 0, 1: 1, 2: 2}
@@ -387,272 +369,287 @@ def _bad(msg):
     raise ValueError("lqp_py_amd: " + msg)
 
 
-def _beta_argument(beta, B, like):
-    """-> (mode, scalar value, device tensor or None): 0 quantile rule, 1 scalar, 2 one value per problem
-    (the reference broadcasts a (B,1) tensor against D (B,n), :171-175)"""
-    if beta is None:
-        return 0, 0.0, None
-    if not torch.is_tensor(beta):
-        return 1, float(beta), None
-    if beta.numel() == 1:
-        return 1, float(beta), None
-    if beta.numel() != B:
-        _bad("a beta tensor must hold one value per problem, e.g. shape (B,1)")
-    return 2, 0.0, beta.detach().to(device=like.device, dtype=like.dtype).reshape(B).contiguous()
-
-
-def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residuals=False, check_hook=None, mutate=False,
-                   holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False):
-    """bounds: (any_lb, any_ub) when the caller KNOWS them (a shard of a larger batch with host-side flags); None: found
-    on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
-    nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound)."""
-    # (what stands between the call and its first kernel launch is the forward time of a step that starts from an idle
-    #  queue -- experiment_1's protocol: errors of EARLIER calls are polled after this one is enqueued, the outputs are
-    #  one allocation)
-    _lib.require_gpu(Q, p, A, b, lb, ub)
-    lib = _lib.load()
-    B, n = Q.shape[0], p.shape[1]
-    m = get_ncon(A, dim=1)
-    dt = _lib.dtype_code(p)
-    dev = p.device
-    if check_hook is not None:
-        sync = True                                   # the strict global stop is host-driven (one launch per check)
-    known = bounds is not None
-    owner = control.get('_owner') or control          # (lqp_py_amd.dist hands the layer a copy of the caller's dict)
-    flags_dev = control.get('_bound_flags_dev')       # (lqp_py_amd.dist: device-side flags of the whole batch)
-    if known:
-        any_bound = bool(bounds[0] or bounds[1])
-    else:
-        any_bound = _assume_any_bound(holder, owner, sync)
-        if any_bound is None:                         # first solve of this layer
-            if sync:
-                any_bound = True
-            elif flags_dev is not None:
-                # a shard: the flags of the WHOLE batch decide (one host read, the same answer on every rank -- a shard
-                # without any finite bound inside a batch that has some must enqueue the schedule its peers enqueue)
-                any_bound = bool(flags_dev.max().item())
-            else:
-                any_bound = any(_finite_bounds(lb, ub))
-    # the control struct of the last call with the same settings is reused (resolving ~25 keys and filling the struct
-    # costs ~15 us, in front of the first kernel launch); anything that holds a tensor (per-problem rho / beta) is
-    # resolved afresh
+def _control_struct(control, B, n, like, any_bound, sync, cacheable):
+    """-> (resolved dict, rho, lqp_boxqp_ctrl, rho tensor, beta tensor).  The struct of the last call with the same settings
+    is reused (resolving ~25 keys and filling it costs ~15 us, in front of the first kernel launch); anything that holds a
+    tensor (per-problem rho / beta) is resolved afresh.  The fields of one CALL (reserved, reserved2, bound_flags_in,
+    host_report, check_hook) are not set here: _forward_attempt writes them, into a cached struct too."""
     ckey, cached = None, None
-    cache = _ctl_cache.__dict__.setdefault('d', {})   # (per thread: the struct is written to below)
-    if check_hook is None:
+    cache = _ctl_cache.__dict__.setdefault('d', {})   # (per thread: every call writes to the struct)
+    if cacheable:
         # (the dict of the last call, unchanged -- one C-level comparison of two dicts -- skips building and hashing the key)
         last = _ctl_cache.__dict__.get('last')
         try:
-            same = last is not None and last[0] is control and last[2] == (n, any_bound, sync, p.dtype) and last[1] == control
+            same = last is not None and last[0] is control and last[2] == (n, any_bound, sync, like.dtype) and last[1] == control
         except Exception:                             # (a value that does not compare to a truth value: a tensor)
             same = False
         if same:
-            ckey, cached = last[3], last[4]
+            return last[4] + (None, None)
+        try:
+            ckey = (tuple(kv for kv in control.items() if kv[0][0] != '_'), n, bool(any_bound), bool(sync), like.dtype)
+            cached = cache.get(ckey)
+        except Exception:                             # an unhashable value, a key that is not a string: no caching
+            ckey = None
+        if cached is not None:
+            _ctl_cache.last = (control, dict(control), (n, any_bound, sync, like.dtype), ckey, cached)
+            return cached + (None, None)
+    r = resolve_control(control, n)
+    rho = r['rho'] if any_bound else 0                # (no finite bound: one iteration solves it, :157-158)
+    rho_mode, rho_value, rho_tensor = _per_problem_argument('rho', '(B,1,1)', rho, B, like)
+    beta_mode, beta_value, beta_tensor = _per_problem_argument('beta', '(B,1)', r['beta'], B, like)
+    if r['linsolve'] not in _LINSOLVE:
+        _bad("control['linsolve'] must be 'auto', 'lu' or 'spd'")
+    ctl = _lib.BoxQPCtrl(
+        linsolve=_LINSOLVE[r['linsolve']], max_iters=int(r['max_iters']), check_solved=int(r['check_solved']),
+        adaptive_rho=int(r['adaptive_rho']), adaptive_rho_iter=int(r['adaptive_rho_iter']),
+        adaptive_rho_max_iter=int(r['adaptive_rho_max_iter']), scale=int(r['scale']),
+        any_lb=int(any_bound), any_ub=int(any_bound), rho_mode=rho_mode, beta_mode=beta_mode, launch_mode=int(r['launch_mode']),
+        eps_abs=float(r['eps_abs']), eps_rel=float(r['eps_rel']), rho_value=rho_value,
+        rho_min=float(r['rho_min']), rho_max=float(r['rho_max']), adaptive_rho_tol=float(r['adaptive_rho_tol']),
+        adaptive_rho_threshold=float(r['adaptive_rho_threshold']), beta_value=beta_value,
+        beta_in=None if beta_tensor is None else beta_tensor.data_ptr())
+    if ckey is not None and rho_tensor is None and beta_tensor is None and not any(torch.is_tensor(v) for v in control.values()):
+        if len(cache) > 64:
+            cache.clear()
+        cache[ckey] = (r, rho, ctl)
+    return r, rho, ctl, rho_tensor, beta_tensor
+
+
+def _output_block(B, n, m, dtype, dev):
+    """-> (x, the six output addresses lqp_boxqp_forward takes, views).  x is its own allocation (a caller that collects
+    solutions across batches keeps n floats per problem, not the iterates and duals); z, u, lams, nus, rho share one, each
+    16-byte aligned.  Only ADDRESSES are needed in front of the launches: views() -> (z, u, lams, nus, rho) is for afterwards
+    (everything in front is host time the GPU idles through in experiment_1's protocol)."""
+    n4, m4 = (n + 3) // 4 * 4, (m + 3) // 4 * 4
+    sizes = (B * n4, B * n4, 2 * B * n4, B * m4, 4 * B)
+    x = torch.empty((B, n, 1), dtype=dtype, device=dev)
+    buf = torch.empty((B * (4 * n4 + m4 + 4),), dtype=dtype, device=dev)
+    es, o_z = buf.element_size(), buf.data_ptr()
+    o_u, o_l, o_nu, o_rho = (o_z + sum(sizes[:k]) * es for k in (1, 2, 3, 4))
+
+    def views():
+        parts = buf.split_with_sizes(sizes)
+        if n4 == n:
+            z, u, lams = parts[0].view(B, n, 1), parts[1].view(B, n, 1), parts[2].view(B, 2 * n, 1)
         else:
-            try:
-                ckey = (tuple(kv for kv in control.items() if kv[0][0] != '_'), n, bool(any_bound), bool(sync), p.dtype)
-                cached = cache.get(ckey)
-            except Exception:                         # an unhashable value, a key that is not a string: no caching
-                ckey = None
-            if cached is not None:
-                _ctl_cache.last = (control, dict(control), (n, any_bound, sync, p.dtype), ckey, cached)
-    if cached is not None:
-        r, rho, ctl = cached
-        rho_mode, rho_value, rho_tensor, beta_tensor = ctl.rho_mode, ctl.rho_value, None, None
-        ctl.bound_flags_in = None if flags_dev is None else flags_dev.data_ptr()
-        ctl.host_report = None
-    else:
-        r = resolve_control(control, n)
-        rho = r['rho']
-        if not any_bound:
-            rho = 0                                     # one iteration solves it (:157-158)
-        rho_mode, rho_value, rho_tensor = _rho_argument(rho, B, p)
-        beta_mode, beta_value, beta_tensor = _beta_argument(r['beta'], B, p)
-        if r['linsolve'] not in _LINSOLVE:
-            _bad("control['linsolve'] must be 'auto', 'lu' or 'spd'")
-        ctl = _lib.BoxQPCtrl(
-            linsolve=_LINSOLVE[r['linsolve']],
-            max_iters=int(r['max_iters']), check_solved=int(r['check_solved']),
-            adaptive_rho=int(r['adaptive_rho']), adaptive_rho_iter=int(r['adaptive_rho_iter']),
-            adaptive_rho_max_iter=int(r['adaptive_rho_max_iter']), scale=int(r['scale']),
-            any_lb=int(any_bound), any_ub=int(any_bound), rho_mode=rho_mode,
-            beta_mode=beta_mode, launch_mode=int(r['launch_mode']),
-            # 1: pipelined (nothing waits); 2: split synchronous call -- enqueue, build the output views while the GPU runs,
-            # then lqp_boxqp_forward_finish polls the report (include/lqp_amd.h)
-            reserved=(2 if (check_hook is None and _SYNC_SPLIT) else 0) if sync else 1,
-            eps_abs=float(r['eps_abs']), eps_rel=float(r['eps_rel']), rho_value=rho_value,
-            rho_min=float(r['rho_min']), rho_max=float(r['rho_max']),
-            adaptive_rho_tol=float(r['adaptive_rho_tol']),
-            adaptive_rho_threshold=float(r['adaptive_rho_threshold']),
-            beta_value=beta_value, beta_in=None if beta_tensor is None else beta_tensor.data_ptr(),
-            bound_flags_in=None if flags_dev is None else flags_dev.data_ptr())
-        if ckey is not None and rho_tensor is None and beta_tensor is None and not any(torch.is_tensor(v) for v in control.values()):
-            if len(cache) > 64:
-                cache.clear()
-            cache[ckey] = (r, rho, ctl)
+            z, u, lams = (parts[k][:B * n * w].view(B, n * w, 1) for k, w in ((0, 1), (1, 1), (2, 2)))
+        return z, u, lams, (parts[3][:B * m].view(B, m, 1) if m > 0 else None), parts[4][:B]
+    return x, (x.data_ptr(), o_z, o_u, o_l, o_nu if m > 0 else None, o_rho), views
+
+
+def _strict_stop_hook(check_hook, ws):
+    """-> (the C callback, the list its exceptions land in).  check_hook(counters) all-reduces (SUM) the four uint32 words of
+    a check -- {not optimal, arrivals, wants rho, ratio trigger} -- in place; it gets a tensor VIEW of the workspace at the
+    device address the library names.  check_index -1: the same reduction over a factorisation's failure vote (include/lqp_amd.h)"""
+    errors = []
+
+    def _c_hook(_user, _stream, counters_ptr, check_index):
+        try:
+            off = int(counters_ptr) - ws.data_ptr()
+            check_hook(ws[off:off + 16].view(torch.int32), int(check_index))
+            return 0
+        except Exception as exc:                      # never let an exception cross the C frame
+            errors.append(exc)
+            return 1
+    return _lib.CHECK_HOOK(_c_hook), errors
+
+
+# What one attempt of a forward solve runs on, and all that a retry rule changes.  bounds: (any_lb, any_ub) when KNOWN; None: assumed
+# from the layer's last solve, compared with the device's flags.  one_call: the library waits itself, nothing shared between workgroups.
+_Try = collections.namedtuple("_Try", "control bounds one_call")
+# What _forward_decide makes of an attempt.  next: the _Try to repeat with; error: what to raise; neither: done.  release, how the report
+# buffer goes back: 'now' (the split wait read every word), 'wait' (kernels of a failed call may still write it: wait for the stream
+# first), 'tail' (a good call: poll the earlier calls' errors, then defer the report or pool it).
+_Verdict = collections.namedtuple("_Verdict", "next error release void_prepared remember", defaults=(None, None, 'wait', False, None))
+
+
+class _Outcome(types.SimpleNamespace):
+    """One trip through the library, not interpreted.  status: of lqp_boxqp_forward, or of lqp_boxqp_forward_finish when the call was
+    split (split_wait); any_bound: what it was enqueued for, known: whether that was given or assumed; dims = (dt, B, n, m)."""
+
+
+def _forward_decide(out, att, owner, look):
+    """Every retry rule of the forward solve, in order of precedence; -> _Verdict.  A pure function (no torch, no library): `look`
+    () -> (any_lb, any_ub) is called only where a rule needs the bounds themselves.  No rule fires twice in one call, by
+    construction: one_call disables the first, linsolve='lu' the second, known bounds the last two, and one_call does not
+    outlive the attempt it was set for.  The first two are the retries the library makes by itself inside a one-call solve
+    (forward_impl, csrc/lqp_amd.hip): status 5 <-> reserved2 bit 1, status 7 <-> linsolve 'lu'."""
+    st, stats = out.status, out.stats
+    if out.split_wait and st == 5 and not att.one_call:
+        # a kernel that shares its problem with a partner workgroup gave up waiting for it (bounded spins; something else
+        # held the CUs): one workgroup per matrix, the loop that needs nobody, instead of failing (ADVICE r4).  That repeat
+        # has no window (while_running) of its own: what this attempt's window prepared is void
+        return _Verdict(next=att._replace(one_call=True), release='now', void_prepared=True)
+    if out.split_wait and st == 7:
+        # the matrix left the symmetric x-update (not symmetric, or Qs + rho I not positive definite in f32): the
+        # reference's algorithm -- the pivoted LU -- takes the solve, as a one-call synchronous forward does by itself
+        return _Verdict(next=_Try(dict(att.control, linsolve='lu', _owner=owner), att.bounds, False), release='now')
+    if out.hook_error:
+        return _Verdict(error=out.hook_error[0])
+    if st == 3:
+        if not out.known and not out.any_bound:
+            # the rho = 0 one-shot was enqueued on the ASSUMPTION that this batch, like the layer's last one, holds no
+            # finite bound.  If it does, the reference would have run its ADMM loop with rho > 0 (:157-158 do not apply),
+            # whose KKT matrix can be regular where [[Q, A^T], [A, 0]] is not (Q = 0: an LP, zero rows): look (cold path)
+            has = look()
+            if has[0] or has[1]:
+                return _Verdict(next=att._replace(bounds=has, one_call=False), remember=True)
+        # the reference's torch.linalg.lu_factor raises on an exactly singular KKT matrix (:215)
+        return _Verdict(error=RuntimeError(f"lqp_py_amd.torch_solve_box_qp: LU factorisation hit an exactly zero pivot "
+                                           f"(batch index {stats.fail_index}); the KKT matrix is singular"))
+    try:
+        _lib.check(st, "torch_solve_box_qp")
+    except RuntimeError as exc:
+        return _Verdict(error=exc)
+    if stats.mode_used == 3 or out.known or stats.any_lb < 0:
+        return _Verdict(release='tail')
+    # the device looked at the bounds: did the schedule we enqueued fit them?
+    seen = bool(stats.any_lb or stats.any_ub)
+    if seen == out.any_bound:
+        return _Verdict(release='tail', remember=seen)
+    return _Verdict(next=att._replace(bounds=(bool(stats.any_lb), bool(stats.any_ub)), one_call=False), release='tail', remember=seen)
+
+
+def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running):
+    """One trip through the library on `att` (a _Try): settle the assumption, fetch the control struct, allocate, launch, make
+    the views and run the caller's window while the GPU works, wait.  -> _Outcome, for _forward_decide to read.  What stands
+    between entry and the first kernel launch is the forward time of a step that starts from an idle queue (experiment_1's
+    protocol): errors of EARLIER calls are polled after this one is enqueued, the outputs are one allocation."""
+    Q, p, A, b, lb, ub = qp
+    control, bounds, one_call = att
+    lib, dev = _lib.load(), p.device
+    dt, B, n, m = _lib.dtype_code(p), Q.shape[0], p.shape[1], get_ncon(A, dim=1)
+    flags_dev = control.get('_bound_flags_dev')       # (lqp_py_amd.dist: device-side flags of the whole batch)
+    known = bounds is not None
+    any_bound = bool(bounds[0] or bounds[1]) if known else _assume_any_bound(holder, owner, sync)
+    if any_bound is None:                             # first solve of this layer: a call that waits can repeat itself
+        # (a shard: the flags of the WHOLE batch decide -- one host read, the same answer on every rank: a shard without any
+        #  finite bound inside a batch that has some must enqueue the schedule its peers enqueue)
+        any_bound = True if sync else bool(flags_dev.max().item()) if flags_dev is not None else any(_finite_bounds(lb, ub))
+    r, rho, ctl, rho_tensor, beta_tensor = _control_struct(control, B, n, p, any_bound, sync, check_hook is None)
     # 1: pipelined (nothing waits); 2: split synchronous call -- enqueue, build the output views while the GPU runs, then
     # lqp_boxqp_forward_finish polls the report (include/lqp_amd.h); 0: the library waits itself (and repeats by itself on the
-    # schedule that needs no partner when a shared kernel timed out: one_call, below)
+    # schedule that needs no partner when a shared kernel timed out: one_call).  reserved2 -- bit 0: keep the factor in the
+    # workspace (unroll: private_ws); bit 1: nothing shared between workgroups (one_call); bit 2: keep the check trace
     ctl.reserved = (2 if (check_hook is None and _SYNC_SPLIT and not one_call) else 0) if sync else 1
-    Qc, pc, Ac, bc, lbc, ubc = (_lib.norm(t, p.dtype) for t in (Q, p, A, b, lb, ub))
-    hook_c = None
+    ctl.reserved2 = (1 if keep_factor else 0) | (2 if one_call else 0) | (4 if r['verbose'] else 0)
+    ctl.bound_flags_in = None if flags_dev is None else flags_dev.data_ptr()
+    Qc, pc, Ac, bc, lbc, ubc = (_lib.norm(t, p.dtype) for t in qp)
     # status / info words arrive in pinned host memory, stored there by the forward's last kernel (include/lqp_amd.h:
     # host_report): an un-synchronised call reads them later, a synchronous one right after its wait -- no copies either way
-    report = _lib.host_report(_lib.ST_WORDS + 2 * B)
+    report, stats = _lib.host_report(_lib.ST_WORDS + 2 * B), _lib.BoxQPStats()
     ctl.host_report = report.data_ptr()
-    stats = _lib.BoxQPStats()
-
-    # x is its own allocation (a caller that collects solutions across batches keeps n floats per problem, not the
-    # iterates and duals); z, u, lams, nus, rho share one.  Only ADDRESSES are needed in front of the launches -- the views
-    # are made after the library call has enqueued them (everything here is host time the GPU idles through in
-    # experiment_1's protocol)
-    n4 = (n + 3) // 4 * 4                  # (every output starts 16-byte aligned)
-    m4 = (m + 3) // 4 * 4
-    x = torch.empty((B, n, 1), dtype=p.dtype, device=dev)
-    outbuf = torch.empty((B * (4 * n4 + m4 + 4),), dtype=p.dtype, device=dev)
-    es = outbuf.element_size()
-    base = outbuf.data_ptr()
-    o_x, o_z, o_u, o_l = x.data_ptr(), base, base + B * n4 * es, base + 2 * B * n4 * es
-    o_nu, o_rho = base + 4 * B * n4 * es, base + (4 * B * n4 + B * m4) * es
+    x, addresses, views = _output_block(B, n, m, p.dtype, dev)
     nbytes = _ws_bytes.get((dt, B, n, m))
     if nbytes is None:
         nbytes = _ws_bytes[(dt, B, n, m)] = lib.lqp_boxqp_forward_workspace_bytes(dt, B, n, m)
     stream = _lib.current_stream_handle(dev)
-    # (private_ws / keep_factor: the unroll mode keeps the solve's workspace -- factor included -- for its backward)
     ws = private_ws if private_ws is not None else _lib.workspace(dev, nbytes, "fwd", stream)
-    ctl.reserved2 = (1 if keep_factor else 0) | (2 if one_call else 0) | (4 if r['verbose'] else 0)      # (bit 1: nothing shared between workgroups, see one_call; bit 2: keep the check trace)
+    hook_c = hook_error = None
     if check_hook is not None:
-        # check_hook(counters) all-reduces (SUM) the four uint32 words of a check -- {not optimal, arrivals, wants rho,
-        # ratio trigger} -- in place; it gets a tensor VIEW of the workspace at the device address the library names.
-        # check_index -1: the same reduction over the failure vote of a factorisation (include/lqp_amd.h)
-        hook_error = []
-
-        def _c_hook(_user, _stream, counters_ptr, check_index):
-            try:
-                off = int(counters_ptr) - ws.data_ptr()
-                check_hook(ws[off:off + 16].view(torch.int32), int(check_index))
-                return 0
-            except Exception as exc:                  # never let an exception cross the C frame
-                hook_error.append(exc)
-                return 1
-        hook_c = _lib.CHECK_HOOK(_c_hook)
+        hook_c, hook_error = _strict_stop_hook(check_hook, ws)      # (hook_c: alive until the library has returned)
         ctl.check_hook = hook_c
     with _lib.on_device(dev):
         st = lib.lqp_boxqp_forward(ctypes.c_void_p(stream), dt, B, n, m,
                                    _lib.ptr(Qc), _lib.ptr(pc), _lib.ptr(Ac), _lib.ptr(bc), _lib.ptr(lbc), _lib.ptr(ubc),
-                                   ctypes.byref(ctl), _lib.ptr(rho_tensor),
-                                   o_x, o_z, o_u, o_l, o_nu if m > 0 else None, o_rho,
+                                   ctypes.byref(ctl), _lib.ptr(rho_tensor), *addresses,
                                    ctypes.byref(stats), _lib.ptr(ws), ws.numel())
     split_wait = st == 0 and stats.mode_used == 4
-    parts = outbuf.split_with_sizes((B * n4, B * n4, 2 * B * n4, B * m4, 4 * B))
-    if n4 == n:
-        z, u, lams = parts[0].view(B, n, 1), parts[1].view(B, n, 1), parts[2].view(B, 2 * n, 1)
-    else:
-        z, u, lams = (parts[k][:B * n * (2 if k == 2 else 1)].view(B, n * (2 if k == 2 else 1), 1) for k in range(3))
-    nus = parts[3][:B * m].view(B, m, 1) if m > 0 else None
-    rho_out = parts[4][:B]
+    z, u, lams, nus, rho_out = views()
     if split_wait:
         if while_running is not None:
             while_running(dict(x=x, u=u, lams=lams, nus=nus, rho_out=rho_out.view(B, 1, 1)), int(stats.linsolve_used))
         # (the views above were made while the GPU ran; now the report: polled in pinned memory, no stream wait)
         st = lib.lqp_boxqp_forward_finish(ctypes.c_void_p(stream), B, ctl.max_iters, ctl.check_solved,
                                           ctypes.c_void_p(report.data_ptr()), ctypes.byref(stats))
-        if st == 5 and not one_call:
-            # a kernel that shares its problem with a partner workgroup gave up waiting for it (bounded spins; something else
-            # held the CUs): the one-call form of the synchronous forward degrades by itself -- one workgroup per matrix, the
-            # loop that needs nobody -- instead of failing (ADVICE r4)
-            _lib._pinned_free.setdefault(report.numel(), []).append(report)
-            if while_running is not None:
-                while_running(None, 0)
-            return _forward_solve(Q, p, A, b, lb, ub, control, bounds=bounds, sync=sync, residuals=residuals, check_hook=check_hook,
-                                  mutate=mutate, holder=holder, private_ws=private_ws, keep_factor=keep_factor,
-                                  while_running=while_running, one_call=True)
-        if st == 7:
-            # the matrix left the symmetric x-update (not symmetric, or Qs + rho I not positive definite in f32): the
-            # reference's algorithm -- the pivoted LU -- takes the solve, as a one-call synchronous forward does by itself
-            _lib._pinned_free.setdefault(report.numel(), []).append(report)
-            return _forward_solve(Q, p, A, b, lb, ub, dict(control, linsolve='lu', _owner=owner), bounds=bounds, sync=sync,
-                                  residuals=residuals, check_hook=check_hook, mutate=mutate, holder=holder, private_ws=private_ws,
-                                  keep_factor=keep_factor, while_running=while_running)
-    if st != 0 or (check_hook is not None and hook_error):
-        # kernels of the failed call may still be in flight, and they write their report into `report`: wait before the
-        # pinned buffer goes back to the pool (cold path)
-        torch.cuda.current_stream(dev).synchronize()
-        _lib._pinned_free.setdefault(report.numel(), []).append(report)
-    if check_hook is not None and hook_error:
-        raise hook_error[0]
-    if st == 3:
-        if not known and not any_bound:
-            # the rho = 0 one-shot was enqueued on the ASSUMPTION that this batch, like the layer's last one, holds no
-            # finite bound.  If it does, the reference would have run its ADMM loop with rho > 0 (:157-158 do not apply),
-            # whose KKT matrix can be regular where [[Q, A^T], [A, 0]] is not (Q = 0: an LP, zero rows): look (cold path)
-            has = _finite_bounds(lb, ub)
-            if has[0] or has[1]:
-                _remember_any_bound(holder, owner, True)
-                return _forward_solve(Q, p, A, b, lb, ub, control, bounds=has, sync=sync, residuals=residuals,
-                                      check_hook=check_hook, mutate=mutate, holder=holder, private_ws=private_ws,
-                                      keep_factor=keep_factor, while_running=while_running)
-        # the reference's torch.linalg.lu_factor raises on an exactly singular KKT matrix (:215)
-        raise RuntimeError(f"lqp_py_amd.torch_solve_box_qp: LU factorisation hit an exactly zero pivot "
-                           f"(batch index {stats.fail_index}); the KKT matrix is singular")
-    _lib.check(st, "torch_solve_box_qp")
-    try:
-        _lib.poll_errors()            # (an error of an EARLIER un-synchronised call surfaces here: this call is enqueued,
-    finally:                          #  its own report is queued behind the poll -- it is never raised at its own call)
-        if stats.mode_used == 3:      # nothing was waited for: the report is read once the stream has passed the call
-            _lib.defer_check("SolveBoxQP.forward", dev, report, B, True,
-                             bounds_check=None if known else (
-                                 any_bound, owner, mutate, lambda _c, seen: _remember_any_bound(holder, owner, seen)))
-        elif report is not None:      # (the library waited after all: nothing left to report late)
-            _lib._pinned_free.setdefault(report.numel(), []).append(report)
-            report = None
-    if stats.mode_used != 3 and not known and stats.any_lb >= 0:
-        # the device looked at the bounds: did the schedule we enqueued fit them?
-        seen = bool(stats.any_lb or stats.any_ub)
-        _remember_any_bound(holder, owner, seen)
-        if seen != any_bound:
-            return _forward_solve(Q, p, A, b, lb, ub, control, bounds=(bool(stats.any_lb), bool(stats.any_ub)), sync=sync,
-                                  residuals=residuals, check_hook=check_hook, mutate=mutate, holder=holder, private_ws=private_ws,
-                                  keep_factor=keep_factor, while_running=while_running)
-    if mutate and not any_bound:
-        control['rho'] = owner['rho'] = 0          # written into the CALLER's dict, as the reference does (:37-38)
-    if r['verbose']:
-        # the reference prints these three lines at every check (:289-294); here the loop runs on the device without the host, so the
-        # trace it kept -- the largest primal and dual error of the batch per check -- is printed once the solve is over
-        n_chk = int(stats.n_check) if stats.n_check >= 0 else int(r['max_iters'] - 1) // int(r['check_solved']) + 1
-        tr = torch.empty((2 * max(min(n_chk, 2048), 1),), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.lqp_boxqp_check_trace(_lib.stream_ptr(dev), dt, B, n, m, _lib.ptr(ws), ws.numel(), min(n_chk, 2048), _lib.ptr(tr)),
-                       "check_trace")
-        trh = tr.cpu()
-        it_last = int(stats.iters) if stats.iters >= 0 else None
-        for c in range(min(n_chk, 2048)):
-            it_c = c * int(r['check_solved'])
-            if it_last is not None and it_c > it_last:
-                break
-            if stats.iters < 0 and float(trh[2 * c]) == 0.0 and float(trh[2 * c + 1]) == 0.0 and c > 0:
-                break                                      # (a pipelined call: the checks that never ran left no mark)
-            print(f'iteration = {it_c}')
-            print(f'|| primal_error|| = {float(trh[2 * c]):.10f}')
-            print(f'|| dual_error|| = {float(trh[2 * c + 1]):.10f}')
+    return _Outcome(status=st, split_wait=split_wait, stats=stats, hook_error=hook_error, any_bound=any_bound, known=known,
+                    report=report, ws=ws, stream=stream, dims=(dt, B, n, m), r=r, rho=rho, rho_mode=ctl.rho_mode,
+                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out)
 
+
+def _print_check_trace(out, dev):
+    """The reference prints three lines at every check (:289-294); here the loop runs on the device without the host, so the
+    trace it kept -- the largest primal and dual error of the batch per check -- is printed once the solve is over."""
+    stats, r, ws = out.stats, out.r, out.ws
+    n_chk = int(stats.n_check) if stats.n_check >= 0 else int(r['max_iters'] - 1) // int(r['check_solved']) + 1
+    tr = torch.empty((2 * max(min(n_chk, 2048), 1),), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().lqp_boxqp_check_trace(_lib.stream_ptr(dev), *out.dims, _lib.ptr(ws), ws.numel(), min(n_chk, 2048),
+                                                     _lib.ptr(tr)), "check_trace")
+    trh = tr.cpu()
+    it_last = int(stats.iters) if stats.iters >= 0 else None
+    for c in range(min(n_chk, 2048)):
+        it_c = c * int(r['check_solved'])
+        if it_last is not None and it_c > it_last:
+            break
+        if stats.iters < 0 and float(trh[2 * c]) == 0.0 and float(trh[2 * c + 1]) == 0.0 and c > 0:
+            break                                      # (a pipelined call: the checks that never ran left no mark)
+        print(f'iteration = {it_c}')
+        print(f'|| primal_error|| = {float(trh[2 * c]):.10f}')
+        print(f'|| dual_error|| = {float(trh[2 * c + 1]):.10f}')
+
+
+def _solution(out, like, residuals):
+    """The dict a forward solve returns, and the record last_forward_status reads."""
+    stats, r, ws, dev = out.stats, out.r, out.ws, like.device
+    dt, B, n, m = out.dims
     # type of the returned rho follows the reference: a python number stays one unless
     # adaptive rho rewrote it (:248-250); None becomes a (B,1,1) tensor (:200-203)
-    if rho_mode == 1 and not stats.rho_updated and not (stats.mode_used == 3 and r['adaptive_rho']):
-        rho_ret = rho
-    else:
-        rho_ret = rho_out.view(B, 1, 1)     # (un-synchronised calls cannot know whether rho was adapted: tensor)
-    sol = {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho_ret, "iter": int(stats.iters)}
+    as_given = out.rho_mode == 1 and not stats.rho_updated and not (stats.mode_used == 3 and r['adaptive_rho'])
+    rho_ret = out.rho if as_given else out.rho_out.view(B, 1, 1)     # (un-synchronised calls cannot know whether rho was adapted: tensor)
+    sol = {"x": out.x, "z": out.z, "u": out.u, "lams": out.lams, "nus": out.nus, "rho": rho_ret, "iter": int(stats.iters)}
     if residuals:                        # errors of the last check (the NumPy twin's extra outputs)
-        pri = torch.empty((B,), dtype=p.dtype, device=dev)
-        dua = torch.empty((B,), dtype=p.dtype, device=dev)
+        pri, dua = (torch.empty((B,), dtype=like.dtype, device=dev) for _ in range(2))
         with torch.cuda.device(dev):
-            _lib.check(lib.lqp_boxqp_last_residuals(_lib.stream_ptr(dev), dt, B, n, m, _lib.ptr(ws), ws.numel(),
-                                                    _lib.ptr(pri), _lib.ptr(dua)), "last_residuals")
+            _lib.check(_lib.load().lqp_boxqp_last_residuals(_lib.stream_ptr(dev), dt, B, n, m, _lib.ptr(ws), ws.numel(),
+                                                            _lib.ptr(pri), _lib.ptr(dua)), "last_residuals")
         sol["primal_error"], sol["dual_error"] = pri, dua
     sol["_stats"] = {k: getattr(stats, k) for k, _ in stats._fields_}
-    _last_forward[(dev.index, stream)] = (
-        ws, dt, B, n, m, dict(sol["_stats"]), int(r['check_solved']), int(r['max_iters']))
+    _last_forward[(dev.index, out.stream)] = (ws, dt, B, n, m, dict(sol["_stats"]), int(r['check_solved']), int(r['max_iters']))
     return sol
+
+
+def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residuals=False, check_hook=None, mutate=False,
+                   holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False):
+    """bounds: (any_lb, any_ub) when the caller KNOWS them (a shard of a larger batch with host-side flags); None: found
+    on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
+    nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound).
+    Attempt, decide, act on the verdict, in a loop: _forward_attempt runs the library once, _forward_decide holds the rules."""
+    _lib.require_gpu(Q, p, A, b, lb, ub)
+    sync = sync or check_hook is not None             # (the strict global stop is host-driven: one launch per check)
+    owner = control.get('_owner') or control          # (lqp_py_amd.dist hands the layer a copy of the caller's dict)
+    att, dev = _Try(control, bounds, one_call), p.device
+    while True:
+        out = _forward_attempt((Q, p, A, b, lb, ub), att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running)
+        v = _forward_decide(out, att, owner, lambda: _finite_bounds(lb, ub))
+        if v.release == 'tail':
+            try:
+                _lib.poll_errors()        # (an error of an EARLIER un-synchronised call surfaces here: this call is enqueued,
+            finally:                      #  its own report is queued behind the poll -- it is never raised at its own call)
+                if out.stats.mode_used == 3:  # nothing was waited for: the report is read once the stream has passed the call
+                    _lib.defer_check("SolveBoxQP.forward", dev, out.report, Q.shape[0], True,
+                                     bounds_check=None if out.known else (
+                                         out.any_bound, owner, mutate, lambda _c, seen: _remember_any_bound(holder, owner, seen)))
+                else:                     # (the library waited after all: nothing left to report late)
+                    _lib.report_done(out.report)
+        else:
+            if v.release == 'wait':       # (cold path)
+                torch.cuda.current_stream(dev).synchronize()
+            _lib.report_done(out.report)
+        if v.void_prepared and while_running is not None:
+            while_running(None, 0)
+        if v.remember is not None:
+            _remember_any_bound(holder, owner, v.remember)
+        if v.error is not None:
+            raise v.error
+        if v.next is None:
+            break
+        att = v.next
+    if mutate and not out.any_bound:
+        att.control['rho'] = owner['rho'] = 0      # written into the CALLER's dict, as the reference does (:37-38)
+    if out.r['verbose']:
+        _print_check_trace(out, dev)
+    return _solution(out, p, residuals)
 
 
 _last_forward = {}
@@ -681,6 +678,35 @@ def last_forward_status(device):
     return st
 
 
+def _grad_outputs(on, B, n, m, dty, dev):
+    """(dQ, dp, dA, db, dlb, dub) of a backward call: an uninitialised tensor where `on` (six flags, same order) says so"""
+    mk = lambda flag, *shape: torch.empty(shape, dtype=dty, device=dev) if flag else None
+    return (mk(on[0], B, n, n), mk(on[1], B, n, 1), mk(on[2] and m > 0, B, m, n), mk(on[3] and m > 0, B, m, 1),
+            mk(on[4], B, n, 1), mk(on[5], B, n, 1))
+
+
+def _backward_call(fn, args, what, fail, report, dev, B, sync):
+    """fn(*args), one lqp_boxqp_backward_* call, and what follows every one of them: status 3 is the reference's "singular"
+    error, the rest goes through _lib.check; then the errors of earlier calls (this call's own report is queued behind the
+    poll), and the report buffer is deferred (nothing waited) or goes back to the pool."""
+    try:
+        with _lib.on_device(dev):
+            st = fn(*args)
+        if st == 3:
+            raise RuntimeError(f"lqp_py_amd.{what}: the input matrix is singular (batch index {fail.value})")
+        _lib.check(st, what)
+    except Exception:
+        _lib.pinned_release(report)     # (a failed call: its pinned report goes back -- quarantined while a queued kernel may still write it)
+        raise
+    try:
+        _lib.poll_errors()
+    finally:
+        if not sync:
+            _lib.defer_check("SolveBoxQP.backward", dev, report, B, False)
+        else:
+            _lib.report_done(report)
+
+
 class _Prepared(dict):
     """What _fp_backward_prepare hands to _fp_backward_run.  A forward that is never followed by its backward (validation with
     grad enabled, an exception, a retry on the other schedule) drops it: the pinned report buffer then goes back to the pool
@@ -694,7 +720,7 @@ class _Prepared(dict):
                 if self.get('pref_reported'):
                     _lib.pinned_release(rep)
                 else:
-                    _lib._pinned_free.setdefault(rep.numel(), []).append(rep)
+                    _lib.report_done(rep)
         except Exception:
             pass
 
@@ -702,6 +728,7 @@ class _Prepared(dict):
 # dQ of a prepared backward is allocated up front (in the window where the host only waits for the forward) up to this many
 # bytes; above, at `backward` itself: a forward without a backward would hold it for nothing -- 1 GB at B = 1024, n = 500
 _PREPARE_DQ_MAX_BYTES = 256 << 20
+_TAIL_DQ = 8 + 3          # (the slot of dQ in _fp_backward_prepare's `tail`, lqp_boxqp_backward_fp's argument list: behind 8 inputs and 3 rho words)
 
 
 def _fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, rho, want, sync=True, linsolve=1, prefactor=False):
@@ -709,28 +736,16 @@ def _fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, rho, want, sync=True, li
     the argument list of lqp_boxqp_backward_fp.  A synchronous layer call runs this WHILE its forward is on the GPU (the host
     would only wait), so that `backward` is one library call behind the autograd engine's thread hop."""
     _lib.require_gpu(x, u, lams, nus, Q, A, lb, ub)
-    lib = _lib.load()
-    B, n = Q.shape[0], Q.shape[1]
-    m = get_ncon(A, dim=1)
-    dt = _lib.dtype_code(x)
-    dev, dty = x.device, x.dtype
-    if rho is None:
-        rho = 1.0                                          # (:356-357)
-    rho_mode, rho_value, rho_tensor = _rho_argument(rho, B, x)
+    lib, B, n, m = _lib.load(), Q.shape[0], Q.shape[1], get_ncon(A, dim=1)
+    dt, dev, dty = _lib.dtype_code(x), x.device, x.dtype
+    rho_mode, rho_value, rho_tensor = _per_problem_argument('rho', '(B,1,1)', 1.0 if rho is None else rho, B, x)     # (:356-357)
     xc, uc, lc, nc, Qc, Ac, lbc, ubc = (_lib.norm(t, dty) for t in (x, u, lams, nus, Q, A, lb, ub))
-    mk = lambda on, shape: torch.empty(shape, dtype=dty, device=dev) if on else None
     late_dQ = bool(want['dQ']) and prefactor and B * n * n * x.element_size() > _PREPARE_DQ_MAX_BYTES
-    dQ = None if late_dQ else mk(want['dQ'], (B, n, n))
-    dp = mk(want['dp'], (B, n, 1))
-    dA = mk(want['dA'] and m > 0, (B, m, n))
-    db = mk(want['db'] and m > 0, (B, m, 1))
-    dlb = mk(want['dlb'], (B, n, 1))
-    dub = mk(want['dub'], (B, n, 1))
-    nbytes = lib.lqp_boxqp_backward_fp_workspace_bytes(dt, B, n, m)
+    dQ, dp, dA, db, dlb, dub = _grad_outputs((want['dQ'] and not late_dQ, want['dp'], want['dA'], want['db'], want['dlb'],
+                                              want['dub']), B, n, m, dty, dev)
     stream = _lib.current_stream_handle(dev)
-    ws = _lib.workspace(dev, nbytes, "bwd", stream)
-    fail = ctypes.c_int32(-1)
-    report = _lib.host_report(B)                        # (the info words go straight into pinned host memory)
+    ws = _lib.workspace(dev, lib.lqp_boxqp_backward_fp_workspace_bytes(dt, B, n, m), "bwd", stream)
+    fail, report = ctypes.c_int32(-1), _lib.host_report(B)      # (the info words go straight into pinned host memory)
     head = (ctypes.c_void_p(stream), dt, B, n, m)
     tail = (_lib.ptr(xc), _lib.ptr(uc), _lib.ptr(lc), _lib.ptr(nc), _lib.ptr(Qc), _lib.ptr(Ac), _lib.ptr(lbc), _lib.ptr(ubc),
             rho_mode, rho_value, _lib.ptr(rho_tensor),
@@ -760,8 +775,7 @@ def _fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, rho, want, sync=True, li
 def _fp_backward_run(prep, dl_dz):
     _lib.require_gpu(dl_dz)
     gc = _lib.norm(dl_dz, prep['dty'])
-    dev, report, B, sync = prep['dev'], prep['report'], prep['B'], prep['sync']
-    linsolve = prep['linsolve']
+    dev, report, B, sync, linsolve = prep['dev'], prep['report'], prep['B'], prep['sync'], prep['linsolve']
     if prep['pref'] is not None and prep['pref'] == _lib.workspace_uses(dev, "bwd", prep['stream']):
         linsolve |= _BWD_PREFACTORED                       # the factorisation made behind the forward is still in the workspace
         if prep.get('pref_reported'):
@@ -775,24 +789,10 @@ def _fp_backward_run(prep, dl_dz):
         Bq, nq = prep['late_dQ']
         dQ = torch.empty((Bq, nq, nq), dtype=prep['dty'], device=dev)
         prep['grads'] = (dQ,) + tuple(prep['grads'][1:])
-        tail = tail[:11] + (_lib.ptr(dQ),) + tail[12:]                 # (the slot of dQ in lqp_boxqp_backward_fp's argument list)
+        tail = tail[:_TAIL_DQ] + (_lib.ptr(dQ),) + tail[_TAIL_DQ + 1:]
     prep['ran'] = True                                                 # (the report buffer is this run's to hand back from here on)
-    try:
-        with _lib.on_device(dev):
-            st = prep['lib'].lqp_boxqp_backward_fp(*prep['head'], _lib.ptr(gc), *tail, linsolve, prep['rep'])
-        if st == 3:
-            raise RuntimeError(f"lqp_py_amd.torch_solve_box_qp_grad: the input matrix is singular (batch index {prep['fail'].value})")
-        _lib.check(st, "torch_solve_box_qp_grad")
-    except Exception:
-        _lib.pinned_release(report)     # (a failed call: its pinned report goes back -- quarantined while a queued kernel may still write it)
-        raise
-    try:
-        _lib.poll_errors()              # (errors of earlier calls; this call's own report is queued behind the poll)
-    finally:
-        if not sync:
-            _lib.defer_check("SolveBoxQP.backward", dev, report, B, False)
-        else:
-            _lib._pinned_free.setdefault(report.numel(), []).append(report)
+    _backward_call(prep['lib'].lqp_boxqp_backward_fp, (*prep['head'], _lib.ptr(gc), *tail, linsolve, prep['rep']),
+                   "torch_solve_box_qp_grad", prep['fail'], report, dev, B, sync)
     return prep['grads']
 
 

@@ -315,3 +315,110 @@ def test_bound_assumption_remembered_for_plain_dicts():
     d["rho"] = torch.ones(3, 1, 1)
     assert S._assume_any_bound(None, d, sync=False) is None
     S._seen_by_dict_id.clear()
+
+
+# ---------------------------------------------------------------- the retry rules of the forward solve (_forward_decide)
+def _outcome(status, split_wait=True, known=False, any_bound=True, mode_used=4, any_lb=1, any_ub=1, hook_error=None):
+    from lqp_py_amd import solve_box_qp_admm_torch as S
+    stats = _lib.BoxQPStats(mode_used=mode_used, any_lb=any_lb, any_ub=any_ub, fail_index=2)
+    return S._Outcome(status=status, split_wait=split_wait, stats=stats, hook_error=hook_error, known=known, any_bound=any_bound)
+
+
+_HOOK_EXC = ValueError("raised inside the strict-stop hook")
+_SINGULAR = "lqp_py_amd.torch_solve_box_qp: LU factorisation hit an exactly zero pivot (batch index 2); the KKT matrix is singular"
+# name -> (outcome, one_call and bounds of the attempt, what `look` answers (None: must not be asked),
+#          expected: what changes in the next attempt (None: no repeat), release, remember, error type and text)
+_DECIDE_ROWS = {
+    "1 time-out of a split call": (dict(status=5), False, None, None, dict(one_call=True), 'now', None, None),
+    "1 ... not twice: one_call set": (dict(status=5, split_wait=False, mode_used=0), True, None, None, None, 'wait', None,
+                                      (RuntimeError, "lqp_py_amd.torch_solve_box_qp: grid barrier timeout")),
+    "1 ... not twice, even if split": (dict(status=5), True, None, None, None, 'wait', None,
+                                       (RuntimeError, "lqp_py_amd.torch_solve_box_qp: grid barrier timeout")),
+    "2 outside the symmetric x-update": (dict(status=7), False, (True, False), None, dict(linsolve='lu'), 'now', None, None),
+    "2 ... drops one_call": (dict(status=7), True, None, None, dict(linsolve='lu', one_call=False), 'now', None, None),
+    "2 ... only after a split wait": (dict(status=7, split_wait=False, mode_used=0), False, None, None, None, 'wait', None,
+                                      (RuntimeError, "lqp_py_amd.torch_solve_box_qp: matrix outside the symmetric x-update")),
+    "3 hook error, status 0": (dict(status=0, split_wait=False, mode_used=0, hook_error=[_HOOK_EXC]), False, None, None, None, 'wait',
+                               None, (ValueError, str(_HOOK_EXC))),
+    "3 hook error first": (dict(status=3, split_wait=False, mode_used=0, any_bound=False, hook_error=[_HOOK_EXC]), False, None, None,
+                           None, 'wait', None, (ValueError, str(_HOOK_EXC))),
+    "4 singular, 'no bound' assumed, some seen": (dict(status=3, any_bound=False), False, None, (False, True),
+                                                  dict(bounds=(False, True)), 'wait', True, None),
+    "4 ... drops one_call": (dict(status=3, split_wait=False, mode_used=0, any_bound=False), True, None, (True, True),
+                             dict(bounds=(True, True), one_call=False), 'wait', True, None),
+    "4 ... none seen": (dict(status=3, any_bound=False), False, None, (False, False), None, 'wait', None, (RuntimeError, _SINGULAR)),
+    "4 ... not twice: bounds known": (dict(status=3, known=True, any_bound=False), False, (False, False), None, None, 'wait', None,
+                                      (RuntimeError, _SINGULAR)),
+    "4 ... bounds were assumed": (dict(status=3, any_bound=True), False, None, None, None, 'wait', None, (RuntimeError, _SINGULAR)),
+    "5 any other status": (dict(status=6, split_wait=False, mode_used=0), False, None, None, None, 'wait', None,
+                           (RuntimeError, "lqp_py_amd.torch_solve_box_qp: unsupported size (n + m <= 4096 in float32, 2048 in float64)")),
+    "6 pipelined: nothing to compare": (dict(status=0, split_wait=False, mode_used=3, any_lb=-1, any_ub=-1), False, None, None, None,
+                                        'tail', None, None),
+    "6 waited, assumption held": (dict(status=0), False, None, None, None, 'tail', True, None),
+    "6 waited, 'no bound' held": (dict(status=0, any_bound=False, any_lb=0, any_ub=0), False, None, None, None, 'tail', False, None),
+    "6 waited, bounds known": (dict(status=0, known=True, any_lb=0, any_ub=0), False, (True, True), None, None, 'tail', None, None),
+    "6 waited, flags not reported": (dict(status=0, any_lb=-1, any_ub=-1), False, None, None, None, 'tail', None, None),
+    "7 bounds assumed, none there": (dict(status=0, any_lb=0, any_ub=0), False, None, None, dict(bounds=(False, False)), 'tail', False,
+                                     None),
+    "7 none assumed, one side there": (dict(status=0, split_wait=False, mode_used=0, any_bound=False, any_lb=0, any_ub=1), True, None,
+                                       None, dict(bounds=(False, True), one_call=False), 'tail', True, None),
+}
+
+
+@pytest.mark.parametrize("row", sorted(_DECIDE_ROWS))
+def test_forward_retry_rules(row):
+    """One row per rule of _forward_decide (numbered as in its order of precedence) and per way a rule must NOT fire: which of
+    control['linsolve'], '_owner', bounds and one_call the next attempt changes and which it keeps, how the report buffer goes
+    back, what is remembered, what is raised.  The prepared backward is voided by the time-out rule alone."""
+    from lqp_py_amd import solve_box_qp_admm_torch as S
+    out_kw, one_call, bounds, look_says, change, release, remember, error = _DECIDE_ROWS[row]
+    owner = dict(eps_abs=1e-5, linsolve='auto')
+    control = dict(owner)                                    # (what lqp_py_amd.dist hands the layer: a copy, owner apart)
+    before = dict(control)
+    att = S._Try(control, bounds, one_call)
+    asked = []
+
+    def look():
+        asked.append(1)
+        assert look_says is not None, "the bounds were looked at"
+        return look_says
+    v = S._forward_decide(_outcome(**out_kw), att, owner, look)
+    assert control == before and owner == before             # nothing is written into either dict
+    assert len(asked) == (0 if look_says is None else 1)
+    assert v.release == release and v.remember is remember
+    assert v.void_prepared is (row == "1 time-out of a split call")
+    if error is not None:
+        assert v.next is None and type(v.error) is error[0] and str(v.error) == error[1]
+        return
+    assert v.error is None
+    if change is None:
+        assert v.next is None
+        return
+    want_control = dict(control, linsolve='lu', _owner=owner) if change.get('linsolve') else control
+    assert v.next.control == want_control
+    if change.get('linsolve'):
+        assert v.next.control['_owner'] is owner and v.next.control is not control
+    else:
+        assert v.next.control is control
+    assert v.next.bounds == change.get('bounds', bounds)
+    assert v.next.one_call is change.get('one_call', False)      # (set by the time-out rule, dropped by every other repeat)
+
+
+def test_per_problem_argument_of_rho_and_beta():
+    """rho and beta share one resolver: None -> the default rule, a number or a one-element tensor -> a scalar, B values -> a
+    tensor of (B,) on the device and in the dtype of the problem; any other size is refused with each one's own text."""
+    from lqp_py_amd.solve_box_qp_admm_torch import _per_problem_argument as arg
+    like = torch.zeros(3, 4, 1, dtype=torch.float64)
+    for name, example in (("rho", "(B,1,1)"), ("beta", "(B,1)")):
+        assert arg(name, example, None, 3, like) == (0, 0.0, None)
+        assert arg(name, example, 0.25, 3, like) == (1, 0.25, None)
+        assert arg(name, example, torch.tensor([[0.5]]), 3, like) == (1, 0.5, None)
+        mode, value, t = arg(name, example, torch.tensor([1.0, 2.0, 3.0]).reshape(3, 1, 1), 3, like)
+        assert (mode, value) == (2, 0.0) and t.shape == (3,) and t.dtype == torch.float64 and t.is_contiguous()
+        assert t.tolist() == [1.0, 2.0, 3.0]
+    with pytest.raises(ValueError) as e:
+        arg("rho", "(B,1,1)", torch.ones(2, 1, 1), 3, like)
+    assert str(e.value) == "lqp_py_amd: a rho tensor must hold one value per problem, e.g. shape (B,1,1)"
+    with pytest.raises(ValueError) as e:
+        arg("beta", "(B,1)", torch.ones(2, 1), 3, like)
+    assert str(e.value) == "lqp_py_amd: a beta tensor must hold one value per problem, e.g. shape (B,1)"

@@ -2482,8 +2482,8 @@ def test_the_callers_control_dict_stays_clean(dev, monkeypatch):
     keys = set(control)
     bounded, free = L.SolveBoxQP(control=control), L.SolveBoxQP(control=control)
     calls = []
-    inner = SB._forward_solve
-    monkeypatch.setattr(SB, "_forward_solve", lambda *a, **k: (calls.append(1), inner(*a, **k))[1])
+    inner = SB._forward_attempt                          # (one entry per trip through the library, repeats included)
+    monkeypatch.setattr(SB, "_forward_attempt", lambda *a, **k: (calls.append(1), inner(*a, **k))[1])
     per_round = []
     for _ in range(3):
         calls.clear()
@@ -2497,6 +2497,32 @@ def test_the_callers_control_dict_stays_clean(dev, monkeypatch):
     assert per_round[0] == 3 and per_round[1:] == [2, 2], per_round      # (only `free`'s first call repeated itself)
     ref = O.solve_box_qp(*[t.cpu() for t in (Q, p, A, b, lb, ub)], O.make_control(**TOL))
     assert err(xb, ref["x"]) < 2e-5 and torch.isfinite(xf).all()
+
+
+def test_singular_one_shot_under_a_stale_no_bound_assumption_repeats(dev, monkeypatch):
+    """Q = 0 with rho = 0: the KKT matrix [[0, A^T], [A, 0]] has rank 2 of 41, the LU meets an exactly zero pivot whatever the
+    rounding.  A layer whose last batch held no finite bound enqueues that one-shot for a bounded batch too; on status 3 it
+    looks at the bounds, finds some and repeats with rho > 0 -- the ADMM loop the reference would have run (its KKT matrix is
+    regular).  Compared bit for bit with the undisturbed solve of a fresh layer, which assumes bounds: no tolerance."""
+    Q, p, A, b, lb, ub = (t.to(dev) for t in O.create_qp_data(40, 4, seed=5))
+    Q0, inf = torch.zeros_like(Q), torch.full_like(lb, float("inf"))
+    mk = lambda: L.box_qp_control(rho=1.0, scale=False, adaptive_rho=False, eps_abs=1e-5, eps_rel=1e-5)
+    x_want = L.SolveBoxQP(control=mk())(Q0, p, A, b, lb, ub)
+    it_want = SB.last_forward_status(dev)["iters"]
+    assert torch.isfinite(x_want).all() and it_want > 0
+    control = mk()
+    second = L.SolveBoxQP(control=control)
+    second(Q, p, A, b, -inf, inf)
+    assert SB._seen_by_module[second] is False and control["rho"] == 0
+    control["rho"] = 1.0
+    calls = []
+    inner = SB._forward_attempt
+    monkeypatch.setattr(SB, "_forward_attempt", lambda *a, **k: (calls.append(1), inner(*a, **k))[1])
+    x = second(Q0, p, A, b, lb, ub)
+    assert torch.equal(x, x_want)
+    assert SB.last_forward_status(dev)["iters"] == it_want
+    assert SB._seen_by_module[second] is True
+    assert len(calls) == 2, len(calls)
 
 
 def test_workgroups_can_ask_which_xcd_they_run_on(dev):
