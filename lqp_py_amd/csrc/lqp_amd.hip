@@ -51,6 +51,10 @@ struct Carver {
             return LQP_ERR_HIP;                                           \
         }                                                                 \
     } while (0)
+// what the launches enqueued so far have left behind, as a status
+inline int last_error() { return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP; }
+// a batch that leaves half the chip idle takes two workgroups (row slabs, halves of the tiles) per problem
+inline int small_batch_split(const int B, const bool gate = true) { return (B <= 128 && gate) ? 2 : 1; }
 
 // dynamic LDS above 64 KB needs an opt-in per kernel
 std::mutex g_attr_mutex;
@@ -227,12 +231,8 @@ const Knobs& knobs() {
 
 // The LU kernels that share a matrix between workgroups (lqp_lu2.hpp, lqp_lu_wide.hpp) need all of them resident at once; the
 // launch checks that they fit, not that the chip is otherwise idle (another stream's kernels, RCCL).  When a hand-off times out
-// (info word -7: the waits are bounded, the kernels drain) the call is repeated ONCE with one workgroup per matrix.
+// (info word -7: the waits are bounded, the kernels drain) the call is repeated ONCE with one workgroup per matrix (SoloScope).
 thread_local bool t_single_wg_lu = false;
-struct SingleWgLu {
-    SingleWgLu() { t_single_wg_lu = true; }
-    ~SingleWgLu() { t_single_wg_lu = false; }
-};
 unsigned long long* g_lu_dbg = nullptr;     // optional device buffer (4 counters per problem), debug only
 
 // ---- LU launch: pick panel width / trailing-update flavour --------------------
@@ -245,7 +245,7 @@ int launch_lu_impl(hipStream_t st, int B, T* M, int N, int ld, size_t mstride, i
     if (rc) return rc;
     { ProfScope ps(st, PC_LU);
       hipLaunchKernelGGL(fn, dim3(B), dim3(NT), lds, st, M, N, ld, mstride, piv, pstride, info, gate, knobs().dbg_setup ? nullptr : g_lu_dbg, nvec); }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 // N <= 512: 512 threads (one row per thread, 256-VGPR budget) -> 32-column panel for f32, 16 for f64;
@@ -261,7 +261,7 @@ int launch_lu_big(hipStream_t st, T* M, int B, int N, int ld, size_t mstride, in
     if (rc) return rc;
     ProfScope ps(st, PC_LU);
     hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, st, M, N, ld, mstride, piv, pstride, info, gate, nvec);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 // Two workgroups per matrix (lqp_lu2.hpp) when the batch leaves half the chip idle: N <= 512, at least three column blocks, 2 B
@@ -282,7 +282,7 @@ int launch_lu2(hipStream_t st, T* M, int B, int N, int ld, size_t mstride, int* 
       // (LQP_DBG_LU2_ABSENT: the hand-offs of workgroups b time out, info = -7, the caller repeats on one workgroup per matrix)
       hipLaunchKernelGGL(fn, dim3(knobs().dbg_lu2_absent ? B : shared_grid(B, 2)), dim3(LU2_NT), lds, st, M, N, ld, mstride, piv, pstride, info, gate, nvec, scr,
                          scr_stride, epoch, knobs().dbg_setup ? nullptr : g_lu_dbg, B, knobs().xcd_local != 0 ? 1 : 0); }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 // Several workgroups per matrix above 1024 rows (lqp_lu_wide.hpp) when the batch leaves most of the chip idle: W = what fits
@@ -311,7 +311,7 @@ int launch_lu_wide(hipStream_t st, T* M, int B, int N, int ld, size_t mstride, i
     { ProfScope ps(st, PC_LU);
       hipLaunchKernelGGL(fn, dim3(W * B), dim3(LQP_NT), lds, st, M, N, ld, mstride, piv, pstride, info, gate, nvec, (int*)scr,
                          2 * scr_stride, epoch, B, knobs().dbg_setup ? nullptr : g_lu_dbg); }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 template <typename T>
@@ -361,10 +361,9 @@ int launch_pack(hipStream_t st, int B, const T* LU, int N, int ld, size_t mstrid
     if (rc) return rc;
     const bool vec_ok = (ld % 4 == 0) && (mstride % 4 == 0) && (((uintptr_t)LU) % (4 * sizeof(T)) == 0);
     ProfScope ps(st, PC_PACK);
-    const int split = (B <= 128 && knobs().split2) ? 2 : 1;      // use the idle half of the chip
-    hipLaunchKernelGGL(fn, dim3(B, split), dim3(LQP_NT), lds, st, LU, N, ld, mstride, piv, pstride, packed,
+    hipLaunchKernelGGL(fn, dim3(B, small_batch_split(B, knobs().split2 != 0)), dim3(LQP_NT), lds, st, LU, N, ld, mstride, piv, pstride, packed,
                        packed_blocks(K) * LQP_BLK, dest, K * LQP_NB, vec_ok ? 1 : 0, gate, nvec);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 template <typename T>
@@ -377,7 +376,7 @@ int launch_solve(hipStream_t st, int B, const T* packed, int N, const int* dest,
     if (rc) return rc;
     ProfScope ps(st, PC_SOLVE);
     hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, st, packed, N, Np, K, dest, rhs, nrhs, bstride, rstride, cstride, nvec);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 // X = M^-1 from the packed factor (lqp_dense.hpp): G workgroups per matrix, each takes column tiles g, g + G, ...
@@ -404,7 +403,7 @@ int launch_lu_inverse_cfg(hipStream_t st, int B, int N, const T* packed, size_t 
                            ldx, gate);
     else
         hipLaunchKernelGGL(fn, dim3(B, G), dim3(256), lds, st, packed, pkstride, N, 0, dest, dstride, X, xstride, ldx, gate);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 // float32: 64-column tiles on v_mfma_f32_32x32x2 while Y fits the LDS (N <= 576), 16-column tiles on v_mfma_f32_16x16x4 above
 template <typename T>
@@ -1429,8 +1428,9 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
 // ---------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------
+// lu_only: the arrays of one pivoted-LU solve and nothing else (lqp_kkt_solve)
 template <typename T>
-size_t carve_backward(void* ws, int B, int n, int m, BwdParams<T>& P) {
+size_t carve_backward(void* ws, int B, int n, int m, BwdParams<T>& P, const bool lu_only = false) {
     P.B = B; P.n = n; P.m = m; P.N = n + m;
     P.Np = round_up(P.N, LQP_NB); P.K = P.Np / LQP_NB;
     Carver c(ws);
@@ -1438,170 +1438,257 @@ size_t carve_backward(void* ws, int B, int n, int m, BwdParams<T>& P) {
     P.piv = c.take<int>((size_t)B * P.Np);
     P.dest = c.take<int>((size_t)B * P.Np);
     P.rhs = c.take<T>((size_t)B * P.Np);
-    P.rhs2 = c.take<T>((size_t)B * P.Np);
-    P.bsc = c.take<T>((size_t)B * P.Np);
-    P.fidx = c.take<int>((size_t)B * n);
-    P.nred = c.take<int>(B);
+    if (!lu_only) {
+        P.rhs2 = c.take<T>((size_t)B * P.Np);
+        P.bsc = c.take<T>((size_t)B * P.Np);
+        P.fidx = c.take<int>((size_t)B * n);
+        P.nred = c.take<int>(B);
+    }
     P.M = c.take<T>((size_t)B * P.Np * P.Np);
     P.packed = c.take<T>((size_t)B * packed_blocks(P.K) * LQP_BLK);
     return c.off + kAlign;
 }
 
+// dynamic LDS of the backward's kernels (k_bwd_chol_solve: bwd_chol_lds_bytes, lqp_boxqp.hpp)
+inline int bwd_build_chol_lds_bytes(int n, int) { return (2 * round_up(n, 8) + LQP_NW + 8 + round_up(n, 64) + 64) * 4; }      // fl | wtot | the KKT form's diagonal weights | the equilibration
+inline int bwd_build_reduced_lds_bytes(int n, int) { return (round_up(n, 8) + LQP_NW + 8) * 4; }                               // fl | wtot
+template <typename T> inline int bwd_residual_lds_bytes(int n, int m) { return (round_up(n, 8) + round_up(m > 0 ? m : 1, 8)) * (int)sizeof(T) + round_up(n, 8) * 4; }      // dvf | dn | fl
+template <typename T> inline int bwd_epilogue_lds_bytes(int n, int m) { return (2 * n + m + 8) * (int)sizeof(T); }
+
+// one backward call as its entry point received it (lqp_boxqp_backward_fp, _fp_prefactor, _backward_kkt)
+struct BwdCall {
+    hipStream_t st = nullptr;
+    int dtype = LQP_F32, B = 0, n = 0, m = 0;
+    const void *g = nullptr, *x = nullptr, *u = nullptr, *lams = nullptr, *nus = nullptr, *Q = nullptr, *A = nullptr, *lb = nullptr,
+               *ub = nullptr, *rho_in = nullptr;
+    int rho_mode = 1; double rho_value = 1.0;
+    void *dQ = nullptr, *dp = nullptr, *dA = nullptr, *db = nullptr, *dlb = nullptr, *dub = nullptr;
+    int32_t* fail_index = nullptr;      // null: the call neither waits nor repeats anything
+    void *ws = nullptr, *host_report = nullptr; size_t ws_bytes = 0;
+    int linsolve = 1;                   // 1 | 2, with LQP_BWD_PREFACTORED / LQP_BWD_REPORTED
+    bool kkt = false, prefactor = false;      // the KKT-system backward (BwdParams::kkt) | the call ahead of the cotangent: phase 1
+};
+
+// BF_CHOL: blocked Cholesky of Q_FF (the fixed-point and the KKT backward alike, P.kkt tells the kernels); the pivoted LU of
+// BF_LU_REDUCED: the bordered free-set system, BF_LU_FULL: the reference's full system (LQP_BWD_FULL), BF_LU_KKT: the reduced KKT system
+enum BwdForm { BF_CHOL, BF_LU_REDUCED, BF_LU_FULL, BF_LU_KKT };
+typedef void (*BwdCholFn)(const BwdParams<float>);
+template <typename T> struct BwdPlan {
+    BwdParams<T> P;                     // what every kernel of the attempt receives
+    BwdForm form = BF_LU_REDUCED;
+    int phase = 0;                      // 0: one call, 1: up to the factor (no cotangent needed), 2: from the cotangent on (= P.phase)
+    const int* nvec = nullptr;          // the reduced system's sizes for the LU chain (null: N rows each)
+    bool reset_report = false;          // the report words are this call's: -1 into each before the first launch
+    bool polls = false;                 // a caller that waits polls the report words; else first_failure waits for the stream
+    bool report_info = false;           // k_report_info right behind the LU
+    bool refine = false;                // one refinement step of the LU form
+    BwdCholFn chol_fn = nullptr;
+    int build_lds = 0, chol_lds = 0, residual_lds = 0, epilogue_lds = 0;
+    dim3 build_grid, residual_grid, epilogue_grid;
+};
+
+// Every decision of one attempt, from one snapshot of the switches; launches nothing.  retry (backward_impl): bit 0 = the LU form,
+// bit 1 = one workgroup per matrix -- either way one call in full, whatever phases the caller asked for.
 template <typename T>
-int backward_impl(hipStream_t st, int B, int n, int m, const void* g, const void* x, const void* u, const void* lams,
-                  const void* nus, const void* Q, const void* A, const void* lb, const void* ub, int rho_mode,
-                  double rho_value, const void* rho_in, void* dQ, void* dp, void* dA, void* db, void* dlb, void* dub,
-                  int32_t* fail_index, void* ws, size_t ws_bytes, int linsolve, void* host_report, const int kkt = 0,
-                  int phase = 0) {
-    const Knobs k = knobs();            // one snapshot of the switches per call (a copy: LQP_ENV_NOCACHE re-reads in place)
-    BwdParams<T> P;
-    memset(&P, 0, sizeof(P));
-    P.kkt = kkt ? 1 : 0;
-    const bool reported = (linsolve & LQP_BWD_REPORTED) != 0;
-    linsolve &= ~LQP_BWD_REPORTED;
-    if (linsolve & LQP_BWD_PREFACTORED) { linsolve &= ~LQP_BWD_PREFACTORED; if (phase == 0 && !kkt) phase = 2; }
-    P.host_report = (int*)host_report;
-    // (the words are set to -1 before the first launch, below -- unless the prefactor call has reported into them and this call
-    //  solves on its factor)
-    bool reset_pending = P.host_report != nullptr;
-    P.early_report = k.bwd_early != 0 ? 1 : 0;
-    const size_t need = carve_backward<T>(ws, B, n, m, P);
-    if (ws_bytes < need) return LQP_ERR_WORKSPACE;
-    if (!k.bwd_equil) P.bsc = nullptr;
-    P.g = (const T*)g; P.x = (const T*)x; P.u = (const T*)u; P.lams = (const T*)lams; P.nus = (const T*)nus;
-    P.Q = (const T*)Q; P.A = (const T*)A; P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in;
-    P.rho_value = (T)rho_value; P.rho_mode = rho_mode;
-    P.dQ = (T*)dQ; P.dp = (T*)dp; P.dA = (T*)dA; P.db = (T*)db; P.dlb = (T*)dlb; P.dub = (T*)dub;
-    P.dbg = g_lu_dbg;
-    // default: solve on the free set only (see k_bwd_build_reduced); LQP_BWD_FULL=1 keeps the full system
-    P.reduced = (k.bwd_full && !kkt) ? 0 : 1;
-    const int* nvec = P.reduced ? P.nred : nullptr;
-    // linsolve 2: the caller vouches for a symmetric Q (the forward's symmetric x-update checked it): the
-    // reduced system goes through a blocked Cholesky of Q_FF instead of the pivoted LU of the bordered matrix
-    bool chol = false;
-    if constexpr (sizeof(T) == 4) {
-        chol = P.reduced && linsolve == 2 && k.bwd_chol && round_up(n, LQP_NB) / LQP_NB <= SPD_BIGK &&
-               m <= SPD_MAXM && bwd_chol_lds_bytes(n, m, m >= 3 ? 4 : 2) <= 160 * 1024;
-    }
-    // the LU form has the same two phases (ABI 11): 1 = free set, reduced system, its pivoted LU and the packed factor -- none of
-    // them needs the cotangent --, 2 = gather the cotangent over the free set, solve (+ refinement), epilogue
-    const bool lu_phases = !chol && P.reduced && !kkt;
-    if (!chol && !lu_phases) {
-        if (phase == 1) return LQP_ERR_UNSUPPORTED;               // (the full-system form, the KKT backward: one call)
+int plan_backward(const BwdCall& c, const Knobs& k, const int retry, BwdPlan<T>& plan) {
+    BwdParams<T>& P = plan.P;
+    const int B = c.B, n = c.n, m = c.m;
+    const int flags = retry ? 0 : c.linsolve & (LQP_BWD_PREFACTORED | LQP_BWD_REPORTED);
+    const int linsolve = retry ? 1 : c.linsolve & ~(LQP_BWD_PREFACTORED | LQP_BWD_REPORTED);
+    // ---- form.  Default: solve on the free set only (see k_bwd_build_reduced); LQP_BWD_FULL=1 keeps the full system.
+    // linsolve 2: the caller vouches for a symmetric Q (the forward's symmetric x-update checked it): the reduced system goes
+    // through a blocked Cholesky of Q_FF instead of the pivoted LU of the bordered matrix -- in float32; float64 takes the LU form
+    P.kkt = c.kkt ? 1 : 0;
+    P.reduced = (k.bwd_full && !c.kkt) ? 0 : 1;
+    const int Kmax = round_up(n, LQP_NB) / LQP_NB;
+    const int nr = m >= 3 ? 4 : 2;                   // (four right-hand sides per round of the block solves)
+    const bool chol = sizeof(T) == 4 && P.reduced && linsolve == 2 && k.bwd_chol && Kmax <= SPD_BIGK && m <= SPD_MAXM &&
+                      bwd_chol_lds_bytes(n, m, nr) <= 160 * 1024;
+    plan.form = chol ? BF_CHOL : !P.reduced ? BF_LU_FULL : c.kkt ? BF_LU_KKT : BF_LU_REDUCED;
+    P.chol = chol ? 1 : 0;
+    plan.nvec = P.reduced ? P.nred : nullptr;
+    // ---- phase.  The Cholesky and the reduced LU form come in two calls too (ABI 11): 1 = free set, system, factor (packed) -- none
+    // of them needs the cotangent --, 2 = gather the cotangent over the free set, solve (+ refinement), epilogue.  The
+    // full-system form and the KKT backward are one call: nothing is enqueued for their prefactor call
+    int phase = retry ? 0 : c.prefactor ? 1 : ((flags & LQP_BWD_PREFACTORED) && !c.kkt) ? 2 : 0;
+    if (plan.form == BF_LU_FULL || plan.form == BF_LU_KKT) {
+        if (phase == 1) return LQP_ERR_UNSUPPORTED;
         phase = 0;
     }
-    P.phase = phase;
+    plan.phase = P.phase = phase;
+    // ---- report words.  A solve-only call whose prefactor call has reported into them neither resets nor stores them again
     // (with LQP_BWD_EARLY=0 the epilogue reports: the words are this call's to reset and to wait for)
-    P.reported = (reported && phase == 2 && P.host_report && P.early_report) ? 1 : 0;
-    if (reset_pending && !P.reported) report_reset(P.host_report, B);
-    reset_pending = false;
-    if constexpr (sizeof(T) == 4) {
-        if (chol) {
-            P.chol = 1;
-            if (phase != 2) {
-                const int lds = (2 * round_up(n, 8) + LQP_NW + 8 + round_up(n, 64) + 64) * 4;      // (fl | wtot | the KKT form's diagonal weights | the equilibration)
-                ProfScope ps(st, PC_BWD_BUILD);
-                const int split = B <= 128 ? 2 : 1;
-                hipLaunchKernelGGL(k_bwd_build_chol<>, dim3(B, split), dim3(LQP_NT), lds, st, P);
-            }
-            const bool nr4 = m >= 3;                   // (four right-hand sides per round of the block solves)
-            const int lds = bwd_chol_lds_bytes(n, m, nr4 ? 4 : 2);
-            {
-                const int Kmax = round_up(n, LQP_NB) / LQP_NB;
-                P.la_maxk = !k.bwd_lookahead ? 0 : (Kmax < SPD_MAXK ? Kmax : SPD_MAXK - 1);
-            }
-            auto chol_fn = nr4 ? k_bwd_chol_solve<4> : k_bwd_chol_solve<0>;
-#if LQP_PIV_MFMA
-            if (k.spd_f16 != 0 && k.bwd_f16 != 0) chol_fn = nr4 ? k_bwd_chol_solve<4, true> : k_bwd_chol_solve<0, true>;
-#endif
-            int r2 = ensure_lds((const void*)chol_fn, lds);
-            if (r2) return r2;
-            ProfScope ps(st, PC_BWD_CHOL);
-            hipLaunchKernelGGL(chol_fn, dim3(B), dim3(LQP_NT), lds, st, P);
-            if (phase == 1) return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
-        }
-    }
+    P.host_report = (int*)c.host_report;
+    P.early_report = k.bwd_early != 0 ? 1 : 0;
+    P.reported = ((flags & LQP_BWD_REPORTED) && phase == 2 && P.host_report && P.early_report) ? 1 : 0;
+    plan.reset_report = P.host_report && !P.reported;
+    plan.polls = P.host_report && k.sync_plan != 0;
+    // a caller that waits (or a prefactor call: its report buffer is the backward call's): the LU is the step that can fail or
+    // time out -- its info words right behind it, see k_report_info
+    plan.report_info = !chol && phase != 2 && P.host_report && (phase == 1 || (P.early_report && c.fail_index));
+    P.lu_reported = (!chol && (plan.report_info || P.reported)) ? 1 : 0;
+    // ---- build (enqueue_build: system and right-hand side, in phase 2 the right-hand side alone), factor, solve
+    if (!k.bwd_equil) P.bsc = nullptr;
+    plan.build_lds = chol ? bwd_build_chol_lds_bytes(n, m) : (P.reduced && phase != 2) ? bwd_build_reduced_lds_bytes(n, m) : 0;
+    // (k_bwd_build_chol's split has never consulted LQP_SPLIT2; k_bwd_gather_rhs and k_bwd_build take one workgroup per problem)
+    plan.build_grid = chol ? dim3(B, small_batch_split(B)) : (P.reduced && phase != 2) ? dim3(B, small_batch_split(B, k.split2 != 0)) : dim3(B);
     if (chol) {
-    } else if (phase == 2) {
-        ProfScope ps(st, PC_BWD_BUILD);
-        hipLaunchKernelGGL(k_bwd_gather_rhs<T>, dim3(B), dim3(256), 0, st, P);
-    } else if (P.reduced) {
-        const int lds = (round_up(n, 8) + LQP_NW + 8) * 4;
-        ProfScope ps(st, PC_BWD_BUILD);
-        const int split = (B <= 128 && k.split2) ? 2 : 1;
-        hipLaunchKernelGGL(k_bwd_build_reduced<T>, dim3(B, split), dim3(LQP_NT), lds, st, P);
-    } else {
-        ProfScope ps(st, PC_BWD_BUILD);
-        hipLaunchKernelGGL(k_bwd_build<T>, dim3(B), dim3(LQP_NT), 0, st, P);
-    }
-    int rc = LQP_OK;
-    if (!chol) {
-        if (phase != 2) {
-            rc = launch_lu(st, P.M, B, P.N, P.Np, (size_t)P.Np * P.Np, P.piv, P.Np, P.info, nullptr, nvec,
-                           (unsigned long long*)P.packed, packed_blocks(P.K) * LQP_BLK * sizeof(T) / 8);
-            if (rc) return rc;
-            // a caller that waits (or a prefactor call: its report buffer is the backward call's): the LU is the step that can
-            // fail or time out -- its info words now, see k_report_info
-            if (P.host_report && (phase == 1 || (P.early_report && fail_index))) {
-                ProfScope ps(st, PC_MISC);
-                hipLaunchKernelGGL(k_report_info<>, dim3((B + 255) / 256), dim3(256), 0, st, (const int*)P.info, P.host_report, B);
-                P.lu_reported = 1;
-            }
-            rc = launch_pack<T>(st, B, P.M, P.N, P.Np, (size_t)P.Np * P.Np, P.piv, P.Np, P.packed, P.dest, nullptr, nvec);
-            if (rc) return rc;
-            if (phase == 1) return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
-        } else if (P.reported) P.lu_reported = 1;
-        rc = launch_solve<T>(st, B, P.packed, P.N, P.dest, P.rhs, 1, (size_t)P.Np, 1, 0, nvec);
-        if (rc) return rc;
-        if (P.reduced && !kkt && k.bwd_refine) {
-            // one refinement step: residual with the original entries (double accumulation), correction solve
-            const int lds = (round_up(n, 8) + round_up(m > 0 ? m : 1, 8)) * (int)sizeof(T) + round_up(n, 8) * 4;
-            { ProfScope ps(st, PC_BWD_BUILD);
-              hipLaunchKernelGGL(k_bwd_residual<T>, dim3(B, (B <= 128 && k.split2) ? 2 : 1), dim3(LQP_NT), lds, st, P); }
-            rc = launch_solve<T>(st, B, P.packed, P.N, P.dest, P.rhs2, 1, (size_t)P.Np, 1, 0, nvec);
-            if (rc) return rc;
-            P.refine = 1;
+        if constexpr (sizeof(T) == 4) {
+            plan.chol_fn = nr == 4 ? k_bwd_chol_solve<4> : k_bwd_chol_solve<0>;
+#if LQP_PIV_MFMA
+            if (k.spd_f16 != 0 && k.bwd_f16 != 0) plan.chol_fn = nr == 4 ? k_bwd_chol_solve<4, true> : k_bwd_chol_solve<0, true>;
+#endif
         }
-    }
-    {
-        const int lds = (2 * n + m + 8) * (int)sizeof(T);
-        auto fn = k_bwd_epilogue<T>;
-        rc = ensure_lds((const void*)fn, lds);
+        plan.chol_lds = bwd_chol_lds_bytes(n, m, nr);
+        P.la_maxk = !k.bwd_lookahead ? 0 : (Kmax < SPD_MAXK ? Kmax : SPD_MAXK - 1);
+        const int rc = ensure_lds((const void*)plan.chol_fn, plan.chol_lds);
         if (rc) return rc;
-        ProfScope ps(st, PC_BWD_EPILOGUE);
-        const int slabs = (k.epi_slabs < 0 ? (B <= 128 ? 2 : 1) : k.epi_slabs);      // row slabs per problem: fill the chip when the batch is small
-        hipLaunchKernelGGL(fn, dim3(B, slabs), dim3(LQP_NT), lds, st, P);
     }
-    if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
-    if (fail_index) {
-        int fi = -1;
-        // torch.linalg.solve checks info (and waits) too.  The epilogue stores the info words into the caller's pinned
-        // memory as it STARTS: the call returns while the gradients are still being written (stream-ordered results)
-        if (P.host_report && k.sync_plan != 0) {
-            rc = wait_report(st, P.host_report, B);
-            if (rc) return rc;
-            bool gave_up = false;                    // (-7: a hand-off of a shared LU timed out)
-            for (int i = 0; i < B; ++i) {
-                const int v = ((const volatile int*)P.host_report)[i];
-                if (v != 0 && fi < 0) fi = i;
-                gave_up = gave_up || v == -7;
-            }
-            rc = gave_up ? LQP_ERR_TIMEOUT : fi >= 0 ? LQP_ERR_SINGULAR : LQP_OK;
-        } else
-            rc = first_failure(st, P.info, B, &fi, P.host_report);
-        if (rc == LQP_ERR_TIMEOUT && !chol && !t_single_wg_lu) {      // a shared LU timed out: once more, one workgroup per matrix
-            SingleWgLu only;
-            return backward_impl<T>(st, B, n, m, g, x, u, lams, nus, Q, A, lb, ub, rho_mode, rho_value, rho_in, dQ, dp, dA,
-                                    db, dlb, dub, fail_index, ws, ws_bytes, 1, host_report, kkt, 0);
-        }
-        if (rc == LQP_ERR_SINGULAR && chol)           // Q_FF not positive definite in f32: the pivoted LU takes it
-            return backward_impl<T>(st, B, n, m, g, x, u, lams, nus, Q, A, lb, ub, rho_mode, rho_value, rho_in, dQ, dp, dA,
-                                    db, dlb, dub, fail_index, ws, ws_bytes, 1, host_report, kkt, 0);
-        *fail_index = fi;
+    // one refinement step: residual with the original entries (double accumulation), correction solve
+    plan.refine = plan.form == BF_LU_REDUCED && k.bwd_refine && phase != 1;
+    P.refine = plan.refine ? 1 : 0;
+    plan.residual_lds = bwd_residual_lds_bytes<T>(n, m);
+    plan.residual_grid = dim3(B, small_batch_split(B, k.split2 != 0));
+    // ---- epilogue: row slabs per problem, fill the chip when the batch is small
+    if (phase != 1) {
+        plan.epilogue_lds = bwd_epilogue_lds_bytes<T>(n, m);
+        plan.epilogue_grid = dim3(B, k.epi_slabs < 0 ? small_batch_split(B) : k.epi_slabs);
+        const int rc = ensure_lds((const void*)k_bwd_epilogue<T>, plan.epilogue_lds);
         if (rc) return rc;
     }
     return LQP_OK;
 }
+
+// ---- the launch steps: they read the plan and decide nothing ----
+template <typename T>
+void enqueue_build(hipStream_t st, const BwdPlan<T>& plan) {
+    const BwdParams<T>& P = plan.P;
+    if (plan.form == BF_CHOL && plan.phase == 2) return;      // (k_bwd_chol_solve gathers the cotangent itself)
+    ProfScope ps(st, PC_BWD_BUILD);
+    if (plan.form == BF_CHOL) {
+        if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(k_bwd_build_chol<>, plan.build_grid, dim3(LQP_NT), plan.build_lds, st, P);
+    } else if (plan.phase == 2) hipLaunchKernelGGL(k_bwd_gather_rhs<T>, plan.build_grid, dim3(256), 0, st, P);
+    else if (P.reduced) hipLaunchKernelGGL(k_bwd_build_reduced<T>, plan.build_grid, dim3(LQP_NT), plan.build_lds, st, P);
+    else hipLaunchKernelGGL(k_bwd_build<T>, plan.build_grid, dim3(LQP_NT), 0, st, P);
+}
+
+// (the Cholesky kernels exist in float32 only: plan_backward never names this form for float64)
+template <typename T>
+void enqueue_chol(hipStream_t st, const BwdPlan<T>& plan) {
+    if constexpr (sizeof(T) == 4) {
+        ProfScope ps(st, PC_BWD_CHOL);
+        hipLaunchKernelGGL(plan.chol_fn, dim3(plan.P.B), dim3(LQP_NT), plan.chol_lds, st, plan.P);
+    }
+}
+
+// The pivoted-LU chain on the system carve_backward laid out, for the backward's LU forms and lqp_kkt_solve: factor (the packed
+// factor's buffer is the shared LUs' scratch until the pack fills it), [the info words into the report buffer], pack, solve.
+// Phase 1 stops behind the pack, phase 2 is the solve alone.
+template <typename T>
+int enqueue_lu_chain(hipStream_t st, const BwdParams<T>& P, const int* nvec, const int phase, const bool report_info) {
+    const size_t mstride = (size_t)P.Np * P.Np;
+    if (phase != 2) {
+        int rc = launch_lu(st, P.M, P.B, P.N, P.Np, mstride, P.piv, P.Np, P.info, nullptr, nvec, (unsigned long long*)P.packed,
+                           packed_blocks(P.K) * LQP_BLK * sizeof(T) / 8);
+        if (rc) return rc;
+        if (report_info) {
+            ProfScope ps(st, PC_MISC);
+            hipLaunchKernelGGL(k_report_info<>, dim3((P.B + 255) / 256), dim3(256), 0, st, (const int*)P.info, P.host_report, P.B);
+        }
+        rc = launch_pack<T>(st, P.B, P.M, P.N, P.Np, mstride, P.piv, P.Np, P.packed, P.dest, nullptr, nvec);
+        if (rc || phase == 1) return rc;
+    }
+    return launch_solve<T>(st, P.B, P.packed, P.N, P.dest, P.rhs, 1, (size_t)P.Np, 1, 0, nvec);
+}
+
+template <typename T>
+int enqueue_refinement(hipStream_t st, const BwdPlan<T>& plan) {
+    const BwdParams<T>& P = plan.P;
+    { ProfScope ps(st, PC_BWD_BUILD);
+      hipLaunchKernelGGL(k_bwd_residual<T>, plan.residual_grid, dim3(LQP_NT), plan.residual_lds, st, P); }
+    return launch_solve<T>(st, P.B, P.packed, P.N, P.dest, P.rhs2, 1, (size_t)P.Np, 1, 0, plan.nvec);
+}
+
+template <typename T>
+void enqueue_epilogue(hipStream_t st, const BwdPlan<T>& plan) {
+    ProfScope ps(st, PC_BWD_EPILOGUE);
+    hipLaunchKernelGGL(k_bwd_epilogue<T>, plan.epilogue_grid, dim3(LQP_NT), plan.epilogue_lds, st, plan.P);
+}
+
+// why an attempt gave up, for backward_impl's retry loop
+// (BG_CHOL_NOT_SPD: Q_FF not positive definite in f32; BG_LU_TIMEOUT: a shared LU never met its partner, info word -7)
+enum BwdGaveUp { BG_NONE = 0, BG_CHOL_NOT_SPD, BG_LU_TIMEOUT };
+struct BwdOutcome { int status, fail_index; BwdGaveUp why; };
+
+// The info words of a finished attempt as (status, first failing problem, cause).  torch.linalg.solve checks info (and waits)
+// too.  A cause is named only while its remedy is untried: the Cholesky form is planned on the first attempt only, and
+// t_single_wg_lu says that the shared LUs are off already.
+template <typename T>
+BwdOutcome read_outcome(hipStream_t st, const BwdPlan<T>& plan) {
+    const BwdParams<T>& P = plan.P;
+    BwdOutcome o = {LQP_OK, -1, BG_NONE};
+    if (plan.polls) {                   // (backward_impl has waited for the words)
+        bool gave_up = false;
+        for (int i = 0; i < P.B; ++i) {
+            const int v = ((const volatile int*)P.host_report)[i];
+            if (v != 0 && o.fail_index < 0) o.fail_index = i;
+            gave_up = gave_up || v == -7;
+        }
+        o.status = gave_up ? LQP_ERR_TIMEOUT : o.fail_index >= 0 ? LQP_ERR_SINGULAR : LQP_OK;
+    } else
+        o.status = first_failure(st, P.info, P.B, &o.fail_index, P.host_report);
+    if (o.status == LQP_ERR_TIMEOUT && plan.form != BF_CHOL && !t_single_wg_lu) o.why = BG_LU_TIMEOUT;
+    else if (o.status == LQP_ERR_SINGULAR && plan.form == BF_CHOL) o.why = BG_CHOL_NOT_SPD;
+    return o;
+}
+
+// carve, then plan / enqueue / read / decide until an attempt ends the call.  Each remedy is taken at most once (read_outcome);
+// a time-out is looked at first, and the two causes exclude each other (one needs an LU form, the other the Cholesky form)
+template <typename T>
+int backward_impl(const BwdCall& c) {
+    const hipStream_t st = c.st;
+    BwdParams<T> P0;
+    memset(&P0, 0, sizeof(P0));
+    if (c.ws_bytes < carve_backward<T>(c.ws, c.B, c.n, c.m, P0)) return LQP_ERR_WORKSPACE;
+    P0.g = (const T*)c.g; P0.x = (const T*)c.x; P0.u = (const T*)c.u; P0.lams = (const T*)c.lams; P0.nus = (const T*)c.nus;
+    P0.Q = (const T*)c.Q; P0.A = (const T*)c.A; P0.lb = (const T*)c.lb; P0.ub = (const T*)c.ub; P0.rho_in = (const T*)c.rho_in;
+    P0.rho_value = (T)c.rho_value; P0.rho_mode = c.rho_mode;
+    P0.dQ = (T*)c.dQ; P0.dp = (T*)c.dp; P0.dA = (T*)c.dA; P0.db = (T*)c.db; P0.dlb = (T*)c.dlb; P0.dub = (T*)c.dub;
+    P0.dbg = g_lu_dbg;
+    SoloScope one_wg_lu;
+    for (int retry = 0;;) {
+        const Knobs k = knobs();            // one snapshot of the switches per attempt (a copy: LQP_ENV_NOCACHE re-reads in place)
+        if (retry & 2) one_wg_lu.enter();
+        BwdPlan<T> plan;
+        plan.P = P0;
+        int rc = plan_backward(c, k, retry, plan);
+        if (rc) return rc;
+        if (plan.reset_report) report_reset(plan.P.host_report, c.B);
+        enqueue_build(st, plan);
+        if (plan.form == BF_CHOL) enqueue_chol(st, plan);
+        else rc = enqueue_lu_chain(st, plan.P, plan.nvec, plan.phase, plan.report_info);
+        if (rc) return rc;
+        if (plan.phase == 1) return last_error();          // (the factor is in the workspace; nothing to wait for)
+        if (plan.refine) rc = enqueue_refinement(st, plan);
+        if (rc) return rc;
+        enqueue_epilogue(st, plan);
+        if (last_error()) return LQP_ERR_HIP;
+        if (!c.fail_index) return LQP_OK;
+        // The kernel that reports stores the info words into the caller's pinned memory as it STARTS: the call returns while the
+        // gradients are still being written (stream-ordered results)
+        if (plan.polls) {
+            rc = wait_report(st, plan.P.host_report, c.B);
+            if (rc) return rc;
+        }
+        const BwdOutcome o = read_outcome(st, plan);
+        switch (o.why) {
+        case BG_NONE: *c.fail_index = o.fail_index; return o.status;
+        case BG_LU_TIMEOUT: retry |= 2; break;             // once more, one workgroup per matrix
+        case BG_CHOL_NOT_SPD: retry |= 1; break;           // once more on the LU form
+        }
+    }
+}
+inline int backward_call(const BwdCall& c) { return c.dtype == LQP_F32 ? backward_impl<float>(c) : backward_impl<double>(c); }
 
 // ---------------------------------------------------------------------------
 // LU / solve / KKT entry points
@@ -1628,7 +1715,7 @@ int lu_factor_impl(hipStream_t st, int B, int N, void* Mio, int32_t* piv_out, in
     if (rc) return rc;
     hipLaunchKernelGGL(k_copy_matrix<T>, dim3(B), dim3(LQP_NT), 0, st, (const T*)M, Np, (size_t)Np * Np, (T*)Mio, N, (size_t)N * N, N);
     hipLaunchKernelGGL(k_copy_ints<int>, dim3(B), dim3(256), 0, st, (const int*)piv, Np, (int*)piv_out, N, N);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 template <typename T> size_t packed_bytes_t(int B, int N) {
@@ -1659,39 +1746,20 @@ int lu_solve_packed_impl(hipStream_t st, int B, int N, int k, const void* buf, v
 }
 
 template <typename T>
-size_t carve_kkt(void* ws, int B, int n, int m, T*& M, T*& packed, T*& rhs, int*& piv, int*& dest, int*& info) {
-    const int N = n + m, Np = round_up(N, LQP_NB), K = Np / LQP_NB;
-    Carver c(ws);
-    info = c.take<int>(B);
-    piv = c.take<int>((size_t)B * Np);
-    dest = c.take<int>((size_t)B * Np);
-    rhs = c.take<T>((size_t)B * Np);
-    M = c.take<T>((size_t)B * Np * Np);
-    packed = c.take<T>((size_t)B * packed_blocks(K) * LQP_BLK);
-    return c.off + kAlign;
-}
-
-template <typename T>
 int kkt_solve_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
                    void* x, void* nus, int32_t* fail_index, void* ws, size_t ws_bytes) {
-    T *M, *packed, *rhs; int *piv, *dest, *info;
-    const size_t need = carve_kkt<T>(ws, B, n, m, M, packed, rhs, piv, dest, info);
-    if (ws_bytes < need) return LQP_ERR_WORKSPACE;
-    const int N = n + m, Np = round_up(N, LQP_NB);
+    BwdParams<T> P;
+    memset(&P, 0, sizeof(P));
+    if (ws_bytes < carve_backward<T>(ws, B, n, m, P, true)) return LQP_ERR_WORKSPACE;
     hipLaunchKernelGGL(k_kkt_build<T>, dim3(B), dim3(LQP_NT), 0, st, (const T*)Q, (const T*)p, (const T*)A, (const T*)b,
-                       n, m, Np, M, rhs, info);
-    int rc = launch_lu(st, M, B, N, Np, (size_t)Np * Np, piv, Np, info, nullptr, nullptr, (unsigned long long*)packed,
-                       packed_blocks(Np / LQP_NB) * LQP_BLK * sizeof(T) / 8);
+                       n, m, P.Np, P.M, P.rhs, P.info);
+    int rc = enqueue_lu_chain(st, P, nullptr, 0, false);
     if (rc) return rc;
-    rc = launch_pack<T>(st, B, M, N, Np, (size_t)Np * Np, piv, Np, packed, dest, nullptr);
-    if (rc) return rc;
-    rc = launch_solve<T>(st, B, packed, N, dest, rhs, 1, (size_t)Np, 1, 0);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_kkt_unpack<T>, dim3(B), dim3(256), 0, st, (const T*)rhs, n, m, Np, (T*)x, (T*)nus);
-    if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
+    hipLaunchKernelGGL(k_kkt_unpack<T>, dim3(B), dim3(256), 0, st, (const T*)P.rhs, n, m, P.Np, (T*)x, (T*)nus);
+    if (last_error()) return LQP_ERR_HIP;
     if (fail_index) {
         int fi = -1;
-        rc = first_failure(st, info, B, &fi);
+        rc = first_failure(st, P.info, B, &fi);
         *fail_index = fi;
         if (rc) return rc;
     }
@@ -1764,7 +1832,7 @@ static int unroll_tape_segment_impl(hipStream_t st, int B, int n, int m, const v
     if (rc) return rc;
     ProfScope ps(st, PC_UNROLL);
     hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, st, P, U);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 // ... and what is summed over the whole tape once every segment has been walked: Asbar / bsbar, Qsbar
@@ -1787,7 +1855,7 @@ static int unroll_tape_finish_impl(hipStream_t st, int B, int n, int m, int iter
         const int tiles = (n + 63) / 64;
         hipLaunchKernelGGL(k_unroll_outer_any<T>, dim3(tiles, tiles, B), dim3(256), 0, st, (const T*)U.DX, (const T*)U.X, (T*)dQs, n, TT);
     }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 template <typename T>
@@ -1823,7 +1891,7 @@ static int unroll_backward_lu_impl(hipStream_t st, int B, int n, int m, const vo
         const int tiles = (n + 63) / 64;
         hipLaunchKernelGGL(k_unroll_outer_any<T>, dim3(tiles, tiles, B), dim3(256), 0, st, (const T*)U.DX, (const T*)U.X, (T*)dQs, n, TT);
     }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 }  // namespace
@@ -1859,7 +1927,7 @@ int lqp_debug_spin(void* stream, int blocks, int usec, int lds_bytes) {
     const int rc = ensure_lds((const void*)k_debug_spin, lds_bytes);
     if (rc) return rc;
     hipLaunchKernelGGL(k_debug_spin, dim3(blocks), dim3(512), lds_bytes, (hipStream_t)stream, (unsigned long long)usec * 100ull);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 // test aid: the XCD every workgroup of a `blocks`-workgroup launch lands on (what the XCD-aware exchange asks at run time)
@@ -1869,7 +1937,7 @@ __global__ __launch_bounds__(512) void k_debug_xcd(int* __restrict__ out) {
 int lqp_debug_xcd(void* stream, int blocks, void* out_dev) {
     if (blocks < 1 || !out_dev) return LQP_ERR_INVALID;
     hipLaunchKernelGGL(k_debug_xcd, dim3(blocks), dim3(512), 0, (hipStream_t)stream, (int*)out_dev);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 int lqp_debug_lu_inverse(void* stream, int dtype, int B, int N, const void* packed_buf, void* X_out) {
@@ -2043,7 +2111,7 @@ int lqp_boxqp_unroll_backward(void* stream, int B, int n, int m, const void* fwd
         hipLaunchKernelGGL(k_unroll_outer<>, dim3(tiles, tiles, B), dim3(256), 0, st, (const float*)U.DX, (const float*)U.X,
                            (float*)dQs, n, T);
     }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 size_t lqp_boxqp_unroll_backward_lu_workspace_bytes(int dtype, int B, int n, int m, int iters) {
@@ -2104,7 +2172,7 @@ int lqp_unroll_scale_colmax(void* stream, int B, int n, const void* Q, void* col
     int dev = 0, cus = 0;
     const int slabs = (current_device_cus(&dev, &cus) && 2 * B <= cus && n >= 128) ? 2 : 1;      // column halves when half the chip is idle
     hipLaunchKernelGGL(k_unroll_scale_colmax<>, dim3(B, slabs), dim3(LQP_NT), 0, st, (const float*)Q, n, (float*)colmax, (int*)argmax, (int*)count);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 int lqp_unroll_scale_grad_slabs(int B, int n) {
@@ -2126,7 +2194,7 @@ int lqp_unroll_scale_grad(void* stream, int B, int n, const void* Q, const void*
     ProfScope ps(st, PC_UNROLL_SCALE);
     hipLaunchKernelGGL(k_unroll_scale_grad<>, dim3(B, slabs), dim3(256), lds, st, (const float*)Q, (const float*)d, (const float*)s,
                        (float*)G, n, (float*)parts);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 int lqp_unroll_scale_vectors(void* stream, int B, int n, int m, int phase, int has_box, int beta_given, double beta_value,
@@ -2153,7 +2221,7 @@ int lqp_unroll_scale_vectors(void* stream, int B, int n, int m, int phase, int h
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(st, PC_UNROLL_SCALE);
     hipLaunchKernelGGL(k_unroll_scale_vectors<>, dim3(B), dim3(LQP_NT), lds, st, P);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 int lqp_unroll_scale_scatter(void* stream, int B, int n, const void* Q, const void* colmax, const void* argmax, const void* count,
@@ -2164,7 +2232,7 @@ int lqp_unroll_scale_scatter(void* stream, int B, int n, const void* Q, const vo
     ProfScope ps(st, PC_UNROLL_SCALE);
     hipLaunchKernelGGL(k_unroll_scale_scatter<>, dim3(B), dim3(LQP_NT), 0, st, (const float*)Q, (const float*)colmax, (const int*)argmax,
                        (const int*)count, (const float*)g_colmax, (float*)G, n);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 int lqp_boxqp_last_residuals(void* stream, int dtype, int B, int n, int m, const void* workspace, size_t workspace_bytes,
@@ -2183,7 +2251,7 @@ int lqp_boxqp_last_residuals(void* stream, int dtype, int B, int n, int m, const
         hipLaunchKernelGGL(k_copy_residuals<double>, dim3((B + 255) / 256), dim3(256), 0, st, L.P.scal, (double*)primal_out,
                            (double*)dual_out, B);
     }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 int lqp_boxqp_check_trace(void* stream, int dtype, int B, int n, int m, const void* workspace, size_t workspace_bytes,
@@ -2203,7 +2271,7 @@ int lqp_boxqp_check_trace(void* stream, int dtype, int B, int n, int m, const vo
     }
     const int words = 2 * (n_checks < kRing ? n_checks : kRing);
     hipLaunchKernelGGL(k_copy_trace<>, dim3((words + 255) / 256), dim3(256), 0, st, src, (float*)trace_out, words);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 size_t lqp_boxqp_backward_fp_workspace_bytes(int dtype, int B, int n, int m) {
@@ -2218,13 +2286,12 @@ int lqp_boxqp_backward_fp_prefactor(void* stream, int dtype, int B, int n, int m
     if (bad_dims(dtype, B, n, m) || !x || !u || !Q || !lb || !ub || !workspace) return LQP_ERR_INVALID;
     if (m > 0 && !A) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
-    if (dtype == LQP_F32)
-        return backward_impl<float>((hipStream_t)stream, B, n, m, nullptr, x, u, nullptr, nullptr, Q, A, lb, ub, 1, 1.0, nullptr,
-                                    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes,
-                                    linsolve == 2 ? 2 : 1, host_report, 0, 1);
-    return backward_impl<double>((hipStream_t)stream, B, n, m, nullptr, x, u, nullptr, nullptr, Q, A, lb, ub, 1, 1.0, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_bytes, 1,
-                                 host_report, 0, 1);
+    BwdCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.linsolve = linsolve == 2 ? 2 : 1; c.host_report = host_report;
+    c.x = x; c.u = u; c.Q = Q; c.A = A; c.lb = lb; c.ub = ub;
+    c.prefactor = true;
+    return backward_call(c);
 }
 
 int lqp_boxqp_backward_fp(void* stream, int dtype, int B, int n, int m, const void* dl_dz, const void* x, const void* u,
@@ -2237,11 +2304,13 @@ int lqp_boxqp_backward_fp(void* stream, int dtype, int B, int n, int m, const vo
     if (rho_mode != 1 && rho_mode != 2) return LQP_ERR_INVALID;
     if (rho_mode == 2 && !rho_in) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LQP_F32)
-        return backward_impl<float>(st, B, n, m, dl_dz, x, u, lams, nus, Q, A, lb, ub, rho_mode, rho_value, rho_in, dQ, dp, dA, db, dlb, dub, fail_index, workspace, workspace_bytes, linsolve, host_report);
-    return backward_impl<double>(st, B, n, m, dl_dz, x, u, lams, nus, Q, A, lb, ub, rho_mode, rho_value, rho_in, dQ, dp, dA, db, dlb, dub, fail_index, workspace, workspace_bytes,
-                                 1 | (linsolve & (LQP_BWD_PREFACTORED | LQP_BWD_REPORTED)), host_report);
+    BwdCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.linsolve = linsolve; c.host_report = host_report;
+    c.g = dl_dz; c.x = x; c.u = u; c.lams = lams; c.nus = nus; c.Q = Q; c.A = A; c.lb = lb; c.ub = ub;
+    c.rho_mode = rho_mode; c.rho_value = rho_value; c.rho_in = rho_in;
+    c.dQ = dQ; c.dp = dp; c.dA = dA; c.db = db; c.dlb = dlb; c.dub = dub; c.fail_index = fail_index;
+    return backward_call(c);
 }
 
 int lqp_boxqp_backward_kkt(void* stream, int dtype, int B, int n, int m, const void* dl_dz, const void* x,
@@ -2251,12 +2320,13 @@ int lqp_boxqp_backward_kkt(void* stream, int dtype, int B, int n, int m, const v
     if (bad_dims(dtype, B, n, m) || !dl_dz || !x || !lams || !Q || !lb || !ub || !workspace) return LQP_ERR_INVALID;
     if (m > 0 && (!A || !nus)) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LQP_F32)
-        return backward_impl<float>(st, B, n, m, dl_dz, x, nullptr, lams, nus, Q, A, lb, ub, 1, 1.0, nullptr, dQ, dp, dA, db, dlb,
-                                    dub, fail_index, workspace, workspace_bytes, linsolve, host_report, 1);
-    return backward_impl<double>(st, B, n, m, dl_dz, x, nullptr, lams, nus, Q, A, lb, ub, 1, 1.0, nullptr, dQ, dp, dA, db, dlb,
-                                 dub, fail_index, workspace, workspace_bytes, 1, host_report, 1);
+    BwdCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.linsolve = linsolve; c.host_report = host_report;
+    c.g = dl_dz; c.x = x; c.lams = lams; c.nus = nus; c.Q = Q; c.A = A; c.lb = lb; c.ub = ub;
+    c.dQ = dQ; c.dp = dp; c.dA = dA; c.db = db; c.dlb = dlb; c.dub = dub; c.fail_index = fail_index;
+    c.kkt = true;
+    return backward_call(c);
 }
 
 size_t lqp_spd_inverse_workspace_bytes(int dtype, int B, int n) {
@@ -2285,7 +2355,7 @@ int lqp_spd_inverse_batched(void* stream, int dtype, int B, int n, const void* K
     { ProfScope ps(st, PC_SPD_INV);
       hipLaunchKernelGGL(dense_fn, dim3(B), dim3(LQP_NT), lds, st, (const float*)K_in, (float*)Kinv_out, Hs,
                          (int*)info_out, n, Ks, Yg); }
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 size_t lqp_lu_factor_workspace_bytes(int dtype, int B, int N) {
@@ -2335,9 +2405,8 @@ int lqp_lu_solve_batched(void* stream, int dtype, int B, int N, int k, const voi
 
 size_t lqp_kkt_solve_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    int *piv, *dest, *info;
-    if (dtype == LQP_F32) { float *M, *pk, *rhs; return carve_kkt<float>(nullptr, B, n, m, M, pk, rhs, piv, dest, info); }
-    double *M, *pk, *rhs; return carve_kkt<double>(nullptr, B, n, m, M, pk, rhs, piv, dest, info);
+    if (dtype == LQP_F32) { BwdParams<float> P; return carve_backward<float>(nullptr, B, n, m, P, true); }
+    BwdParams<double> P; return carve_backward<double>(nullptr, B, n, m, P, true);
 }
 
 int lqp_kkt_solve(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
@@ -2361,7 +2430,7 @@ int lqp_qp_outer_grads(void* stream, int dtype, int B, int n, int m, const void*
     else
         hipLaunchKernelGGL(k_outer_grads<double>, dim3(B), dim3(LQP_NT), 0, st, (const double*)dx, (const double*)x,
                            (const double*)dnu, (const double*)nus, n, m, (double*)dQ, (double*)dA);
-    return hipGetLastError() == hipSuccess ? LQP_OK : LQP_ERR_HIP;
+    return last_error();
 }
 
 }  // extern "C"

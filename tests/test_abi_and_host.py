@@ -37,11 +37,38 @@ def test_workspace_queries_and_argument_checks_without_gpu():
     assert lib.lqp_boxqp_forward_workspace_bytes(0, 128, 500, 1) > 128 * 512 * 512 * 4 * 2
     assert lib.lqp_boxqp_forward_workspace_bytes(7, 1, 1, 0) == 0          # unknown dtype
     assert lib.lqp_lu_packed_bytes(1, 2, 100) > 2 * 128 * 128 * 8
+    # the KKT solve's and the backward's workspaces share one carve: (dtype, B, n, m) -> bytes of each, as every build so far gave them
+    for (dt, B, n, m), (kkt, bwd) in {(0, 3, 40, 3): (150272, 152576), (0, 1, 1, 0): (50432, 51456), (0, 2, 513, 17): (5617664, 5631488),
+                                      (1, 3, 40, 3): (298496, 302336), (1, 1, 1, 0): (99840, 101376),
+                                      (1, 2, 513, 17): (11225600, 11248640)}.items():
+        assert lib.lqp_kkt_solve_workspace_bytes(dt, B, n, m) == kkt, (dt, B, n, m)
+        assert lib.lqp_boxqp_backward_fp_workspace_bytes(dt, B, n, m) == bwd, (dt, B, n, m)
     # null pointers are rejected before anything touches the device
     ctl = _lib.BoxQPCtrl(max_iters=10, check_solved=1)
     assert lib.lqp_boxqp_forward(None, 0, 1, 4, 0, None, None, None, None, None, None, ctypes.byref(ctl), None,
                                  None, None, None, None, None, None, None, None, 0) == 1
     assert lib.lqp_status_string(3).decode().startswith("singular")
+
+
+@pytest.mark.parametrize("dt", [0, 1])
+def test_backward_refuses_before_it_touches_anything(monkeypatch, dt):
+    """A workspace one byte short, and a prefactor call for a form without phases (LQP_BWD_FULL=1): the status comes back
+    before any launch -- no GPU is needed to see it -- and before the report words or fail_index are written."""
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(1 << 16)
+    p = ctypes.c_void_p(ctypes.addressof(buf))            # (never dereferenced on these paths)
+    B, n, m = 3, 40, 3
+    need = lib.lqp_boxqp_backward_fp_workspace_bytes(dt, B, n, m)
+    fail, rep = ctypes.c_int32(-5), (ctypes.c_int32 * B)(7, 7, 7)
+    rp = ctypes.cast(rep, ctypes.c_void_p)
+    assert lib.lqp_boxqp_backward_fp(None, dt, B, n, m, p, p, p, p, p, p, p, p, p, 1, 1.0, None, p, p, p, p, p, p,
+                                     ctypes.byref(fail), p, need - 1, 2, rp) == 2
+    assert lib.lqp_boxqp_backward_fp_prefactor(None, dt, B, n, m, p, p, p, p, p, p, p, need - 1, 2, rp) == 2
+    assert lib.lqp_boxqp_backward_kkt(None, dt, B, n, m, p, p, p, p, p, p, p, p, p, p, p, p, p, p, ctypes.byref(fail), p,
+                                      need - 1, 1, rp) == 2
+    monkeypatch.setenv("LQP_BWD_FULL", "1")
+    assert lib.lqp_boxqp_backward_fp_prefactor(None, dt, B, n, m, p, p, p, p, p, p, p, need, 2, rp) == 6
+    assert list(rep) == [7, 7, 7] and fail.value == -5
 
 
 def test_control_factory_and_resolution_traps():

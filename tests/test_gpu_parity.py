@@ -1002,6 +1002,91 @@ def test_backward_factorisation_ahead_of_the_cotangent_falls_back(dev):
             assert torch.isfinite(t1).all() and torch.equal(t1, t2), (dtype, ls)
 
 
+# Launches per kernel class of one backward, by form and by way of calling it: "one" = lqp_boxqp_backward_fp / _kkt alone,
+# "pre" = lqp_boxqp_backward_fp_prefactor, "run" = the solve-only call behind it.  Synchronous calls with a report buffer.
+_BWD_CLASSES = ("bwd_build", "bwd_cholesky", "lu_factor", "pack", "packed_solve", "bwd_epilogue", "misc")
+_CHOL = dict(one=(1, 1, 0, 0, 0, 1, 0), pre=(1, 1, 0, 0, 0, 0, 0), run=(0, 1, 0, 0, 0, 1, 0))      # build | factor (+ solves) | epilogue
+# reduced LU: build, LU, info words to the host, pack | [gather,] solve, residual (a bwd_build launch), correction solve, epilogue
+_LU = dict(one=(2, 0, 1, 1, 2, 1, 1), pre=(1, 0, 1, 1, 0, 0, 1), run=(2, 0, 0, 0, 2, 1, 0))
+_LU_NOREFINE = dict(one=(1, 0, 1, 1, 1, 1, 1), pre=(1, 0, 1, 1, 0, 0, 1), run=(1, 0, 0, 0, 1, 1, 0))
+_LU_LATE = dict(_LU, one=(2, 0, 1, 1, 2, 1, 0))      # LQP_BWD_EARLY=0: the epilogue reports, a prefactor call still does itself
+_ONE_LU = dict(one=(1, 0, 1, 1, 1, 1, 1))            # full system, KKT: no phases, no refinement
+_BWD_SCHEDULES = [
+    # id, form, dtype, n, B, m, linsolve, env, counts
+    ("chol_m0", "fp", torch.float32, 40, 3, 0, 2, {}, _CHOL),
+    ("chol_m2", "fp", torch.float32, 40, 3, 2, 2, {}, _CHOL),
+    ("chol_m3_four_rhs", "fp", torch.float32, 40, 3, 3, 2, {}, _CHOL),
+    ("chol_B129", "fp", torch.float32, 40, 129, 1, 2, {}, _CHOL),
+    ("lu_f32", "fp", torch.float32, 40, 3, 3, 1, {"LQP_BWD_REFINE": "1"}, _LU),
+    ("lu_f64", "fp", torch.float64, 40, 3, 3, 1, {"LQP_BWD_REFINE": "1"}, _LU),
+    ("lu_f64_asked_for_chol", "fp", torch.float64, 40, 3, 3, 2, {}, _LU),
+    ("lu_f32_norefine", "fp", torch.float32, 40, 3, 3, 1, {"LQP_BWD_REFINE": "0"}, _LU_NOREFINE),
+    ("lu_f64_norefine", "fp", torch.float64, 40, 3, 3, 1, {"LQP_BWD_REFINE": "0"}, _LU_NOREFINE),
+    ("lu_f32_two_workgroups", "fp", torch.float32, 200, 3, 2, 1, {}, _LU),
+    ("full_f32", "fp", torch.float32, 40, 3, 3, 1, {"LQP_BWD_FULL": "1"}, _ONE_LU),
+    ("full_f64", "fp", torch.float64, 40, 3, 3, 1, {"LQP_BWD_FULL": "1"}, _ONE_LU),
+    ("kkt_f32", "kkt", torch.float32, 40, 3, 3, 1, {}, _ONE_LU),
+    ("kkt_f64", "kkt", torch.float64, 40, 3, 3, 1, {}, _ONE_LU),
+    ("kkt_f32_chol", "kkt", torch.float32, 40, 3, 3, 2, {}, dict(one=_CHOL["one"])),
+    ("chol_late_report", "fp", torch.float32, 40, 3, 2, 2, {"LQP_BWD_EARLY": "0"}, _CHOL),
+    ("lu_f32_late_report", "fp", torch.float32, 40, 3, 3, 1, {"LQP_BWD_EARLY": "0"}, _LU_LATE),
+    ("chol_stream_sync", "fp", torch.float32, 40, 3, 2, 2, {"LQP_SYNC_PLAN": "0"}, _CHOL),
+    ("lu_f32_stream_sync", "fp", torch.float32, 40, 3, 3, 1, {"LQP_SYNC_PLAN": "0"}, _LU),
+]
+
+
+@pytest.mark.parametrize("form,dtype,n,B,m,linsolve,env,counts", [r[1:] for r in _BWD_SCHEDULES], ids=[r[0] for r in _BWD_SCHEDULES])
+def test_backward_schedules_launch_by_launch(dev, monkeypatch, form, dtype, n, B, m, linsolve, env, counts):
+    """Every form of the backward (Cholesky of Q_FF, reduced LU, full-system LU, KKT) in every way of calling it: the launches
+    per kernel class are the ones written in _BWD_SCHEDULES, prefactor + solve-only gives the bits of the one call, and a form
+    without phases answers the prefactor call with "unsupported" before it has launched anything."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    Q, _, _, _, lb, ub = O.create_qp_data(n, B, seed=n + B + m, with_eq=False)
+    g = torch.Generator().manual_seed(100 + n + m)
+    A = torch.randn(B, m, n, generator=g) if m else None
+    x = 0.3 * torch.randn(B, n, 1, generator=g)
+    u = torch.where(torch.rand(B, n, 1, generator=g) < 0.25, 4.0 * torch.sign(x), torch.zeros_like(x))      # x + u leaves the box: not free
+    lams = 0.1 * torch.rand(B, 2 * n, 1, generator=g)
+    nus = torch.randn(B, m, 1, generator=g) if m else None
+    cot = torch.randn(B, n, 1, generator=g)
+    Q, A, lb, ub, x, u, lams, nus, cot = (None if t is None else t.to(dtype).to(dev) for t in (Q, A, lb, ub, x, u, lams, nus, cot))
+    want = dict(dQ=True, dp=True, dA=True, db=True, dlb=True, dub=True)
+
+    def counted(fn):
+        _lib.profile(enable=True, reset=True)
+        try:
+            out = fn()
+            torch.cuda.synchronize()
+            used = _lib.profile()
+        finally:
+            _lib.profile(enable=False)
+        return out, tuple(used[c][1] for c in _BWD_CLASSES)
+
+    if form == "kkt":
+        grads, c_one = counted(lambda: SB._kkt_backward(cot, x, lams, nus, Q, A, lb, ub, flags=(True, True), linsolve=linsolve))
+        assert c_one == counts["one"], c_one
+        assert all(torch.isfinite(t).all() for t in grads[:6] if t is not None)
+        return
+    prepare = lambda pre: SB._fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, 1.0, want, sync=True, linsolve=linsolve, prefactor=pre)
+    if "pre" not in counts:          # no phases: the prefactor call refuses, the backward call then runs in full
+        prep, c_pre = counted(lambda: prepare(True))
+        assert prep["pref"] is None and c_pre == (0,) * len(_BWD_CLASSES), c_pre
+        grads, c_one = counted(lambda: SB._fp_backward_run(prep, cot))
+        assert c_one == counts["one"], c_one
+        assert all(torch.isfinite(t).all() for t in grads[:6] if t is not None)
+        return
+    g_one, c_one = counted(lambda: SB._fp_backward_run(prepare(False), cot))
+    prep, c_pre = counted(lambda: prepare(True))
+    assert prep["pref"] is not None and prep["pref_reported"]
+    g_two, c_run = counted(lambda: SB._fp_backward_run(prep, cot))
+    assert (c_one, c_pre, c_run) == (counts["one"], counts["pre"], counts["run"]), (c_one, c_pre, c_run)
+    for t1, t2 in zip(g_one[:6], g_two[:6]):
+        assert (t1 is None) == (t2 is None)
+        if t1 is not None:
+            assert torch.isfinite(t1).all() and torch.equal(t1, t2)
+
+
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_shared_lu_that_times_out_degrades(dev, monkeypatch, dtype):
     """The two-workgroup LU with its partner workgroups missing (LQP_DBG_LU2_ABSENT: what a chip whose CUs are held by somebody

@@ -1,6 +1,6 @@
 """The schedules of the forward solve and of its backward, as data (no GPU needed to import this module).
 
-Every row names one tier the library can select by itself (plan_forward / backward_impl in csrc/lqp_amd.hip) and says how to
+Every row names one tier the library can select by itself (plan_forward / plan_backward in csrc/lqp_amd.hip) and says how to
 reach it: shape, dtype, batch size -- a symbolic expression of the CU count --, control keys and LQP_* environment overrides.
 It also says what the forward must report having run (`sig`, compared with sol["_stats"]) and how many iterations the solve is
 pinned to (`K`).  tests/test_gpu_tiers.py runs every row on the GPU against the CPU oracle: the truth is the oracle in float64,
