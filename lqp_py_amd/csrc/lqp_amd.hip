@@ -198,7 +198,7 @@ int env_int(const char* name, int dflt) {
     X(hot_past, "LQP_HOT_PAST", 1)                    /* the persistent two-workgroup loop runs on past rho events that change nothing */ \
     X(hot_rounds, "LQP_HOT_ROUNDS", 2)                /* with a GIVEN rho, rounds of {rho update, gated refactorisation, hot loop again} enqueued behind the first hot launch */ \
     X(bwd_equil, "LQP_BWD_EQUIL", 1)                  /* power-of-two symmetric equilibration of the Cholesky backward's free-set block */ \
-    X(bwd_f16, "LQP_BWD_F16", 1)                      /* the backward's look-ahead Cholesky with its tile products on the float16 pipe (with LQP_SPD_F16) */ \
+    X(bwd_f16, "LQP_BWD_F16", 1)                      /* the backward's look-ahead Cholesky with its tile products on the float16 pipe (with LQP_SPD_F16; backward='kkt' keeps float32 products) */ \
     X(spd_turns, "LQP_SPD_TURNS", 1)                  /* more matrices than half the CUs -> the resident sweep anyway, its pairs taking turns on the chip */ \
     X(spd_f16, "LQP_SPD_F16", 1)                      /* the resident sweep's panel products on the float16 matrix pipe (two-half operands); 0: float32 matrix instructions */ \
     X(spd_split, "LQP_SPD_SPLIT", -1) \
@@ -1536,7 +1536,10 @@ int plan_backward(const BwdCall& c, const Knobs& k, const int retry, BwdPlan<T>&
         if constexpr (sizeof(T) == 4) {
             plan.chol_fn = nr == 4 ? k_bwd_chol_solve<4> : k_bwd_chol_solve<0>;
 #if LQP_PIV_MFMA
-            if (k.spd_f16 != 0 && k.bwd_f16 != 0) plan.chol_fn = nr == 4 ? k_bwd_chol_solve<4, true> : k_bwd_chol_solve<0, true>;
+            // (not the KKT backward: its weights span 1e-8 .. 1e8, and dlb / dub = lam dx / slack divide the dx of a variable at its
+            //  bound by 1e-8: with the two-half products they came out at 5 to 19 times the error of a float32 LAPACK solve, with
+            //  float32 products at 1.2 times at most -- tests/kkt_table.py, row chol_bwdf16off_n330)
+            if (k.spd_f16 != 0 && k.bwd_f16 != 0 && !c.kkt) plan.chol_fn = nr == 4 ? k_bwd_chol_solve<4, true> : k_bwd_chol_solve<0, true>;
 #endif
         }
         plan.chol_lds = bwd_chol_lds_bytes(n, m, nr);

@@ -176,7 +176,7 @@ def _kkt_backward(dl_dz, x, lams, nus, Q, A, lb, ub, flags=None, linsolve=1, wan
     true the whole backward is the library's (lqp_boxqp_backward_kkt: the reduced system on the fixed-point backward's
     kernels, gradients formed in its epilogue); since round 5 the one-sided and unbounded cases too, with the reference's
     bookkeeping of which half of dl_dh goes where (:565-584) applied to the kernel's outputs.  _KKT_NATIVE = False keeps
-    the composition below."""
+    the composition below.  Pinned by tests/kkt_table.py: every form and entry against the oracle's float64 solve_box_qp_grad_kkt."""
     from .solve_qp_eqcon_torch import _kkt_solve
     _lib.require_gpu(dl_dz, x, lams, nus, Q, A, lb, ub)
     n = Q.shape[1]

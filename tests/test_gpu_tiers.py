@@ -4,6 +4,7 @@ For each row: the HIP solve with eps_abs = eps_rel = 1e-12 and max_iters = K + 1
 row's signature; the truth is the oracle in float64 on the same inputs, the budget the oracle in float32 (the same algorithm
 with LAPACK's rounding).  Float32 rows: |hip - t64| <= R |t32 - t64| + F scale for x, z, u, lams, nus, rho and for the fixed-point
 gradients of a fixed cotangent through the module (the prefactored backward of the row's forward); float64 rows: 1e-9 scale.
+The rows with backward='kkt' compare their gradients with the oracle's KKT-system backward of the HIP solve's own x, lams, nus.
 Rows that force a knob run once more with it flipped and must differ observably (or, `same`, give the same bits).  Every
 ratio |hip - t64| / |t32 - t64| goes to the session's parity report (tests/parity_report.py), case "tier:<row>".
 """
@@ -104,9 +105,17 @@ def test_tier_against_the_pinned_oracle(dev, cus, monkeypatch, name):
     # ---- outputs and gradients on the sampled problems ----
     hip = {k: _pick(sol[k], idx, dev) for k in T.OUTPUTS}
     res = T.compare(r, hip, t32, t64)
-    if r["ctl"].get("backward", "fixed_point") != "kkt":        # (the oracle's backward is the fixed-point one)
-        hg = {k: _pick(v, idx, dev) for k, v in run["grads"].items()}
-        res.update({k: v for k, v in T.compare(r, hg, None if t32 is None else t32["grads"], t64["grads"], keys=T.GRADS).items()})
+    hg = {k: _pick(v, idx, dev) for k, v in run["grads"].items()}
+    if r["ctl"].get("backward", "fixed_point") != "kkt":
+        g32, g64 = None if t32 is None else t32["grads"], t64["grads"]
+    else:
+        # backward='kkt' is a function of the solve's own x, lams, nus: the oracle's KKT backward on the HIP solve's values, converted
+        # exactly to float64 for the truth and evaluated in float32 for the budget (tests/test_gpu_kkt.py holds the KKT backward's own rows)
+        def kkt(dtype):
+            a = [None if t is None else t.to(dtype) for t in (cot[idx], hip["x"], hip["lams"], hip["nus"], sub[0], sub[2], sub[4], sub[5])]
+            return dict(zip(T.GRADS, O.solve_box_qp_grad_kkt(*a)[:4]))
+        g32, g64 = None if t32 is None else kkt(torch.float32), kkt(torch.float64)
+    res.update({k: v for k, v in T.compare(r, hg, g32, g64, keys=T.GRADS).items()})
     for k, rec in res.items():
         P.record(case, k, rec["err"], rec["scale"], ratio=rec.get("ratio"), budget=rec.get("budget"), bar=rec["bar"],
                  R=r["R"], F=r["F"], dtype=r["dtype"])
