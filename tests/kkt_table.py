@@ -6,6 +6,7 @@ oracle (the truth, on the float32 values converted exactly) receive the same num
 the GPU against oracle.boxqp_oracle.solve_box_qp_grad_kkt with tier_table.compare (float32 rows |hip - t64| <= R |t32 - t64| + F scale,
 float64 rows 1e-9 scale) and checks which form ran; tests/test_kkt_table.py checks, without a GPU, the oracle itself (golden g12,
 full against reduced system, the bookkeeping of one-sided batches), the coverage of the rows and that the comparator sees errors.
+tests/fp_table.py is this table's twin for the fixed-point backward (rows choose the size of the free set).
 
 Row fields:
   name, n, m, dtype ("f32" | "f64"), B (int, or an expression of `cus`)

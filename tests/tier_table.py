@@ -7,7 +7,8 @@ pinned to (`K`).  tests/test_gpu_tiers.py runs every row on the GPU against the 
 the error budget is the oracle in float32 (the same algorithm with LAPACK's rounding), see `compare`.  tests/test_tier_table.py
 checks, without a GPU, that the rows cover every schedule-selecting knob and both sides of every size threshold, and that the
 comparator can see a one-tile error of 1e-4.  The rows with backward='kkt' compare their gradients with the oracle's KKT-system
-backward; tests/kkt_table.py holds that backward's own rows (forms, block counts, one-sided batches).
+backward; tests/kkt_table.py holds that backward's own rows (forms, block counts, one-sided batches).  tests/fp_table.py holds the
+fixed-point backward's own rows: synthetic fixed points whose free set has a chosen size, all six gradients.
 
 Row fields:
   name, n, m, dtype ("f32" | "f64"), B (int, or an expression of `cus` such as "cus//4 + 1")
