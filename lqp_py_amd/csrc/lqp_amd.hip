@@ -18,6 +18,7 @@
 #include <mutex>
 #include <vector>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 
 using namespace lqp;
@@ -234,6 +235,7 @@ const Knobs& knobs() {
 // (info word -7: the waits are bounded, the kernels drain) the call is repeated ONCE with one workgroup per matrix (SoloScope).
 thread_local bool t_single_wg_lu = false;
 unsigned long long* g_lu_dbg = nullptr;     // optional device buffer (4 counters per problem), debug only
+std::atomic<unsigned int> g_unroll_run{1u};     // launches of the two-workgroup unroll sweep so far: each one's hand-off words carry its number
 
 // ---- LU launch: pick panel width / trailing-update flavour --------------------
 template <typename T, int PB, bool MFMA, int NT>
@@ -1769,84 +1771,142 @@ int kkt_solve_impl(hipStream_t st, int B, int n, int m, const void* Q, const voi
     return LQP_OK;
 }
 
-bool bad_dims(int dtype, int B, int n, int m) {
-    return (dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1 || m < 0;
-}
+// ---------------------------------------------------------------------------
+// unroll=True: backward through the unrolled loop (lqp_unroll.hpp)
+// ---------------------------------------------------------------------------
+// one unroll call as its entry point received it (lqp_boxqp_unroll_backward, _backward_lu, _tape_segment, _tape_finish)
+struct UnrollCall {
+    hipStream_t st = nullptr;
+    int dtype = LQP_F32, B = 0, n = 0, m = 0, iters = 0;
+    const void* fwd_ws = nullptr; size_t fwd_ws_bytes = 0;      // the solve's own workspace (null: _tape_finish reads none)
+    void* scratch = nullptr; size_t scratch_bytes = 0;
+    const void* g = nullptr;
+    void *dQs = nullptr, *dps = nullptr, *dAs = nullptr, *dbs = nullptr, *dlbs = nullptr, *dubs = nullptr, *drho = nullptr, *dD = nullptr;
+    // _tape_segment alone: x-updates [k0, k1) with the epoch's packed factor and rho (lqp_unroll.hpp, UnrollLuParams)
+    int k0 = 0, k1 = 0, mode = 0, inj_k = -1;
+    const void *packed_buf = nullptr, *rho = nullptr, *inj = nullptr;
+    void* state = nullptr;
+    void **zrows = nullptr, **urows = nullptr, **xrows = nullptr;
+};
 
-}  // namespace
-
-// ===========================================================================
-namespace {
-// ---- the tape whose x-update is the pivoted LU (float32 / float64, any m): lqp_unroll.hpp, k_unroll_sweep_lu ----
-template <typename T> struct UnrollLuCarve { UnrollLuParams<T> U; size_t bytes; };
-template <typename T>
-static UnrollLuCarve<T> carve_unroll_lu(void* ws, int B, int n, int m, int TT, bool segments = false) {
-    UnrollLuCarve<T> c;
-    memset(&c.U, 0, sizeof(c.U));
+// UP: UnrollParams, the tape of the symmetric x-update (float32), or UnrollLuParams<T>, the tape of the pivoted LU (any m)
+template <typename UP> constexpr bool kSymTape = std::is_same<UP, UnrollParams>::value;
+// the scratch of a tape of TT x-updates, U zeroed and carved -> bytes
+template <typename T, typename UP>
+size_t carve_tape(void* ws, int B, int n, int m, int TT, bool segments, UP& U) {
+    memset(&U, 0, sizeof(U));
     Carver cv(ws);
-    const int mm = m > 0 ? m : 1;
-    c.U.X = cv.take<T>((size_t)B * TT * n);
-    c.U.W = cv.take<T>((size_t)B * TT * n);
-    c.U.DX = cv.take<T>((size_t)B * TT * n);
-    c.U.NU = cv.take<T>((size_t)B * TT * mm);
-    c.U.DNU = cv.take<T>((size_t)B * TT * mm);
-    c.U.MK = cv.take<signed char>((size_t)B * TT * n);
-    if (segments) {             // (a tape in segments also keeps z_{k+1}, u_{k+1}: the rho adaptation reads them)
-        c.U.Zr = cv.take<T>((size_t)B * TT * n);
-        c.U.Ur = cv.take<T>((size_t)B * TT * n);
+    const size_t rows = (size_t)B * TT, mm = m > 0 ? m : 1;
+    U.X = cv.take<T>(rows * n);
+    U.W = cv.take<T>(rows * n);
+    U.DX = cv.take<T>(rows * n);
+    U.NU = cv.take<T>(rows * mm);
+    if constexpr (!kSymTape<UP>) U.DNU = cv.take<T>(rows * mm);
+    U.MK = cv.take<signed char>(rows * n);
+    if constexpr (!kSymTape<UP>) {
+        if (segments) {             // (a tape in segments also keeps z_{k+1}, u_{k+1}: the rho adaptation reads them)
+            U.Zr = cv.take<T>(rows * n);
+            U.Ur = cv.take<T>(rows * n);
+        }
+        U.inj_k = -1;
     }
-    c.U.inj_k = -1;
-    c.bytes = cv.off + kAlign;
-    return c;
+    return cv.off + kAlign;
 }
 
-// one segment [k0, k1) of a tape whose factor changes along it (a solve in which rho was adapted): replay and / or reverse walk
-// with the epoch's packed factor and rho (lqp_unroll.hpp, UnrollLuParams)
-template <typename T>
-static int unroll_tape_segment_impl(hipStream_t st, int B, int n, int m, const void* fwd_workspace, size_t fwd_workspace_bytes, int iters,
-                                    int k0, int k1, int mode, const void* packed_buf, const void* rho, void* state, int inj_k,
-                                    const void* inj, const void* dl_dx, void* dps, void* dlbs, void* dubs, void* drho, void* dD,
-                                    void* scratch, size_t scratch_bytes, void** zrows, void** urows, void** xrows) {
-    FwdLayout<T> L = carve_forward<T>((void*)fwd_workspace, B, n, m);
-    if (fwd_workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-    const FwdParams<T>& P = L.P;
-    const int TT = iters + 1;
-    UnrollLuCarve<T> c = carve_unroll_lu<T>(scratch, B, n, m, TT, true);
-    if (scratch_bytes < c.bytes) return LQP_ERR_WORKSPACE;
-    if (zrows) *zrows = c.U.Zr;
-    if (urows) *urows = c.U.Ur;
-    if (xrows) *xrows = c.U.X;
-    if (k1 <= k0) return LQP_OK;             // (a query of the row pointers)
-    UnrollLuParams<T>& U = c.U;
-    U.T_ = TT; U.k0 = k0; U.k1 = k1; U.mode = mode;
-    if (packed_buf) {
-        int* dest; T* packed;
-        carve_packed<T>((void*)packed_buf, B, P.N, dest, packed);
-        U.packed_ov = packed; U.dest_ov = dest;
+// Both workspaces of a call, checked in one order by every entry: the forward's (P: null when the entry reads none), what the symmetric
+// x-update takes, the tape's scratch.  U comes back carved and otherwise zero.
+template <typename T, typename UP>
+int carve_unroll_call(const UnrollCall& c, const bool segments, FwdParams<T>* P, UP& U, int& TT) {
+    if (P) {
+        const FwdLayout<T> L = carve_forward<T>((void*)c.fwd_ws, c.B, c.n, c.m);
+        if (c.fwd_ws_bytes < L.bytes) return LQP_ERR_WORKSPACE;
+        *P = L.P;
+        if (kSymTape<UP> && (P->Ks > SPD_BIGK || c.m > SPD_MAXM)) return LQP_ERR_UNSUPPORTED;      // (what the symmetric x-update takes)
     }
-    U.rho_ov = (const T*)rho;
-    U.state = (T*)state;
-    U.inj_k = inj ? inj_k : -1; U.inj = (const T*)inj;
-    U.g = (const T*)dl_dx;
-    U.dps = (T*)dps; U.dlbs = (T*)dlbs; U.dubs = (T*)dubs; U.dD = (T*)dD; U.drho = (T*)drho;
+    TT = c.iters + 1;
+    return c.scratch_bytes < carve_tape<T>(c.scratch, c.B, c.n, c.m, TT, segments, U) ? LQP_ERR_WORKSPACE : LQP_OK;
+}
+template <typename T, typename UP> void tape_outputs(const UnrollCall& c, UP& U) {
+    U.g = (const T*)c.g;
+    U.dps = (T*)c.dps; U.dlbs = (T*)c.dlbs; U.dubs = (T*)c.dubs; U.dD = (T*)c.dD; U.dAs = (T*)c.dAs; U.dbs = (T*)c.dbs; U.drho = (T*)c.drho;
+}
+
+// ---- the symmetric tape (float32): which sweep a call launches, decided before the launch ----
+typedef void (*UnrollOneFn)(const FwdParams<float>, const UnrollParams);
+typedef void (*UnrollSplitFn)(const FwdParams<float>, const UnrollParams, const unsigned int);
+struct UnrollSymPlan {
+    UnrollSplitFn split_fn = nullptr;       // k_unroll_sweep_split: two workgroups per QP, or ...
+    UnrollOneFn one_fn = nullptr;           // ... k_unroll_sweep: one
+    int lds = 0, grid = 0;
+};
+// Ks (5 ... SPD_MAXK) -> the instance of the two-workgroup sweep and its LDS bytes (m <= 1 has an instance of its own at Ks = 8 only)
+UnrollSplitFn unroll_split_fn(const int Ks, const int m, int& lds) {
+#define LQP_KS_CASE(KS) case KS: lds = unroll_split_lds_bytes<KS>(m); return k_unroll_sweep_split<KS, SPD_MAXM>
+    switch (Ks) {
+        case 8: lds = unroll_split_lds_bytes<8>(m); return m <= 1 ? k_unroll_sweep_split<8, 1> : k_unroll_sweep_split<8, SPD_MAXM>;
+        LQP_KS_CASE(7); LQP_KS_CASE(6); default: LQP_KS_CASE(5);
+    }
+#undef LQP_KS_CASE
+}
+// two workgroups per QP when half the chip would idle (the split loop's products, lqp_unroll.hpp: k_unroll_sweep_split) and all of
+// them are resident at once; launches nothing
+UnrollSymPlan plan_unroll_sym(const FwdParams<float>& P, const int rl, const Knobs& k) {
+    UnrollSymPlan plan;
+    Device d;
+    if (P.xchg && P.Ks >= 5 && P.Ks <= SPD_MAXK && k.unroll_split != 0) {
+        const UnrollSplitFn fn = unroll_split_fn(P.Ks, P.m, plan.lds);
+        if (current_device_cus(&d.dev, &d.cus) && fits(d, fn, 512, plan.lds, shared_grid(P.B, 2))) plan.split_fn = fn;
+    }
+    if (plan.split_fn) {
+        plan.grid = (k.dbg_loop_absent & 4) ? P.B : shared_grid(P.B, 2);
+    } else {
+        plan.one_fn = P.m <= 1 ? k_unroll_sweep<1> : k_unroll_sweep<SPD_MAXM>;
+        plan.lds = unroll_lds_bytes(P.m, P.Ks, rl);
+        plan.grid = P.B;
+    }
+    return plan;
+}
+
+int unroll_backward_sym_impl(const UnrollCall& c) {
+    FwdParams<float> P; UnrollParams U; int T;
+    int rc = carve_unroll_call<float>(c, false, &P, U, T);
+    if (rc) return rc;
+    U.T = T;
+    U.rl = unroll_lds_blocks(c.m, P.Ks);
+    tape_outputs<float>(c, U);
+    const UnrollSymPlan plan = plan_unroll_sym(P, U.rl, knobs());
+    if (plan.split_fn) {
+        ProfScope ps(c.st, PC_UNROLL);
+        hipLaunchKernelGGL(plan.split_fn, dim3(plan.grid), dim3(512), plan.lds, c.st, P, U, g_unroll_run.fetch_add(1u));
+    } else {
+        rc = ensure_lds((const void*)plan.one_fn, plan.lds);
+        if (rc) return rc;
+        ProfScope ps(c.st, PC_UNROLL);
+        hipLaunchKernelGGL(plan.one_fn, dim3(plan.grid), dim3(LQP_NT), plan.lds, c.st, P, U);
+    }
+    if (c.dQs) {
+        ProfScope ps(c.st, PC_UNROLL);
+        const int tiles = (c.n + 63) / 64;
+        hipLaunchKernelGGL(k_unroll_outer<>, dim3(tiles, tiles, c.B), dim3(256), 0, c.st, (const float*)U.DX, (const float*)U.X,
+                           (float*)c.dQs, c.n, T);
+    }
+    return last_error();
+}
+
+// ---- the tape whose x-update is the pivoted LU (float32 / float64, any m): the launch steps ----
+template <typename T>
+int enqueue_lu_sweep(hipStream_t st, const FwdParams<T>& P, const UnrollLuParams<T>& U) {
     const int lds = unroll_lu_lds_bytes<T>(P.Np);
     auto fn = k_unroll_sweep_lu<T>;
     const int rc = ensure_lds((const void*)fn, lds);
     if (rc) return rc;
     ProfScope ps(st, PC_UNROLL);
-    hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, st, P, U);
-    return last_error();
+    hipLaunchKernelGGL(fn, dim3(P.B), dim3(LQP_NT), lds, st, P, U);
+    return LQP_OK;
 }
-
-// ... and what is summed over the whole tape once every segment has been walked: Asbar / bsbar, Qsbar
+// what is summed over the whole tape once it has been walked: Asbar / bsbar from the scratch rows, Qsbar
 template <typename T>
-static int unroll_tape_finish_impl(hipStream_t st, int B, int n, int m, int iters, void* dQs, void* dAs, void* dbs, void* scratch,
-                                   size_t scratch_bytes) {
-    const int TT = iters + 1;
-    UnrollLuCarve<T> c = carve_unroll_lu<T>(scratch, B, n, m, TT, true);
-    if (scratch_bytes < c.bytes) return LQP_ERR_WORKSPACE;
-    UnrollLuParams<T>& U = c.U;
-    U.T_ = TT; U.dAs = (T*)dAs; U.dbs = (T*)dbs;
+void enqueue_tape_sums(hipStream_t st, const UnrollLuParams<T>& U, int B, int n, int m, void* dQs) {
     if (m > 0) {
         ProfScope ps(st, PC_UNROLL);
         int slabs = (m * n + 255) / 256;
@@ -1856,45 +1916,64 @@ static int unroll_tape_finish_impl(hipStream_t st, int B, int n, int m, int iter
     if (dQs) {
         ProfScope ps(st, PC_UNROLL);
         const int tiles = (n + 63) / 64;
-        hipLaunchKernelGGL(k_unroll_outer_any<T>, dim3(tiles, tiles, B), dim3(256), 0, st, (const T*)U.DX, (const T*)U.X, (T*)dQs, n, TT);
+        hipLaunchKernelGGL(k_unroll_outer_any<T>, dim3(tiles, tiles, B), dim3(256), 0, st, (const T*)U.DX, (const T*)U.X, (T*)dQs, n, U.T_);
     }
-    return last_error();
 }
 
 template <typename T>
-static int unroll_backward_lu_impl(hipStream_t st, int B, int n, int m, const void* fwd_workspace, size_t fwd_workspace_bytes, int iters,
-                                   const void* dl_dx, void* dQs, void* dps, void* dAs, void* dbs, void* dlbs, void* dubs, void* drho,
-                                   void* dD, void* scratch, size_t scratch_bytes) {
-    FwdLayout<T> L = carve_forward<T>((void*)fwd_workspace, B, n, m);
-    if (fwd_workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-    const FwdParams<T>& P = L.P;
-    const int TT = iters + 1;
-    UnrollLuCarve<T> c = carve_unroll_lu<T>(scratch, B, n, m, TT);
-    if (scratch_bytes < c.bytes) return LQP_ERR_WORKSPACE;
-    UnrollLuParams<T>& U = c.U;
+int unroll_backward_lu_impl(const UnrollCall& c) {
+    FwdParams<T> P; UnrollLuParams<T> U; int TT;
+    int rc = carve_unroll_call<T>(c, false, &P, U, TT);
+    if (rc) return rc;
     U.T_ = TT;
-    U.g = (const T*)dl_dx;
-    U.dps = (T*)dps; U.dlbs = (T*)dlbs; U.dubs = (T*)dubs; U.dD = (T*)dD; U.dAs = (T*)dAs; U.dbs = (T*)dbs; U.drho = (T*)drho;
-    {
-        const int lds = unroll_lu_lds_bytes<T>(P.Np);
-        auto fn = k_unroll_sweep_lu<T>;
-        const int rc = ensure_lds((const void*)fn, lds);
-        if (rc) return rc;
-        ProfScope ps(st, PC_UNROLL);
-        hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, st, P, U);
-    }
-    if (m > 0) {
-        ProfScope ps(st, PC_UNROLL);
-        int slabs = (m * n + 255) / 256;
-        if (slabs > 64) slabs = 64;
-        hipLaunchKernelGGL(k_unroll_lu_eq<T>, dim3(B, slabs), dim3(256), 0, st, U, n, m);
-    }
-    if (dQs) {
-        ProfScope ps(st, PC_UNROLL);
-        const int tiles = (n + 63) / 64;
-        hipLaunchKernelGGL(k_unroll_outer_any<T>, dim3(tiles, tiles, B), dim3(256), 0, st, (const T*)U.DX, (const T*)U.X, (T*)dQs, n, TT);
-    }
+    tape_outputs<T>(c, U);
+    rc = enqueue_lu_sweep<T>(c.st, P, U);
+    if (rc) return rc;
+    enqueue_tape_sums<T>(c.st, U, c.B, c.n, c.m, c.dQs);
     return last_error();
+}
+
+// one segment [k0, k1) of a tape whose factor changes along it (a solve in which rho was adapted): replay and / or reverse walk
+// with the epoch's packed factor and rho (lqp_unroll.hpp, UnrollLuParams)
+template <typename T>
+int unroll_tape_segment_impl(const UnrollCall& c) {
+    FwdParams<T> P; UnrollLuParams<T> U; int TT;
+    const int rc = carve_unroll_call<T>(c, true, &P, U, TT);
+    if (rc) return rc;
+    if (c.zrows) *c.zrows = U.Zr;
+    if (c.urows) *c.urows = U.Ur;
+    if (c.xrows) *c.xrows = U.X;
+    if (c.k1 <= c.k0) return LQP_OK;             // (a query of the row pointers)
+    U.T_ = TT; U.k0 = c.k0; U.k1 = c.k1; U.mode = c.mode;
+    if (c.packed_buf) {
+        int* dest; T* packed;
+        carve_packed<T>((void*)c.packed_buf, c.B, P.N, dest, packed);
+        U.packed_ov = packed; U.dest_ov = dest;
+    }
+    U.rho_ov = (const T*)c.rho;
+    U.state = (T*)c.state;
+    U.inj_k = c.inj ? c.inj_k : -1; U.inj = (const T*)c.inj;
+    tape_outputs<T>(c, U);
+    const int rs = enqueue_lu_sweep<T>(c.st, P, U);
+    return rs ? rs : last_error();
+}
+
+// ... and what is summed over the whole tape once every segment has been walked
+template <typename T>
+int unroll_tape_finish_impl(const UnrollCall& c) {
+    UnrollLuParams<T> U; int TT;
+    const int rc = carve_unroll_call<T>(c, true, (FwdParams<T>*)nullptr, U, TT);
+    if (rc) return rc;
+    U.T_ = TT; U.dAs = (T*)c.dAs; U.dbs = (T*)c.dbs;
+    enqueue_tape_sums<T>(c.st, U, c.B, c.n, c.m, c.dQs);
+    return last_error();
+}
+
+// one call for either dtype: f is a generic lambda over a value of the element type, by_dtype(dtype, [&](auto t) { ... decltype(t) ... })
+template <typename F> inline auto by_dtype(const int dtype, F f) { return dtype == LQP_F32 ? f(float()) : f(double()); }
+
+bool bad_dims(int dtype, int B, int n, int m) {
+    return (dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1 || m < 0;
 }
 
 }  // namespace
@@ -1946,16 +2025,13 @@ int lqp_debug_xcd(void* stream, int blocks, void* out_dev) {
 int lqp_debug_lu_inverse(void* stream, int dtype, int B, int N, const void* packed_buf, void* X_out) {
     if (bad_dims(dtype, B, N, 0) || !packed_buf || !X_out || N > (dtype == LQP_F32 ? 2048 : 1024)) return LQP_ERR_INVALID;
     const int K = round_up(N, LQP_NB) / LQP_NB;
-    if (dtype == LQP_F32) {
-        int* dest; float* packed;
-        carve_packed<float>((void*)packed_buf, B, N, dest, packed);
-        return launch_lu_inverse<float>((hipStream_t)stream, B, N, packed, packed_blocks(K) * LQP_BLK, dest, K * LQP_NB,
-                                        (float*)X_out, (size_t)N * N, N, nullptr);
-    }
-    int* dest; double* packed;
-    carve_packed<double>((void*)packed_buf, B, N, dest, packed);
-    return launch_lu_inverse<double>((hipStream_t)stream, B, N, packed, packed_blocks(K) * LQP_BLK, dest, K * LQP_NB,
-                                     (double*)X_out, (size_t)N * N, N, nullptr);
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        int* dest; T* packed;
+        carve_packed<T>((void*)packed_buf, B, N, dest, packed);
+        return launch_lu_inverse<T>((hipStream_t)stream, B, N, packed, packed_blocks(K) * LQP_BLK, dest, K * LQP_NB, (T*)X_out,
+                                    (size_t)N * N, N, nullptr);
+    });
 }
 
 int lqp_profile_classes(void) { return PC_COUNT; }
@@ -2000,13 +2076,10 @@ int lqp_boxqp_forward_layout(int dtype, int B, int n, int m, size_t* status_offs
                              size_t* info_offset, size_t* info_bytes) {
     if (bad_dims(dtype, B, n, m) || !status_offset || !status_bytes || !info_offset || !info_bytes) return LQP_ERR_INVALID;
     char* base = (char*)4096;       // any non-null base: only offsets are used
-    if (dtype == LQP_F32) {
-        FwdLayout<float> L = carve_forward<float>(base, B, n, m);
+    by_dtype(dtype, [&](auto t) {
+        const FwdLayout<decltype(t)> L = carve_forward<decltype(t)>(base, B, n, m);
         *status_offset = (char*)L.P.status - base; *info_offset = (char*)L.P.info - base;
-    } else {
-        FwdLayout<double> L = carve_forward<double>(base, B, n, m);
-        *status_offset = (char*)L.P.status - base; *info_offset = (char*)L.P.info - base;
-    }
+    });
     *status_bytes = sizeof(int) * ST_WORDS;
     *info_bytes = sizeof(int) * (size_t)B;
     return LQP_OK;
@@ -2014,7 +2087,7 @@ int lqp_boxqp_forward_layout(int dtype, int B, int n, int m, size_t* status_offs
 
 size_t lqp_boxqp_forward_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    return dtype == LQP_F32 ? carve_forward<float>(nullptr, B, n, m).bytes : carve_forward<double>(nullptr, B, n, m).bytes;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes; });
 }
 
 int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
@@ -2030,9 +2103,9 @@ int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* 
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)
-    if (dtype == LQP_F32)
-        return forward_impl<float>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0);
-    return forward_impl<double>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0);
+    return by_dtype(dtype, [&](auto t) {
+        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0);
+    });
 }
 
 int lqp_boxqp_forward_finish(void* stream, int B, int max_iters, int check_solved, const void* host_report,
@@ -2044,24 +2117,11 @@ int lqp_boxqp_forward_finish(void* stream, int B, int max_iters, int check_solve
     return rc == LQP_RETRY_LU ? LQP_ERR_NOT_SPD : rc;
 }
 
-// ---- unroll=True: backward through the unrolled loop (lqp_unroll.hpp) ----
-struct UnrollCarve { UnrollParams U; size_t bytes; };
-static UnrollCarve carve_unroll(void* ws, int B, int n, int m, int T) {
-    UnrollCarve c;
-    memset(&c.U, 0, sizeof(c.U));
-    Carver cv(ws);
-    c.U.X = cv.take<float>((size_t)B * T * n);
-    c.U.W = cv.take<float>((size_t)B * T * n);
-    c.U.DX = cv.take<float>((size_t)B * T * n);
-    c.U.NU = cv.take<float>((size_t)B * T * (m > 0 ? m : 1));
-    c.U.MK = cv.take<signed char>((size_t)B * T * n);
-    c.bytes = cv.off + kAlign;
-    return c;
-}
-
+// ---- unroll=True: backward through the unrolled loop (the unroll section above) ----
 size_t lqp_boxqp_unroll_backward_workspace_bytes(int B, int n, int m, int iters) {
     if (B < 1 || n < 1 || m < 0 || iters < 0) return 0;
-    return carve_unroll(nullptr, B, n, m, iters + 1).bytes;
+    UnrollParams U;
+    return carve_tape<float>(nullptr, B, n, m, iters + 1, false, U);
 }
 
 int lqp_boxqp_unroll_backward(void* stream, int B, int n, int m, const void* fwd_workspace, size_t fwd_workspace_bytes,
@@ -2070,56 +2130,16 @@ int lqp_boxqp_unroll_backward(void* stream, int B, int n, int m, const void* fwd
     if (B < 1 || n < 1 || m < 0 || iters < 0 || !fwd_workspace || !dl_dx || !dps || !dlbs || !dubs || !drho || !dD || !scratch)
         return LQP_ERR_INVALID;
     if (m > 0 && (!dAs || !dbs)) return LQP_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    FwdLayout<float> L = carve_forward<float>((void*)fwd_workspace, B, n, m);
-    if (fwd_workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-    const FwdParams<float>& P = L.P;
-    if (P.Ks > SPD_BIGK || m > SPD_MAXM) return LQP_ERR_UNSUPPORTED;      // (what the symmetric x-update takes)
-    const int T = iters + 1;
-    UnrollCarve c = carve_unroll(scratch, B, n, m, T);
-    if (scratch_bytes < c.bytes) return LQP_ERR_WORKSPACE;
-    UnrollParams& U = c.U;
-    U.T = T;
-    U.rl = unroll_lds_blocks(m, P.Ks);
-    U.g = (const float*)dl_dx;
-    U.dps = (float*)dps; U.dlbs = (float*)dlbs; U.dubs = (float*)dubs; U.dD = (float*)dD;
-    U.dAs = (float*)dAs; U.dbs = (float*)dbs; U.drho = (float*)drho;
-    // two workgroups per QP when half the chip would idle (the split loop's products, lqp_unroll.hpp: k_unroll_sweep_split)
-    bool split_done = false;
-    if (P.xchg && P.Ks >= 5 && P.Ks <= SPD_MAXK && knobs().unroll_split != 0) {
-        void (*fn2)(const FwdParams<float>, const UnrollParams, const unsigned int) =
-            P.Ks == 8 ? (m <= 1 ? k_unroll_sweep_split<8, 1> : k_unroll_sweep_split<8, SPD_MAXM>)
-            : P.Ks == 7 ? k_unroll_sweep_split<7, SPD_MAXM> : P.Ks == 6 ? k_unroll_sweep_split<6, SPD_MAXM> : k_unroll_sweep_split<5, SPD_MAXM>;
-        const int lds2 = P.Ks == 8 ? unroll_split_lds_bytes<8>(m) : P.Ks == 7 ? unroll_split_lds_bytes<7>(m)
-                       : P.Ks == 6 ? unroll_split_lds_bytes<6>(m) : unroll_split_lds_bytes<5>(m);
-        Device d;
-        if (current_device_cus(&d.dev, &d.cus) && fits(d, fn2, 512, lds2, shared_grid(B, 2))) {
-            static std::atomic<unsigned int> run{1u};
-            ProfScope ps(st, PC_UNROLL);
-            hipLaunchKernelGGL(fn2, dim3((knobs().dbg_loop_absent & 4) ? B : shared_grid(B, 2)), dim3(512), lds2, st, P, U, run.fetch_add(1u));
-            split_done = true;
-        }
-    }
-    if (!split_done) {
-        const int lds = unroll_lds_bytes(m, P.Ks, U.rl);
-        auto sweep_fn = m <= 1 ? k_unroll_sweep<1> : k_unroll_sweep<SPD_MAXM>;
-        int rc = ensure_lds((const void*)sweep_fn, lds);
-        if (rc) return rc;
-        ProfScope ps(st, PC_UNROLL);
-        hipLaunchKernelGGL(sweep_fn, dim3(B), dim3(LQP_NT), lds, st, P, U);
-    }
-    if (dQs) {
-        ProfScope ps(st, PC_UNROLL);
-        const int tiles = (n + 63) / 64;
-        hipLaunchKernelGGL(k_unroll_outer<>, dim3(tiles, tiles, B), dim3(256), 0, st, (const float*)U.DX, (const float*)U.X,
-                           (float*)dQs, n, T);
-    }
-    return last_error();
+    UnrollCall c;
+    c.st = (hipStream_t)stream; c.B = B; c.n = n; c.m = m; c.iters = iters;
+    c.fwd_ws = fwd_workspace; c.fwd_ws_bytes = fwd_workspace_bytes; c.scratch = scratch; c.scratch_bytes = scratch_bytes;
+    c.g = dl_dx; c.dQs = dQs; c.dps = dps; c.dAs = dAs; c.dbs = dbs; c.dlbs = dlbs; c.dubs = dubs; c.drho = drho; c.dD = dD;
+    return unroll_backward_sym_impl(c);
 }
 
 size_t lqp_boxqp_unroll_backward_lu_workspace_bytes(int dtype, int B, int n, int m, int iters) {
     if (bad_dims(dtype, B, n, m) || iters < 0) return 0;
-    return dtype == LQP_F32 ? carve_unroll_lu<float>(nullptr, B, n, m, iters + 1).bytes : carve_unroll_lu<double>(nullptr, B, n, m, iters + 1).bytes;
+    return by_dtype(dtype, [&](auto t) { UnrollLuParams<decltype(t)> U; return carve_tape<decltype(t)>(nullptr, B, n, m, iters + 1, false, U); });
 }
 
 int lqp_boxqp_unroll_backward_lu(void* stream, int dtype, int B, int n, int m, const void* fwd_workspace, size_t fwd_workspace_bytes,
@@ -2129,18 +2149,16 @@ int lqp_boxqp_unroll_backward_lu(void* stream, int dtype, int B, int n, int m, c
         return LQP_ERR_INVALID;
     if (m > 0 && (!dAs || !dbs)) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LQP_F32)
-        return unroll_backward_lu_impl<float>(st, B, n, m, fwd_workspace, fwd_workspace_bytes, iters, dl_dx, dQs, dps, dAs, dbs, dlbs, dubs,
-                                              drho, dD, scratch, scratch_bytes);
-    return unroll_backward_lu_impl<double>(st, B, n, m, fwd_workspace, fwd_workspace_bytes, iters, dl_dx, dQs, dps, dAs, dbs, dlbs, dubs,
-                                           drho, dD, scratch, scratch_bytes);
+    UnrollCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m; c.iters = iters;
+    c.fwd_ws = fwd_workspace; c.fwd_ws_bytes = fwd_workspace_bytes; c.scratch = scratch; c.scratch_bytes = scratch_bytes;
+    c.g = dl_dx; c.dQs = dQs; c.dps = dps; c.dAs = dAs; c.dbs = dbs; c.dlbs = dlbs; c.dubs = dubs; c.drho = drho; c.dD = dD;
+    return by_dtype(dtype, [&](auto t) { return unroll_backward_lu_impl<decltype(t)>(c); });
 }
 
 size_t lqp_boxqp_unroll_tape_workspace_bytes(int dtype, int B, int n, int m, int iters) {
     if (bad_dims(dtype, B, n, m) || iters < 0) return 0;
-    return dtype == LQP_F32 ? carve_unroll_lu<float>(nullptr, B, n, m, iters + 1, true).bytes
-                            : carve_unroll_lu<double>(nullptr, B, n, m, iters + 1, true).bytes;
+    return by_dtype(dtype, [&](auto t) { UnrollLuParams<decltype(t)> U; return carve_tape<decltype(t)>(nullptr, B, n, m, iters + 1, true, U); });
 }
 
 int lqp_boxqp_unroll_tape_segment(void* stream, int dtype, int B, int n, int m, const void* fwd_workspace, size_t fwd_workspace_bytes,
@@ -2151,20 +2169,22 @@ int lqp_boxqp_unroll_tape_segment(void* stream, int dtype, int B, int n, int m, 
         return LQP_ERR_INVALID;
     if (k1 > k0 && (mode & 2) && (!dl_dx || !dps || !dlbs || !dubs || !drho || !dD)) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == LQP_F32)
-        return unroll_tape_segment_impl<float>(st, B, n, m, fwd_workspace, fwd_workspace_bytes, iters, k0, k1, mode, packed_buf, rho, state,
-                                               inj_k, inj, dl_dx, dps, dlbs, dubs, drho, dD, scratch, scratch_bytes, z_rows, u_rows, x_rows);
-    return unroll_tape_segment_impl<double>(st, B, n, m, fwd_workspace, fwd_workspace_bytes, iters, k0, k1, mode, packed_buf, rho, state,
-                                            inj_k, inj, dl_dx, dps, dlbs, dubs, drho, dD, scratch, scratch_bytes, z_rows, u_rows, x_rows);
+    UnrollCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m; c.iters = iters;
+    c.fwd_ws = fwd_workspace; c.fwd_ws_bytes = fwd_workspace_bytes; c.scratch = scratch; c.scratch_bytes = scratch_bytes;
+    c.g = dl_dx; c.dps = dps; c.dlbs = dlbs; c.dubs = dubs; c.drho = drho; c.dD = dD;
+    c.k0 = k0; c.k1 = k1; c.mode = mode; c.packed_buf = packed_buf; c.rho = rho; c.state = state; c.inj_k = inj_k; c.inj = inj;
+    c.zrows = z_rows; c.urows = u_rows; c.xrows = x_rows;
+    return by_dtype(dtype, [&](auto t) { return unroll_tape_segment_impl<decltype(t)>(c); });
 }
 
 int lqp_boxqp_unroll_tape_finish(void* stream, int dtype, int B, int n, int m, int iters, void* dQs, void* dAs, void* dbs, void* scratch,
                                  size_t scratch_bytes) {
     if (bad_dims(dtype, B, n, m) || iters < 0 || !scratch || (m > 0 && (!dAs || !dbs))) return LQP_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    return dtype == LQP_F32 ? unroll_tape_finish_impl<float>(st, B, n, m, iters, dQs, dAs, dbs, scratch, scratch_bytes)
-                            : unroll_tape_finish_impl<double>(st, B, n, m, iters, dQs, dAs, dbs, scratch, scratch_bytes);
+    UnrollCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m; c.iters = iters;
+    c.scratch = scratch; c.scratch_bytes = scratch_bytes; c.dQs = dQs; c.dAs = dAs; c.dbs = dbs;
+    return by_dtype(dtype, [&](auto t) { return unroll_tape_finish_impl<decltype(t)>(c); });
 }
 
 int lqp_unroll_scale_colmax(void* stream, int B, int n, const void* Q, void* colmax, void* argmax, void* count) {
@@ -2243,18 +2263,13 @@ int lqp_boxqp_last_residuals(void* stream, int dtype, int B, int n, int m, const
     if (bad_dims(dtype, B, n, m) || !workspace) return LQP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) return LQP_OK;
-    if (dtype == LQP_F32) {
-        FwdLayout<float> L = carve_forward<float>(const_cast<void*>(workspace), B, n, m);
-        if (workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-        hipLaunchKernelGGL(k_copy_residuals<float>, dim3((B + 255) / 256), dim3(256), 0, st, L.P.scal, (float*)primal_out,
-                           (float*)dual_out, B);
-    } else {
-        FwdLayout<double> L = carve_forward<double>(const_cast<void*>(workspace), B, n, m);
-        if (workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-        hipLaunchKernelGGL(k_copy_residuals<double>, dim3((B + 255) / 256), dim3(256), 0, st, L.P.scal, (double*)primal_out,
-                           (double*)dual_out, B);
-    }
-    return last_error();
+    return by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        const FwdLayout<T> L = carve_forward<T>(const_cast<void*>(workspace), B, n, m);
+        if (workspace_bytes < L.bytes) return (int)LQP_ERR_WORKSPACE;
+        hipLaunchKernelGGL(k_copy_residuals<T>, dim3((B + 255) / 256), dim3(256), 0, st, L.P.scal, (T*)primal_out, (T*)dual_out, B);
+        return last_error();
+    });
 }
 
 int lqp_boxqp_check_trace(void* stream, int dtype, int B, int n, int m, const void* workspace, size_t workspace_bytes,
@@ -2262,16 +2277,13 @@ int lqp_boxqp_check_trace(void* stream, int dtype, int B, int n, int m, const vo
     if (bad_dims(dtype, B, n, m) || !workspace || !trace_out || n_checks < 0) return LQP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (B == 0 || n_checks == 0) return LQP_OK;
-    const unsigned int* src;
-    if (dtype == LQP_F32) {
-        FwdLayout<float> L = carve_forward<float>(const_cast<void*>(workspace), B, n, m);
-        if (workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
+    const unsigned int* src = nullptr;
+    const size_t need = by_dtype(dtype, [&](auto t) {
+        const FwdLayout<decltype(t)> L = carve_forward<decltype(t)>(const_cast<void*>(workspace), B, n, m);
         src = L.vtrace_area;
-    } else {
-        FwdLayout<double> L = carve_forward<double>(const_cast<void*>(workspace), B, n, m);
-        if (workspace_bytes < L.bytes) return LQP_ERR_WORKSPACE;
-        src = L.vtrace_area;
-    }
+        return L.bytes;
+    });
+    if (workspace_bytes < need) return LQP_ERR_WORKSPACE;
     const int words = 2 * (n_checks < kRing ? n_checks : kRing);
     hipLaunchKernelGGL(k_copy_trace<>, dim3((words + 255) / 256), dim3(256), 0, st, src, (float*)trace_out, words);
     return last_error();
@@ -2279,8 +2291,7 @@ int lqp_boxqp_check_trace(void* stream, int dtype, int B, int n, int m, const vo
 
 size_t lqp_boxqp_backward_fp_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    if (dtype == LQP_F32) { BwdParams<float> P; return carve_backward<float>(nullptr, B, n, m, P); }
-    BwdParams<double> P; return carve_backward<double>(nullptr, B, n, m, P);
+    return by_dtype(dtype, [&](auto t) { BwdParams<decltype(t)> P; return carve_backward<decltype(t)>(nullptr, B, n, m, P); });
 }
 
 int lqp_boxqp_backward_fp_prefactor(void* stream, int dtype, int B, int n, int m, const void* x, const void* u, const void* Q,
@@ -2364,8 +2375,7 @@ int lqp_spd_inverse_batched(void* stream, int dtype, int B, int n, const void* K
 size_t lqp_lu_factor_workspace_bytes(int dtype, int B, int N) {
     if (bad_dims(dtype, B, N, 0)) return 0;
     int* piv; unsigned long long* scr;
-    if (dtype == LQP_F32) { float* M; return carve_lu<float>(nullptr, B, N, M, piv, scr); }
-    double* M; return carve_lu<double>(nullptr, B, N, M, piv, scr);
+    return by_dtype(dtype, [&](auto t) { decltype(t)* M; return carve_lu<decltype(t)>(nullptr, B, N, M, piv, scr); });
 }
 
 int lqp_lu_factor_batched(void* stream, int dtype, int B, int N, void* M_inout, int32_t* piv_out, int32_t* info_out,
@@ -2373,13 +2383,12 @@ int lqp_lu_factor_batched(void* stream, int dtype, int B, int N, void* M_inout, 
     if (bad_dims(dtype, B, N, 0) || !M_inout || !piv_out || !info_out || !workspace) return LQP_ERR_INVALID;
     if (N > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == LQP_F32 ? lu_factor_impl<float>(st, B, N, M_inout, piv_out, info_out, workspace, workspace_bytes)
-                            : lu_factor_impl<double>(st, B, N, M_inout, piv_out, info_out, workspace, workspace_bytes);
+    return by_dtype(dtype, [&](auto t) { return lu_factor_impl<decltype(t)>(st, B, N, M_inout, piv_out, info_out, workspace, workspace_bytes); });
 }
 
 size_t lqp_lu_packed_bytes(int dtype, int B, int N) {
     if (bad_dims(dtype, B, N, 0)) return 0;
-    return dtype == LQP_F32 ? packed_bytes_t<float>(B, N) : packed_bytes_t<double>(B, N);
+    return by_dtype(dtype, [&](auto t) { return packed_bytes_t<decltype(t)>(B, N); });
 }
 size_t lqp_lu_solve_workspace_bytes(int dtype, int B, int N) { return lqp_lu_packed_bytes(dtype, B, N); }
 
@@ -2387,15 +2396,14 @@ int lqp_lu_pack(void* stream, int dtype, int B, int N, const void* LU, const int
     if (bad_dims(dtype, B, N, 0) || !LU || !piv || !packed) return LQP_ERR_INVALID;
     if (N > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == LQP_F32 ? lu_pack_impl<float>(st, B, N, LU, piv, packed) : lu_pack_impl<double>(st, B, N, LU, piv, packed);
+    return by_dtype(dtype, [&](auto t) { return lu_pack_impl<decltype(t)>(st, B, N, LU, piv, packed); });
 }
 
 int lqp_lu_solve_packed(void* stream, int dtype, int B, int N, int k, const void* packed, void* rhs_inout) {
     if (bad_dims(dtype, B, N, 0) || k < 1 || !packed || !rhs_inout) return LQP_ERR_INVALID;
     if (N > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == LQP_F32 ? lu_solve_packed_impl<float>(st, B, N, k, packed, rhs_inout)
-                            : lu_solve_packed_impl<double>(st, B, N, k, packed, rhs_inout);
+    return by_dtype(dtype, [&](auto t) { return lu_solve_packed_impl<decltype(t)>(st, B, N, k, packed, rhs_inout); });
 }
 
 int lqp_lu_solve_batched(void* stream, int dtype, int B, int N, int k, const void* LU, const int32_t* piv, void* rhs_inout,
@@ -2408,8 +2416,7 @@ int lqp_lu_solve_batched(void* stream, int dtype, int B, int N, int k, const voi
 
 size_t lqp_kkt_solve_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    if (dtype == LQP_F32) { BwdParams<float> P; return carve_backward<float>(nullptr, B, n, m, P, true); }
-    BwdParams<double> P; return carve_backward<double>(nullptr, B, n, m, P, true);
+    return by_dtype(dtype, [&](auto t) { BwdParams<decltype(t)> P; return carve_backward<decltype(t)>(nullptr, B, n, m, P, true); });
 }
 
 int lqp_kkt_solve(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
@@ -2418,8 +2425,7 @@ int lqp_kkt_solve(void* stream, int dtype, int B, int n, int m, const void* Q, c
     if (m > 0 && (!A || !b || !nus)) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
-    return dtype == LQP_F32 ? kkt_solve_impl<float>(st, B, n, m, Q, p, A, b, x, nus, fail_index, workspace, workspace_bytes)
-                            : kkt_solve_impl<double>(st, B, n, m, Q, p, A, b, x, nus, fail_index, workspace, workspace_bytes);
+    return by_dtype(dtype, [&](auto t) { return kkt_solve_impl<decltype(t)>(st, B, n, m, Q, p, A, b, x, nus, fail_index, workspace, workspace_bytes); });
 }
 
 int lqp_qp_outer_grads(void* stream, int dtype, int B, int n, int m, const void* dx, const void* x, const void* dnu,
@@ -2427,12 +2433,11 @@ int lqp_qp_outer_grads(void* stream, int dtype, int B, int n, int m, const void*
     if (bad_dims(dtype, B, n, m) || !dx || !x) return LQP_ERR_INVALID;
     if (m > 0 && dA && (!dnu || !nus)) return LQP_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == LQP_F32)
-        hipLaunchKernelGGL(k_outer_grads<float>, dim3(B), dim3(LQP_NT), 0, st, (const float*)dx, (const float*)x,
-                           (const float*)dnu, (const float*)nus, n, m, (float*)dQ, (float*)dA);
-    else
-        hipLaunchKernelGGL(k_outer_grads<double>, dim3(B), dim3(LQP_NT), 0, st, (const double*)dx, (const double*)x,
-                           (const double*)dnu, (const double*)nus, n, m, (double*)dQ, (double*)dA);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(k_outer_grads<T>, dim3(B), dim3(LQP_NT), 0, st, (const T*)dx, (const T*)x, (const T*)dnu, (const T*)nus, n, m,
+                           (T*)dQ, (T*)dA);
+    });
     return last_error();
 }
 

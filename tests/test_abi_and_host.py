@@ -71,6 +71,122 @@ def test_backward_refuses_before_it_touches_anything(monkeypatch, dt):
     assert list(rep) == [7, 7, 7] and fail.value == -5
 
 
+# (B, n, m, iters) -> scratch bytes of lqp_boxqp_unroll_backward (float32 only) | of _backward_lu | of the tape in segments, (f32, f64) each
+_UNROLL_BYTES = {(1, 1, 0, 0): (1281, (1537, 1537), (2052, 2056)),
+                 (3, 40, 3, 7): (13248, (13760, 25792), (21504, 41216)),
+                 (2, 513, 17, 20): (283690, (286762, 551210), (459432, 896336))}
+_UNROLL_ROWS = {0: (13568, 17408, 0), 1: (25600, 33280, 0)}      # (3, 40, 3, 7): offsets of the z, u, x rows in the tape's scratch
+
+
+def _never_read():
+    buf = ctypes.create_string_buffer(64)
+    return buf, ctypes.c_void_p(ctypes.addressof(buf))
+
+
+@pytest.mark.parametrize("dt", [0, 1])
+def test_unroll_workspace_queries_and_row_offsets_are_pinned(dt):
+    """The three workspace queries of the unroll entries and where the query form of lqp_boxqp_unroll_tape_segment (k1 <= k0) says the
+    rows of iterates live, as every build so far gave them: callers size their scratch by the first and unrolled.py views the rows
+    in it by the second.  The query launches nothing and dereferences nothing."""
+    lib = _lib.load()
+    for (B, n, m, iters), (sym, lu, tape) in _UNROLL_BYTES.items():
+        assert lib.lqp_boxqp_unroll_backward_workspace_bytes(B, n, m, iters) == sym, (B, n, m, iters)
+        assert lib.lqp_boxqp_unroll_backward_lu_workspace_bytes(dt, B, n, m, iters) == lu[dt], (dt, B, n, m, iters)
+        assert lib.lqp_boxqp_unroll_tape_workspace_bytes(dt, B, n, m, iters) == tape[dt], (dt, B, n, m, iters)
+    B, n, m, iters = 3, 40, 3, 7
+    keep, p = _never_read()
+    z, u, x = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+    assert lib.lqp_boxqp_unroll_tape_segment(None, dt, B, n, m, p, lib.lqp_boxqp_forward_workspace_bytes(dt, B, n, m), iters, 0, 0, 0, None,
+                                             None, None, -1, None, None, None, None, None, None, None, p, _UNROLL_BYTES[(B, n, m, iters)][2][dt],
+                                             ctypes.byref(z), ctypes.byref(u), ctypes.byref(x)) == 0
+    assert (z.value - p.value, u.value - p.value, x.value - p.value) == _UNROLL_ROWS[dt]
+
+
+@pytest.mark.parametrize("dt", [0, 1])
+def test_unroll_entries_refuse_before_they_touch_anything(dt):
+    """The four unroll entries answer a null pointer (1), a forward workspace one byte short (2), a scratch one byte short (2) and a size
+    they do not take (6) before any launch -- no GPU is needed to see it, no buffer is read -- and in that order: the symmetric entry
+    says "unsupported" for n = 1025, m = 17 although its scratch is too short as well."""
+    lib = _lib.load()
+    keep, p = _never_read()
+    B, n, m, iters = 3, 40, 3, 7
+    fwd = lib.lqp_boxqp_forward_workspace_bytes(dt, B, n, m)
+    fwd32 = lib.lqp_boxqp_forward_workspace_bytes(0, B, n, m)
+    sym, lu, tape = (v if isinstance(v, int) else v[dt] for v in _UNROLL_BYTES[(B, n, m, iters)])
+    outs = (p,) * 8                                          # dQs, dps, dAs, dbs, dlbs, dubs, drho, dD
+
+    def backward_sym(fw=p, fw_bytes=fwd32, scratch=p, scratch_bytes=sym, n=n, m=m):
+        return lib.lqp_boxqp_unroll_backward(None, B, n, m, fw, fw_bytes, iters, p, *outs, scratch, scratch_bytes)
+
+    def backward_lu(fw=p, fw_bytes=fwd, scratch=p, scratch_bytes=lu, n=n, m=m):
+        return lib.lqp_boxqp_unroll_backward_lu(None, dt, B, n, m, fw, fw_bytes, iters, p, *outs, scratch, scratch_bytes)
+
+    def segment(fw=p, fw_bytes=fwd, scratch=p, scratch_bytes=tape, n=n, m=m, dps=p):
+        return lib.lqp_boxqp_unroll_tape_segment(None, dt, B, n, m, fw, fw_bytes, iters, 0, iters + 1, 3, p, p, p, -1, None, p, dps, p, p, p, p,
+                                                 scratch, scratch_bytes, None, None, None)
+
+    def finish(scratch=p, scratch_bytes=tape, dAs=p):
+        return lib.lqp_boxqp_unroll_tape_finish(None, dt, B, n, m, iters, p, dAs, p, scratch, scratch_bytes)
+
+    for entry, fw_bytes, scratch_bytes in ((backward_sym, fwd32, sym), (backward_lu, fwd, lu), (segment, fwd, tape)):
+        assert entry(fw=None) == 1 and entry(scratch=None) == 1, entry.__name__
+        assert entry(fw_bytes=fw_bytes - 1) == 2 and entry(scratch_bytes=scratch_bytes - 1) == 2, entry.__name__
+    assert segment(dps=None) == 1
+    assert finish(scratch=None) == 1 and finish(dAs=None) == 1 and finish(scratch_bytes=tape - 1) == 2      # (it reads no forward workspace)
+    rows = (4096, 2048)[dt]                                  # n + m above the pivoted LU's limit: before either workspace is looked at
+    assert backward_lu(n=rows, m=1, fw_bytes=0, scratch_bytes=0) == 6 and segment(n=rows, m=1, fw_bytes=0, scratch_bytes=0) == 6
+    big = lib.lqp_boxqp_forward_workspace_bytes(0, B, 1025, 17)
+    assert backward_sym(n=1025, m=17, fw_bytes=big, scratch_bytes=0) == 6
+    assert backward_sym(n=1025, m=17, fw_bytes=big - 1, scratch_bytes=0) == 2      # (the forward workspace still comes first)
+
+
+def test_tape_segments_cut_where_rho_may_change():
+    from lqp_py_amd.unrolled import _tape_segments
+    assert _tape_segments(31, True, 10, 1000) == [(0, 10), (10, 20), (20, 30), (30, 31)]
+    assert _tape_segments(31, True, 10, 20) == [(0, 10), (10, 31)]             # (no event at or past adaptive_rho_max_iter)
+    assert _tape_segments(10, True, 10, 1000) == [(0, 10)]
+    assert _tape_segments(1, True, 1, 1000) == [(0, 1)]
+    assert _tape_segments(31, False, 10, 1000) == [(0, 31)] and _tape_segments(1, False, 1, 1000) == [(0, 1)]
+    import unroll_table
+    assert [unroll_table._segments(K, it, mx) for K, it, mx in ((30, 10, 1000), (30, 10, 20), (9, 10, 1000), (0, 1, 1000))] == [4, 2, 1, 1]
+
+
+def test_chain_by_autograd_against_autograd_called_directly():
+    """Three tensor leaves (one of them needs no gradient) and a None among them; pairs whose output is a number or whose cotangent is
+    None drop out, a cotangent comes in another shape than its output: exactly what torch.autograd.grad gives when called directly."""
+    from lqp_py_amd.unrolled import _chain_by_autograd
+    g = torch.Generator().manual_seed(11)
+    rnd = lambda *shape: torch.randn(*shape, dtype=torch.float64, generator=g)
+    a0, c0, d0, g1, g2, g3 = rnd(2, 3, 1), rnd(2, 3, 1), rnd(2, 1, 1), rnd(2, 3, 1), rnd(2), rnd(2, 3, 1)
+
+    def graph():
+        a, c, d = a0.clone().requires_grad_(True), c0.clone(), d0.clone().requires_grad_(True)
+        return (a, c, d), (a * d + c, (a * a * c).sum(dim=1) / d.reshape(2, 1), torch.sin(a) * c)
+    (a, c, d), (o1, o2, o3) = graph()
+    got = _chain_by_autograd([(o1, g1), (1.0, g3), (o2, g2), (o3, None)], [a, None, c, d])
+    (a, c, d), (o1, o2, o3) = graph()
+    want = torch.autograd.grad([o1, o2], [a, d], [g1, g2.reshape(2, 1)])
+    assert got[1] is None and got[2] is None and torch.equal(got[0], want[0]) and torch.equal(got[3], want[1])
+    (a, c, d), (o1, o2, o3) = graph()
+    assert _chain_by_autograd([(1.0, g3), (o3, None)], [a, None, c, d]) == [None, None, None, None]       # (nothing to differentiate)
+    assert _chain_by_autograd([(o1.detach(), g1)], [None, c]) == [None, None]
+
+
+@pytest.mark.parametrize("m", [0, 2])
+def test_kkt_matrix_is_the_literal_expression(m):
+    from lqp_py_amd.unrolled import _kkt_matrix
+    g = torch.Generator().manual_seed(5)
+    B, n = 3, 4
+    Qs, rho = torch.randn(B, n, n, generator=g), torch.rand(B, 1, 1, generator=g) + 0.5
+    As = torch.randn(B, m, n, generator=g) if m > 0 else None
+    M = Qs + rho * torch.eye(n).unsqueeze(0)
+    if m > 0:
+        M = torch.cat((torch.cat((M, As.transpose(1, 2)), 2), torch.cat((As, torch.zeros(B, m, m)), 2)), 1)
+    got = _kkt_matrix(Qs, As, rho)
+    assert got.shape == (B, n + m, n + m) and torch.equal(got, M)
+    assert torch.equal(_kkt_matrix(Qs, As, 0.25), _kkt_matrix(Qs, As, torch.full((B, 1, 1), 0.25)))       # (rho as a number)
+
+
 def test_control_factory_and_resolution_traps():
     c = L.box_qp_control(check_solved=3, adaptive_rho_max_iter=7, reduce='max')
     assert c["check_terimnation"] == 3 and "check_solved" not in c and c["reduce"] == 'max'

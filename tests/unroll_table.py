@@ -46,13 +46,9 @@ K_EV32 = 30
 
 
 def _segments(K, ar_iter, ar_max=1000):
-    """Segments the epoch walk cuts a tape of K + 1 x-updates into (unrolled._backward_with_rho_events)."""
-    TT, k, nseg = K + 1, 0, 0
-    while k < TT:
-        nxt = (k // ar_iter + 1) * ar_iter
-        k = nxt if (nxt < ar_max and nxt < TT) else TT
-        nseg += 1
-    return nseg
+    """Segments the epoch walk cuts a tape of K + 1 x-updates into (unrolled._tape_segments)."""
+    from lqp_py_amd.unrolled import _tape_segments
+    return len(_tape_segments(K + 1, True, ar_iter, ar_max))
 
 
 def expect(r):
