@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LQP_ABI_VERSION 13
+#define LQP_ABI_VERSION 14
 
 enum { LQP_F32 = 0, LQP_F64 = 1 };
 
@@ -87,7 +87,12 @@ typedef struct lqp_boxqp_ctrl {
                                         LQP_ERR_TIMEOUT passes when it repeats the forward; bit 2 (ABI 12): keep a
                                         trace of the convergence checks -- the largest primal and dual error over the batch at
                                         every check, what the reference prints under verbose=True (:289-294) -- for
-                                        lqp_boxqp_check_trace                                                            */
+                                        lqp_boxqp_check_trace; bit 3 (ABI 14): the problems are independent -- every
+                                        problem is solved as the reference would solve it in a batch of one: it stops at the
+                                        first check at which IT is optimal and adapts rho from its own residual ratio, so its
+                                        result does not depend on what else is in the batch.  stats.iters and status word [1]
+                                        then carry the largest per-problem count; lqp_boxqp_problem_iters copies out all of
+                                        them.  Not with check_hook (LQP_ERR_INVALID)                                     */
     double eps_abs;
     double eps_rel;
     double rho_value;
@@ -144,6 +149,9 @@ typedef struct lqp_boxqp_stats {
                               * on the symmetric path splits every product between two CUs */
     int32_t any_lb;          /* 1: some lower bound of the batch is finite (:129), 0: none, -1: not known on the host */
     int32_t any_ub;          /* the same for the upper bounds (:130)                                                 */
+    int32_t loop_kind;       /* (ABI 14) the kernel family of the first (hot) loop launch: 0 one workgroup per QP, 1 the split loop
+                              * (two / four workgroups, matrix in registers; also its turn-taking segments), 2 the small loop
+                              * (n <= 128), 3 two streaming workgroups (n > 512), 4 / 5 the dense LU-tier loops        */
 } lqp_boxqp_stats;
 
 int lqp_abi_version(void);
@@ -288,6 +296,16 @@ int lqp_unroll_scale_scatter(void* stream, int B, int n, const void* Q, const vo
 int lqp_boxqp_last_residuals(void* stream, int dtype, int B, int n, int m,
                              const void* workspace, size_t workspace_bytes,
                              void* primal_out, void* dual_out);
+
+/* ABI 14: the iteration count of every problem of the LAST forward that used `workspace`, which must have run with
+ * ctrl.reserved2 bit 3 (LQP_ERR_INVALID otherwise): iters_out[b] = the iteration at whose check problem b was optimal,
+ * or max_iters - 1 for one that never was -- B int32 on the DEVICE.  Enqueued on `stream`, nothing is waited for.
+ * Which forward ran last on a workspace the library remembers by its ADDRESS until the next forward on that address: a
+ * workspace that was freed and whose memory came back as another one is the caller's to keep apart.  After such a forward
+ * lqp_boxqp_stats.n_factor counts factorisation launches as always; an event inside the continuation kernel counts once when
+ * any problem refactorised at it.                                                                                          */
+int lqp_boxqp_problem_iters(void* stream, int dtype, int B, int n, int m,
+                            const void* workspace, size_t workspace_bytes, int32_t* iters_out);
 
 /* ABI 12: the trace of a forward solve that ran with ctrl.reserved2 bit 2 -- for check c = 0 .. n_checks - 1 (held at
  * iteration c * check_solved) trace_out[2 c] = max over the batch of ||D r||_inf, trace_out[2 c + 1] = max of ||D s||_inf,

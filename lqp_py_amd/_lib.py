@@ -16,10 +16,10 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_PATH = os.environ.get("LQP_LIB", os.path.join(CSRC, "liblqp_amd.so"))   # LQP_LIB: A/B builds
-SOURCES = ["lqp_amd.hip", "lqp_unroll.hpp", "lqp_boxqp.hpp", "lqp_lu.hpp", "lqp_lu_big.hpp", "lqp_lu2.hpp", "lqp_lu_wide.hpp", "lqp_dense.hpp", "lqp_trsv.hpp", "lqp_spd.hpp", "lqp_f16x2.hpp", "lqp_common.hpp"]
+SOURCES = ["lqp_amd.hip", "lqp_unroll.hpp", "lqp_boxqp.hpp", "lqp_loop_split.inc", "lqp_loop_small.inc", "lqp_lu.hpp", "lqp_lu_big.hpp", "lqp_lu2.hpp", "lqp_lu_wide.hpp", "lqp_dense.hpp", "lqp_trsv.hpp", "lqp_spd.hpp", "lqp_f16x2.hpp", "lqp_common.hpp"]
 
 LQP_F32, LQP_F64 = 0, 1
-ABI_VERSION = 13
+ABI_VERSION = 14
 STATUS = {0: "ok", 1: "invalid argument", 2: "workspace too small", 3: "singular", 4: "HIP error",
           5: "grid barrier timeout", 6: "unsupported size (n + m <= 4096 in float32, 2048 in float64)", 7: "matrix outside the symmetric x-update"}
 
@@ -44,7 +44,7 @@ class BoxQPCtrl(ctypes.Structure):
 class BoxQPStats(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in (
         "iters", "n_factor", "n_solve", "n_check", "rho_updated", "fail_index", "n_launch", "mode_used", "linsolve_used",
-        "factor_launches", "loop_workgroups", "any_lb", "any_ub")]
+        "factor_launches", "loop_workgroups", "any_lb", "any_ub", "loop_kind")]
 
 
 # every symbol include/lqp_amd.h declares: name -> (restype, argtypes)
@@ -81,6 +81,7 @@ SYMBOLS = {
     "lqp_unroll_scale_vectors": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_double] + [_P] * 13 + [c_int] + [_P] * 7),
     "lqp_unroll_scale_scatter": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P]),
     "lqp_boxqp_last_residuals": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P]),
+    "lqp_boxqp_problem_iters": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "lqp_boxqp_check_trace": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, c_int, _P]),
     "lqp_boxqp_backward_fp_workspace_bytes": (c_size_t, [c_int] * 4),
     "lqp_boxqp_backward_fp_prefactor": (c_int, [_P, c_int, c_int, c_int, c_int] + [_P] * 6 + [_P, c_size_t, c_int, _P]),

@@ -5,6 +5,12 @@ key, including the two keys the solver never reads back
 (``check_terimnation`` and ``adaptive_rho_max_iter``; the solver reads
 ``check_solved`` / ``adaptive_max_iter``, solve_box_qp_admm_torch.py:139,148),
 so a dict built here behaves exactly like one built by the reference.
+
+Extension keys of this package travel through ``**kwargs`` like any unknown
+key: ``linsolve`` ('auto' | 'lu' | 'spd'), ``sync`` (False: nothing waits for
+the GPU), ``launch_mode`` (0 | 1 | 2) and ``stop`` ('all', the reference's
+rule: the batch iterates until every problem is optimal at one check | 'each':
+every problem is solved as a batch of one, see ``torch_solve_box_qp``).
 """
 
 

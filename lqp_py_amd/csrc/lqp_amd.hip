@@ -20,6 +20,7 @@
 #include <string>
 #include <type_traits>
 #include <unordered_map>
+#include <unordered_set>
 
 using namespace lqp;
 
@@ -527,7 +528,21 @@ template <typename T> struct FwdLayout {
     FwdParams<T> P;
     size_t bytes;
     unsigned int* vtrace_area;      // [kRing][2]: the check trace (FwdParams::vtrace points here when ctrl.reserved2 bit 2 asks for it)
+    int* pstat_area;                // [B][PS_WORDS]: per-problem stopping (FwdParams::pstat points here when ctrl.reserved2 bit 3 asks for it)
 };
+// the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
+// by ADDRESS: an entry goes when another forward runs on the address; memory that was freed and handed out again without a forward in
+// between still counts as known (include/lqp_amd.h says so: the caller owns the workspace's lifetime)
+std::mutex g_each_mu;
+std::unordered_set<const void*> g_each_ws;
+inline void each_ws_note(const void* ws, const bool each) {
+    std::lock_guard<std::mutex> lk(g_each_mu);
+    if (each) g_each_ws.insert(ws); else g_each_ws.erase(ws);
+}
+inline bool each_ws_known(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_each_mu);
+    return g_each_ws.count(ws) != 0;
+}
 
 template <typename T>
 FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
@@ -562,6 +577,7 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     P.dnx_words = (B <= 256 && n <= DENSE_NMAX && P.N <= 1024) ? DNX_WORDS
                 : (B <= 64 && P.N <= 2048) ? (int)std::max((size_t)DNX_WORDS, densew_xchg_words<T>(n)) : 0;
     P.dnx = P.dnx_words ? c.take<unsigned long long>((size_t)B * P.dnx_words) : nullptr;
+    L.pstat_area = c.take<int>((size_t)B * PS_WORDS);      // (behind everything that was there before ABI 14: no offset moved)
     L.bytes = c.off + kAlign;
     return L;
 }
@@ -577,6 +593,12 @@ template <int NP> SweepFn spd_resident_fn(const int Ks, const bool f16) {
 #else
 #define LQP_KS_CASE(KS) case KS: return k_spd_resident<KS, NP, false>
 #endif
+    if constexpr (NP == 2) switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
+    switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
+#undef LQP_KS_CASE
+}
+template <int NP> SplitFn loop_split_each_fn(const int Ks) {
+#define LQP_KS_CASE(KS) case KS: return k_admm_loop_split_each<KS, 512, false, NP>
     if constexpr (NP == 2) switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
     switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
 #undef LQP_KS_CASE
@@ -629,6 +651,7 @@ template <typename T> struct FwdPlan {
     LoopFn tail_fn = nullptr; int tail_lds = 0;                     // continuation launches (LQP_NT threads)
     SplitFn split_fn = nullptr; int split_nt = 512, split_lds = 0;  // LOOP_SPLIT and loop_split_seg
     int mode = 0;                       // 2: persistent loop kernel, 1: one launch per check segment
+    bool each = false;                  // ctrl.reserved2 bit 3: every problem stops and adapts rho as a batch of one (P.pstat)
     bool inkernel_refactor = false;     // the continuation kernel refactorises at its adaptive-rho events itself
     // the scheduler
     bool up_front = false;              // run_planned: the whole schedule enqueued before anything is waited for
@@ -653,6 +676,10 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     const bool solo = (retry & 4) != 0;
     plan = FwdPlan<T>();
     plan.retry = retry; plan.solo = solo;
+    // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
+    // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
+    const bool each = P.pstat != nullptr;
+    plan.each = each;
     plan.dbg_loop_absent = k.dbg_loop_absent;
     P.xcd_local = k.xcd_local != 0 ? 1 : 0;
     P.dbg_qpass = k.dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
@@ -777,11 +804,12 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     // blocks save.  Kept selectable (LQP_LOOP512=1) for re-measurement; continuation launches always use 1024.
     const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && k.resident != 0 &&
                           loop_lds_bytes<T>(n, m, P.Np, true) <= 160 * 1024;
-    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0;
+    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0 && !each;
     plan.loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident);
     plan.loop_nt = hot512 ? 512 : 1024;
     plan.loop_fn = k_admm_loop<T, false, false, 1024>;
     plan.tail_fn = k_admm_loop<T, false, true, 1024>;        // same code, own name: continuation launches
+    if (each) { plan.loop_fn = k_admm_loop_each<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, false, true, 1024, false>; }
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
     //  separate gated kernels, and the continuation kernel's LDS does not have to hold an LU panel)
@@ -790,6 +818,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     plan.inkernel_refactor = P.N <= 1024;
     if constexpr (sizeof(T) == 4) {
         if (resident) { plan.loop_fn = k_admm_loop<T, true, false, 1024>; plan.tail_fn = k_admm_loop<T, true, true, 1024>; }
+        if (resident && each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, false>; }
         if (hot512) plan.loop_fn = k_admm_loop<T, true, false, 512>;
         if (spd) {
             P.sym_rl = sym_resident_lds_blocks(n, m, P.Ks);
@@ -798,11 +827,12 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             plan.loop_nt = 1024;
             plan.loop_fn = k_admm_loop<T, true, false, 1024, true>;
             plan.tail_fn = k_admm_loop<T, true, true, 1024, true>;
+            if (each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, true>; }
             // optional 512-thread first launch (8 elements per thread, 12 register-resident blocks).  Measured at
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
             // blocks show, the product is bound by the un-overlapped sum of its resident and streamed phases.
-            if (k.sym512) {
+            if (k.sym512 && !each) {
                 P.sym_rl_hot = sym_resident_lds_blocks(n, m, P.Ks, resident_regs<512>(), 8);
                 plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl_hot, 8);
                 plan.loop_nt = 512;
@@ -857,12 +887,12 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             // four workgroups per QP (one column pair each) when the batch leaves room for them: B <= #CUs / 4
             if (P.Ks >= 7 && 4 * B <= d.cus && k.loop_split4 != 0) {
                 plan.split_lds = split_loop_lds_bytes<512, 4>(P.Ks, m);
-                plan.split_fn = loop_split_fn<4>(P.Ks, false);
+                plan.split_fn = each ? loop_split_each_fn<4>(P.Ks) : loop_split_fn<4>(P.Ks, false);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 4))) loop_np = 4;
             }
             if (loop_np != 4) {
                 plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-                plan.split_fn = loop_split_fn<2>(P.Ks, g_lu_dbg != nullptr);
+                plan.split_fn = each ? loop_split_each_fn<2>(P.Ks) : loop_split_fn<2>(P.Ks, g_lu_dbg != nullptr);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 2))) loop_np = 2;
             }
             if (loop_np > 1) { plan.kind = LOOP_SPLIT; plan.kind_wg = loop_np; }
@@ -870,7 +900,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // above 512 rows (BASELINE configs[3]: n = 1000): the streaming loop of the symmetric path with TWO workgroups per problem, each
         // streaming one range of whole block columns of H (admm_loop_body_from, NP == 2): twice the registers and LDS under the same
         // matrix (16 % -> 32 % of it on chip), half the stream per CU -- one CU alone pulls 58 GB/s, 29 us per iteration at n = 1000
-        if (spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && plan.loop_nt == 1024 && k.loop_np2 != 0 && !solo &&
+        if (spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && plan.loop_nt == 1024 && k.loop_np2 != 0 && !solo && !each &&
             !(retry & 2) && fits(d, k_admm_loop_np2<>, 1024, plan.loop_lds, shared_grid(B, 2))) {
             plan.kind = LOOP_NP2; plan.kind_wg = 2;
         }
@@ -881,13 +911,13 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         if (spd && mode == 1 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 &&
             k.loop_split != 0 && k.loop_split_seg != 0 && !(retry & 2) && !solo && 2 * B > d.cus) {
             plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-            plan.split_fn = loop_split_fn<2>(P.Ks, false);
+            plan.split_fn = each ? loop_split_each_fn<2>(P.Ks) : loop_split_fn<2>(P.Ks, false);
             plan.loop_split_seg = fits(d, plan.split_fn, plan.split_nt, plan.split_lds, 0);
         }
     }
     // LU tier, persistent mode, n <= 256, 2 B workgroups resident: the explicit inverse of the KKT matrix in the registers of two
     // workgroups per problem (lqp_dense.hpp) -- float64, many equality rows, non-symmetric Q, control['linsolve'] = 'lu'
-    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0) {
+    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0 && !each) {
         const int dense_lds = dense_loop_lds_bytes<T>(m);
         if (lu_inverse_lds_bytes<T>(P.Np) <= 160 * 1024 && fits(d, k_admm_loop_dense<T>, DENSE_NT, dense_lds, shared_grid(B, 2))) {
             plan.kind = LOOP_DENSE; plan.kind_lds = dense_lds; plan.kind_wg = 2;
@@ -895,7 +925,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     }
     // ... and for batches that leave most of the chip idle, any n the inverse kernel takes: W workgroups per problem, each with its
     // rows of the inverse in registers (k_admm_loop_dense_w): a matrix-vector product spreads over CUs, triangular solves do not
-    if (!spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && lu_inverse_fits<T>(P.Np) &&
+    if (!spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && !each && lu_inverse_fits<T>(P.Np) &&
         (size_t)P.dnx_words >= densew_xchg_words<T>(n)) {
         const int densew_lds = densew_lds_bytes<T>(n, m);
         const int tpr = densew_tpr(n, densew_cpt<T>());
@@ -908,7 +938,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
         if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
             const int small_lds = small_loop_lds_bytes(m);
-            if (fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
+            if (each ? fits(d, k_admm_loop_small_each<>, 256, small_lds, B) : fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
         }
         // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
         // (ctrl.reserved2 bit 0: the caller will read the corrected H from the workspace afterwards -- lqp_boxqp_unroll_backward --
@@ -935,15 +965,17 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     // counters of the check before and only hands over to the continuation kernel when the event changes something
     // (FwdParams::hot_past).  Its range is the whole solve; the continuation launch is enqueued from the first event
     // iteration on and finds its real starting point in status[ST_RESUME].
-    plan.hot_past = plan.up_front && plan.kind == LOOP_SPLIT && spd && plan.inkernel_refactor && ctl->adaptive_rho && k.hot_past != 0 &&
+    // (each: the hot launch ends at the first possible event -- the continuation kernel takes the problem's own decision there)
+    plan.hot_past = !each && plan.up_front && plan.kind == LOOP_SPLIT && spd && plan.inkernel_refactor && ctl->adaptive_rho && k.hot_past != 0 &&
                     ar_iter < ctl->adaptive_rho_max_iter && ar_iter < max_iters;
     P.hot_past = plan.hot_past ? 1 : 0;
     // A GIVEN rho is the case in which the adaptation does fire (`rho = 0.01`: three factorisations, 281 iterations,
     // 4.5 ms with everything behind iteration 100 on the continuation kernel).  Enqueue a few rounds of {the event
     // on the gated kernels of the refactorisation, the hot loop again from where it stopped}: each costs a solve that
     // is over ~5 launches that leave at once -- which is why the automatic rho (it practically never adapts) gets none.
-    plan.hot_rounds = ctl->rho_mode != 0 ? k.hot_rounds : 0;
-    plan.tail_epilogue = k.tail_epilogue != 0;
+    plan.hot_rounds = (ctl->rho_mode != 0 && !each) ? k.hot_rounds : 0;
+    // (each: workgroups leave the last launch at different times -- workgroup 0 cannot report the status block from inside it)
+    plan.tail_epilogue = k.tail_epilogue != 0 && !each;
     plan.spec_launches = k.spec_launches;
     plan.factor_launches = spd ? (spd_big_split ? 2 * P.Ks + 2 : spd_split ? (spd_resident ? 3 : P.Ks + 2) : 1) : 2;
     plan.loop_workgroups = plan.loop_split_seg ? 2 : plan.kind_wg;      // (what the loop's launches put on a problem)
@@ -1057,7 +1089,8 @@ void launch_hot(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, c
             hipLaunchKernelGGL(plan.split_fn, dim3((absent & 1) ? B : shared_grid(B, plan.kind_wg)), dim3(plan.split_nt), plan.split_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_SMALL:
-            hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            if (plan.each) hipLaunchKernelGGL(k_admm_loop_small_each<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            else hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_NP2:
             hipLaunchKernelGGL(k_admm_loop_np2<>, dim3((absent & 8) ? B : shared_grid(B, 2)), dim3(1024), plan.loop_lds, st, P, 0, e, ctr_base, -1, 1);
@@ -1104,6 +1137,7 @@ void fill_stats(lqp_boxqp_stats* stats, const FwdPlan<T>& plan, const int mode_u
     stats->linsolve_used = plan.spd ? 2 : 1;
     stats->factor_launches = plan.factor_launches;
     stats->loop_workgroups = plan.loop_workgroups;
+    stats->loop_kind = plan.loop_split_seg ? (int)LOOP_SPLIT : (mode_used == 1 ? (int)LOOP_ONE : (int)plan.kind);
 }
 
 // why an attempt gave up, for forward_impl's retry loop
@@ -1391,6 +1425,12 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         P.scale = ctl->scale; P.bound_flags_in = (const int*)ctl->bound_flags_in;
         // verbose: the largest primal / dual error of the batch at every check (lqp_boxqp_check_trace)
         if (ctl->reserved2 & 4) P.vtrace = L.vtrace_area;
+        // per-problem stopping (control['stop'] = 'each'); a strict global stop over shards is its opposite
+        if (ctl->reserved2 & 8) {
+            if (ctl->check_hook) return LQP_ERR_INVALID;
+            P.pstat = L.pstat_area;
+        }
+        each_ws_note(ws, P.pstat != nullptr);
         P.host_report = (int*)ctl->host_report;
         P.zero_words = (int)(((char*)(P.counters + (size_t)kRing * CT_WORDS) - (char*)P.status) / sizeof(int));
         P.rho_mode = ctl->rho_mode; P.beta_mode = ctl->beta_mode;
@@ -2270,6 +2310,23 @@ int lqp_boxqp_last_residuals(void* stream, int dtype, int B, int n, int m, const
         hipLaunchKernelGGL(k_copy_residuals<T>, dim3((B + 255) / 256), dim3(256), 0, st, L.P.scal, (T*)primal_out, (T*)dual_out, B);
         return last_error();
     });
+}
+
+int lqp_boxqp_problem_iters(void* stream, int dtype, int B, int n, int m, const void* workspace, size_t workspace_bytes,
+                            int32_t* iters_out) {
+    if (bad_dims(dtype, B, n, m) || !workspace || !iters_out) return LQP_ERR_INVALID;
+    if (!each_ws_known(workspace)) return LQP_ERR_INVALID;      // (the last forward on this workspace did not run with bit 3)
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0) return LQP_OK;
+    const int* src = nullptr;
+    const size_t need = by_dtype(dtype, [&](auto t) {
+        const FwdLayout<decltype(t)> L = carve_forward<decltype(t)>(const_cast<void*>(workspace), B, n, m);
+        src = L.pstat_area;
+        return L.bytes;
+    });
+    if (workspace_bytes < need) return LQP_ERR_WORKSPACE;
+    hipLaunchKernelGGL(k_copy_iters<>, dim3((B + 255) / 256), dim3(256), 0, st, src, (int*)iters_out, B);
+    return last_error();
 }
 
 int lqp_boxqp_check_trace(void* stream, int dtype, int B, int n, int m, const void* workspace, size_t workspace_bytes,

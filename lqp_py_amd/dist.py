@@ -16,12 +16,16 @@ slice with no data-path communication; the only exchanges are
 Default: the stopping rule is evaluated per shard -- a shard stops when all of
 ITS problems are optimal, so iteration counts may differ between shards
 (results agree with the single-process solve within the tolerances).
+With ``control['stop'] = 'each'`` every problem stops, and adapts rho, as a
+batch of one: its result and its iteration count do not depend on the sharding
+at all, and no per-check collective is needed for that (``dist_strict_stop``
+on top of it is refused: a global stop is its opposite).
 ``dl_dQ`` is never gathered.
 """
 import torch
 import torch.distributed as dist
 
-from .solve_box_qp_admm_torch import SolveBoxQPLayer
+from .solve_box_qp_admm_torch import SolveBoxQPLayer, check_stop
 
 _INF = float("inf")
 
@@ -140,6 +144,7 @@ class ShardedBoxQP(torch.nn.Module):
 
     def forward(self, Q, p, A, b, lb, ub):
         ctl = self.control
+        check_stop(ctl)                         # ('each' with dist_strict_stop: refused here, before any collective)
         if _active(self.group):
             # private keys for the layer: the flags of the WHOLE batch (a shard without any finite bound must still run
             # the ADMM path the whole batch runs) and, in strict mode, the per-check all-reduce

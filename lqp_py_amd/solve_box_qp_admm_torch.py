@@ -145,7 +145,15 @@ class BoxQPTH:
 
 
 def torch_solve_box_qp(Q, p, A, b, lb, ub, control):
-    """Forward solve; returns {"x","z","u","lams","nus","rho","iter"} (reference :108-333)."""
+    """Forward solve; returns {"x","z","u","lams","nus","rho","iter"} (reference :108-333).
+
+    control['stop'] = 'each' (extension; default 'all', the reference's torch.all at :312): every problem is solved as the reference
+    would solve it in a batch of one -- it stops at the first check at which IT is optimal, and at an adaptive-rho event it adapts
+    iff its own residuals ask for it -- so its result does not depend on what else is in the batch or on how the batch was sharded.
+    "iter" is then the largest per-problem count and "iters" a (B,) int32 device tensor of all of them.  With verbose=True the
+    trace printed is the maximum over the problems still running at each check.  Not with unroll=True, dist_strict_stop or a
+    check hook (ValueError)."""
+    check_stop(control)
     if control.get('unroll', False):
         # autograd through the loop (:328-329 returns the bare x); see lqp_py_amd/unrolled.py
         from .unrolled import unrolled_solve_box_qp
@@ -345,7 +353,23 @@ def resolve_control(control, n_x):
         verbose=g('verbose', False),
         launch_mode=g('launch_mode', 0),         # extension: 0 auto, 1 segmented, 2 persistent
         linsolve=g('linsolve', 'auto'),          # extension: 'auto' | 'lu' (the reference's cached LU) | 'spd'
+        stop=g('stop', 'all'),                   # extension: 'all' (the reference's torch.all, :312) | 'each' (every problem as a batch of one)
     )
+
+
+def check_stop(control, check_hook=None):
+    """control['stop'] and what it cannot be combined with; -> True for 'each'.  Raises at the call, before any launch.  The one place
+    that holds these rules: torch_solve_box_qp, _forward_solve, lqp_py_amd.dist and lqp_py_amd.unrolled all come here."""
+    stop = control.get('stop', 'all')
+    if not isinstance(stop, str) or stop not in ('all', 'each'):
+        _bad("control['stop'] must be 'all' or 'each'")
+    if stop == 'all':
+        return False
+    if control.get('unroll', False):
+        _bad("control['stop'] = 'each' cannot be combined with unroll=True: the tape has one length")
+    if control.get('dist_strict_stop', False) or check_hook is not None or control.get('_check_hook') is not None:
+        _bad("control['stop'] = 'each' cannot be combined with dist_strict_stop or a check hook: a global stop is its opposite")
+    return True
 
 
 def _per_problem_argument(name, example, value, B, like):
@@ -530,9 +554,11 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
     # 1: pipelined (nothing waits); 2: split synchronous call -- enqueue, build the output views while the GPU runs, then
     # lqp_boxqp_forward_finish polls the report (include/lqp_amd.h); 0: the library waits itself (and repeats by itself on the
     # schedule that needs no partner when a shared kernel timed out: one_call).  reserved2 -- bit 0: keep the factor in the
-    # workspace (unroll: private_ws); bit 1: nothing shared between workgroups (one_call); bit 2: keep the check trace
+    # workspace (unroll: private_ws); bit 1: nothing shared between workgroups (one_call); bit 2: keep the check trace;
+    # bit 3: the problems are independent (control['stop'] = 'each')
+    each = r['stop'] == 'each'
     ctl.reserved = (2 if (check_hook is None and _SYNC_SPLIT and not one_call) else 0) if sync else 1
-    ctl.reserved2 = (1 if keep_factor else 0) | (2 if one_call else 0) | (4 if r['verbose'] else 0)
+    ctl.reserved2 = (1 if keep_factor else 0) | (2 if one_call else 0) | (4 if r['verbose'] else 0) | (8 if each else 0)
     ctl.bound_flags_in = None if flags_dev is None else flags_dev.data_ptr()
     Qc, pc, Ac, bc, lbc, ubc = (_lib.norm(t, p.dtype) for t in qp)
     # status / info words arrive in pinned host memory, stored there by the forward's last kernel (include/lqp_amd.h:
@@ -556,6 +582,13 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
                                    ctypes.byref(stats), _lib.ptr(ws), ws.numel())
     split_wait = st == 0 and stats.mode_used == 4
     z, u, lams, nus, rho_out = views()
+    iters = None
+    if each and st == 0:
+        # the per-problem iteration counts: a copy kernel behind the solve on its stream, into a device tensor -- no host wait
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(lib.lqp_boxqp_problem_iters(ctypes.c_void_p(stream), dt, B, n, m, _lib.ptr(ws), ws.numel(), _lib.ptr(iters)),
+                       "problem_iters")
     if split_wait:
         if while_running is not None:
             while_running(dict(x=x, u=u, lams=lams, nus=nus, rho_out=rho_out.view(B, 1, 1)), int(stats.linsolve_used))
@@ -564,7 +597,7 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
                                           ctypes.c_void_p(report.data_ptr()), ctypes.byref(stats))
     return _Outcome(status=st, split_wait=split_wait, stats=stats, hook_error=hook_error, any_bound=any_bound, known=known,
                     report=report, ws=ws, stream=stream, dims=(dt, B, n, m), r=r, rho=rho, rho_mode=ctl.rho_mode,
-                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out)
+                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out, iters=iters)
 
 
 def _print_check_trace(out, dev):
@@ -598,6 +631,8 @@ def _solution(out, like, residuals):
     as_given = out.rho_mode == 1 and not stats.rho_updated and not (stats.mode_used == 3 and r['adaptive_rho'])
     rho_ret = out.rho if as_given else out.rho_out.view(B, 1, 1)     # (un-synchronised calls cannot know whether rho was adapted: tensor)
     sol = {"x": out.x, "z": out.z, "u": out.u, "lams": out.lams, "nus": out.nus, "rho": rho_ret, "iter": int(stats.iters)}
+    if out.iters is not None:            # control['stop'] = 'each': every problem's own count; "iter" is the largest
+        sol["iters"] = out.iters
     if residuals:                        # errors of the last check (the NumPy twin's extra outputs)
         pri, dua = (torch.empty((B,), dtype=like.dtype, device=dev) for _ in range(2))
         with torch.cuda.device(dev):
@@ -615,6 +650,7 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
     on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
     nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound).
     Attempt, decide, act on the verdict, in a loop: _forward_attempt runs the library once, _forward_decide holds the rules."""
+    check_stop(control, check_hook)
     _lib.require_gpu(Q, p, A, b, lb, ub)
     sync = sync or check_hook is not None             # (the strict global stop is host-driven: one launch per check)
     owner = control.get('_owner') or control          # (lqp_py_amd.dist hands the layer a copy of the caller's dict)
@@ -657,7 +693,7 @@ _last_forward = {}
 
 def last_forward_status(device):
     """Bookkeeping of the most recent forward solve on `device`, on the CURRENT stream (workspaces are per stream): {"iters", "n_check", "n_factor", "mode_used",
-    "linsolve_used", "factor_launches", "loop_workgroups_per_qp"}.  A call that did not wait for the GPU
+    "linsolve_used", "factor_launches", "loop_workgroups_per_qp", "loop_kind"}.  A call that did not wait for the GPU
     (control['sync'] = False) could not report its iteration count; it is read here from the device-side status
     block of that call's workspace (this waits for the device).  Valid until the next forward on the same stream."""
     device = torch.device(device)

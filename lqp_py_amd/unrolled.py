@@ -482,6 +482,8 @@ class _NotNative(Exception):
 def unrolled_solve_box_qp(Q, p, A, b, lb, ub, r, has_lb, has_ub, control=None):
     """``r`` is the resolved control (solve_box_qp_admm_torch.resolve_control). Returns x only,
     as the reference does in unroll mode (:328-329)."""
+    from .solve_box_qp_admm_torch import check_stop
+    check_stop(dict(control or {}, stop=r.get('stop', 'all'), unroll=True))
     if (control is not None and p.dtype in (torch.float32, torch.float64) and (has_lb or has_ub)
             and os.environ.get("LQP_UNROLL_NATIVE", "1") != "0"):
         try:

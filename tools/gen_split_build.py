@@ -33,6 +33,10 @@ GROUPS = [
     ("split_c", lambda n: re.search(r"k_admm_loop_split<(3|4), 512, false, 2>", n)),
     ("split_a", lambda n: re.search(r"k_admm_loop_split<(5|6|7), 512, false, 2>", n)),
     ("split_b", lambda n: "k_admm_loop_split<" in n),
+    ("split_each_b", lambda n: re.search(r"k_admm_loop_split_each<(3|4|8), 512, false, 2>|k_admm_loop_split_each<\d, 512, false, 4>", n)),
+    ("split_each_a", lambda n: "k_admm_loop_split_each<" in n),
+    ("loop_each_tail", lambda n: re.search(r"k_admm_loop_each<\w+, \w+, true,", n)),
+    ("loop_each_hot", lambda n: "k_admm_loop_each<" in n),
     ("loop_tail", lambda n: re.search(r"k_admm_loop<\w+, \w+, true,", n)),
     ("loop_hot", lambda n: "k_admm_loop<" in n),
     ("dense", lambda n: "k_lu_inverse<" in n or "k_admm_loop_dense" in n),
@@ -40,7 +44,7 @@ GROUPS = [
     ("lu_a", lambda n: re.search(r"k_lu_factor<float, (32|16), true|k_lu_factor_big|k_lu_factor_wide", n)),
     ("lu_b", lambda n: "k_lu_factor<" in n),
     ("spd", lambda n: re.search(r"k_spd_|k_bwd_chol_solve|k_bwd_build_chol", n)),
-    ("unroll", lambda n: "k_unroll_" in n or "k_admm_loop_small" in n),
+    ("unroll", lambda n: "k_unroll_" in n or "k_admm_loop_small<" in n),
     ("misc", lambda n: True),
 ]
 
@@ -82,6 +86,16 @@ EXTRA = [
     "void lqp::k_spd_inverse<2>(lqp::FwdParams<float>, int const*)",
     "void lqp::k_spd_inverse_dense<1>(float const*, float*, float*, int*, int, int, float*)",
     "void lqp::k_spd_inverse_dense<2>(float const*, float*, float*, int*, int, int, float*)",
+    "void lqp::k_copy_iters<0>(int const*, int*, int)",
+    "void lqp::k_admm_loop_small_each<0>(lqp::FwdParams<float>, int, int, int)",
+] + [
+    f"void lqp::k_admm_loop_split_each<{ks}, 512, false, {np_}>(lqp::FwdParams<float>, int, int, int)"
+    for ks, np_ in ((3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4))
+] + [
+    # control['stop'] = 'each': the one-workgroup loop, hot and continuation (LU f64 | LU f32 | LU f32 resident | symmetric)
+    f"void lqp::k_admm_loop_each<{t}, {res}, {tail}, 1024, {sym}>(lqp::FwdParams<{t}>, int, int, int, int, int)"
+    for tail in ("false", "true")
+    for t, res, sym in (("double", "false", "false"), ("float", "false", "false"), ("float", "true", "false"), ("float", "true", "true"))
 ]
 
 
