@@ -1356,6 +1356,88 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b) {
     }
 }
 // ---------------------------------------------------------------------------
+// The steps an ADMM loop kernel is composed from (this file, lqp_loop_small.hpp, lqp_loop_split.hpp, lqp_dense.hpp): the
+// element-wise update, the stopping check and its record, the blocking verdict and the stop record of stop = 'each'.
+// Stateless; what differs between the kernels -- who owns which element, who reports, how many arrive -- is an argument.
+// (Which kernel uses which step, and why some keep their own lines: DESIGN.md section 10.)
+// ---------------------------------------------------------------------------
+// z-update, residuals and dual of one element (:271-282)
+template <typename T> struct AdmmStep { T zn, r, s, un; };
+template <typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step(const T xi, const T zp, const T ui, const T lb, const T ub, const T rho) {
+    T zn = xi + ui;
+    zn = tmin(tmax(zn, lb), ub);                             // (:273-276; an infinite bound is a no-op)
+    const T r = xi - zn;
+    return {zn, r, rho * (zn - zp), ui + r};
+}
+// ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
+// exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu without touching Q -- it only feeds a tolerance SCALE; the
+// caller forms it from wherever its w, As and nu live.  ACC: the thread owns several elements (fold) or one (assign).
+template <bool ACC, typename T>
+__device__ __forceinline__ void admm_step_norms(T (&mx)[6], const AdmmStep<T>& st, const T xi, const T di, const T rho, const T qx) {
+    const T nm[6] = {tabs(di * st.r), tabs(di * st.s), tabs(di * xi), tabs(di * st.zn), tabs((rho * di) * st.un), tabs(qx / di)};
+#pragma unroll
+    for (int q = 0; q < 6; ++q) mx[q] = ACC ? tmax(mx[q], nm[q]) : nm[q];
+}
+// The stopping check (:285-313) from the six norms of a problem: is it optimal, does it want another rho (:239-245), and the
+// ratio for that step.  The ONE decision that fixes every iteration count and every adaptive-rho event.
+template <typename T> struct LoopCheck { T ratio; bool solved, wants, trig; };
+template <typename T>
+__device__ __forceinline__ LoopCheck<T> loop_check(const FwdParams<T>& P, const T (&mv)[6], const T pnorm) {
+    const T tiny = T(1e-16);
+    const T pri_scale = tmax(tmax(mv[2], mv[3]), tiny);
+    const T tol_p = P.eps_abs + P.eps_rel * pri_scale;
+    const T dua_scale = tmax(tmax(tmax(mv[4], mv[5]), pnorm), tiny);
+    const T tol_d = P.eps_abs + P.eps_rel * dua_scale;
+    const bool solved = (mv[0] < tol_p) && (mv[1] < tol_d);
+    const bool wants = (mv[0] > tmax(tol_p, P.ar_thr)) || (mv[1] > tmax(tol_d, P.ar_thr));
+    const T num = tmax(mv[0] / pri_scale, tiny);
+    const T den = tmax(mv[1] / dua_scale, tiny);
+    const T ratio = tsqrt(num / den);
+    const bool trig = (ratio > P.ar_tol) || (ratio < P.ar_inv_tol);
+    return {ratio, solved, wants, trig};
+}
+// the check's record (one thread of the reporting workgroup): the problem's scalars -- SC_PRI / SC_DUA: primal / dual error of this
+// check (the NumPy twin returns them); SC_TRIG: stop = 'each' only, where the problem decides its own rho event -- and the trace
+template <bool EACH, typename T>
+__device__ __forceinline__ void loop_check_store(const FwdParams<T>& P, T* scal, const LoopCheck<T>& ck, const T (&mv)[6],
+                                                 const int it) {
+    scal[SC_RATIO] = ck.ratio;
+    scal[SC_WANTS] = ck.wants ? T(1) : T(0);
+    if constexpr (EACH) scal[SC_TRIG] = ck.trig ? T(1) : T(0);
+    scal[SC_PRI] = mv[0];
+    scal[SC_DUA] = mv[1];
+    trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
+}
+// The blocking verdict (all workgroups resident): device-wide "all optimal?" (torch.all at :312) once `arrivals` workgroups have
+// arrived.  True: the loop ends at iteration `it` (or a wait timed out); `writer` -- one thread of the grid -- says so.
+template <typename T>
+__device__ __forceinline__ bool loop_all_optimal(const FwdParams<T>& P, unsigned int* ct, const unsigned int arrivals, const int it,
+                                                 const bool writer) {
+    grid_wait(ct + CT_ARRIVE, arrivals, P.status);
+    const unsigned int notopt = __hip_atomic_load(ct + CT_NOTOPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (notopt != 0 && !tmo) return false;
+    if (writer) {
+        P.status[ST_FINAL_ITER] = it;
+        __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return true;
+}
+// stop = 'each': problem b stopped at iteration `it` (one thread, after the iterate was stored).  The batch's final iteration is the
+// largest; the count of stopped problems goes behind the RETURNED maximum, and whoever makes it B has therefore seen every maximum
+// land before it raises ST_DONE
+template <typename T>
+__device__ __forceinline__ void each_stop(const FwdParams<T>& P, const int b, const int it) {
+    int* ps_ = P.pstat + (size_t)b * PS_WORDS;
+    ps_[PS_FINAL] = it;
+    ps_[PS_DONE] = 1;
+    const int r1 = atomicMax(P.status + ST_FINAL_ITER, it);
+    asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1) : "memory");
+    const int nd = __hip_atomic_fetch_add(P.status + ST_NDONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (nd + 1 == P.B) __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ---------------------------------------------------------------------------
 // The ADMM loop (:235-313).  RES: resident head of the factor stream (registers + LDS); SYM: symmetric-inverse
 // x-update instead of the cached triangular solves; NT: threads.
 // TAIL = continuation launch of the speculative (no host sync) schedule.  It has its own name in traces /
@@ -1411,6 +1493,17 @@ __device__ __forceinline__ void loop_event_count(const FwdParams<T>& P, const in
     } else {
         if (b == 0 && threadIdx.x == 0) { P.status[ST_NFACTOR] += 1; P.status[ST_RHO_UPDATED] = 1; }
     }
+}
+// the masked rho update of an event that fires (:246-256): the new rho of problem b, stored and counted; the caller refactorises
+template <typename T, bool EACH>
+__device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, const int b, const int seg0) {
+    T rho_ = scal[SC_RHO];
+    if (scal[SC_WANTS] != T(0)) rho_ = rho_ * scal[SC_RATIO];
+    rho_ = tmin(tmax(rho_, P.rho_min), P.rho_max);
+    __syncthreads();
+    if (threadIdx.x == 0) scal[SC_RHO] = rho_;
+    loop_event_count<T, EACH>(P, b, seg0);
+    return rho_;
 }
 template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
@@ -1510,12 +1603,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
             if (nxt < P.ar_max && nxt < seg1) seg1 = nxt;
             if (seg0 > 0 && seg0 % P.ar_iter == 0 && seg0 < P.ar_max) {
                 if (loop_event_fires<T, EACH>(P, scal, seg0)) {
-                    T rho_ = scal[SC_RHO];
-                    if (scal[SC_WANTS] != T(0)) rho_ = rho_ * scal[SC_RATIO];
-                    rho_ = tmin(tmax(rho_, P.rho_min), P.rho_max);
-                    __syncthreads();
-                    if (tid == 0) scal[SC_RHO] = rho_;
-                    loop_event_count<T, EACH>(P, b, seg0);
+                    const T rho_ = loop_event_rho<T, EACH>(P, scal, b, seg0);
                     wg_spd_factor(P, b, rho_, smem, false);
                     __syncthreads();
                 }
@@ -1533,12 +1621,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
             if (seg0 > 0 && seg0 % P.ar_iter == 0 && seg0 < P.ar_max) {
                 if (loop_event_fires<T, EACH>(P, scal, seg0)) {
                     constexpr int kPB = sizeof(T) == 4 ? 16 : 8;
-                    T rho_ = scal[SC_RHO];
-                    if (scal[SC_WANTS] != T(0)) rho_ = rho_ * scal[SC_RATIO];
-                    rho_ = tmin(tmax(rho_, P.rho_min), P.rho_max);
-                    __syncthreads();
-                    if (tid == 0) scal[SC_RHO] = rho_;
-                    loop_event_count<T, EACH>(P, b, seg0);
+                    const T rho_ = loop_event_rho<T, EACH>(P, scal, b, seg0);
                     const bool lazy_ = P.scale && P.qs_lazy;
                     const T* Qs_ = (P.scale && !lazy_) ? (P.Qs + (size_t)b * n * P.ldq) : (P.Q + (size_t)b * n * n);
                     assemble_kkt_rows(P, b, Qs_, (P.scale && !lazy_) ? P.ldq : n, V, rho_, true, lazy_ ? V.D : nullptr);
@@ -1594,6 +1677,10 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         for (int i = tid; i < Np; i += NT) dest[i] = gdest[i];
     }
     const T* xv = SYM ? xs : v;                              // where the x-update leaves x
+    auto store_state = [&]() {                               // the iterate as it stands, for the next launch / the epilogue
+        for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xv[i]; }
+        loop_store_nu<T, NT, SYM>(V, v, bs + m, n, m);
+    };
     __syncthreads();
 
     unsigned long long dbt[4] = {0, 0, 0, 0}, dt0 = 0;      // debug: cycles in rhs / product / combine / update+check
@@ -1780,18 +1867,9 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 if (solved) {
                     // leave with the state of iteration `it`: the iterate first, then the words that say so
                     __syncthreads();
-                    for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xv[i]; }
-                    loop_store_nu<T, NT, SYM>(V, v, bs + m, n, m);
+                    store_state();
                     if (tid == 0) {
-                        int* ps_ = P.pstat + (size_t)b * PS_WORDS;
-                        ps_[PS_FINAL] = it;
-                        ps_[PS_DONE] = 1;
-                        // the batch's final iteration is the largest; the count of stopped problems goes behind the RETURNED
-                        // maximum, and whoever makes it B has therefore seen every maximum land before it raises ST_DONE
-                        const int r1 = atomicMax(P.status + ST_FINAL_ITER, it);
-                        asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1) : "memory");
-                        const int nd = __hip_atomic_fetch_add(P.status + ST_NDONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (nd + 1 == P.B) __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        each_stop(P, b, it);
                     }
                     return;
                 }
@@ -1830,8 +1908,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     // leave the loop with the state of iteration `it`
                     __syncthreads();
                     if (lead) {
-                        for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xv[i]; }
-                        loop_store_nu<T, NT, SYM>(V, v, bs + m, n, m);
+                        store_state();
                     }
                     if (dbg_on && tid == 0 && lead) {
                         dbt[3] += clock64() - dt0;
@@ -1849,8 +1926,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         for (int q = 0; q < 4; ++q) P.dbg[(size_t)b * 8 + q] += dbt[q];
     // ---- save state for the next launch / the epilogue ----
     if (lead) {
-        for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xv[i]; }
-        loop_store_nu<T, NT, SYM>(V, v, bs + m, n, m);
+        store_state();
     }
     if constexpr (EACH) {       // not optimal so far: the last iteration it ran (max_iters - 1 once the schedule is through)
         if (tid == 0) P.pstat[(size_t)b * PS_WORDS + PS_FINAL] = it1 - 1;
@@ -1890,79 +1966,6 @@ __global__ __launch_bounds__(NT) void k_admm_loop_each(const FwdParams<T> P, con
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_body<T, RES, TAIL, NT, SYM, 1, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
-
-// ---------------------------------------------------------------------------
-// The same loop with TWO workgroups per QP (symmetric x-update, f32, 2 B <= #CUs, Ks >= SPLIT_MINK): workgroups b
-// and b + B hold one half of the blocks of H each, ALL of them on chip for the whole launch (lqp_spd.hpp,
-// wg_sym_gemv_split), and exchange their partial products every iteration:
-//   thread e < Nps combines its element of this workgroup's partial, publishes it as ONE 8-byte granule
-//   {tag, value} (agent-scope relaxed atomic store = sc1 write-through store), polls the partner's granule of the
-//   same element (sc1 loads, L1 bypassed) until the tag matches, and adds the two partials in the fixed order
-//   part 0 + part 1 -- both workgroups then hold bit-identical iterates and run the element-wise update and the
-//   checks redundantly (part 0 alone reports to the counters / writes state).
-// Two granule buffers alternate by iteration parity: a workgroup can be at most one exchange ahead of its
-// partner, so a granule is never overwritten before it was read.  The area is zeroed by k_fwd_setup of the same
-// forward (tags start at 1).  Spins are bounded: a timeout sets ST_TIMEOUT and the kernel still drains.
-//
-// The global stop (torch.all(is_optimal), :312) does not block the loop.  At a check, part 0 adds {not optimal?,
-// arrival} to the check's counter word with ONE 64-bit atomic, both workgroups keep a snapshot of the iterate and go
-// on iterating; in the following iterations part 0 reads the counter word while its product runs (the load's latency
-// is hidden), and once all B arrivals are in, the verdict travels to the partner in the top bits of that iteration's
-// granule tags.  "All optimal" -> both restore the snapshot, part 0 stores it and the kernel exits with the
-// reference's iteration count (the 1-3 speculative iterations are dropped); otherwise the snapshot is forgotten.
-// A verdict still open at the next check or at the last iteration of the launch is waited for (bounded spin).
-//
-// LDS (floats; every offset but the last three arrays is a compile-time constant):
-//   [rl blocks] v yrow cvl part[NW][Nps] z u ps lb ub D xs sz su sx (Nps each) red[NW*8+8] flags[8] | bs nus snu (m each)
-// ---------------------------------------------------------------------------
-template <int NT, int NP = 2> __host__ __device__ constexpr int split_loop_lds_floats(int Ks) {
-    return split_lds_blocks<NT, NP>(Ks) * LQP_BLK + (3 + NT / 64 + 10) * Ks * LQP_NB + (NT / 64) * 8 + 8 + 8;
-}
-template <int NT, int NP = 2> __host__ __device__ inline int split_loop_lds_bytes(int Ks, int m) {
-    // + the equality block: As, G, T (m x Nps each), S, S^-1 (m x m), s0, b, nu, nu snapshot
-    return (split_loop_lds_floats<NT, NP>(Ks) + 3 * m * Ks * LQP_NB + 2 * m * m + 4 * m + 8) * 4;
-}
-
-// ---------------------------------------------------------------------------
-// The hot loop for SMALL problems (symmetric path, n <= 128: BASELINE configs[1], n = 100): the 1024-thread kernel above
-// spends 8.4 k cycles per iteration there -- a 16-wave static walk with per-block LDS slots and partial-sum slices, sized
-// for 36 blocks, around THREE blocks of work.  Here: 256 threads, the whole (unpacked, full) matrix -H in registers --
-// thread t holds the 64 entries of row t >> 1, columns 64 (t & 1) .. -- the product is 64 FMAs per thread against
-// broadcast reads of w and ONE lane-pair add; element e of every vector lives in thread e's registers (threads 0..127).
-// Same iteration, same check (:285-313, blocking device-wide stop) and same exit state as admm_loop_body; first (hot)
-// launch only, continuation launches (adaptive-rho events, a counter ring turn) run the general kernel.
-// LDS: w[128] | y[128] | nus[m] | red[4 * 8 + 8]
-// ---------------------------------------------------------------------------
-__host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 + (m > 0 ? m : 1) + 4 * 8 + 8 + 8) * 4; }
-
-// (control['stop'] = 'each': k_admm_loop_small_each -- the problem's own verdict ends its workgroup; no arrival word, no grid_wait)
-#define LQP_SMALL_KERNEL k_admm_loop_small
-#define LQP_SMALL_EACH false
-#include "lqp_loop_small.inc"
-#undef LQP_SMALL_KERNEL
-#undef LQP_SMALL_EACH
-#define LQP_SMALL_KERNEL k_admm_loop_small_each
-#define LQP_SMALL_EACH true
-#include "lqp_loop_small.inc"
-#undef LQP_SMALL_KERNEL
-#undef LQP_SMALL_EACH
-
-// NP = 4 (batches up to a quarter of the CUs): one column pair per workgroup, every partial product published once and
-// fetched by the three others; the sum runs over the parts in their order on every workgroup (identical iterates).
-// EACH (control['stop'] = 'each'): the partners hold bit-identical iterates and compute the same six norms, so each of them reaches the
-// problem's verdict in the same iteration with no message: no arrival word, no snapshot, no look-back, no verdict in the tags (all
-// compiled out).  Optimal -> the lead workgroup stores the iterate and marks pstat[b], every workgroup of the problem returns.  The hot
-// launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop_each) takes the problem's own decision.
-#define LQP_SPLIT_KERNEL k_admm_loop_split
-#define LQP_SPLIT_EACH false
-#include "lqp_loop_split.inc"
-#undef LQP_SPLIT_KERNEL
-#undef LQP_SPLIT_EACH
-#define LQP_SPLIT_KERNEL k_admm_loop_split_each
-#define LQP_SPLIT_EACH true
-#include "lqp_loop_split.inc"
-#undef LQP_SPLIT_KERNEL
-#undef LQP_SPLIT_EACH
 
 // all problems optimal at the check held in `slot` (iteration `it_check`)?  -> DONE
 template <int LQP_ANY = 0>      // (a template only so that the split build can place its one instance: tools/gen_split_build.py)

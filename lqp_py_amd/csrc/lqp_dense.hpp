@@ -371,24 +371,14 @@ __global__ __launch_bounds__(DENSE_NT) void k_admm_loop_dense(const FwdParams<T>
             const T xi = xs[i];
             const T zp = z[i];
             const T ui = u[i];
-            T zn = xi + ui;
-            zn = tmin(tmax(zn, lb[i]), ub[i]);
-            const T rr = xi - zn;
-            const T ss = rho * (zn - zp);
-            const T un = ui + rr;
-            if (in) { z[i] = zn; u[i] = un; }
+            const AdmmStep<T> sp = admm_step(xi, zp, ui, lb[i], ub[i], rho);
+            if (in) { z[i] = sp.zn; u[i] = sp.un; }
             if (check && in) {
-                const T di = D[i];
-                mx[0] = tabs(di * rr);
-                mx[1] = tabs(di * ss);
-                mx[2] = tabs(di * xi);
-                mx[3] = tabs(di * zn);
-                mx[4] = tabs((rho * di) * un);
                 T qx = -ps[i] + rho * (zp - ui) - rho * xi;
                 for (int k = 0; k < m; ++k) qx -= V.As[(size_t)k * n + i] * nul[k];
-                mx[5] = tabs(qx / di);
+                admm_step_norms<false>(mx, sp, xi, D[i], rho, qx);
             }
-            wl[(i >> 6) * WS + (i & 63)] = in ? -ps[i] + rho * (zn - un) : T(0);
+            wl[(i >> 6) * WS + (i & 63)] = in ? -ps[i] + rho * (sp.zn - sp.un) : T(0);
         }
         if (check) {
             T mv[6] = {mx[0], mx[1], mx[2], mx[3], mx[4], mx[5]};
@@ -404,15 +394,12 @@ __global__ __launch_bounds__(DENSE_NT) void k_admm_loop_dense(const FwdParams<T>
             const T den = tmax(mv[1] / dua_scale, tiny);
             const T ratio = tsqrt(num / den);
             const bool trig = (ratio > P.ar_tol) || (ratio < P.ar_inv_tol);
+            const LoopCheck<T> ck{ratio, solved, wants, trig};      // (loop_check's lines, kept here: see DESIGN.md section 10)
             unsigned int* ct = P.counters + (size_t)slot * CT_WORDS;
             if (tid == 0) {
                 unsigned int r1 = 0, r2 = 0;
                 if (part == 0) {
-                    scal[SC_RATIO] = ratio;
-                    scal[SC_WANTS] = wants ? T(1) : T(0);
-                    scal[SC_PRI] = mv[0];
-                    scal[SC_DUA] = mv[1];
-                    trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
+                    loop_check_store<false>(P, scal, ck, mv, it);
                     if (wants) r1 = atomicAdd(ct + CT_WANTS, 1u);
                     if (trig) r2 = atomicAdd(ct + CT_TRIG, 1u);
                 }
@@ -422,14 +409,7 @@ __global__ __launch_bounds__(DENSE_NT) void k_admm_loop_dense(const FwdParams<T>
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             ++slot;
-            grid_wait(ct + CT_ARRIVE, 2u * (unsigned int)P.B, P.status);      // device-wide "all optimal?" (torch.all at :312)
-            const unsigned int notopt = __hip_atomic_load(ct + CT_NOTOPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (notopt == 0 || tmo) {
-                if (blockIdx.x == 0 && tid == 0) {
-                    P.status[ST_FINAL_ITER] = it;
-                    __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+            if (loop_all_optimal(P, ct, 2u * (unsigned int)P.B, it, blockIdx.x == 0 && tid == 0)) {
                 __syncthreads();
                 break;
             }
@@ -609,24 +589,14 @@ __global__ __launch_bounds__(DENSEW_NT) void k_admm_loop_dense_w(const FwdParams
             const T xi = xs[i];
             const T zp = z[i];
             const T ui = u[i];
-            T zn = xi + ui;
-            zn = tmin(tmax(zn, lb[i]), ub[i]);
-            const T rr = xi - zn;
-            const T ss = rho * (zn - zp);
-            const T un = ui + rr;
-            z[i] = zn; u[i] = un;
+            const AdmmStep<T> sp = admm_step(xi, zp, ui, lb[i], ub[i], rho);
+            z[i] = sp.zn; u[i] = sp.un;
             if (check) {
-                const T di = D[i];
-                mx[0] = tmax(mx[0], tabs(di * rr));
-                mx[1] = tmax(mx[1], tabs(di * ss));
-                mx[2] = tmax(mx[2], tabs(di * xi));
-                mx[3] = tmax(mx[3], tabs(di * zn));
-                mx[4] = tmax(mx[4], tabs((rho * di) * un));
                 T qx = -ps[i] + rho * (zp - ui) - rho * xi;
                 for (int k = 0; k < m; ++k) qx -= V.As[(size_t)k * n + i] * nul[k];
-                mx[5] = tmax(mx[5], tabs(qx / di));
+                admm_step_norms<true>(mx, sp, xi, D[i], rho, qx);
             }
-            wl[(i / CPT) * WS + (i % CPT)] = -ps[i] + rho * (zn - un);
+            wl[(i / CPT) * WS + (i % CPT)] = -ps[i] + rho * (sp.zn - sp.un);
         }
         if (check) {
             T mv[6] = {mx[0], mx[1], mx[2], mx[3], mx[4], mx[5]};
@@ -642,15 +612,12 @@ __global__ __launch_bounds__(DENSEW_NT) void k_admm_loop_dense_w(const FwdParams
             const T den = tmax(mv[1] / dua_scale, tiny);
             const T ratio = tsqrt(num / den);
             const bool trig = (ratio > P.ar_tol) || (ratio < P.ar_inv_tol);
+            const LoopCheck<T> ck{ratio, solved, wants, trig};      // (loop_check's lines, kept here: see DESIGN.md section 10)
             unsigned int* ct = P.counters + (size_t)slot * CT_WORDS;
             if (tid == 0) {
                 unsigned int r1 = 0, r2 = 0;
                 if (part == 0) {
-                    scal[SC_RATIO] = ratio;
-                    scal[SC_WANTS] = wants ? T(1) : T(0);
-                    scal[SC_PRI] = mv[0];
-                    scal[SC_DUA] = mv[1];
-                    trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
+                    loop_check_store<false>(P, scal, ck, mv, it);
                     if (wants) r1 = atomicAdd(ct + CT_WANTS, 1u);
                     if (trig) r2 = atomicAdd(ct + CT_TRIG, 1u);
                 }
@@ -660,14 +627,7 @@ __global__ __launch_bounds__(DENSEW_NT) void k_admm_loop_dense_w(const FwdParams
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             ++slot;
-            grid_wait(ct + CT_ARRIVE, (unsigned int)gridDim.x, P.status);      // device-wide "all optimal?" (torch.all at :312)
-            const unsigned int notopt = __hip_atomic_load(ct + CT_NOTOPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (notopt == 0 || tmo) {
-                if (blockIdx.x == 0 && tid == 0) {
-                    P.status[ST_FINAL_ITER] = it;
-                    __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+            if (loop_all_optimal(P, ct, (unsigned int)gridDim.x, it, blockIdx.x == 0 && tid == 0)) {
                 __syncthreads();
                 break;
             }

@@ -1,9 +1,24 @@
-// the body of k_admm_loop_small / k_admm_loop_small_each (included once for each by lqp_boxqp.hpp: LQP_SMALL_KERNEL, LQP_SMALL_EACH)
-template <int LQP_ANY = 0>
-__global__ __launch_bounds__(256) void LQP_SMALL_KERNEL(const FwdParams<float> P, const int it0, const int it1,
-                                                        const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    constexpr bool EACH = LQP_SMALL_EACH;
+// The ADMM loop of the symmetric path for n <= 128: k_admm_loop_small and, for control['stop'] = 'each', k_admm_loop_small_each
+#pragma once
+#include "lqp_boxqp.hpp"
+
+namespace lqp {
+
+// ---------------------------------------------------------------------------
+// The hot loop for SMALL problems (symmetric path, n <= 128: BASELINE configs[1], n = 100): the 1024-thread kernel above
+// spends 8.4 k cycles per iteration there -- a 16-wave static walk with per-block LDS slots and partial-sum slices, sized
+// for 36 blocks, around THREE blocks of work.  Here: 256 threads, the whole (unpacked, full) matrix -H in registers --
+// thread t holds the 64 entries of row t >> 1, columns 64 (t & 1) .. -- the product is 64 FMAs per thread against
+// broadcast reads of w and ONE lane-pair add; element e of every vector lives in thread e's registers (threads 0..127).
+// Same iteration, same check (:285-313, blocking device-wide stop) and same exit state as admm_loop_body; first (hot)
+// launch only, continuation launches (adaptive-rho events, a counter ring turn) run the general kernel.
+// LDS: w[128] | y[128] | nus[m] | red[4 * 8 + 8]
+// ---------------------------------------------------------------------------
+__host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 + (m > 0 ? m : 1) + 4 * 8 + 8 + 8) * 4; }
+// EACH (control['stop'] = 'each'): the problem's own verdict ends its workgroup; no arrival word, no grid_wait
+template <bool EACH>
+__device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
+                                                     char* smem) {
     typedef float T;
     constexpr int NT = 256;
     const int b = blockIdx.x, n = P.n, m = P.m, Ks = P.Ks;
@@ -91,23 +106,13 @@ __global__ __launch_bounds__(256) void LQP_SMALL_KERNEL(const FwdParams<float> P
         if (live) {
             const T wi = wv[e];
             xi = cvi - yv[e];
-            const T zp = zi;
-            T zn = xi + ui;
-            zn = tmin(tmax(zn, lbi), ubi);                       // (:273-276; an infinite bound is a no-op)
-            const T rr_ = xi - zn;
-            const T ss = rho * (zn - zp);
-            const T un = ui + rr_;
-            zi = zn;
-            ui = un;
+            const AdmmStep<T> sp = admm_step(xi, zi, ui, lbi, ubi, rho);
+            zi = sp.zn;
+            ui = sp.un;
             if (check) {
-                mx[0] = tabs(di * rr_);
-                mx[1] = tabs(di * ss);
-                mx[2] = tabs(di * xi);
-                mx[3] = tabs(di * zn);
-                mx[4] = tabs((rho * di) * un);
-                T qx = wi - rho * xi;                            // Qs x = w - rho x - As^T nu (see admm_loop_body)
+                T qx = wi - rho * xi;
                 for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + e] * nus_l[q];
-                mx[5] = tabs(qx / di);
+                admm_step_norms<false>(mx, sp, xi, di, rho, qx);
             }
         }
         __syncthreads();                                         // (everybody has read w and y)
@@ -115,56 +120,30 @@ __global__ __launch_bounds__(256) void LQP_SMALL_KERNEL(const FwdParams<float> P
         if (check) {
             T mv[6] = {mx[0], mx[1], mx[2], mx[3], mx[4], mx[5]};
             wg_max_n<T, 6, NT / 64>(mv, red);
-            const T tiny = T(1e-16);
-            const T pri_scale = tmax(tmax(mv[2], mv[3]), tiny);
-            const T tol_p = P.eps_abs + P.eps_rel * pri_scale;
-            const T dua_scale = tmax(tmax(tmax(mv[4], mv[5]), pnorm), tiny);
-            const T tol_d = P.eps_abs + P.eps_rel * dua_scale;
-            const bool solved = (mv[0] < tol_p) && (mv[1] < tol_d);
-            const bool wants = (mv[0] > tmax(tol_p, P.ar_thr)) || (mv[1] > tmax(tol_d, P.ar_thr));
-            const T num = tmax(mv[0] / pri_scale, tiny);
-            const T den = tmax(mv[1] / dua_scale, tiny);
-            const T ratio = tsqrt(num / den);
-            const bool trig = (ratio > P.ar_tol) || (ratio < P.ar_inv_tol);
+            const LoopCheck<T> ck = loop_check(P, mv, pnorm);
             unsigned int* ct = P.counters + (size_t)slot * CT_WORDS;
             if constexpr (EACH) {
                 if (tid == 0) {
-                    scal[SC_RATIO] = ratio;
-                    scal[SC_WANTS] = wants ? T(1) : T(0);
-                    scal[SC_TRIG] = trig ? T(1) : T(0);
-                    scal[SC_PRI] = mv[0];
-                    scal[SC_DUA] = mv[1];
-                    trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
-                    if (!solved) atomicAdd(ct + CT_NOTOPT, 1u);      // (k_check_done at the end of a host-driven chunk reads the slot)
+                    loop_check_store<true>(P, scal, ck, mv, it);
+                    if (!ck.solved) atomicAdd(ct + CT_NOTOPT, 1u);      // (k_check_done at the end of a host-driven chunk reads the slot)
                 }
                 ++slot;
-                if (solved) { each_done = true; final_it = it; break; }      // (uniform: every thread holds the reduced norms)
+                if (ck.solved) { each_done = true; final_it = it; break; }      // (uniform: every thread holds the reduced norms)
             } else {
-            if (tid == 0) {
-                scal[SC_RATIO] = ratio;
-                scal[SC_WANTS] = wants ? T(1) : T(0);
-                scal[SC_PRI] = mv[0];
-                scal[SC_DUA] = mv[1];
-                trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
-                unsigned int r1 = 0, r2 = 0;
-                if (wants) r1 = atomicAdd(ct + CT_WANTS, 1u);
-                if (trig) r2 = atomicAdd(ct + CT_TRIG, 1u);
-                asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1), "v"(r2) : "memory");
-                __hip_atomic_fetch_add((unsigned long long*)(ct + CT_NOTOPT), (solved ? 0ull : 1ull) | (1ull << 32),
-                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            ++slot;
-            grid_wait(ct + CT_ARRIVE, gridDim.x, P.status);      // device-wide "all optimal?" (torch.all at :312)
-            const unsigned int notopt = __hip_atomic_load(ct + CT_NOTOPT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (notopt == 0 || tmo) {
-                if (b == 0 && tid == 0) {
-                    P.status[ST_FINAL_ITER] = it;
-                    __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ++slot;
+                if (tid == 0) {
+                    loop_check_store<false>(P, scal, ck, mv, it);
+                    // the arrival and the verdict in ONE 64-bit add (NOTOPT and ARRIVE share an aligned word) behind the RETURNED adds:
+                    // whoever sees the last arrival sees every counter of the check (see admm_loop_body)
+                    unsigned int r1 = 0, r2 = 0;
+                    if (ck.wants) r1 = atomicAdd(ct + CT_WANTS, 1u);
+                    if (ck.trig) r2 = atomicAdd(ct + CT_TRIG, 1u);
+                    asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1), "v"(r2) : "memory");
+                    __hip_atomic_fetch_add((unsigned long long*)(ct + CT_NOTOPT), (ck.solved ? 0ull : 1ull) | (1ull << 32),
+                                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-                break;
+                if (loop_all_optimal(P, ct, gridDim.x, it, b == 0 && tid == 0)) break;
             }
-            }       // (!EACH)
         }
         __syncthreads();
     }
@@ -174,15 +153,21 @@ __global__ __launch_bounds__(256) void LQP_SMALL_KERNEL(const FwdParams<float> P
     for (int q = tid; q < m; q += NT) V.nu[q] = nus_l[q];
     if constexpr (EACH) {
         if (tid == 0) {
-            int* ps_ = P.pstat + (size_t)b * PS_WORDS;
-            ps_[PS_FINAL] = final_it;          // (the iteration it stopped at, or the last one it ran)
-            if (each_done) {
-                ps_[PS_DONE] = 1;
-                const int r1 = atomicMax(P.status + ST_FINAL_ITER, final_it);
-                asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1) : "memory");
-                const int nd = __hip_atomic_fetch_add(P.status + ST_NDONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (nd + 1 == P.B) __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (each_done) each_stop(P, b, final_it);
+            else P.pstat[(size_t)b * PS_WORDS + PS_FINAL] = final_it;      // (not optimal so far: the last iteration it ran)
         }
     }
 }
+template <int LQP_ANY = 0>      // (a template only so that the split build can place its one instance: tools/gen_split_build.py)
+__global__ __launch_bounds__(256) void k_admm_loop_small(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_small_body<false>(P, it0, it1, ctr_base, smem);
+}
+template <int LQP_ANY = 0>
+__global__ __launch_bounds__(256) void k_admm_loop_small_each(const FwdParams<float> P, const int it0, const int it1,
+                                                              const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_small_body<true>(P, it0, it1, ctr_base, smem);
+}
+
+}  // namespace lqp

@@ -1,12 +1,51 @@
-// the body of k_admm_loop_split / k_admm_loop_split_each (lqp_boxqp.hpp includes this file once for each, with LQP_SPLIT_KERNEL the
-// kernel's name and LQP_SPLIT_EACH false / true): one text, two kernel names -- the default's instances keep their symbols and their code
-template <int KS, int NT, bool DBG = false, int NP = 2>
-__global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P, const int it0_in, const int it1,
-                                                       const int ctr_base_in) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    constexpr bool EACH = LQP_SPLIT_EACH;
+// The ADMM loop of the symmetric path on two or four workgroups per problem, the matrix in their registers: k_admm_loop_split and,
+// for control['stop'] = 'each', k_admm_loop_split_each
+#pragma once
+#include "lqp_boxqp.hpp"
+
+namespace lqp {
+
+// ---------------------------------------------------------------------------
+// The same loop with TWO workgroups per QP (symmetric x-update, f32, 2 B <= #CUs, Ks >= SPLIT_MINK): workgroups b
+// and b + B hold one half of the blocks of H each, ALL of them on chip for the whole launch (lqp_spd.hpp,
+// wg_sym_gemv_split), and exchange their partial products every iteration:
+//   thread e < Nps combines its element of this workgroup's partial, publishes it as ONE 8-byte granule
+//   {tag, value} (agent-scope relaxed atomic store = sc1 write-through store), polls the partner's granule of the
+//   same element (sc1 loads, L1 bypassed) until the tag matches, and adds the two partials in the fixed order
+//   part 0 + part 1 -- both workgroups then hold bit-identical iterates and run the element-wise update and the
+//   checks redundantly (part 0 alone reports to the counters / writes state).
+// Two granule buffers alternate by iteration parity: a workgroup can be at most one exchange ahead of its
+// partner, so a granule is never overwritten before it was read.  The area is zeroed by k_fwd_setup of the same
+// forward (tags start at 1).  Spins are bounded: a timeout sets ST_TIMEOUT and the kernel still drains.
+//
+// The global stop (torch.all(is_optimal), :312) does not block the loop.  At a check, part 0 adds {not optimal?,
+// arrival} to the check's counter word with ONE 64-bit atomic, both workgroups keep a snapshot of the iterate and go
+// on iterating; in the following iterations part 0 reads the counter word while its product runs (the load's latency
+// is hidden), and once all B arrivals are in, the verdict travels to the partner in the top bits of that iteration's
+// granule tags.  "All optimal" -> both restore the snapshot, part 0 stores it and the kernel exits with the
+// reference's iteration count (the 1-3 speculative iterations are dropped); otherwise the snapshot is forgotten.
+// A verdict still open at the next check or at the last iteration of the launch is waited for (bounded spin).
+//
+// LDS (floats; every offset but the last three arrays is a compile-time constant):
+//   [rl blocks] v yrow cvl part[NW][Nps] z u ps lb ub D xs sz su sx (Nps each) red[NW*8+8] flags[8] | bs nus snu (m each)
+// ---------------------------------------------------------------------------
+template <int NT, int NP = 2> __host__ __device__ constexpr int split_loop_lds_floats(int Ks) {
+    return split_lds_blocks<NT, NP>(Ks) * LQP_BLK + (3 + NT / 64 + 10) * Ks * LQP_NB + (NT / 64) * 8 + 8 + 8;
+}
+template <int NT, int NP = 2> __host__ __device__ inline int split_loop_lds_bytes(int Ks, int m) {
+    // + the equality block: As, G, T (m x Nps each), S, S^-1 (m x m), s0, b, nu, nu snapshot
+    return (split_loop_lds_floats<NT, NP>(Ks) + 3 * m * Ks * LQP_NB + 2 * m * m + 4 * m + 8) * 4;
+}
+// NP = 4 (batches up to a quarter of the CUs): one column pair per workgroup, every partial product published once and
+// fetched by the three others; the sum runs over the parts in their order on every workgroup (identical iterates).
+// EACH (control['stop'] = 'each'): the partners hold bit-identical iterates and compute the same six norms, so each of them reaches the
+// problem's verdict in the same iteration with no message: no arrival word, no snapshot, no look-back, no verdict in the tags (all
+// compiled out).  Optimal -> the lead workgroup stores the iterate and marks pstat[b], every workgroup of the problem returns.  The hot
+// launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop_each) takes the problem's own decision.
+// (P by value: a reference to the kernel's parameter block costs the default's instances registers)
+template <int KS, int NT, bool DBG, int NP, bool EACH>
+__device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, int it0, const int it1, int ctr_base, char* smem) {
     typedef float T;
-    int it0 = it0_in, ctr_base = ctr_base_in;
     if (P.hot_resume) {            // (a later round of the hot loop: it goes on where the round before stopped)
         const int r = __builtin_amdgcn_readfirstlane(P.status[ST_RESUME]);
         if (r <= 0) return;
@@ -244,6 +283,10 @@ __global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P,
             }
         }
     };
+    auto store_state = [&]() {                                // the iterate as it stands (part 0)
+        for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xs[i]; }
+        for (int r = tid; r < m; r += NT) V.nu[r] = nus_l[r];
+    };
     auto leave_with_snapshot = [&]() {                        // every problem was optimal at iteration pend_it
         if (blockIdx.x == 0 && tid == 0) {
             P.status[ST_FINAL_ITER] = pend_it;
@@ -345,28 +388,17 @@ __global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P,
         if (tid < Nps) {
             const int i = tid;
             xs[i] = xi;
-            const T zp = z[i];
-            const T ui = u[i];
-            T zn = xi + ui;
-            zn = tmin(tmax(zn, lb[i]), ub[i]);
-            const T r = xi - zn;
-            const T s = rho * (zn - zp);
-            const T un = ui + r;
+            const AdmmStep<T> sp = admm_step(xi, z[i], u[i], lb[i], ub[i], rho);
+            const T zn = sp.zn, un = sp.un;
             const bool in = i < n;
             if (in) { z[i] = zn; u[i] = un; }
             if constexpr (COLD) {
                 if (check) {
                     if constexpr (!EACH) { sz[i] = zn; su[i] = un; sx[i] = xi; }      // snapshot for a late "all optimal"
                     if (in) {
-                        const T di = D[i];
-                        mx[0] = tabs(di * r);
-                        mx[1] = tabs(di * s);
-                        mx[2] = tabs(di * xi);
-                        mx[3] = tabs(di * zn);
-                        mx[4] = tabs((rho * di) * un);
                         T qx = v[i] - rho * xi;
                         for (int q = 0; q < m; ++q) qx -= Asl[(size_t)q * Nps + i] * nus_l[q];
-                        mx[5] = tabs(qx / di);
+                        admm_step_norms<false>(mx, sp, xi, D[i], rho, qx);
                     }
                 }
             }
@@ -384,61 +416,8 @@ __global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P,
                     for (int q = 0; q < 6; ++q) red[w * 8 + q] = mx[q];
                 }
                 __syncthreads();
-                if constexpr (EACH) {
-                    if (tid == 0) {                           // (every workgroup of the problem: the very same numbers, the same verdict)
-                        T mv[6];
-#pragma unroll
-                        for (int q = 0; q < 6; ++q) mv[q] = red[q];
-#pragma unroll 1
-                        for (int ww = 1; ww < NWV; ++ww) {
-#pragma unroll
-                            for (int q = 0; q < 6; ++q) mv[q] = tmax(mv[q], red[ww * 8 + q]);
-                        }
-                        const T tiny = T(1e-16);
-                        const T pri_scale = tmax(tmax(mv[2], mv[3]), tiny);
-                        const T tol_p = P.eps_abs + P.eps_rel * pri_scale;
-                        const T dua_scale = tmax(tmax(tmax(mv[4], mv[5]), pnorm), tiny);
-                        const T tol_d = P.eps_abs + P.eps_rel * dua_scale;
-                        const bool solved = (mv[0] < tol_p) && (mv[1] < tol_d);
-                        flags[4] = solved ? 1 : 0;
-                        if (part_id == 0) {
-                            const bool wants = (mv[0] > tmax(tol_p, P.ar_thr)) || (mv[1] > tmax(tol_d, P.ar_thr));
-                            const T num = tmax(mv[0] / pri_scale, tiny);
-                            const T den = tmax(mv[1] / dua_scale, tiny);
-                            const T ratio = tsqrt(num / den);
-                            const bool trig = (ratio > P.ar_tol) || (ratio < P.ar_inv_tol);
-                            scal[SC_RATIO] = ratio;
-                            scal[SC_WANTS] = wants ? T(1) : T(0);
-                            scal[SC_TRIG] = trig ? T(1) : T(0);
-                            scal[SC_PRI] = mv[0];
-                            scal[SC_DUA] = mv[1];
-                            trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
-                            // not optimal: into the check's slot in every mode (k_check_done at the end of a host-driven chunk)
-                            if (!solved) atomicAdd(P.counters + (size_t)slot * CT_WORDS + CT_NOTOPT, 1u);
-                        }
-                    }
-                    ++slot;
-                    __syncthreads();
-                    if (flags[4]) {
-                        // leave with the state of iteration `it`: the iterate first, then the words that say so
-                        if (part_id == 0) {
-                            for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xs[i]; }
-                            for (int r = tid; r < m; r += NT) V.nu[r] = nus_l[r];
-                            if (tid == 0) {
-                                int* ps_ = P.pstat + (size_t)b * PS_WORDS;
-                                ps_[PS_FINAL] = it;
-                                ps_[PS_DONE] = 1;
-                                const int r1 = atomicMax(P.status + ST_FINAL_ITER, it);
-                                asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1) : "memory");
-                                const int nd = __hip_atomic_fetch_add(P.status + ST_NDONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                if (nd + 1 == P.B) __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                        }
-                        return 1;
-                    }
-                } else {
-                if (part_id == 0 && tid == 0) {               // (the partner computed the very same numbers)
-                    T mv[6];
+                T mv[6];                                       // (only the thread that folds them holds the norms)
+                auto fold_norms = [&]() {
 #pragma unroll
                     for (int q = 0; q < 6; ++q) mv[q] = red[q];
 #pragma unroll 1
@@ -446,32 +425,47 @@ __global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P,
 #pragma unroll
                         for (int q = 0; q < 6; ++q) mv[q] = tmax(mv[q], red[ww * 8 + q]);
                     }
-                    const T tiny = T(1e-16);
-                    const T pri_scale = tmax(tmax(mv[2], mv[3]), tiny);
-                    const T tol_p = P.eps_abs + P.eps_rel * pri_scale;
-                    const T dua_scale = tmax(tmax(tmax(mv[4], mv[5]), pnorm), tiny);
-                    const T tol_d = P.eps_abs + P.eps_rel * dua_scale;
-                    const bool solved = (mv[0] < tol_p) && (mv[1] < tol_d);
-                    const bool wants = (mv[0] > tmax(tol_p, P.ar_thr)) || (mv[1] > tmax(tol_d, P.ar_thr));
-                    const T num = tmax(mv[0] / pri_scale, tiny);
-                    const T den = tmax(mv[1] / dua_scale, tiny);
-                    const T ratio = tsqrt(num / den);
-                    const bool trig = (ratio > P.ar_tol) || (ratio < P.ar_inv_tol);
-                    unsigned int* ct = P.counters + (size_t)slot * CT_WORDS;
-                    scal[SC_RATIO] = ratio;
-                    scal[SC_WANTS] = wants ? T(1) : T(0);
-                    scal[SC_PRI] = mv[0];
-                    scal[SC_DUA] = mv[1];
-                    trace_check(P.vtrace, it, P.check_solved, P.ring, mv[0], mv[1]);
-                    if (wants) atomicAdd(ct + CT_WANTS, 1u);
-                    if (trig) atomicAdd(ct + CT_TRIG, 1u);
-                    atomicAdd((unsigned long long*)ct, (1ull << 32) | (solved ? 0ull : 1ull));   // {not optimal, arrival}
+                };
+                if constexpr (EACH) {
+                    if (tid == 0) {                           // (every workgroup of the problem: the very same numbers, the same verdict)
+                        fold_norms();
+                        const LoopCheck<T> ck = loop_check(P, mv, pnorm);
+                        flags[4] = ck.solved ? 1 : 0;
+                        if (part_id == 0) {
+                            loop_check_store<true>(P, scal, ck, mv, it);
+                            // not optimal: into the check's slot in every mode (k_check_done at the end of a host-driven chunk)
+                            if (!ck.solved) atomicAdd(P.counters + (size_t)slot * CT_WORDS + CT_NOTOPT, 1u);
+                        }
+                    }
+                    ++slot;
+                    __syncthreads();
+                    if (flags[4]) {
+                        // leave with the state of iteration `it`: the iterate first, then the words that say so
+                        if (part_id == 0) {
+                            store_state();
+                            if (tid == 0) each_stop(P, b, it);
+                        }
+                        return 1;
+                    }
+                } else {
+                    if (part_id == 0 && tid == 0) {               // (the partner computed the very same numbers)
+                        fold_norms();
+                        const LoopCheck<T> ck = loop_check(P, mv, pnorm);
+                        unsigned int* ct = P.counters + (size_t)slot * CT_WORDS;
+                        loop_check_store<false>(P, scal, ck, mv, it);
+                        // NOT the ordered arrival of the blocking loops: these adds to WANTS / TRIG are not waited for before the
+                        // arrival, while the hot_past reader below reads both words once it has seen B arrivals.  The four words of a
+                        // slot share one 16-byte line; whether the ordered form (a round trip per check in the headline's loop) would
+                        // cost time here has not been measured.
+                        if (ck.wants) atomicAdd(ct + CT_WANTS, 1u);
+                        if (ck.trig) atomicAdd(ct + CT_TRIG, 1u);
+                        atomicAdd((unsigned long long*)ct, (1ull << 32) | (ck.solved ? 0ull : 1ull));   // {not optimal, arrival}
+                    }
+                    pend_word = (const unsigned long long*)(P.counters + (size_t)slot * CT_WORDS);
+                    pend_it = it;
+                    pending = !P.split_seg;        // (one launch per check segment: the verdict is the next launch's / k_check_done's)
+                    ++slot;
                 }
-                pend_word = (const unsigned long long*)(P.counters + (size_t)slot * CT_WORDS);
-                pend_it = it;
-                pending = !P.split_seg;        // (one launch per check segment: the verdict is the next launch's / k_check_done's)
-                ++slot;
-                }       // (!EACH)
             }
         }
         if (dbg_on) { const unsigned long long t = clock64(); dbt[4] += t - dt0; dt0 = t; }
@@ -539,8 +533,7 @@ __global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P,
     }
     if (!EACH && P.hot_past && blockIdx.x == 0 && tid == 0) P.status[ST_RESUME] = it;      // (where the continuation launch goes on)
     if (part_id == 0) {
-        for (int i = tid; i < n; i += NT) { V.z[i] = z[i]; V.u[i] = u[i]; V.x[i] = xs[i]; }
-        for (int r = tid; r < m; r += NT) V.nu[r] = nus_l[r];
+        store_state();
         if constexpr (EACH) { if (tid == 0) P.pstat[(size_t)b * PS_WORDS + PS_FINAL] = it1 - 1; }      // (not optimal so far)
     }
     // the loop goes on in a continuation launch, which reads the blocks from global memory: there they still lack the
@@ -548,6 +541,18 @@ __global__ __launch_bounds__(NT) void LQP_SPLIT_KERNEL(const FwdParams<float> P,
     if (eq_here) {
         T* packed_w = P.packed + (size_t)b * packed_blocks(P.K) * LQP_BLK;
         LQP_BY_PART((split_resident_store<KS, PARTC, NT, NP>(rr, lds_res, packed_w)));
-#undef LQP_BY_PART
     }
+#undef LQP_BY_PART
 }
+template <int KS, int NT, bool DBG = false, int NP = 2>
+__global__ __launch_bounds__(NT) void k_admm_loop_split(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_split_body<KS, NT, DBG, NP, false>(P, it0, it1, ctr_base, smem);
+}
+template <int KS, int NT, bool DBG = false, int NP = 2>
+__global__ __launch_bounds__(NT) void k_admm_loop_split_each(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_split_body<KS, NT, DBG, NP, true>(P, it0, it1, ctr_base, smem);
+}
+
+}  // namespace lqp

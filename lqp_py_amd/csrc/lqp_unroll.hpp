@@ -18,6 +18,8 @@
 #pragma once
 #include "lqp_boxqp.hpp"
 #include "lqp_dense.hpp"
+#include "lqp_loop_small.hpp"
+#include "lqp_loop_split.hpp"
 
 namespace lqp {
 
