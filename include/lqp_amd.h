@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LQP_ABI_VERSION 14
+#define LQP_ABI_VERSION 15
 
 enum { LQP_F32 = 0, LQP_F64 = 1 };
 
@@ -180,6 +180,15 @@ int lqp_debug_xcd(void* stream, int blocks, void* out_dev);
  * (`packed`: the buffer lqp_lu_pack filled).  Any N whose column tile fits the LDS: float32 to 2048 (above 576 rows on 16-column
  * tiles), float64 to about 1100; LQP_ERR_UNSUPPORTED beyond.  No reference counterpart. */
 int lqp_debug_lu_inverse(void* stream, int dtype, int B, int N, const void* packed, void* X_out);
+/* test access to the block solves of the Cholesky backward (csrc/lqp_spd.hpp; ABI 15): L L^T X = V, float32, one workgroup per
+ * problem.  `packed`: B factors of sym_blocks(Kmax) = Kmax (Kmax + 1) / 2 blocks of 64 x 64 each, problem b's own kb[b] <= Kmax
+ * block rows laid out as the backward lays them out (lower blocks column by column, block (i, j) at j kb - j (j - 1) / 2 + i - j,
+ * row-major inside a block, diagonal blocks holding the INVERSE of L's diagonal block); kb: B int32 on the device; V, X_out:
+ * (B, nrhs, 64 Kmax), X_out zero past 64 kb[b].  nr = 2 | 4 right-hand sides per round; which = 0: wg_chol_solve_n whatever
+ * kb[b], 1: what k_bwd_chol_solve calls (the register-resident solve up to its block limit, wg_chol_solve_n above).
+ * Kmax <= 8, nrhs <= 32.  No reference counterpart. */
+int lqp_debug_chol_solve(void* stream, int B, int Kmax, const void* packed, const void* kb, int nrhs, int nr, int which,
+                         const void* V, void* X_out);
 
 /* ---- forward ADMM solve ------------------------------------------------
  * Replaces torch_solve_box_qp (lqp_py/solve_box_qp_admm_torch.py:108-333):

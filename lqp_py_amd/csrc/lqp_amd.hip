@@ -2074,6 +2074,19 @@ int lqp_debug_lu_inverse(void* stream, int dtype, int B, int N, const void* pack
     });
 }
 
+int lqp_debug_chol_solve(void* stream, int B, int Kmax, const void* packed, const void* kb, int nrhs, int nr, int which,
+                         const void* V, void* X_out) {
+    if (B < 1 || Kmax < 1 || Kmax > SPD_MAXK || nrhs < 1 || nrhs > 32 || (nr != 2 && nr != 4) || (which != 0 && which != 1) ||
+        !packed || !kb || !V || !X_out) return LQP_ERR_INVALID;
+    const int lds = debug_chol_solve_lds_bytes(Kmax, nrhs, nr);
+    auto fn = nr == 4 ? k_debug_chol_solve<4> : k_debug_chol_solve<2>;
+    const int rc = ensure_lds((const void*)fn, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, (hipStream_t)stream, (const float*)packed, (const int*)kb, (const float*)V,
+                       (float*)X_out, Kmax, nrhs, which);
+    return last_error();
+}
+
 int lqp_profile_classes(void) { return PC_COUNT; }
 
 const char* lqp_profile_class_name(int c) {

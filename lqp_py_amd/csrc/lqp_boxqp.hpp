@@ -2420,21 +2420,23 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_chol_solve(const BwdParams<float
     float* S = part + NR * LQP_NW * 64;
     float* wv = S + m * m;
     float* dn = wv + m;
-    if (P.phase == 2) {                    // the cotangent arrives only now: gathered over the free set of phase 1
-        const float* g = P.g + (size_t)b * n;
-        const int* fidx = P.fidx + (size_t)b * n;
-        const float* bs_ = P.bsc ? P.bsc + (size_t)b * Np : nullptr;
-        for (int e = tid; e < Nb; e += LQP_NT) u0[e] = e < nf ? -g[fidx[e]] * (bs_ ? bs_[e] : 1.f) : 0.f;
-    } else {
-        for (int e = tid; e < Nb; e += LQP_NT) u0[e] = rhs[e];
-    }
-    for (int q = 0; q < m; ++q)
-        for (int e = tid; e < Nb; e += LQP_NT) G[(size_t)q * Npm + e] = AF[(size_t)q * Npm + e];
-    __syncthreads();
-    if (Kb > 0)
-        for (int c0 = 0; c0 < 1 + m; c0 += NR)
-            wg_chol_solve_n<NR>(Ls, Kb, u0 + (size_t)c0 * Npm, Npm, (1 + m - c0) < NR ? (1 + m - c0) : NR, acc, t, part,
-                                (P.dbg && P.la_maxk == 0) ? P.dbg + (size_t)b * 8 : nullptr);
+    auto fill = [&]() {                    // (wg_chol_solve_all: ahead of its request for the factor's blocks and a barrier; at most one element per thread and loop)
+        if (P.phase == 2) {                // the cotangent arrives only now: gathered over the free set of phase 1
+            const float* g = P.g + (size_t)b * n;
+            const int* fidx = P.fidx + (size_t)b * n;
+            const float* bs_ = P.bsc ? P.bsc + (size_t)b * Np : nullptr;
+#pragma unroll 1
+            for (int e = tid; e < Nb; e += LQP_NT) u0[e] = e < nf ? -g[fidx[e]] * (bs_ ? bs_[e] : 1.f) : 0.f;
+        } else {
+#pragma unroll 1
+            for (int e = tid; e < Nb; e += LQP_NT) u0[e] = rhs[e];
+        }
+        for (int q = 0; q < m; ++q)
+#pragma unroll 1
+            for (int e = tid; e < Nb; e += LQP_NT) G[(size_t)q * Npm + e] = AF[(size_t)q * Npm + e];
+    };
+    wg_chol_solve_all<NR>(Ls, Kb, u0, Npm, 1 + m, acc, t, part, true, fill,
+                          (P.dbg && P.la_maxk == 0) ? P.dbg + (size_t)b * 8 : nullptr);
     if (P.dbg && tid == 0) { const unsigned long long t = clock64(); P.dbg[(size_t)b * 8 + 1] = t - dt0; dt0 = t; }
     if (m > 0) {
         // S = A_F G - eps I,  wv = A_F u0  (one wave per entry)
@@ -2495,6 +2497,34 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_chol_solve(const BwdParams<float
     }
     for (int q = tid; q < m; q += LQP_NT) rhs[nf + q] = dn[q];
     if (P.dbg && tid == 0) P.dbg[(size_t)b * 8 + 2] = clock64() - dt0;
+}
+
+// test aid (lqp_debug_chol_solve): the block solves of k_bwd_chol_solve alone, on the caller's packed factors and right-hand sides.
+// reg = 0: wg_chol_solve_n whatever the block count.  LDS: acc[NR * Npm] | X[nrhs * Npm] | t[NR * 64] | part[NR * NW * 64]
+__host__ __device__ inline int debug_chol_solve_lds_bytes(int Kmax, int nrhs, int nr) {
+    return ((nr + nrhs) * Kmax * LQP_NB + nr * 64 + nr * LQP_NW * 64) * 4;
+}
+template <int NR>
+__global__ __launch_bounds__(LQP_NT) void k_debug_chol_solve(const float* __restrict__ packed, const int* __restrict__ kb,
+                                                             const float* __restrict__ V, float* __restrict__ Xo, const int Kmax,
+                                                             const int nrhs, const int reg) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    const int b = blockIdx.x, tid = threadIdx.x, Npm = Kmax * LQP_NB;
+    const int K = min(max(kb[b], 0), Kmax), Nb = K * LQP_NB;
+    const float* Ls = packed + (size_t)b * sym_blocks(Kmax) * LQP_BLK;
+    const float* Vb = V + (size_t)b * nrhs * Npm;
+    float* Xb = Xo + (size_t)b * nrhs * Npm;
+    float* acc = (float*)smem;
+    float* X = acc + (size_t)NR * Npm;
+    float* t = X + (size_t)nrhs * Npm;
+    float* part = t + NR * 64;
+    auto fill = [&]() {
+        for (int c = 0; c < nrhs; ++c)
+            for (int e = tid; e < Nb; e += LQP_NT) X[(size_t)c * Npm + e] = Vb[(size_t)c * Npm + e];
+    };
+    wg_chol_solve_all<NR>(Ls, K, X, Npm, nrhs, acc, t, part, reg != 0, fill);
+    for (int c = 0; c < nrhs; ++c)
+        for (int e = tid; e < Npm; e += LQP_NT) Xb[(size_t)c * Npm + e] = e < Nb ? X[(size_t)c * Npm + e] : 0.f;
 }
 
 // One step of iterative refinement for the LU form of the reduced system: r = rhs - M d with the ORIGINAL entries

@@ -3495,4 +3495,224 @@ __device__ __forceinline__ void wg_chol_solve_n(const float* __restrict__ Ls, co
     if (dbg && threadIdx.x == 0) dbg[5] += clock64() - c0;
 }
 
+// ---- the same solve with the factor in registers (chol_reg_maxk block rows at most) ----
+// wg_chol_solve_n asks L2 for every block column behind the barrier that ended the previous one, twice per round of right-hand sides,
+// and every one of its barriers (__syncthreads: vmcnt(0)) drains those loads.  A factor of K <= 6 is at most 21 blocks = 84 VGPRs at
+// 16 bytes per thread and block, and the solves share no live state with the factorisation ahead of them.  So: the blocks are
+// requested ONCE, in one burst (chol_regs_load) behind the caller's right-hand-side fill -- behind, because vmcnt counts in order:
+// a fill issued after the burst waits for all of it (measured: 6 k cycles) --, and serve both substitutions of every round; the
+// barriers order LDS traffic only (wg_barrier_lds), so the burst arrives under the first column steps.  The forward
+// substitution's running sums stay in the register of the thread that owns them (the cq == 0 lane of row r, for every block row),
+// which forms the next column's t itself: two barriers per column on the way down instead of three.  The last column's y does
+// not go through LDS and a barrier: the cq == 0 lane's sum -- the one wg_chol_solve_n stores; the 16 lanes of a row add the
+// same quads in different orders -- goes to its row by ds_bpermute, and the zero sum it would be reduced by is not formed
+// (x - (+0) is x).  Every value sees the operations of wg_chol_solve_n in the same order -- dot4, rowgroup_sum, col_fold, the
+// order of the acc additions and of the 16 partial sums --, hence the same bits (tests/test_gpu_chol_solve.py).
+// LQP_CHOL_SOLVE_REG=0 (A/B builds): wg_chol_solve_n for every K.
+#ifndef LQP_CHOL_SOLVE_REG
+#define LQP_CHOL_SOLVE_REG 1
+#endif
+// Most block rows K of a factor that is solved out of registers, and the blocks NB that stay there.  Two right-hand sides per round:
+// K <= 5 is whole (15 blocks = 60 VGPRs); the 21 blocks of K = 6 with the running sums, the y pieces and the addresses do not fit 128
+// VGPRs without spilling, so six registers' worth of blocks is shared: block column 0, which the forward substitution needs
+// first and the backward substitution last, and block columns 3 .. 5, for which it is the other way round -- each set is requested
+// again two column steps ahead of its first use, its latency under those steps.  Four right-hand sides per round: the sums
+// (4 K) and the y pieces (16) leave room for 10 blocks, K = 5 and 6 keep wg_chol_solve_n.
+template <int NR> constexpr int chol_reg_maxk() { return NR > 2 ? 4 : 6; }
+template <int NR> constexpr int chol_reg_blocks() { return NR > 2 ? 10 : 15; }
+template <int V> struct IntC { static constexpr int value = V; };
+// this thread's 16 bytes of each block; the burst ahead of the solves: blocks 0 .. NB-1 of the packed factor (column by column,
+// block (i, j) at sym_idx(i, j, K)) -- all of them for sym_blocks(K) <= NB, block columns 0 .. 2 for K = 6
+template <int NB> struct CholRegs { V4<float> b[NB]; };
+__device__ __forceinline__ V4<float> chol_blk_load(const float* __restrict__ Ls, const int q) {
+    return *(const V4<float>*)(Ls + (size_t)q * LQP_BLK + threadIdx.x * 4);
+}
+// the same inside the round loop: the block's offset is formed where it is used (as constants, the twelve addresses of the shared
+// form are hoisted out of the loop into 24 VGPRs that the blocks need)
+__device__ __forceinline__ V4<float> chol_blk_reload(const float* __restrict__ Ls, int q) {
+    asm volatile("" : "+s"(q));
+    return chol_blk_load(Ls, q);
+}
+template <int NB>
+__device__ __forceinline__ void chol_regs_load(const float* __restrict__ Ls, const int K, CholRegs<NB>& R) {
+    const int nblk = sym_blocks(K);
+#pragma unroll
+    for (int q = 0; q < NB; ++q)
+        if (q < nblk) R.b[q] = chol_blk_load(Ls, q);
+}
+
+// dot4 and the transposed product's multiply-add as wg_chol_solve_n's are compiled (a1 b1 first, then a0 b0, a2 b2, a3 b3 fused; every
+// term of a column sum fused, the first one onto +0): written out, because left to the contraction pass a few of the unrolled sites
+// here came out in the other order -- one unit in the last place of a dot product, and not the same bits any more
+__device__ __forceinline__ float chol_dot4(const V4<float>& a, const V4<float>& b) {
+    return __builtin_fmaf(a.v[3], b.v[3], __builtin_fmaf(a.v[2], b.v[2], __builtin_fmaf(a.v[0], b.v[0], a.v[1] * b.v[1])));
+}
+
+template <int K, int NR, int NB>
+__device__ __forceinline__ void wg_chol_solve_reg(const float* __restrict__ Ls, CholRegs<NB>& R, float* __restrict__ X,
+                                                  const int xs, const int nc, float* __restrict__ t, float* __restrict__ part,
+                                                  unsigned long long* __restrict__ dbg = nullptr) {
+    constexpr bool SHARE = sym_blocks(K) > NB;               // block columns >= 3 in the registers of block column 0
+    constexpr int NSH = SHARE ? sym_blocks(K) - NB : 0;
+    static_assert(!SHARE || (NSH == K && sym_idx(3, 3, K) == NB), "the shared form: K = 6 on 15 resident blocks");
+    unsigned long long c0 = dbg ? clock64() : 0;
+    const int tid = threadIdx.x, r = tid >> 4, cq = tid & 15, lane = tid & 63, w = tid >> 6;
+    const int tc = tid >> 6, te = tid & 63;                  // (column, element) of the per-column 64-vectors
+    auto blk = [&](const int i, const int j) -> const V4<float>& {
+        const int q = sym_idx(i, j, K);
+        return R.b[q < NB ? q : q - NB];
+    };
+    // ---- L y = v, column by column ----
+    float acc[NR][K];
+    float yl[NR];                                            // the last column's y, row r (all 16 lanes of the row)
+#pragma unroll
+    for (int c = 0; c < NR; ++c) {
+        yl[c] = 0.f;
+#pragma unroll
+        for (int i = 0; i < K; ++i) acc[c][i] = 0.f;
+    }
+    if (cq == 0) {
+#pragma unroll
+        for (int c = 0; c < NR; ++c)
+            if (c < nc) t[c * 64 + r] = X[(size_t)c * xs + r] - acc[c][0];
+    }
+    wg_barrier_lds();
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int c = 0; c < NR; ++c) {
+            if (c < nc) {
+                const float s1 = rowgroup_sum<LQP_NT>(chol_dot4(blk(j, j), *(const V4<float>*)(t + c * 64 + cq * 4)));
+                if (j + 1 < K) { if (cq == 0) X[(size_t)c * xs + j * 64 + r] = s1; }
+                else yl[c] = __int_as_float(__builtin_amdgcn_ds_bpermute((lane & 48) << 2, __float_as_int(s1)));
+            }
+        }
+        if (j + 1 < K) {
+            wg_barrier_lds();
+            V4<float> yj[NR];
+#pragma unroll
+            for (int c = 0; c < NR; ++c) yj[c] = *(const V4<float>*)(X + (size_t)(c < nc ? c : 0) * xs + j * 64 + cq * 4);
+#pragma unroll
+            for (int i = j + 1; i < K; ++i) {
+#pragma unroll
+                for (int c = 0; c < NR; ++c)
+                    if (c < nc) acc[c][i] += rowgroup_sum<LQP_NT>(chol_dot4(blk(i, j), yj[c]));
+            }
+            if constexpr (SHARE) {                           // (block column 0 is done with: its registers take columns 3 ..)
+                if (j == 0) {
+#pragma unroll
+                    for (int q = 0; q < NSH; ++q) R.b[q] = chol_blk_reload(Ls, NB + q);
+                }
+            }
+            if (cq == 0) {                                   // (row r of every block row belongs to this thread)
+#pragma unroll
+                for (int c = 0; c < NR; ++c)
+                    if (c < nc) t[c * 64 + r] = X[(size_t)c * xs + (j + 1) * 64 + r] - acc[c][j + 1];
+            }
+            wg_barrier_lds();
+        }
+    }
+    // ---- L^T x = y, from the last block column up ----
+    auto fold = [&](float (&a2)[4], const int c) {           // column sums of this wave's 4 rows -> part[c][w][64]
+        col_fold<4>(a2);
+        part[((size_t)c * LQP_NW + w) * 64 + cq * 4 + col_fold_elem(lane)] = a2[0];
+    };
+    if (dbg && threadIdx.x == 0) { const unsigned long long c1 = clock64(); dbg[4] += c1 - c0; c0 = c1; }
+#pragma unroll
+    for (int j = K - 1; j >= 0; --j) {
+        if constexpr (SHARE) {                               // (block columns 3 .. are done with; the next round starts with column 0)
+            if (j == 2) {
+#pragma unroll
+                for (int q = 0; q < NSH; ++q) R.b[q] = chol_blk_reload(Ls, q);
+            }
+        }
+        float a2[NR][4];
+        float tr[NR];
+        if (j + 1 < K) {
+#pragma unroll
+            for (int c = 0; c < NR; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a2[c][e] = 0.f;
+#pragma unroll
+            for (int i = j + 1; i < K; ++i) {
+#pragma unroll
+                for (int c = 0; c < NR; ++c) {
+                    const float xi = X[(size_t)(c < nc ? c : 0) * xs + i * 64 + r];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a2[c][e] = __builtin_fmaf(blk(i, j).v[e], xi, a2[c][e]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NR; ++c) fold(a2[c], c);
+            wg_barrier_lds();
+            if (tc < nc) {
+                float sum = 0.f;
+#pragma unroll
+                for (int ww = 0; ww < LQP_NW; ++ww) sum += part[((size_t)tc * LQP_NW + ww) * 64 + te];
+                t[tc * 64 + te] = X[(size_t)tc * xs + j * 64 + te] - sum;
+            }
+            wg_barrier_lds();
+#pragma unroll
+            for (int c = 0; c < NR; ++c) tr[c] = t[c * 64 + r];
+        } else {
+#pragma unroll
+            for (int c = 0; c < NR; ++c) tr[c] = yl[c];
+        }
+#pragma unroll
+        for (int c = 0; c < NR; ++c) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) a2[c][e] = blk(j, j).v[e] * tr[c];
+            fold(a2[c], c);
+        }
+        wg_barrier_lds();
+        if (tc < nc) {
+            float sum = 0.f;
+#pragma unroll
+            for (int ww = 0; ww < LQP_NW; ++ww) sum += part[((size_t)tc * LQP_NW + ww) * 64 + te];
+            X[(size_t)tc * xs + j * 64 + te] = sum;
+        }
+        wg_barrier_lds();
+    }
+    if (dbg && threadIdx.x == 0) dbg[5] += clock64() - c0;
+}
+
+// All ntot right-hand sides X[c * xs + ..] (LDS), NR per round.  `fill` writes them (and whatever else the caller has to put
+// into LDS ahead of the solves); the request for the factor's blocks and a barrier follow it.
+// reg = false: wg_chol_solve_n whatever K (the debug entry compares the two).
+template <int NR, typename Fill>
+__device__ __forceinline__ void wg_chol_solve_all(const float* __restrict__ Ls, const int K, float* __restrict__ X, const int xs,
+                                                  const int ntot, float* __restrict__ acc, float* __restrict__ t,
+                                                  float* __restrict__ part, const bool reg, Fill&& fill,
+                                                  unsigned long long* __restrict__ dbg = nullptr) {
+    auto rounds = [&](auto&& solve) {
+        for (int c0 = 0; c0 < ntot; c0 += NR) solve(X + (size_t)c0 * xs, (ntot - c0) < NR ? (ntot - c0) : NR);
+    };
+#if LQP_CHOL_SOLVE_REG
+    constexpr int MAXK = chol_reg_maxk<NR>(), NB = chol_reg_blocks<NR>();
+    if (reg && K >= 1 && K <= MAXK) {
+        fill();
+        CholRegs<NB> R;
+        chol_regs_load<NB>(Ls, K, R);
+        wg_barrier_lds();
+        auto run = [&](auto kc) {
+            constexpr int KC = decltype(kc)::value;
+            if constexpr (KC <= MAXK)
+                rounds([&](float* Xc, const int nc) { wg_chol_solve_reg<KC, NR, NB>(Ls, R, Xc, xs, nc, t, part, dbg); });
+        };
+        switch (K) {
+            case 1: run(IntC<1>{}); break;
+            case 2: run(IntC<2>{}); break;
+            case 3: run(IntC<3>{}); break;
+            case 4: run(IntC<4>{}); break;
+            case 5: run(IntC<5>{}); break;
+            default: run(IntC<6>{}); break;
+        }
+        return;
+    }
+#endif
+    fill();
+    __syncthreads();
+    if (K > 0) rounds([&](float* Xc, const int nc) { wg_chol_solve_n<NR>(Ls, K, Xc, xs, nc, acc, t, part, dbg); });
+}
+
 }  // namespace lqp
