@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define LQP_ABI_VERSION 15
+#define LQP_ABI_VERSION 16
 
 enum { LQP_F32 = 0, LQP_F64 = 1 };
 
@@ -189,6 +189,14 @@ int lqp_debug_lu_inverse(void* stream, int dtype, int B, int N, const void* pack
  * Kmax <= 8, nrhs <= 32.  No reference counterpart. */
 int lqp_debug_chol_solve(void* stream, int B, int Kmax, const void* packed, const void* kb, int nrhs, int nr, int which,
                          const void* V, void* X_out);
+/* test access to the factorisation of the Cholesky backward (csrc/lqp_spd.hpp; ABI 16): in place on `packed_inout`, B matrices of
+ * sym_blocks(Kmax) blocks of 64 x 64 each in the layout above with kb = ceil(nf[b] / 64) block rows, holding the LOWER blocks of a
+ * symmetric positive definite matrix of order nf[b] (nf: B int32 on the device) padded with the identity to 64 kb, float32.  One
+ * workgroup per problem runs what k_bwd_chol_solve would for that block count (f16 = 1: its float16 tile products) and leaves L_ij
+ * below the diagonal, inv(L_jj) on it.  which = 0: every pivot block eliminates its 64 columns, 1: the last one stops behind
+ * column nf[b] (what LQP_PIV_COLS=1 runs).  info_out: B int32, 0 or 1 + the index of the first pivot that is not positive.
+ * Kmax <= 8.  No reference counterpart. */
+int lqp_debug_chol_factor(void* stream, int B, int Kmax, void* packed_inout, const void* nf, int f16, int which, void* info_out);
 
 /* ---- forward ADMM solve ------------------------------------------------
  * Replaces torch_solve_box_qp (lqp_py/solve_box_qp_admm_torch.py:108-333):

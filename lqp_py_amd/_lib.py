@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("LQP_LIB", os.path.join(CSRC, "liblqp_amd.so"))   # LQ
 SOURCES = ["lqp_amd.hip", "lqp_unroll.hpp", "lqp_boxqp.hpp", "lqp_loop_split.hpp", "lqp_loop_small.hpp", "lqp_lu.hpp", "lqp_lu_big.hpp", "lqp_lu2.hpp", "lqp_lu_wide.hpp", "lqp_dense.hpp", "lqp_trsv.hpp", "lqp_spd.hpp", "lqp_f16x2.hpp", "lqp_common.hpp"]
 
 LQP_F32, LQP_F64 = 0, 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 STATUS = {0: "ok", 1: "invalid argument", 2: "workspace too small", 3: "singular", 4: "HIP error",
           5: "grid barrier timeout", 6: "unsupported size (n + m <= 4096 in float32, 2048 in float64)", 7: "matrix outside the symmetric x-update"}
 
@@ -62,6 +62,7 @@ SYMBOLS = {
     "lqp_debug_xcd": (c_int, [_P, c_int, _P]),
     "lqp_debug_lu_inverse": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
     "lqp_debug_chol_solve": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "lqp_debug_chol_factor": (c_int, [_P, c_int, c_int, _P, _P, c_int, c_int, _P]),
     "lqp_boxqp_forward_workspace_bytes": (c_size_t, [c_int] * 4),
     "lqp_boxqp_forward": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
                                   ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P,

@@ -214,12 +214,17 @@ struct Knobs {
 #define LQP_KNOB_FIELD(field, env, dflt) int field;
     LQP_KNOBS(LQP_KNOB_FIELD)
 #undef LQP_KNOB_FIELD
+    // LQP_PIV_COLS (default 1): the last pivot block of the backward's look-ahead Cholesky and of the resident sweep stops behind
+    // the matrix's last real column (wg_pivot_block_mfma, COLS); 0: all 64 columns, the identity padding included.  Not in the list above: it selects no
+    // schedule and changes no bit (tests/test_gpu_pivot_cols.py) -- it exists for the A/B timing.  docs/KNOBS.md, below its table.
+    int piv_cols;
 };
 Knobs read_knobs() {
     Knobs k;
 #define LQP_KNOB_READ(field, env, dflt) k.field = env_int(env, dflt);
     LQP_KNOBS(LQP_KNOB_READ)
 #undef LQP_KNOB_READ
+    k.piv_cols = env_int("LQP_PIV_COLS", 1);
     return k;
 }
 const Knobs& knobs() {
@@ -756,6 +761,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     plan.spd_split = spd_split; plan.spd_turns = spd_turns; plan.spd_big_split = spd_big_split; plan.spd_resident = spd_resident;
     // rho = ||Qs||_F / sqrt(n): the norm is summed by k_spd_begin, which reads all of Q anyway, and rho is added to the
     // diagonal by the resident sweep -- the setup kernel then makes one pass over Q instead of two
+    P.piv_cols = k.piv_cols != 0 ? 1 : 0;
     P.rho_late = (spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late) ? 1 : 0;
     // ... and above 512 rows on two workgroups per matrix: the sums k_spd_begin leaves are turned into rho by k_spd_rho_big
     plan.rho_late_big = spd_big_split && !spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late != 0 &&
@@ -1586,6 +1592,7 @@ int plan_backward(const BwdCall& c, const Knobs& k, const int retry, BwdPlan<T>&
         }
         plan.chol_lds = bwd_chol_lds_bytes(n, m, nr);
         P.la_maxk = !k.bwd_lookahead ? 0 : (Kmax < SPD_MAXK ? Kmax : SPD_MAXK - 1);
+        P.piv_cols = k.piv_cols != 0 ? 1 : 0;
         const int rc = ensure_lds((const void*)plan.chol_fn, plan.chol_lds);
         if (rc) return rc;
     }
@@ -2084,6 +2091,25 @@ int lqp_debug_chol_solve(void* stream, int B, int Kmax, const void* packed, cons
     if (rc) return rc;
     hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, (hipStream_t)stream, (const float*)packed, (const int*)kb, (const float*)V,
                        (float*)X_out, Kmax, nrhs, which);
+    return last_error();
+}
+
+int lqp_debug_chol_factor(void* stream, int B, int Kmax, void* packed_inout, const void* nf, int f16, int which, void* info_out) {
+    if (B < 1 || Kmax < 1 || Kmax > SPD_MAXK || (f16 != 0 && f16 != 1) || (which != 0 && which != 1) || !packed_inout || !nf || !info_out)
+        return LQP_ERR_INVALID;
+#if !LQP_PIV_MFMA
+    if (f16) return LQP_ERR_UNSUPPORTED;
+#endif
+    // LDS and look-ahead limit as plan_backward sets them for n = 64 Kmax
+    const int a0 = spd_lds_bytes(Kmax);
+    const int lds = (Kmax < SPD_MAXK && chol_la_lds_bytes(Kmax) > a0) ? chol_la_lds_bytes(Kmax) : a0;
+    const int la_maxk = !knobs().bwd_lookahead ? 0 : (Kmax < SPD_MAXK ? Kmax : SPD_MAXK - 1);
+    auto fn = f16 ? k_debug_chol_factor<true> : k_debug_chol_factor<false>;
+    const int rc = ensure_lds((const void*)fn, lds);
+    if (rc) return rc;
+    if (hipMemsetAsync(info_out, 0, (size_t)B * sizeof(int), (hipStream_t)stream) != hipSuccess) return LQP_ERR_HIP;
+    hipLaunchKernelGGL(fn, dim3(B), dim3(LQP_NT), lds, (hipStream_t)stream, (float*)packed_inout, (const int*)nf, (int*)info_out, Kmax,
+                       la_maxk, which);
     return last_error();
 }
 

@@ -59,6 +59,7 @@ template <typename T> struct FwdParams {
                                          // (continuation kernel / 512-thread first launch)
     unsigned long long* dbg;             // optional cycle counters (8 per problem), debug only
     int dbg_qpass;                       // LQP_DBG_QPASS=1: the caller's debug buffer has a second half of B x 8 words for the stamps of the sweep's pass over Q
+    int piv_cols;                        // 1: the resident sweep's last pivot block stops behind column n (LQP_PIV_COLS; in the alignment gap in front of the pointer: no offset moves)
     unsigned long long* dbg_setup;       // the same words for k_fwd_setup's stamps (LQP_DBG_SETUP=1: then only those)
     int spd;                             // 1: symmetric-inverse path (no KKT matrix M is assembled)
     int qs_lazy;                         // 1: the scaled matrix Qs is not stored; its readers compute (D_i Q_ij) D_j
@@ -1265,6 +1266,7 @@ __global__ __launch_bounds__(RS_NT) void k_spd_resident(const FwdParams<float> P
     lr.q = qpass ? P.Q + (size_t)b * P.n * P.n : nullptr;
     lr.cmx = qpass ? prep_scratch(P, b) : nullptr;
     lr.dbg_tid = 64 * (P.dbg_qpass >> 8);
+    lr.piv_cols = P.piv_cols;
     lr.qdbg = (qpass && P.dbg && (P.dbg_qpass & 1) && part == 0) ? P.dbg + (size_t)(P.B + b) * 8 : nullptr;      // (LQP_DBG_QPASS=1: the debug buffer holds 2 B x 8 words)
     lr.fro_self = (fused && P.rho_mode == 0) ? 1 : 0;
     lr.rho_given = (fused && P.rho_mode != 0) ? P.scal[(size_t)b * SC_WORDS + SC_RHO] : 0.f;
@@ -2097,6 +2099,7 @@ template <typename T> struct BwdParams {
                                //    (dlam = diag(1/s) G dx) to [[Q + diag(w), A^T], [A, 0]] [dx; dnu] = [-g; 0],
                                //    w = lam_lo / s_lo + lam_hi / s_hi (both clamped at 1e-8, :450-452): every variable is "free",
                                //    w takes the place of the 1e-8 regulariser, and the epilogue forms dlb / dub from dlam
+    int piv_cols;              // 1: the look-ahead Cholesky's last pivot block stops behind the last free variable (LQP_PIV_COLS)
 };
 
 // diagonal weight of the KKT-system backward for variable i (see BwdParams::kkt)
@@ -2391,7 +2394,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_chol_solve(const BwdParams<float
     float* rhs = P.rhs + (size_t)b * Np;
     unsigned long long dt0 = P.dbg ? clock64() : 0;
     if (Kb > 0 && P.phase != 2) {
-        if (Kb <= P.la_maxk) wg_chol_factor_la<F16>(Ls, Kb, P.info + b, smem, P.dbg ? P.dbg + (size_t)b * 8 : nullptr);
+        if (Kb <= P.la_maxk) wg_chol_factor_la<F16>(Ls, Kb, P.info + b, smem, P.dbg ? P.dbg + (size_t)b * 8 : nullptr, P.piv_cols ? nf : 0);
         else if (Kb <= SPD_MAXK) wg_chol_factor(Ls, Kb, P.info + b, smem);
         else wg_chol_factor_big(Ls, Kb, P.info + b, smem);
     }
@@ -2525,6 +2528,22 @@ __global__ __launch_bounds__(LQP_NT) void k_debug_chol_solve(const float* __rest
     wg_chol_solve_all<NR>(Ls, K, X, Npm, nrhs, acc, t, part, reg != 0, fill);
     for (int c = 0; c < nrhs; ++c)
         for (int e = tid; e < Npm; e += LQP_NT) Xb[(size_t)c * Npm + e] = e < Nb ? X[(size_t)c * Npm + e] : 0.f;
+}
+
+// test aid (lqp_debug_chol_factor): the factorisation k_bwd_chol_solve chooses for Kb = ceil(nf / 64) alone, in place on the caller's
+// lower blocks (sym_idx(i, j, Kb) of each problem's sym_blocks(Kmax) blocks, the last block padded with the identity as
+// k_bwd_build_chol pads it).  cols = 0: every pivot block takes its 64 columns; 1: the last one stops behind column nf.
+template <bool F16>
+__global__ __launch_bounds__(LQP_NT) void k_debug_chol_factor(float* __restrict__ packed, const int* __restrict__ nf,
+                                                              int* __restrict__ info, const int Kmax, const int la_maxk, const int cols) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    const int b = blockIdx.x;
+    const int nfb = min(max(nf[b], 0), Kmax * LQP_NB);
+    const int Kb = round_up(nfb, LQP_NB) / LQP_NB;
+    float* Ls = packed + (size_t)b * sym_blocks(Kmax) * LQP_BLK;
+    if (Kb == 0) return;
+    if (Kb <= la_maxk) wg_chol_factor_la<F16>(Ls, Kb, info + b, smem, nullptr, cols ? nfb : 0);
+    else wg_chol_factor(Ls, Kb, info + b, smem);
 }
 
 // One step of iterative refinement for the LU form of the reduced system: r = rhs - M d with the ORIGINAL entries

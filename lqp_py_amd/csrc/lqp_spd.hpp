@@ -669,15 +669,25 @@ __device__ __forceinline__ V4<float> ld16_handoff(const float* __restrict__ p) {
 //                barrier and leave): the role code is not even compiled in -- a caller that has already branched on the
 //                wave number keeps the roles' registers out of its other branch this way.
 // IN_W (with GSYNC): the tile already sits in the W area (row stride SPD_LS), src_blk is not read.
-template <bool GSYNC = false, bool ROLES = true, bool IN_W = false, bool WMAX = false>
+// COLS: the tile holds `ncols` (1..64, the same in every wave) real columns and the identity behind them -- the last block of
+//       a matrix whose order is no multiple of 64.  Panels P with 4 P >= ncols are run by NO role: eliminating a column of
+//       the identity changes nothing (pivot 1, coefficients -0, every update x + (-0 * y) = x), so W and W^T come out with
+//       the bits of the 64-column run -- the padding rows of W are the rows of the identity its accumulators start from, their
+//       scales the constant 1 -- while the chain ends up to fifteen panels (~1.06 k cycles each) earlier.  The unrolled
+//       bodies stay as they are, each behind a scalar test.  words[0] still ends at rbase + 16: whichever chain wave ran
+//       last publishes that (wave 0 when ncols <= 32: wave 3 then has nothing to do).  Without COLS: the code as it was.
+template <bool GSYNC = false, bool ROLES = true, bool IN_W = false, bool WMAX = false, bool COLS = false>
 __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ src_blk, float* __restrict__ W,
                                                     float* __restrict__ WT, float* __restrict__ pcol,
                                                     int* __restrict__ flag, const int kbase,
                                                     int* __restrict__ gwords = nullptr, const int gcall = 0,
                                                     const float diag_add = 0.f,         // (!GSYNC: added to the tile's diagonal as it is staged)
                                                     const bool handoff = false,         // (!GSYNC: src_blk was stored by another workgroup of this launch)
-                                                    float* __restrict__ wmax_out = nullptr) {      // [4]: waves 1, 2 leave max |W| of what they store (LDS)
+                                                    float* __restrict__ wmax_out = nullptr,        // [4]: waves 1, 2 leave max |W| of what they store (LDS)
+                                                    const int ncols = 64) {             // (COLS)
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, li = lane & 31, lh = lane >> 5;
+    // panels that are run (1..16), in a scalar register
+    [[maybe_unused]] const int npan = COLS ? __builtin_amdgcn_readfirstlane((ncols + 3) >> 2) : 16;
     float* const svals = pcol;                                        // [64]: 1 / sqrt(pivot)
     int* const words = GSYNC ? gwords : (int*)(pcol + 64);            // [0] panels published, [1] consumers done
     float* const queue = WT;                                          // [16][4][64] coefficient columns
@@ -811,6 +821,7 @@ __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ sr
 #pragma unroll
         for (int P = 0; P < 8; ++P) {
             const int c0 = 4 * P, n0 = c0 + 4, q0 = 4 * (n0 / 8), LH = (n0 / 4) & 1;
+            if constexpr (COLS) { if (P > 0 && P >= npan) break; }   // (the rest is padding)
             __builtin_amdgcn_sched_barrier(0);                       // (one scheduling region per panel)
             float ncu[4], y[4];
             if (P > 0) {
@@ -859,12 +870,14 @@ __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ sr
             }
             PIV_STAMP(2 + P);
         }
+        if constexpr (COLS) { if (npan <= 8) pub = rbase + 15; }    // (no panel for wave 3: this is the block's last word)
         publish(8);
         PIV_STAMP(20);
         return;
     }
     if (w == 3) {
         // ================= quadrant (1,1) of the Schur complement: follows panels 0..7, then the chain =================
+        if constexpr (COLS) { if (npan <= 8) return; }               // (nobody reads this quadrant then)
         f32x16 S11;
 #pragma unroll
         for (int q = 0; q < 16; ++q) S11[q] = tile_o[(32 + qoff(q)) * ld + 32];
@@ -892,6 +905,7 @@ __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ sr
 #pragma unroll
         for (int P = 8; P < 16; ++P) {
             const int c0 = 4 * P, n0 = c0 + 4, rr = n0 - 32, q0 = 4 * (rr / 8), LH = (rr / 4) & 1;
+            if constexpr (COLS) { if (P > 8 && P >= npan) break; }
             __builtin_amdgcn_sched_barrier(0);
             float ncu[4], y[4];
             if (P > 8) publish(P);
@@ -933,6 +947,7 @@ __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ sr
             }
             PIV_STAMP(96 + 2 + (P - 8));
         }
+        if constexpr (COLS) pub = rbase + 15;
         publish(16);
         PIV_STAMP(96 + 20);
         return;
@@ -955,6 +970,7 @@ __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ sr
         for (int P = CB0 ? 0 : 8; P < 16; ++P) {                 // (column block 1 is untouched by the upper half)
             const int c0 = 4 * P, I = c0 / 32, rr = c0 % 32, q0 = 4 * (rr / 8), LH = (rr / 4) & 1;
             __builtin_amdgcn_sched_barrier(0);
+            if (!COLS || P < npan) {                             // (COLS: a panel of padding leaves the accumulators as they are)
             wait_published(rbase + P + 1);
             float cf[4];
             {
@@ -994,14 +1010,36 @@ __device__ __forceinline__ void wg_pivot_block_mfma(const float* __restrict__ sr
                 Wa = mfma(a1_01, b_01, Wa);
                 Wa = mfma(a1_23, b_23, Wa);
             }
+            }
             if (P & 1) {
                 const int g = P / 2;                     // rows 8 g + e + 4 lh, e = 0..3
+                if constexpr (!COLS) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int rowc = 8 * g + e;
                     const float d = dg_o[rowc * 65 + (rowc >= 32 ? 32 * SPD_LS - 2048 : 0)];
                     bad = (!(d > 0.f) && bad == 0) ? rowc + 4 * lh_o + 1 : bad;
                     sc[(CB0 ? 4 * g : 4 * (g - 4)) + e] = __builtin_amdgcn_rsqf(d);
+                }
+                } else if (P - 1 < npan) {
+                    // Lane half 1 holds the rows of panel P, which may be padding behind a real panel P - 1: its queue entries were
+                    // never written and may hold anything.  Such rows take the pivot of the identity, 1, through the same
+                    // instruction as the others and never count as bad.
+                    const bool real = 2 * g + lh_o < npan;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int rowc = 8 * g + e;
+                        const float q = dg_o[rowc * 65 + (rowc >= 32 ? 32 * SPD_LS - 2048 : 0)];
+                        const float d = real ? q : 1.f;
+                        bad = (!(d > 0.f) && bad == 0) ? rowc + 4 * lh_o + 1 : bad;
+                        sc[(CB0 ? 4 * g : 4 * (g - 4)) + e] = __builtin_amdgcn_rsqf(d);
+                    }
+                } else {
+                    float one = 1.f;                     // (opaque: the instruction's 1 / sqrt(1), not the compiler's)
+                    asm volatile("" : "+v"(one));
+                    one = __builtin_amdgcn_rsqf(one);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) sc[(CB0 ? 4 * g : 4 * (g - 4)) + e] = one;
                 }
             }
         }
@@ -2141,6 +2179,7 @@ struct RsLateRho {
     float* cmx;               // global scratch of this problem: [NP][64 K + 2] words (column maxima | asymmetry | magnitude)
     unsigned long long* qdbg; // optional: 8 cycle stamps of the pass (tools/gpu_resident_phases.py), workgroup 0 of the matrix
     int dbg_tid;              // the thread whose phase stamps go to dbg (LQP_DBG_QPASS bits 8..: its wave)
+    int piv_cols;             // 1: the last pivot block stops behind column n (wg_pivot_block_mfma, COLS; LQP_PIV_COLS)
 };
 // (the scaling vector from the column maxima: supplied by the kernel, which knows the problem's parameters)
 //  scaling(red, d, work): every thread of the workgroup; red: n column maxima, d: n values out, work: 8 + RS_NW floats (LDS)
@@ -2184,7 +2223,7 @@ __device__ __forceinline__ void wg_spd_sweep_resident_v2(const float* Hsrc, floa
                                                          float* __restrict__ xb, unsigned int* __restrict__ fl,
                                                          const unsigned int epoch, const int part, int* __restrict__ info,
                                                          int* __restrict__ status_timeout, char* smem,
-                                                         const RsLateRho lr = RsLateRho{0, 0, 0.f, 0.f, nullptr, nullptr, 0, 0.f, 0, nullptr, nullptr, nullptr, 0},
+                                                         const RsLateRho lr = RsLateRho{0, 0, 0.f, 0.f, nullptr, nullptr, 0, 0.f, 0, nullptr, nullptr, nullptr, 0, 0},
                                                          unsigned long long* __restrict__ dbg = nullptr,
                                                          const DFn hooks = DFn{}) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -2574,8 +2613,10 @@ __device__ __forceinline__ void wg_spd_sweep_resident_v2(const float* Hsrc, floa
             if (dbg) { const unsigned long long t = clock64(); dbt[0] += t - dt0; dt0 = t; }
             // ---- pivot tile -> W, W^T by waves 0..3 | panel tiles -> LDS by waves 4..7 (slot s holds P_i = A_ik, i.e.
             //      block (k, i) transposed when i < k) ----
-            wg_pivot_block_mfma<false, PIVOT, false, F16>(xbk + (size_t)(K - 1) * LQP_BLK, W, WT, pcol, flag, k * 64, nullptr, 0, diag_add, true,
-                                                          pcol + 128);
+            // (the last block's padding is left out by the float16 instances, the ones that run by default: with it the float32
+            //  instance of K = 8 needs 40 B of scratch for its 8 -- tests/test_abi_and_host.py -- and keeps its 64 columns)
+            wg_pivot_block_mfma<false, PIVOT, false, F16, F16>(xbk + (size_t)(K - 1) * LQP_BLK, W, WT, pcol, flag, k * 64, nullptr, 0, diag_add, true,
+                                                               pcol + 128, (k == K - 1 && lr.piv_cols) ? lr.n - 64 * (K - 1) : 64);
             // (lane parts of every LDS / global address of this step, opaque: as loop invariants of the step loop they
             //  would be formed once, held in registers -- one per distinct address -- and spilled with the tiles)
             int li_s = li, lh_s = lh, tid_s = tid;
@@ -3144,9 +3185,11 @@ __host__ __device__ inline int chol_la_lds_bytes(int K) { return spd_lds_bytes(K
 // (lqp_f16x2.hpp), as in the resident sweep.  W stays the chain waves' float32 copy (they overwrite it as soon as the tile
 // waves let go): every tile wave builds the six cells of W it multiplies with in its registers; L_ik = Y goes to its block
 // in global memory straight from the accumulators, its split image replaces the panel rows in LDS.
+// nreal: the order of the matrix when its last block is padded with the identity behind column nreal - 64 (K - 1) (the chain
+// then leaves the padding's panels out: wg_pivot_block_mfma, COLS); 0: every block takes its 64 columns.
 template <bool F16 = false>
 __device__ __forceinline__ void wg_chol_factor_la(float* __restrict__ Hs, const int K, int* __restrict__ info, char* smem,
-                                                  unsigned long long* __restrict__ dbg = nullptr) {
+                                                  unsigned long long* __restrict__ dbg = nullptr, const int nreal = 0) {
     constexpr int NCH = CHOL_LA_CHAIN, NTW = LQP_NW - NCH, NTT = NTW * 64;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
@@ -3171,7 +3214,8 @@ __device__ __forceinline__ void wg_chol_factor_la(float* __restrict__ Hs, const 
             lds_wait_ge(sy + 4, k);                         // W / W^T of step k-1 are no longer read
             if (dbg && tid == 0) { const unsigned long long c1 = clock64(); dbg[4] += c1 - c0; c0 = c1; }
 #if LQP_PIV_MFMA
-            wg_pivot_block_mfma<true, true, false, F16>(St, W, WT, pcol, flag, k * 64, sy + 5, k, 0.f, false, pcol + 128);
+            wg_pivot_block_mfma<true, true, false, F16, true>(St, W, WT, pcol, flag, k * 64, sy + 5, k, 0.f, false, pcol + 128,
+                                                              (k == K - 1 && nreal > 0) ? nreal - 64 * (K - 1) : 64);
 #else
             wg_pivot_block<NCH, true>(St, W, WT, pcol, flag, k * 64, sy + 0, &gt);
 #endif

@@ -43,7 +43,7 @@ GROUPS = [
     ("lu2", lambda n: "k_lu_factor2<" in n),
     ("lu_a", lambda n: re.search(r"k_lu_factor<float, (32|16), true|k_lu_factor_big|k_lu_factor_wide", n)),
     ("lu_b", lambda n: "k_lu_factor<" in n),
-    ("spd", lambda n: re.search(r"k_spd_|k_bwd_chol_solve|k_bwd_build_chol|k_debug_chol_solve", n)),
+    ("spd", lambda n: re.search(r"k_spd_|k_bwd_chol_solve|k_bwd_build_chol|k_debug_chol_solve|k_debug_chol_factor", n)),
     ("unroll", lambda n: "k_unroll_" in n or "k_admm_loop_small<" in n),
     ("misc", lambda n: True),
 ]
@@ -90,6 +90,8 @@ EXTRA = [
     "void lqp::k_admm_loop_small_each<0>(lqp::FwdParams<float>, int, int, int)",
     "void lqp::k_debug_chol_solve<2>(float const*, int const*, float const*, float*, int, int, int)",
     "void lqp::k_debug_chol_solve<4>(float const*, int const*, float const*, float*, int, int, int)",
+    "void lqp::k_debug_chol_factor<false>(float*, int const*, int*, int, int, int)",
+    "void lqp::k_debug_chol_factor<true>(float*, int const*, int*, int, int, int)",
 ] + [
     f"void lqp::k_admm_loop_split_each<{ks}, 512, false, {np_}>(lqp::FwdParams<float>, int, int, int)"
     for ks, np_ in ((3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4))

@@ -28,6 +28,11 @@ for la in (0, 1):
     c = dbg.view(B, 8).double()
     print("lookahead %d  mean cycles: factor %.0f  solves %.0f  schur+finish %.0f   mean Kb %.2f (min %d max %d)" % (
         la, c[:, 0].mean(), c[:, 1].mean(), c[:, 2].mean(), c[:, 3].mean(), int(c[:, 3].min()), int(c[:, 3].max())))
+    for kb in sorted(set(int(v) for v in c[:, 3].tolist())):       # (the kernel lasts as long as its slowest workgroup: the largest Kb)
+        s = c[c[:, 3] == kb]
+        print("   Kb %d: %3d problems  factor %.0f  solves %.0f  schur+finish %.0f  (max factor %.0f)" % (
+            kb, s.shape[0], s[:, 0].mean(), s[:, 1].mean(), s[:, 2].mean(), s[:, 0].max()) +
+            ("  pivot blocks %.0f" % s[:, 5].mean() if la else ""))
     if la:
         print("   chain waves: waits %.0f  pivot blocks %.0f   tile waves: wait for W %.0f  rest of step %.0f" % (
             c[:, 4].mean(), c[:, 5].mean(), c[:, 6].mean(), c[:, 7].mean()))
