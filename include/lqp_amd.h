@@ -12,7 +12,11 @@
  *     the matching *_workspace_bytes query;
  *   - all tensor pointers are DEVICE pointers to dense, batch-first,
  *     row-major (C-contiguous) arrays, exactly the layout of a contiguous
- *     torch tensor of the stated shape;
+ *     torch tensor of the stated shape; every vector, matrix and workspace
+ *     pointer is 16-byte aligned (the kernels take 16-byte loads and stores
+ *     where a row length allows; the Python shim copies a tensor that is
+ *     not), arrays of one scalar per problem (rho, beta, info, iteration
+ *     counts) need the alignment of their element only;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
  *   - dtype: LQP_F32 or LQP_F64 (the arithmetic type of every tensor).
  */

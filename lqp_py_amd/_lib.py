@@ -438,16 +438,25 @@ def release_workspaces(device=None):
             del _ws_cache[key]
 
 
+def aligned(t):
+    """`t` (contiguous) at an address the kernels' 16-byte accesses may take: the tensor itself, or a copy when it starts in the
+    middle of a 16-byte line -- a slice of a flat parameter vector, a shard [lo:hi] of a batch with an odd n (include/lqp_amd.h:
+    vector and matrix arguments are 16-byte aligned; a fresh allocation always is)."""
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def norm(t, dtype):
-    """contiguous, right dtype -- the tensor itself when it already is (only its address is used)"""
-    if t is None or (t.dtype == dtype and t.is_contiguous()):
+    """contiguous, right dtype, 16-byte aligned -- the tensor itself when it already is (only its address is used)"""
+    if t is None:
         return t
+    if t.dtype == dtype and t.is_contiguous():
+        return aligned(t)
     t = t.detach()
     if t.dtype != dtype:
         t = t.to(dtype)
-    return t if t.is_contiguous() else t.contiguous()
+    return aligned(t if t.is_contiguous() else t.contiguous())
 
 
 def c(t):
-    """contiguous, detached view of a tensor (None passes through)"""
-    return None if t is None else t.detach().contiguous()
+    """contiguous, detached, 16-byte aligned view of a tensor (None passes through)"""
+    return None if t is None else aligned(t.detach().contiguous())
