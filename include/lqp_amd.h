@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define LQP_ABI_VERSION 16
+#define LQP_ABI_VERSION 17
 
 enum { LQP_F32 = 0, LQP_F64 = 1 };
 
@@ -134,6 +134,14 @@ typedef struct lqp_boxqp_ctrl {
                                         word to -1 before its first launch and POLLS them (all stored words are >= 0)
                                         instead of synchronising the stream: it returns about a microsecond after the
                                         last kernel's stores, not after an interrupt-driven stream wait.            */
+    double alpha;                    /* ABI 17, appended (every earlier offset holds): over-relaxation of the ADMM step.  The
+                                        z- and the dual update of an iteration see alpha x + (1 - alpha) z_prev in place of
+                                        x; the residuals of the check, the next right-hand side and the returned x do not
+                                        change, and the fixed point (x = z) is the same.  0 = not set = 1 (the reference's
+                                        plain step; a zero-initialised struct keeps it); otherwise finite and inside (0, 2),
+                                        and 1 whenever reserved2 bit 0 is set (the unrolled backward replays the plain
+                                        step): LQP_ERR_INVALID else.  Ignored by the rho = 0 one-shot, which does not
+                                        iterate.                                                                        */
 } lqp_boxqp_ctrl;
 
 /* Host-side bookkeeping returned by the forward solve. */
@@ -159,6 +167,8 @@ typedef struct lqp_boxqp_stats {
 } lqp_boxqp_stats;
 
 int lqp_abi_version(void);
+/* ABI 17: sizeof(lqp_boxqp_ctrl) as this library was built -- a caller whose struct is shorter was built against an older header */
+size_t lqp_boxqp_ctrl_bytes(void);
 const char* lqp_status_string(int status);
 
 /* ---- measurement hooks (not part of the reference surface) ----------------

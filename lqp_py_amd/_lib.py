@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("LQP_LIB", os.path.join(CSRC, "liblqp_amd.so"))   # LQ
 SOURCES = ["lqp_amd.hip", "lqp_unroll.hpp", "lqp_boxqp.hpp", "lqp_loop_split.hpp", "lqp_loop_small.hpp", "lqp_lu.hpp", "lqp_lu_big.hpp", "lqp_lu2.hpp", "lqp_lu_wide.hpp", "lqp_dense.hpp", "lqp_trsv.hpp", "lqp_spd.hpp", "lqp_f16x2.hpp", "lqp_common.hpp"]
 
 LQP_F32, LQP_F64 = 0, 1
-ABI_VERSION = 16
+ABI_VERSION = 17
 STATUS = {0: "ok", 1: "invalid argument", 2: "workspace too small", 3: "singular", 4: "HIP error",
           5: "grid barrier timeout", 6: "unsupported size (n + m <= 4096 in float32, 2048 in float64)", 7: "matrix outside the symmetric x-update"}
 
@@ -38,7 +38,8 @@ class BoxQPCtrl(ctypes.Structure):
             "eps_abs", "eps_rel", "rho_value", "rho_min", "rho_max", "adaptive_rho_tol",
             "adaptive_rho_threshold", "beta_value")] + [
         ("beta_in", ctypes.c_void_p), ("check_hook", CHECK_HOOK), ("check_hook_user", ctypes.c_void_p),
-        ("bound_flags_in", ctypes.c_void_p), ("host_report", ctypes.c_void_p)]
+        ("bound_flags_in", ctypes.c_void_p), ("host_report", ctypes.c_void_p),
+        ("alpha", ctypes.c_double)]                   # ABI 17: over-relaxation factor, 0 = not set = 1
 
 
 class BoxQPStats(ctypes.Structure):
@@ -51,6 +52,7 @@ class BoxQPStats(ctypes.Structure):
 _P = c_void_p
 SYMBOLS = {
     "lqp_abi_version": (c_int, []),
+    "lqp_boxqp_ctrl_bytes": (c_size_t, []),
     "lqp_status_string": (ctypes.c_char_p, [c_int]),
     "lqp_profile_enable": (None, [c_int]),
     "lqp_profile_reset": (None, []),

@@ -8,9 +8,12 @@ so a dict built here behaves exactly like one built by the reference.
 
 Extension keys of this package travel through ``**kwargs`` like any unknown
 key: ``linsolve`` ('auto' | 'lu' | 'spd'), ``sync`` (False: nothing waits for
-the GPU), ``launch_mode`` (0 | 1 | 2) and ``stop`` ('all', the reference's
+the GPU), ``launch_mode`` (0 | 1 | 2), ``stop`` ('all', the reference's
 rule: the batch iterates until every problem is optimal at one check | 'each':
-every problem is solved as a batch of one, see ``torch_solve_box_qp``).
+every problem is solved as a batch of one, see ``torch_solve_box_qp``) and
+``alpha`` (over-relaxation factor of the ADMM step inside (0, 2); default 1.0,
+the reference's plain step; ``box_qp_control(alpha=1.6)`` is OSQP's setting.
+Same fixed point, fewer iterations; not with ``unroll=True``).
 """
 
 

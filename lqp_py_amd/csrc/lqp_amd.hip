@@ -1448,6 +1448,8 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         P.ar_thr = (T)ctl->adaptive_rho_threshold; P.beta_value = (T)ctl->beta_value;
         P.ar_iter = ctl->adaptive_rho_iter < 1 ? 1 : ctl->adaptive_rho_iter;
         P.ar_max = ctl->adaptive_rho_max_iter; P.ring = kRing;
+        const double alpha = ctl->alpha == 0.0 ? 1.0 : ctl->alpha;       // (0: not set)
+        P.alpha = (T)alpha; P.alpha_c = (T)(1.0 - alpha); P.relax = alpha != 1.0 ? 1 : 0;
     }
     Device d;
     if (!current_device_cus(&d.dev, &d.cus)) return LQP_ERR_HIP;
@@ -2028,6 +2030,7 @@ bool bad_dims(int dtype, int B, int n, int m) {
 extern "C" {
 
 int lqp_abi_version(void) { return LQP_ABI_VERSION; }
+size_t lqp_boxqp_ctrl_bytes(void) { return sizeof(lqp_boxqp_ctrl); }
 
 void lqp_profile_enable(int on) {
     std::lock_guard<std::mutex> lock(g_prof_mutex);
@@ -2179,6 +2182,10 @@ int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* 
     if (ctrl->rho_mode == 2 && !rho_in) return LQP_ERR_INVALID;
     if (ctrl->beta_mode == 2 && !ctrl->beta_in) return LQP_ERR_INVALID;
     if (ctrl->max_iters < 1) return LQP_ERR_INVALID;
+    // over-relaxation: 0 = not set = 1; else inside (0, 2) (NaN fails both comparisons), and the factor kept for the unroll sweep
+    // (reserved2 bit 0) belongs to the plain step its tapes replay
+    if (ctrl->alpha != 0.0 && !(ctrl->alpha > 0.0 && ctrl->alpha < 2.0)) return LQP_ERR_INVALID;
+    if (ctrl->alpha != 0.0 && ctrl->alpha != 1.0 && (ctrl->reserved2 & 1)) return LQP_ERR_INVALID;
     if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)

@@ -106,7 +106,9 @@ template <typename T> struct FwdParams {
     // controls
     int scale, rho_mode, beta_mode, check_solved, adaptive_rho;
     T eps_abs, eps_rel, rho_value, rho_min, rho_max, ar_tol, ar_inv_tol, ar_thr, beta_value;
-    int* pstat;               // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
+    T alpha, alpha_c;         // over-relaxation factor (control['alpha']; 1 = the reference's plain step) and 1 - alpha, see admm_relax
+    int relax;                // 1: alpha != 1
+    int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
 };
 
 // vector block of problem b: [ps | lbs | ubs | D | z | u | x | As (m*n) | bs | E | nu | cv | Tm (m*n) | s0]
@@ -1363,14 +1365,50 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b) {
 // Stateless; what differs between the kernels -- who owns which element, who reports, how many arrive -- is an argument.
 // (Which kernel uses which step, and why some keep their own lines: DESIGN.md section 10.)
 // ---------------------------------------------------------------------------
-// z-update, residuals and dual of one element (:271-282)
-template <typename T> struct AdmmStep { T zn, r, s, un; };
+// The over-relaxed iterate xh = alpha x + (1 - alpha) z_prev (control['alpha'], OSQP's relaxation; alpha_c = 1 - alpha from the host).
+// alpha == 1, the reference: x itself, bit for bit, and nothing between x and z but one scalar BRANCH on the uniform flag P.relax.  As
+// a select, the factor, its mask and the wait for z_prev sat on the path from x to z in every iteration of the plain step (2.5 % of
+// the split loop's time); the empty statement keeps the compiler from turning the branch back into one.
 template <typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step(const T xi, const T zp, const T ui, const T lb, const T ub, const T rho) {
-    T zn = xi + ui;
+__device__ __forceinline__ T admm_relax(const T xi, const T zp, const FwdParams<T>& P) {
+    T xh = xi;
+    if (P.relax) {
+        asm volatile("");
+        xh = P.alpha * xi + P.alpha_c * zp;
+    }
+    return xh;
+}
+// z-update, residuals and dual of one element (:271-282).  The projection and the dual see xh; the primal residual of the
+// check stays x - z (the unrelaxed x, as in OSQP); at alpha == 1, xh - zn is r
+template <typename T> struct AdmmStep { T zn, r, s, un; };
+template <bool RELAX, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                    const T rho) {
+    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
+    T zn = xh + ui;
     zn = tmin(tmax(zn, lb), ub);                             // (:273-276; an infinite bound is a no-op)
     const T r = xi - zn;
-    return {zn, r, rho * (zn - zp), ui + r};
+    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
+}
+template <typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                 const T rho) {
+    if (P.relax) {
+        asm volatile("");
+        return admm_step_as<true>(P, xi, zp, ui, lb, ub, rho);
+    }
+    return admm_step_as<false>(P, xi, zp, ui, lb, ub, rho);
+}
+// ... for a kernel that decides on P.relax outside its iteration (k_admm_loop_split: one hot loop per value, so that the plain step's
+// loop is the code it was): the step as a tag -- plain, relaxed, or the run-time branch of admm_step
+struct RelaxOff { static constexpr int kind = 0; };
+struct RelaxOn { static constexpr int kind = 1; };
+struct RelaxDyn { static constexpr int kind = 2; };
+template <typename TAG, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                     const T rho) {
+    if constexpr (TAG::kind == 2) return admm_step(P, xi, zp, ui, lb, ub, rho);
+    else return admm_step_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho);
 }
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
 // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu without touching Q -- it only feeds a tolerance SCALE; the
@@ -1773,11 +1811,12 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 if (i < n) {
                     const T zp = z[i];
                     const T ui = u[i];
-                    T zn = xi + ui;
+                    const T xh = admm_relax(xi, zp, P);      // (the lines of admm_step)
+                    T zn = xh + ui;
                     zn = tmin(tmax(zn, lb[i]), ub[i]);     // (:273-276; an infinite bound is a no-op)
                     const T r = xi - zn;
                     const T s = rho * (zn - zp);
-                    const T un = ui + r;
+                    const T un = ui + (xh - zn);
                     z[i] = zn;
                     u[i] = un;
                     if (check) {
@@ -1817,11 +1856,12 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 const T xi = v[i];
                 const T zp = z[i];
                 const T ui = u[i];
-                T zn = xi + ui;
+                const T xh = admm_relax(xi, zp, P);          // (the lines of admm_step)
+                T zn = xh + ui;
                 zn = tmin(tmax(zn, lb[i]), ub[i]);
                 const T r = xi - zn;
                 const T s = rho * (zn - zp);
-                const T un = ui + r;
+                const T un = ui + (xh - zn);
                 z[i] = zn;
                 u[i] = un;
                 if (check) {

@@ -371,7 +371,7 @@ __global__ __launch_bounds__(DENSE_NT) void k_admm_loop_dense(const FwdParams<T>
             const T xi = xs[i];
             const T zp = z[i];
             const T ui = u[i];
-            const AdmmStep<T> sp = admm_step(xi, zp, ui, lb[i], ub[i], rho);
+            const AdmmStep<T> sp = admm_step(P, xi, zp, ui, lb[i], ub[i], rho);
             if (in) { z[i] = sp.zn; u[i] = sp.un; }
             if (check && in) {
                 T qx = -ps[i] + rho * (zp - ui) - rho * xi;
@@ -589,7 +589,7 @@ __global__ __launch_bounds__(DENSEW_NT) void k_admm_loop_dense_w(const FwdParams
             const T xi = xs[i];
             const T zp = z[i];
             const T ui = u[i];
-            const AdmmStep<T> sp = admm_step(xi, zp, ui, lb[i], ub[i], rho);
+            const AdmmStep<T> sp = admm_step(P, xi, zp, ui, lb[i], ub[i], rho);
             z[i] = sp.zn; u[i] = sp.un;
             if (check) {
                 T qx = -ps[i] + rho * (zp - ui) - rho * xi;

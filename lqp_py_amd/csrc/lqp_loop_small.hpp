@@ -106,7 +106,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
         if (live) {
             const T wi = wv[e];
             xi = cvi - yv[e];
-            const AdmmStep<T> sp = admm_step(xi, zi, ui, lbi, ubi, rho);
+            const AdmmStep<T> sp = admm_step(P, xi, zi, ui, lbi, ubi, rho);
             zi = sp.zn;
             ui = sp.un;
             if (check) {

@@ -303,7 +303,9 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
     // variant carries none of that code, and the hot iterations run in an inner loop of their own below, so the
     // register allocator keeps the resident blocks (and everything else the product needs) out of scratch there.
     // Returns 1 when the workgroup is done (all problems were optimal at the last check).
-    auto iterate = [&](auto cold_tag, const int it, const bool check) -> int {
+    // relax_tag: how the element-wise step takes control['alpha'] -- the hot loop exists once per value of P.relax (RelaxOff: the plain
+    // step's loop, the code it was before the factor existed; RelaxOn), a cold iteration branches at run time (RelaxDyn)
+    auto iterate = [&](auto cold_tag, auto relax_tag, const int it, const bool check) -> int {
         constexpr bool COLD = decltype(cold_tag)::value;
         if (dbg_on) dt0 = clock64();
         // ---- part 0: look at the open verdict while the product runs ----
@@ -388,7 +390,7 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         if (tid < Nps) {
             const int i = tid;
             xs[i] = xi;
-            const AdmmStep<T> sp = admm_step(xi, z[i], u[i], lb[i], ub[i], rho);
+            const AdmmStep<T> sp = admm_step_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho);
             const T zn = sp.zn, un = sp.un;
             const bool in = i < n;
             if (in) { z[i] = zn; u[i] = un; }
@@ -504,15 +506,23 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         }
         const bool check = (it % P.check_solved) == 0;
         if (check || it + 1 == it1) {
-            left = iterate(std::true_type(), it, check);
+            left = iterate(std::true_type(), RelaxDyn(), it, check);
             ++it;
         } else {
             int e = (it / P.check_solved + 1) * P.check_solved;      // next special iteration: a check or the last one
             if (e > it1 - 1) e = it1 - 1;
+            if (P.relax) {
 #pragma unroll 1
-            for (; it < e; ++it) {
-                left = iterate(std::false_type(), it, false);
-                if (left) break;
+                for (; it < e; ++it) {
+                    left = iterate(std::false_type(), RelaxOn(), it, false);
+                    if (left) break;
+                }
+            } else {
+#pragma unroll 1
+                for (; it < e; ++it) {
+                    left = iterate(std::false_type(), RelaxOff(), it, false);
+                    if (left) break;
+                }
             }
         }
     }

@@ -20,6 +20,9 @@ With ``control['stop'] = 'each'`` every problem stops, and adapts rho, as a
 batch of one: its result and its iteration count do not depend on the sharding
 at all, and no per-check collective is needed for that (``dist_strict_stop``
 on top of it is refused: a global stop is its opposite).
+``control['alpha']`` (over-relaxation) is a setting of every shard's own loop:
+it needs no exchange, with or without ``dist_strict_stop``; every rank must
+pass the same value, like every other setting.
 ``dl_dQ`` is never gathered.
 """
 import torch

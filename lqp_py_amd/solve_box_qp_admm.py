@@ -55,7 +55,8 @@ def _bound_vector(value, n_x, fallback):
 
 def solve_box_qp(Q, p, A=None, b=None, lb=-float("inf"), ub=float("inf"), control=None):
     """argmin 0.5 x'Qx + p'x  s.t.  A x = b, lb <= x <= ub for one problem (lqp_py/solve_box_qp_admm.py:45-91).
-    Returns {"x","z","u","lam","nu","rho","primal_error","dual_error","iter"} with 1-D arrays, like the reference."""
+    Returns {"x","z","u","lam","nu","rho","primal_error","dual_error","iter"} with 1-D arrays, like the reference.
+    The extension keys of the torch layer hold here too (``control['alpha']``: over-relaxation, see ``torch_solve_box_qp``)."""
     Q = make_matrix(Q)
     p = make_matrix(p)[:, 0]
     if A is not None:
