@@ -129,7 +129,8 @@ typedef struct lqp_boxqp_ctrl {
                                         lqp_boxqp_forward_layout), [16..16+B) the info word of every problem,
                                         [16+B..16+2B) per-problem flag bits {1: a lower bound is finite, 2: an upper
                                         bound is finite, 4: its workgroup saw a barrier timeout, 8: its matrix left the
-                                        symmetric x-update}.  Valid once the stream has passed the call (an event):
+                                        symmetric x-update, 65536 (bit 16, added within ABI 17): flagged primal
+                                        infeasible by lqp_boxqp_forward_detect}.  Valid once the stream has passed the call (an event):
                                         ctrl.reserved = 1 callers read it then.  A synchronous call sets every
                                         word to -1 before its first launch and POLLS them (all stored words are >= 0)
                                         instead of synchronising the stream: it returns about a microsecond after the
@@ -337,6 +338,36 @@ int lqp_boxqp_last_residuals(void* stream, int dtype, int B, int n, int m,
  * any problem refactorised at it.                                                                                          */
 int lqp_boxqp_problem_iters(void* stream, int dtype, int B, int n, int m,
                             const void* workspace, size_t workspace_bytes, int32_t* iters_out);
+
+/* ---- primal infeasibility detection (added within ABI 17: new symbols only, no struct and no offset changed) ----------
+ * lqp_boxqp_forward_detect is lqp_boxqp_forward (the same implementation; lqp_boxqp_forward is the call with detection off)
+ * with one more test at every stopping check of a problem: the differences dy, dg, dnu of y = rho u, g = Qs x + s and nu
+ * between this check and the last one of the same problem (all in the scaled problem the loop iterates on) give
+ *   N = |dy|_inf,  c1 = |dg|_inf / N,  c2 = (sum_i [ubs_i max(dy_i, 0) + lbs_i min(dy_i, 0)] + bs^T dnu) / N
+ * and the problem is PRIMAL INFEASIBLE iff N > 0, c1 <= eps_prim_inf and c2 <= -eps_prim_inf (a term of an infinite bound counts
+ * 0 while |dy_i| <= eps_prim_inf N and makes c2 = +inf otherwise): OSQP's Farkas certificate of {A x = b, lb <= x <= ub} =
+ * empty, with differences taken check to check.  A check behind a change of the problem's rho only refreshes the snapshot.
+ * Optimality is tested first.  A flagged problem stops like an optimal one: its iterate of that check is what x, z, u, nus
+ * hold, lqp_boxqp_problem_iters names the check, lqp_boxqp_problem_status says 2, and bit 16 of its flag word in
+ * ctrl.host_report is set.
+ * It needs ctrl.reserved2 bit 3 (every problem stops on its own) and refuses ctrl.check_hook and reserved2 bit 0;
+ * eps_prim_inf must be finite and inside (0, 1).  LQP_ERR_INVALID otherwise, before anything is touched.  The workspace is
+ * lqp_boxqp_forward_detect_workspace_bytes: the forward's layout, unchanged, and behind it two snapshots (2 n + m values and
+ * four words of the solve's dtype each) per problem, which a kernel of the call initialises.  The rho = 0 one-shot (no finite
+ * bound in the batch) does not iterate and ignores eps_prim_inf.                                                             */
+size_t lqp_boxqp_forward_detect_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m,
+                             const void* Q, const void* p, const void* A, const void* b,
+                             const void* lb, const void* ub,
+                             const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                             void* x, void* z, void* u, void* lams, void* nus, void* rho_out,
+                             lqp_boxqp_stats* stats,
+                             void* workspace, size_t workspace_bytes, double eps_prim_inf);
+/* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
+ * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
+ * optimal, 2 primal infeasible -- B int32 on the DEVICE.  Enqueued on `stream`, nothing is waited for.                       */
+int lqp_boxqp_problem_status(void* stream, int dtype, int B, int n, int m,
+                             const void* workspace, size_t workspace_bytes, int32_t* status_out);
 
 /* ABI 12: the trace of a forward solve that ran with ctrl.reserved2 bit 2 -- for check c = 0 .. n_checks - 1 (held at
  * iteration c * check_solved) trace_out[2 c] = max over the batch of ||D r||_inf, trace_out[2 c + 1] = max of ||D s||_inf,

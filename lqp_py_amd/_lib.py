@@ -69,6 +69,11 @@ SYMBOLS = {
     "lqp_boxqp_forward": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
                                   ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P,
                                   ctypes.POINTER(BoxQPStats), _P, c_size_t]),
+    "lqp_boxqp_forward_detect_workspace_bytes": (c_size_t, [c_int] * 4),      # (added within ABI 17)
+    "lqp_boxqp_forward_detect": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
+                                         ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P,
+                                         ctypes.POINTER(BoxQPStats), _P, c_size_t, c_double]),
+    "lqp_boxqp_problem_status": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "lqp_boxqp_forward_finish": (c_int, [_P, c_int, c_int, c_int, _P, ctypes.POINTER(BoxQPStats)]),
     "lqp_boxqp_forward_layout": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 4),
     "lqp_boxqp_unroll_backward_workspace_bytes": (c_size_t, [c_int] * 4),
@@ -246,7 +251,7 @@ def stream_ptr(device):
 # ---- deferred error reporting for calls that did not synchronise with the host -----------------
 class _Pending:
     """status / LU-info words of an un-synchronised call, copied to pinned memory on the call's stream"""
-    __slots__ = ("what", "event", "status", "info", "bounds_check", "keep", "flags")
+    __slots__ = ("what", "event", "status", "info", "bounds_check", "keep", "flags", "raise_infeasible", "ignore")
 
     def __init__(self, what, event, status, info, bounds_check=None):
         self.what, self.event, self.status, self.info, self.bounds_check = what, event, status, info, bounds_check
@@ -299,6 +304,17 @@ def _pinned(words):
 
 ST_WORDS = 16                # status block, include/lqp_amd.h (lqp_boxqp_ctrl.host_report)
 RP_LB, RP_UB, RP_TIMEOUT, RP_NOTSPD = 1, 2, 4, 8
+RP_INFEAS = 1 << 16          # the problem was flagged primal infeasible (control['infeasible'], lqp_boxqp_forward_detect)
+
+
+class InfeasibleQPError(RuntimeError):
+    """control['infeasible'] = 'raise': the layer's forward flagged problems primal infeasible -- {A x = b} and [lb, ub] do not meet.
+    ``indices``: their batch indices, a sorted list."""
+
+    def __init__(self, what, indices):
+        self.indices = sorted(int(i) for i in indices)
+        super().__init__(f"lqp_py_amd.{what}: primal infeasible problem(s) at batch index {self.indices}: the equality constraints "
+                         "cannot be met inside the box (control['infeasible'] = 'flag' returns their status instead of raising)")
 
 
 def host_report(words):
@@ -307,11 +323,13 @@ def host_report(words):
     return _pinned(words)        # (the library sets every word to -1 before its first launch)
 
 
-def defer_check(what, device, report, B, forward, bounds_check=None):
+def defer_check(what, device, report, B, forward, bounds_check=None, raise_infeasible=False, ignore=None):
     """Queue the report of an un-synchronised call: `report` is the pinned buffer given to the library as host_report
     (forward: 16 status words | B info words | B flag words; backward: B info words).
     bounds_check = (assumed, control, mutate, remember): the call was enqueued ASSUMING that the batch holds some /
-    no finite bound; status words 12 / 13 hold what the setup kernel found."""
+    no finite bound; status words 12 / 13 hold what the setup kernel found.
+    raise_infeasible: bit 16 of a problem's flag word (flagged primal infeasible) raises InfeasibleQPError.  ignore: a (B,) bool
+    device tensor -- info words of these problems are not errors (the backward of a batch that holds flagged problems)."""
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(device))
     with _pending_lock:
@@ -319,6 +337,7 @@ def defer_check(what, device, report, B, forward, bounds_check=None):
                      report[ST_WORDS:ST_WORDS + B] if forward else report[:B], bounds_check)
         p.keep = (report,)
         p.flags = report[ST_WORDS + B:ST_WORDS + 2 * B] if forward else None
+        p.raise_infeasible, p.ignore = bool(raise_infeasible), ignore
         _pending.append(p)
         backlog = len(_pending)
     if backlog > 64:
@@ -341,6 +360,8 @@ def poll_errors(block=False):
         if int(rep[0]) == -1:               # (-1: the library's "nothing arrived"; every stored word is >= 0 or -7)
             raise RuntimeError(f"lqp_py_amd.{p.what}: the call's report never arrived in host memory")
         info = p.info.numpy()
+        if p.ignore is not None:
+            info = numpy.where(p.ignore.cpu().numpy(), 0, info)
         if (info == -7).any():              # a workgroup of a shared LU (two per matrix / wide) waited for its partner in vain
             for t in getattr(p, "keep", ()):
                 report_done(t)
@@ -349,7 +370,8 @@ def poll_errors(block=False):
                                "CUs were held by somebody else); the outputs are not valid.  Repeat with control['sync']=True, which "
                                "falls back to one workgroup per matrix by itself, or pass reserved2 bit 1 (lqp_boxqp_ctrl) for that schedule")
         bad = info.nonzero()[0]
-        flags = int(numpy.bitwise_or.reduce(p.flags.numpy())) if p.flags is not None else 0
+        flags_each = p.flags.numpy().copy() if p.flags is not None else None      # (copied: the buffer goes back to the pool below)
+        flags = int(numpy.bitwise_or.reduce(flags_each)) if flags_each is not None else 0
         status7 = (int(p.status[7]) or (flags & RP_NOTSPD)) if p.status is not None else 0
         status5 = (int(p.status[5]) or (flags & RP_TIMEOUT)) if p.status is not None else 0
         seen_words = (int(p.status[12]), int(p.status[13])) if p.status is not None else (1, 1)
@@ -379,6 +401,8 @@ def poll_errors(block=False):
                                f"zero pivot for batch index {int(bad[0])}; the matrix is singular")
         if status5:
             raise RuntimeError(f"lqp_py_amd.{p.what}: in-kernel grid barrier timed out")
+        if p.raise_infeasible and (flags & RP_INFEAS):
+            raise InfeasibleQPError(p.what, (flags_each & RP_INFEAS).nonzero()[0].tolist())
 
 
 _ws_cache = {}

@@ -14,6 +14,16 @@ every problem is solved as a batch of one, see ``torch_solve_box_qp``) and
 ``alpha`` (over-relaxation factor of the ADMM step inside (0, 2); default 1.0,
 the reference's plain step; ``box_qp_control(alpha=1.6)`` is OSQP's setting.
 Same fixed point, fewer iterations; not with ``unroll=True``).
+
+``infeasible`` (absent or None: off | 'raise' | 'flag') turns on primal
+infeasibility detection -- {A x = b} and [lb, ub] do not meet -- at every
+stopping check of a problem; it needs ``stop='each'`` and refuses
+``unroll=True``.  'raise': the layer raises ``lqp_py_amd.InfeasibleQPError``
+(``.indices``) once the batch is done; 'flag': it returns x,
+``lqp_py_amd.last_problem_status(device)`` says which problems were flagged
+(2), and their gradient rows are zero.  ``torch_solve_box_qp`` never raises
+for it: its dict holds ``"status"`` whenever ``stop='each'``.
+``eps_prim_inf`` (default 1e-4, inside (0, 1)) is the certificate's threshold.
 """
 
 

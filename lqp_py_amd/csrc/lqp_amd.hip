@@ -534,6 +534,8 @@ template <typename T> struct FwdLayout {
     size_t bytes;
     unsigned int* vtrace_area;      // [kRing][2]: the check trace (FwdParams::vtrace points here when ctrl.reserved2 bit 2 asks for it)
     int* pstat_area;                // [B][PS_WORDS]: per-problem stopping (FwdParams::pstat points here when ctrl.reserved2 bit 3 asks for it)
+    void* snap_area;                // [B][snap_stride]: the infeasibility certificate's snapshots, BEHIND `bytes` (lqp_boxqp_forward_detect alone)
+    size_t detect_bytes;            // ... and the size that holds them
 };
 // the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
 // by ADDRESS: an entry goes when another forward runs on the address; memory that was freed and handed out again without a forward in
@@ -584,6 +586,9 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     P.dnx = P.dnx_words ? c.take<unsigned long long>((size_t)B * P.dnx_words) : nullptr;
     L.pstat_area = c.take<int>((size_t)B * PS_WORDS);      // (behind everything that was there before ABI 14: no offset moved)
     L.bytes = c.off + kAlign;
+    c.off = L.bytes;                // (nothing in front of it moves, and lqp_boxqp_forward_workspace_bytes says what it said)
+    L.snap_area = c.take<T>((size_t)B * snap_stride(n, m));
+    L.detect_bytes = c.off + kAlign;
     return L;
 }
 
@@ -815,7 +820,9 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     plan.loop_nt = hot512 ? 512 : 1024;
     plan.loop_fn = k_admm_loop<T, false, false, 1024>;
     plan.tail_fn = k_admm_loop<T, false, true, 1024>;        // same code, own name: continuation launches
+    const bool detect = each && P.snap != nullptr;      // (control['infeasible']: the EACH instances with the certificate in their check)
     if (each) { plan.loop_fn = k_admm_loop_each<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, false, true, 1024, false>; }
+    if (detect) { plan.loop_fn = k_admm_loop_each_detect<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each_detect<T, false, true, 1024, false>; }
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
     //  separate gated kernels, and the continuation kernel's LDS does not have to hold an LU panel)
@@ -825,6 +832,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     if constexpr (sizeof(T) == 4) {
         if (resident) { plan.loop_fn = k_admm_loop<T, true, false, 1024>; plan.tail_fn = k_admm_loop<T, true, true, 1024>; }
         if (resident && each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, false>; }
+        if (resident && detect) { plan.loop_fn = k_admm_loop_each_detect<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each_detect<T, true, true, 1024, false>; }
         if (hot512) plan.loop_fn = k_admm_loop<T, true, false, 512>;
         if (spd) {
             P.sym_rl = sym_resident_lds_blocks(n, m, P.Ks);
@@ -834,6 +842,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             plan.loop_fn = k_admm_loop<T, true, false, 1024, true>;
             plan.tail_fn = k_admm_loop<T, true, true, 1024, true>;
             if (each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, true>; }
+            if (detect) { plan.loop_fn = k_admm_loop_each_detect<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each_detect<T, true, true, 1024, true>; }
             // optional 512-thread first launch (8 elements per thread, 12 register-resident blocks).  Measured at
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
@@ -944,7 +953,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
         if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
             const int small_lds = small_loop_lds_bytes(m);
-            if (each ? fits(d, k_admm_loop_small_each<>, 256, small_lds, B) : fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
+            if (detect ? fits(d, k_admm_loop_small_each_detect<>, 256, small_lds, B) : each ? fits(d, k_admm_loop_small_each<>, 256, small_lds, B) : fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
         }
         // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
         // (ctrl.reserved2 bit 0: the caller will read the corrected H from the workspace afterwards -- lqp_boxqp_unroll_backward --
@@ -1095,7 +1104,8 @@ void launch_hot(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, c
             hipLaunchKernelGGL(plan.split_fn, dim3((absent & 1) ? B : shared_grid(B, plan.kind_wg)), dim3(plan.split_nt), plan.split_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_SMALL:
-            if (plan.each) hipLaunchKernelGGL(k_admm_loop_small_each<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            if (plan.each && P.snap) hipLaunchKernelGGL(k_admm_loop_small_each_detect<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            else if (plan.each) hipLaunchKernelGGL(k_admm_loop_small_each<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             else hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_NP2:
@@ -1420,9 +1430,9 @@ template <typename T>
 int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
-                 int retry = 0) {
+                 int retry = 0, const double eps_prim_inf = 0.0) {      // (eps_prim_inf > 0: lqp_boxqp_forward_detect)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    if (ws_bytes < L.bytes) return LQP_ERR_WORKSPACE;
+    if (ws_bytes < (eps_prim_inf > 0.0 ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
@@ -1435,6 +1445,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         if (ctl->reserved2 & 8) {
             if (ctl->check_hook) return LQP_ERR_INVALID;
             P.pstat = L.pstat_area;
+            if (eps_prim_inf > 0.0) { P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m); P.eps_pinf = (T)eps_prim_inf; }
         }
         each_ws_note(ws, P.pstat != nullptr);
         P.host_report = (int*)ctl->host_report;
@@ -1462,6 +1473,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         int rc = plan_forward(P, ctl, retry, k, d, plan);
         if (rc) return rc;
         int n_launch = 0;
+        if (P.snap) { hipLaunchKernelGGL(k_snap_init<T>, dim3((2 * B + 255) / 256), dim3(256), 0, st, P.snap, P.snap_stride, B); ++n_launch; }
         rc = enqueue_prologue(st, P, plan, n_launch);
         if (rc) return rc;
         const Attempt a = plan.up_front ? run_planned(st, P, plan, ctl, stats, n_launch) : run_chunked(st, P, plan, ctl, stats, n_launch);
@@ -2172,10 +2184,16 @@ size_t lqp_boxqp_forward_workspace_bytes(int dtype, int B, int n, int m) {
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes; });
 }
 
-int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
-                      const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
-                      void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
-                      void* workspace, size_t workspace_bytes) {
+size_t lqp_boxqp_forward_detect_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).detect_bytes; });
+}
+
+// lqp_boxqp_forward (eps_prim_inf = 0: no detection) and lqp_boxqp_forward_detect
+static int forward_entry(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                         const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                         void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
+                         void* workspace, size_t workspace_bytes, const double eps_prim_inf) {
     if (bad_dims(dtype, B, n, m) || !Q || !p || !lb || !ub || !ctrl || !x || !z || !u || !lams || !rho_out || !workspace)
         return LQP_ERR_INVALID;
     if (m > 0 && (!A || !b || !nus)) return LQP_ERR_INVALID;
@@ -2190,8 +2208,28 @@ int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* 
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)
     return by_dtype(dtype, [&](auto t) {
-        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0);
+        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf);
     });
+}
+
+int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                      const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                      void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
+                      void* workspace, size_t workspace_bytes) {
+    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
+                         workspace_bytes, 0.0);
+}
+
+int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                             const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                             void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
+                             void* workspace, size_t workspace_bytes, double eps_prim_inf) {
+    // refused before anything is touched: a threshold outside (0, 1) (NaN fails both comparisons), no per-problem stop, a check
+    // hook (a global stop), the factor kept for the unroll sweep
+    if (!(eps_prim_inf > 0.0 && eps_prim_inf < 1.0)) return LQP_ERR_INVALID;
+    if (!ctrl || !(ctrl->reserved2 & 8) || (ctrl->reserved2 & 1) || ctrl->check_hook) return LQP_ERR_INVALID;
+    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
+                         workspace_bytes, eps_prim_inf);
 }
 
 int lqp_boxqp_forward_finish(void* stream, int B, int max_iters, int check_solved, const void* host_report,
@@ -2372,6 +2410,23 @@ int lqp_boxqp_problem_iters(void* stream, int dtype, int B, int n, int m, const 
     });
     if (workspace_bytes < need) return LQP_ERR_WORKSPACE;
     hipLaunchKernelGGL(k_copy_iters<>, dim3((B + 255) / 256), dim3(256), 0, st, src, (int*)iters_out, B);
+    return last_error();
+}
+
+int lqp_boxqp_problem_status(void* stream, int dtype, int B, int n, int m, const void* workspace, size_t workspace_bytes,
+                             int32_t* status_out) {
+    if (bad_dims(dtype, B, n, m) || !workspace || !status_out) return LQP_ERR_INVALID;
+    if (!each_ws_known(workspace)) return LQP_ERR_INVALID;      // (the last forward on this workspace did not run with bit 3)
+    hipStream_t st = (hipStream_t)stream;
+    if (B == 0) return LQP_OK;
+    const int* src = nullptr;
+    const size_t need = by_dtype(dtype, [&](auto t) {
+        const FwdLayout<decltype(t)> L = carve_forward<decltype(t)>(const_cast<void*>(workspace), B, n, m);
+        src = L.pstat_area;
+        return L.bytes;
+    });
+    if (workspace_bytes < need) return LQP_ERR_WORKSPACE;
+    hipLaunchKernelGGL(k_copy_pstatus<>, dim3((B + 255) / 256), dim3(256), 0, st, src, (int*)status_out, B);
     return last_error();
 }
 

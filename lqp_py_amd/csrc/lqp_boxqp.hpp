@@ -26,7 +26,8 @@ enum { ST_DONE = 0, ST_FINAL_ITER = 1, ST_GATE = 2, ST_NFACTOR = 3, ST_RHO_UPDAT
 enum { PS_DONE = 0, PS_FINAL = 1, PS_RESUME = 2, PS_NFACTOR = 3, PS_WORDS = 4 };
 // host report (lqp_boxqp_ctrl.host_report): [ST_WORDS status words as workgroup 0 of the forward's last kernel sees them |
 // B info words | B flag words], written straight into pinned host memory by that kernel
-enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8 };
+enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
+       RP_INFEAS = 1 << 16 };     // control['infeasible']: the problem was flagged primal infeasible (each_stop)
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -109,7 +110,17 @@ template <typename T> struct FwdParams {
     T alpha, alpha_c;         // over-relaxation factor (control['alpha']; 1 = the reference's plain step) and 1 - alpha, see admm_relax
     int relax;                // 1: alpha != 1
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
+    T* snap;                 // B * snap_stride: control['infeasible'] (stop = 'each' only) -- the certificate's snapshots, or null = no detection
+    size_t snap_stride;
+    T eps_pinf;              // control['eps_prim_inf']
 };
+// control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
+// number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split_each:
+// bit-identical iterates, at most one hand-off apart) write the same values and never a slot somebody still reads.
+// A slot: [rho it was taken at | mark = iteration + 1 (0: none, k_snap_init) | - | - | y (n) | g (n) | nu (m)]
+enum { SN_RHO = 0, SN_MARK = 1, SN_HEAD = 4 };
+__host__ __device__ inline size_t snap_slot_len(int n, int m) { return (size_t)round_up(SN_HEAD + 2 * n + m, 4); }
+__host__ __device__ inline size_t snap_stride(int n, int m) { return 2 * snap_slot_len(n, m); }
 
 // vector block of problem b: [ps | lbs | ubs | D | z | u | x | As (m*n) | bs | E | nu | cv | Tm (m*n) | s0]
 // (cv, Tm, s0: constant term c, T = G S^-1 and S^-1 b of the symmetric-inverse path, lqp_spd.hpp)
@@ -1467,15 +1478,106 @@ __device__ __forceinline__ bool loop_all_optimal(const FwdParams<T>& P, unsigned
 // stop = 'each': problem b stopped at iteration `it` (one thread, after the iterate was stored).  The batch's final iteration is the
 // largest; the count of stopped problems goes behind the RETURNED maximum, and whoever makes it B has therefore seen every maximum
 // land before it raises ST_DONE
+// why = 1: optimal; 2: flagged primal infeasible (control['infeasible']) -- also bit RP_INFEAS of the problem's flag word, which the
+// forward's last kernel reports as it stands
 template <typename T>
-__device__ __forceinline__ void each_stop(const FwdParams<T>& P, const int b, const int it) {
+__device__ __forceinline__ void each_stop(const FwdParams<T>& P, const int b, const int it, const int why = 1) {
     int* ps_ = P.pstat + (size_t)b * PS_WORDS;
     ps_[PS_FINAL] = it;
-    ps_[PS_DONE] = 1;
+    ps_[PS_DONE] = why;
+    if (why == 2) P.bflags[b] |= RP_INFEAS;
     const int r1 = atomicMax(P.status + ST_FINAL_ITER, it);
     asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1) : "memory");
     const int nd = __hip_atomic_fetch_add(P.status + ST_NDONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (nd + 1 == P.B) __hip_atomic_store(P.status + ST_DONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// ---- control['infeasible'] (stop = 'each' only; P.snap != null): the primal infeasibility certificate at a check ----
+// OSQP's test with the differences taken check to check, in the scaled problem: y = rho u, g = Qs x + s, nu of THIS check against the
+// snapshot of the last one -- dy, dg, dnu; N = |dy|_inf; c1 = |dg|_inf / N; c2 = (sum_i [ubs_i max(dy_i, 0) + lbs_i min(dy_i, 0)] +
+// bs^T dnu) / N.  Infeasible iff N > 0, c1 <= eps and c2 <= -eps: dy + As^T dnu = -dg by the x-update's stationarity, so (dy, dnu) is a
+// Farkas certificate of {As x = bs, lbs <= x <= ubs} = empty.  An infinite bound: its term counts 0 while |dy_i| <= eps N, else c2 = +inf
+// (0 * inf is never formed).  The snapshot is valid iff it is the last check's and rho has not changed since (an adaptive-rho event
+// of this problem changes y's scale: the check behind it only refreshes).  Composed like the other steps: infeas_view (which slots,
+// valid?), infeas_elem per element the caller owns, infeas_nu per equality row, infeas_decide on the four reduced numbers
+// {N, |dg|_inf, largest |dy_i| on an infinite bound, the sum}, infeas_mark by one thread.  All of it on check iterations only.
+template <typename T> struct InfeasView { const T* prev; T* next; int n; bool valid; };
+template <typename T>
+__device__ __forceinline__ InfeasView<T> infeas_view(const FwdParams<T>& P, const int b, const int it, const T rho) {
+    T* base = P.snap + (size_t)b * P.snap_stride;
+    const size_t len = P.snap_stride / 2;
+    const int c = it / P.check_solved;
+    const T* prev = base + (size_t)((c + 1) & 1) * len;
+    const bool valid = it >= P.check_solved && prev[SN_MARK] == T(it - P.check_solved + 1) && prev[SN_RHO] == rho;
+    return {prev, base + (size_t)(c & 1) * len, P.n, valid};
+}
+template <typename T>
+__device__ __forceinline__ void infeas_elem(T (&ia)[4], const InfeasView<T>& S, const int i, const T y, const T g, const T lb,
+                                            const T ub) {
+    // (the other slot is read whether or not it is valid: the loads then do not wait for the slot's head, a memory round trip less on
+    //  the check's path; what an invalid slot holds -- inside the region, whatever it is -- is dropped)
+    const T py = S.prev[SN_HEAD + i], pg = S.prev[SN_HEAD + S.n + i];
+    S.next[SN_HEAD + i] = y;
+    S.next[SN_HEAD + S.n + i] = g;
+    if (S.valid) {
+        const T dy = y - py, dg = g - pg;
+        ia[0] = tmax(ia[0], tabs(dy));
+        ia[1] = tmax(ia[1], tabs(dg));
+        const T bnd = dy > T(0) ? ub : lb;
+        if (dy != T(0)) {
+            if (tabs(bnd) <= std::numeric_limits<T>::max()) ia[3] += bnd * dy;
+            else ia[2] = tmax(ia[2], tabs(dy));
+        }
+    }
+}
+template <typename T>
+__device__ __forceinline__ void infeas_nu(T (&ia)[4], const InfeasView<T>& S, const int r, const T nu, const T bsr) {
+    const T pnu = S.prev[SN_HEAD + 2 * S.n + r];
+    S.next[SN_HEAD + 2 * S.n + r] = nu;
+    if (S.valid) ia[3] += bsr * (nu - pnu);
+}
+template <typename T>
+__device__ __forceinline__ void infeas_mark(const InfeasView<T>& S, const int it, const T rho) {
+    S.next[SN_RHO] = rho;
+    S.next[SN_MARK] = T(it + 1);
+}
+template <typename T>
+__device__ __forceinline__ bool infeas_decide(const FwdParams<T>& P, const InfeasView<T>& S, const T (&iv)[4]) {
+    if (!S.valid) return false;
+    const T N = iv[0];
+    if (!(N > T(0))) return false;
+    if (iv[2] > P.eps_pinf * N) return false;                 // (c2 = +inf)
+    return iv[1] / N <= P.eps_pinf && iv[3] / N <= -P.eps_pinf;
+}
+// {max, max, max, sum} over the workgroup (NWV waves; red: NWV * 8 + 8 words, as wg_max_n), the same numbers in every thread
+template <typename T, int NWV>
+__device__ __forceinline__ void infeas_reduce(T (&ia)[4], T* red) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) ia[q] = wave_max(ia[q]);
+    ia[3] = wave_sum(ia[3]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[w * 8 + q] = ia[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        T r = red[q];
+#pragma unroll 1
+        for (int ww = 1; ww < NWV; ++ww) r = q < 3 ? tmax(r, red[ww * 8 + q]) : r + red[ww * 8 + q];
+        ia[q] = r;
+    }
+}
+// the rest of the step behind the element pass (every thread of the workgroup, uniform): equality rows, reduction, decision, mark.
+// nus / bs: the duals of this check and the scaled right-hand side, wherever the caller holds them
+template <typename T, int NT>
+__device__ __forceinline__ bool infeas_finish(const FwdParams<T>& P, const InfeasView<T>& S, T (&ia)[4], const T* nus,
+                                              const T* bs, const int it, const T rho, T* red) {
+    for (int r = threadIdx.x; r < P.m; r += NT) infeas_nu(ia, S, r, nus[r], bs[r]);
+    infeas_reduce<T, NT / 64>(ia, red);
+    if (threadIdx.x == 0) infeas_mark(S, it, rho);
+    return infeas_decide(P, S, ia);
 }
 // ---------------------------------------------------------------------------
 // The ADMM loop (:235-313).  RES: resident head of the factor stream (registers + LDS); SYM: symmetric-inverse
@@ -1498,7 +1600,7 @@ __device__ __forceinline__ void each_stop(const FwdParams<T>& P, const int b, co
 // stops at the first check at which IT is optimal (its workgroup stores the iterate, marks pstat[b] and returns), it adapts rho at
 // an event iff its own `wants && trig` of the last check say so, and nothing crosses workgroups: no grid_wait, no arrival word,
 // no decision from the counters.  A launch begins by reading pstat[b].done and leaves at once when it is set.
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false, bool DETECT = false>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem);
 // does the adaptive-rho event at iteration seg0 change this problem's rho?  The reference's decision over the whole batch, from the
@@ -1545,7 +1647,9 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
     loop_event_count<T, EACH>(P, b, seg0);
     return rho_;
 }
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false>
+// DETECT (EACH only; control['infeasible']): the certificate at every check (infeas_view ...), instances of their own: inside the one body
+// its registers cost the plain EACH kernels 3 % of their time
+template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false, bool DETECT = false>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
                                                const int prev_slot,      // slot of the last check before it0, -1: none / known not done
@@ -1556,12 +1660,13 @@ __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int 
         // this problem stopped in an earlier launch: its iterate is not touched again
         if (__builtin_amdgcn_readfirstlane(P.pstat[(size_t)blockIdx.x * PS_WORDS + PS_DONE])) return;
     }
-    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH, DETECT>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH, bool DETECT>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
+    static_assert(!DETECT || EACH, "the infeasibility certificate is part of a problem's own stopping check");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
     int b = blockIdx.x, part_id = 0;
     if constexpr (NP == 2) { if (!shared_map((int)blockIdx.x, P.B, 2, b, part_id)) return; }
@@ -1732,6 +1837,9 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         T mx[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) mx[q] = T(0);
+        T ia[4] = {T(0), T(0), T(0), T(0)};                      // (DETECT: the certificate's terms, see infeas_view)
+        InfeasView<T> isv = {nullptr, nullptr, n, false};
+        if constexpr (DETECT) { if (check) isv = infeas_view(P, b, it, rho); }
         // ||Q x / D||_inf of the check (:299) without touching Q: the x-update solved (Qs + rho I) x + As^T nu = w
         // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu.  It only feeds a tolerance SCALE.
         if constexpr (SYM) {
@@ -1829,6 +1937,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                         T qx = v[i] - rho * xi;
                         for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + i] * nus_l[q];
                         mx[5] = tmax(mx[5], tabs(qx / di));
+                        if constexpr (DETECT) infeas_elem(ia, isv, i, rho * un, qx + s, lb[i], ub[i]);
                     }
                     wn = -ps[i] + rho * (zn - un);           // next iteration's right-hand side
                 }
@@ -1874,6 +1983,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     T qx = -ps[i] + rho * (zp - ui) - rho * xi;
                     for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + i] * nul[q];
                     mx[5] = tmax(mx[5], tabs(qx / di));
+                    if constexpr (DETECT) infeas_elem(ia, isv, i, rho * un, qx + s, lb[i], ub[i]);
                 }
             }
         }
@@ -1906,12 +2016,14 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     if (!solved) atomicAdd(ct + CT_NOTOPT, 1u);
                 }
                 ++slot;
-                if (solved) {
+                bool flagged = false;                        // control['infeasible']: primal infeasible at this check (optimal comes first)
+                if constexpr (DETECT) flagged = infeas_finish<T, NT>(P, isv, ia, SYM ? bs + m : v + n, bs, it, rho, red) && !solved;
+                if (solved || flagged) {
                     // leave with the state of iteration `it`: the iterate first, then the words that say so
                     __syncthreads();
                     store_state();
                     if (tid == 0) {
-                        each_stop(P, b, it);
+                        each_stop(P, b, it, flagged ? 2 : 1);
                     }
                     return;
                 }
@@ -2008,6 +2120,13 @@ __global__ __launch_bounds__(NT) void k_admm_loop_each(const FwdParams<T> P, con
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_body<T, RES, TAIL, NT, SYM, 1, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
+// ... with the infeasibility certificate at every check (control['infeasible']; DETECT)
+template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
+__global__ __launch_bounds__(NT) void k_admm_loop_each_detect(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
+                                                              const int prev_slot, const int persistent) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_body<T, RES, TAIL, NT, SYM, 1, true, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+}
 
 // all problems optimal at the check held in `slot` (iteration `it_check`)?  -> DONE
 template <int LQP_ANY = 0>      // (a template only so that the split build can place its one instance: tools/gen_split_build.py)
@@ -2088,6 +2207,22 @@ template <int LQP_ANY = 0>
 __global__ void k_copy_iters(const int* __restrict__ pstat, int* __restrict__ out, const int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) out[b] = pstat[(size_t)b * PS_WORDS + PS_FINAL];
+}
+// how every problem of a control['stop'] = 'each' solve ended (lqp_boxqp_problem_status): 0 optimal, 1 out of iterations, 2 flagged
+// primal infeasible
+template <int LQP_ANY = 0>
+__global__ void k_copy_pstatus(const int* __restrict__ pstat, int* __restrict__ out, const int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < B) {
+        const int d = pstat[(size_t)b * PS_WORDS + PS_DONE];
+        out[b] = d == 1 ? 0 : (d == 2 ? 2 : 1);
+    }
+}
+// control['infeasible']: no problem has a snapshot yet -- the marks of both slots (infeas_view), at the head of every attempt
+template <typename T>
+__global__ void k_snap_init(T* __restrict__ snap, const size_t stride, const int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * B) snap[(size_t)(i >> 1) * stride + (size_t)(i & 1) * (stride / 2) + SN_MARK] = T(0);
 }
 template <typename T>
 __global__ void k_copy_residuals(const T* __restrict__ scal, T* __restrict__ pri, T* __restrict__ dua, const int B) {

@@ -16,7 +16,9 @@ namespace lqp {
 // ---------------------------------------------------------------------------
 __host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 + (m > 0 ? m : 1) + 4 * 8 + 8 + 8) * 4; }
 // EACH (control['stop'] = 'each'): the problem's own verdict ends its workgroup; no arrival word, no grid_wait
-template <bool EACH>
+// DETECT (EACH only; control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
+// check iterations, and the certificate's registers in it cost the plain EACH kernel 12 % of its time
+template <bool EACH, bool DETECT = false>
 __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                      char* smem) {
     typedef float T;
@@ -29,6 +31,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
     }
     if (it0 >= it1) return;
     bool each_done = false;
+    int each_why = 1;                   // (DETECT) 2: the problem stopped because it was flagged primal infeasible
     int final_it = it1 - 1;
     T* const wv = (T*)smem;
     T* const yv = wv + 128;
@@ -103,6 +106,9 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
         T mx[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) mx[q] = T(0);
+        T ia[4] = {T(0), T(0), T(0), T(0)};                      // (DETECT: the certificate's terms, see infeas_view)
+        InfeasView<T> isv = {nullptr, nullptr, n, false};
+        if constexpr (DETECT) { if (check) isv = infeas_view(P, b, it, rho); }
         if (live) {
             const T wi = wv[e];
             xi = cvi - yv[e];
@@ -113,6 +119,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
                 T qx = wi - rho * xi;
                 for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + e] * nus_l[q];
                 admm_step_norms<false>(mx, sp, xi, di, rho, qx);
+                if constexpr (DETECT) infeas_elem(ia, isv, e, rho * sp.un, qx + sp.s, lbi, ubi);
             }
         }
         __syncthreads();                                         // (everybody has read w and y)
@@ -128,6 +135,10 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
                     if (!ck.solved) atomicAdd(ct + CT_NOTOPT, 1u);      // (k_check_done at the end of a host-driven chunk reads the slot)
                 }
                 ++slot;
+                if constexpr (DETECT) {
+                    const bool flagged = infeas_finish<T, NT>(P, isv, ia, nus_l, V.bs, it, rho, red) && !ck.solved;
+                    if (flagged) { each_done = true; each_why = 2; final_it = it; break; }
+                }
                 if (ck.solved) { each_done = true; final_it = it; break; }      // (uniform: every thread holds the reduced norms)
             } else {
                 ++slot;
@@ -153,7 +164,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
     for (int q = tid; q < m; q += NT) V.nu[q] = nus_l[q];
     if constexpr (EACH) {
         if (tid == 0) {
-            if (each_done) each_stop(P, b, final_it);
+            if (each_done) each_stop(P, b, final_it, each_why);
             else P.pstat[(size_t)b * PS_WORDS + PS_FINAL] = final_it;      // (not optimal so far: the last iteration it ran)
         }
     }
@@ -168,6 +179,12 @@ __global__ __launch_bounds__(256) void k_admm_loop_small_each(const FwdParams<fl
                                                               const int ctr_base) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_small_body<true>(P, it0, it1, ctr_base, smem);
+}
+template <int LQP_ANY = 0>
+__global__ __launch_bounds__(256) void k_admm_loop_small_each_detect(const FwdParams<float> P, const int it0, const int it1,
+                                                                     const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_small_body<true, true>(P, it0, it1, ctr_base, smem);
 }
 
 }  // namespace lqp

@@ -387,6 +387,9 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         T mx[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) mx[q] = T(0);
+        T ia[4] = {T(0), T(0), T(0), T(0)};                   // (EACH, control['infeasible']: the certificate's terms, see infeas_view)
+        InfeasView<T> isv = {nullptr, nullptr, n, false};
+        if constexpr (COLD && EACH) { if (check && P.snap) isv = infeas_view(P, b, it, rho); }
         if (tid < Nps) {
             const int i = tid;
             xs[i] = xi;
@@ -401,6 +404,8 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
                         T qx = v[i] - rho * xi;
                         for (int q = 0; q < m; ++q) qx -= Asl[(size_t)q * Nps + i] * nus_l[q];
                         admm_step_norms<false>(mx, sp, xi, D[i], rho, qx);
+                        // (every workgroup of the problem stores the same values into the same slot, see snap_stride)
+                        if constexpr (EACH) { if (P.snap) infeas_elem(ia, isv, i, rho * un, qx + sp.s, lb[i], ub[i]); }
                     }
                 }
             }
@@ -441,11 +446,15 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
                     }
                     ++slot;
                     __syncthreads();
-                    if (flags[4]) {
+                    int why = flags[4];                       // 1: optimal
+                    if (P.snap) {
+                        if (infeas_finish<T, NT>(P, isv, ia, nus_l, bs, it, rho, red) && !why) why = 2;      // flagged primal infeasible
+                    }
+                    if (why) {
                         // leave with the state of iteration `it`: the iterate first, then the words that say so
                         if (part_id == 0) {
                             store_state();
-                            if (tid == 0) each_stop(P, b, it);
+                            if (tid == 0) each_stop(P, b, it, why);
                         }
                         return 1;
                     }

@@ -23,6 +23,10 @@ on top of it is refused: a global stop is its opposite).
 ``control['alpha']`` (over-relaxation) is a setting of every shard's own loop:
 it needs no exchange, with or without ``dist_strict_stop``; every rank must
 pass the same value, like every other setting.
+``control['infeasible']`` / ``control['eps_prim_inf']`` (primal infeasibility
+detection) travel the same way and are allowed only where ``'each'`` is:
+every shard flags its own problems (``'raise'``: ``InfeasibleQPError.indices``
+are indices into the rank's shard), no exchange is needed.
 ``dl_dQ`` is never gathered.
 """
 import torch

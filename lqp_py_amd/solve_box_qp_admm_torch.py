@@ -15,6 +15,7 @@ import collections
 import ctypes
 import numbers
 import os
+import re
 import threading
 import types
 import weakref
@@ -89,7 +90,10 @@ class SolveBoxQPLayer(torch.autograd.Function):
                                                     prefactor=_PREFACTOR_BWD)
         sol = _forward_solve(Q, p, A, b, lb, ub, control, bounds=control.get('_global_bounds'), sync=sync,
                              check_hook=control.get('_check_hook'), mutate=True,
-                             holder=control.get('_holder') or getattr(_tls, 'holder', None), while_running=while_running)
+                             holder=control.get('_holder') or getattr(_tls, 'holder', None), while_running=while_running,
+                             raise_infeasible=control.get('infeasible') == 'raise')
+        # control['infeasible'] = 'flag': the rows of a flagged problem are zero in every gradient (masked on the device, no host sync)
+        ctx.flagged = (sol['status'] == 2) if control.get('infeasible') == 'flag' and sol.get('status') is not None else None
         ctx.rho = sol['rho']
         st_ = sol['_stats']
         ctx.bound_flags = (bool(st_['any_lb']), bool(st_['any_ub'])) if st_['any_lb'] >= 0 else None     # (pipelined: not known)
@@ -101,6 +105,40 @@ class SolveBoxQPLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dl_dz):
         x, u, lams, nus, Q, A, lb, ub = ctx.saved_tensors
+        if ctx.flagged is None:
+            return SolveBoxQPLayer._backward(ctx, dl_dz, x, u, lams, nus, Q, A, lb, ub)
+        # The iterate of a flagged problem is no solution: whatever the backward makes of it -- a singular reduced system among it -- is
+        # not a gradient and not an error.  Its rows are exactly zero; a "singular" report is raised only if a problem that was NOT
+        # flagged is behind it (cold path: the one host read of the mask).
+        _tls.flagged = ctx.flagged           # (a backward that does not wait reports late: _backward_call hands the mask to that report)
+        try:
+            grads = SolveBoxQPLayer._backward(ctx, dl_dz, x, u, lams, nus, Q, A, lb, ub)
+        except RuntimeError as exc:
+            at = re.search(r"batch index (-?\d+)", str(exc))
+            if "singular" not in str(exc) or at is None or int(at.group(1)) < 0 or not bool(ctx.flagged[int(at.group(1))]):
+                raise
+            keep = (~ctx.flagged).nonzero().flatten()
+            part = lambda t: None if t is None else t[keep]
+            sub = SolveBoxQPLayer._backward_plain(ctx, part(dl_dz), part(x), part(u), part(lams), part(nus), part(Q), part(A), part(lb),
+                                                  part(ub), None if not torch.is_tensor(ctx.rho) or ctx.rho.numel() == 1 else ctx.rho[keep])
+            grads = tuple(None if g is None else torch.zeros((Q.shape[0],) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
+                          .index_copy_(0, keep, g) for g in sub)
+        finally:
+            _tls.flagged = None
+        gone = ctx.flagged.view(-1, 1, 1)
+        return tuple(None if g is None else torch.where(gone, torch.zeros((), dtype=g.dtype, device=g.device), g) for g in grads)
+
+    @staticmethod
+    def _backward_plain(ctx, dl_dz, x, u, lams, nus, Q, A, lb, ub, rho):
+        rho = ctx.rho if rho is None else rho
+        if ctx.backward_method == 'kkt':
+            return _kkt_backward(dl_dz, x, lams, nus, Q, A, lb, ub, flags=ctx.bound_flags, linsolve=ctx.linsolve,
+                                 want=_wanted(ctx.needs_input_grad, A), sync=ctx.sync)
+        return _fp_backward(dl_dz, x, u, lams, nus, Q, A, lb, ub, rho, _wanted(ctx.needs_input_grad, A), sync=ctx.sync,
+                            linsolve=ctx.linsolve)
+
+    @staticmethod
+    def _backward(ctx, dl_dz, x, u, lams, nus, Q, A, lb, ub):
         if ctx.backward_method == 'kkt':
             return _kkt_backward(dl_dz, x, lams, nus, Q, A, lb, ub, flags=ctx.bound_flags, linsolve=ctx.linsolve,
                                  want=_wanted(ctx.needs_input_grad, A), sync=ctx.sync)
@@ -164,7 +202,15 @@ def torch_solve_box_qp(Q, p, A, b, lb, ub, control):
     there), hence both backward forms.  A number or a one-element tensor inside (0, 2), anything else is a ValueError at the call;
     1.6 takes about a third of the iterations off the reference's count.  Every loop kernel takes it: with
     stop='each', sync=False, any launch_mode and linsolve, under lqp_py_amd.dist with and without dist_strict_stop.  Not with
-    unroll=True (ValueError: the tape replays the unrelaxed step).  A batch without any finite bound does not iterate and ignores it."""
+    unroll=True (ValueError: the tape replays the unrelaxed step).  A batch without any finite bound does not iterate and ignores it.
+
+    control['infeasible'] (extension; absent or None: off | 'raise' | 'flag') with control['eps_prim_inf'] (default 1e-4, inside
+    (0, 1)): primal infeasibility detection, only with stop='each' (ValueError otherwise, and with unroll=True).  At every check of
+    a problem the differences of y = rho u, g = Qs x + s and nu against the check before (same rho) are tested as a Farkas
+    certificate of {A x = b} and [lb, ub] not meeting -- OSQP's test; the rule is in DESIGN.md section 7.  A flagged problem stops
+    like an optimal one, x, z, u hold its iterate of that check.  This function never raises for it: with stop='each', detection on
+    or off, the dict holds "status", a (B,) int32 device tensor -- 0 optimal, 1 ended at max_iters without being optimal, 2 primal
+    infeasible.  The layer raises lqp_py_amd.InfeasibleQPError ('raise') or zeroes the gradient rows of flagged problems ('flag')."""
     check_stop(control)
     if control.get('unroll', False):
         # autograd through the loop (:328-329 returns the bare x); see lqp_py_amd/unrolled.py
@@ -349,7 +395,10 @@ def resolve_control(control, n_x):
     g = control.get
     check = g('check_solved', max(round((n_x ** 0.5) / 10) * 10, 1))
     ar_iter = max(round(g('adaptive_rho_iter', 100) / check) * check, 1)
+    infeasible, eps_prim_inf = check_infeasible(control)
     return dict(
+        infeasible=infeasible,                   # extension: None | 'raise' | 'flag' -- primal infeasibility detection (stop='each' only)
+        eps_prim_inf=eps_prim_inf,               # ... and its threshold, inside (0, 1)
         max_iters=g('max_iters', 10_000),
         eps_abs=max(g('eps_abs', 1e-3), 1e-12),
         eps_rel=max(g('eps_rel', 1e-3), 1e-12),
@@ -386,11 +435,34 @@ def check_alpha(control):
     return a
 
 
+def check_infeasible(control):
+    """control['infeasible'] and control['eps_prim_inf'] -> (None | 'raise' | 'flag', eps as a float).  Raises at the call, before any
+    launch; the one place that holds this rule (check_stop comes here).  Detection lives in the per-problem stop: the key needs
+    stop='each' and cannot be combined with unroll=True."""
+    mode = control.get('infeasible')
+    if mode is not None and not (isinstance(mode, str) and mode in ('raise', 'flag')):
+        _bad("control['infeasible'] must be None, 'raise' or 'flag'")
+    eps = control.get('eps_prim_inf', 1e-4)
+    if eps.__class__ is not float:
+        if isinstance(eps, bool) or not (isinstance(eps, numbers.Real) or (torch.is_tensor(eps) and eps.numel() == 1)):
+            _bad("control['eps_prim_inf'] must be a number (or a one-element tensor) inside (0, 1)")
+        eps = float(eps)
+    if not 0.0 < eps < 1.0:                       # (NaN fails both comparisons)
+        _bad("control['eps_prim_inf'] must be inside (0, 1)")
+    if mode is not None:
+        if control.get('stop', 'all') != 'each':
+            _bad("control['infeasible'] needs control['stop'] = 'each': the certificate is part of a problem's own stopping check")
+        if control.get('unroll', False):
+            _bad("control['infeasible'] cannot be combined with unroll=True: the tape has one length")
+    return mode, eps
+
+
 def check_stop(control, check_hook=None):
     """control['stop'] and what it cannot be combined with; -> True for 'each'.  Raises at the call, before any launch.  The one place
     that holds these rules: torch_solve_box_qp, _forward_solve, lqp_py_amd.dist and lqp_py_amd.unrolled all come here (and, through
-    it, to check_alpha: control['alpha'] is refused at the same places)."""
+    it, to check_alpha and check_infeasible: control['alpha'] and control['infeasible'] are refused at the same places)."""
     check_alpha(control)
+    check_infeasible(control)
     stop = control.get('stop', 'all')
     if not isinstance(stop, str) or stop not in ('all', 'each'):
         _bad("control['stop'] must be 'all' or 'each'")
@@ -598,29 +670,38 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
     report, stats = _lib.host_report(_lib.ST_WORDS + 2 * B), _lib.BoxQPStats()
     ctl.host_report = report.data_ptr()
     x, addresses, views = _output_block(B, n, m, p.dtype, dev)
-    nbytes = _ws_bytes.get((dt, B, n, m))
+    # control['infeasible'] (with stop='each' alone, check_stop): the entry point with the certificate, and its larger workspace -- the
+    # forward's layout with the snapshots behind it.  Key absent: the entry point and the size there always were
+    detect = each and r['infeasible'] is not None
+    nbytes = _ws_bytes.get((dt, B, n, m, detect))
     if nbytes is None:
-        nbytes = _ws_bytes[(dt, B, n, m)] = lib.lqp_boxqp_forward_workspace_bytes(dt, B, n, m)
+        size_of = lib.lqp_boxqp_forward_detect_workspace_bytes if detect else lib.lqp_boxqp_forward_workspace_bytes
+        nbytes = _ws_bytes[(dt, B, n, m, detect)] = size_of(dt, B, n, m)
     stream = _lib.current_stream_handle(dev)
     ws = private_ws if private_ws is not None else _lib.workspace(dev, nbytes, "fwd", stream)
     hook_c = hook_error = None
     if check_hook is not None:
         hook_c, hook_error = _strict_stop_hook(check_hook, ws)      # (hook_c: alive until the library has returned)
         ctl.check_hook = hook_c
+    args = (ctypes.c_void_p(stream), dt, B, n, m,
+            _lib.ptr(Qc), _lib.ptr(pc), _lib.ptr(Ac), _lib.ptr(bc), _lib.ptr(lbc), _lib.ptr(ubc),
+            ctypes.byref(ctl), _lib.ptr(rho_tensor), *addresses,
+            ctypes.byref(stats), _lib.ptr(ws), ws.numel())
     with _lib.on_device(dev):
-        st = lib.lqp_boxqp_forward(ctypes.c_void_p(stream), dt, B, n, m,
-                                   _lib.ptr(Qc), _lib.ptr(pc), _lib.ptr(Ac), _lib.ptr(bc), _lib.ptr(lbc), _lib.ptr(ubc),
-                                   ctypes.byref(ctl), _lib.ptr(rho_tensor), *addresses,
-                                   ctypes.byref(stats), _lib.ptr(ws), ws.numel())
+        st = lib.lqp_boxqp_forward_detect(*args, float(r['eps_prim_inf'])) if detect else lib.lqp_boxqp_forward(*args)
     split_wait = st == 0 and stats.mode_used == 4
     z, u, lams, nus, rho_out = views()
-    iters = None
+    iters = pstatus = None
     if each and st == 0:
-        # the per-problem iteration counts: a copy kernel behind the solve on its stream, into a device tensor -- no host wait
+        # the per-problem iteration counts, and how every problem ended (0 optimal, 1 out of iterations, 2 primal infeasible): two copy
+        # kernels behind the solve on its stream, into device tensors -- no host wait
         iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        pstatus = torch.empty((B,), dtype=torch.int32, device=dev)
         with _lib.on_device(dev):
             _lib.check(lib.lqp_boxqp_problem_iters(ctypes.c_void_p(stream), dt, B, n, m, _lib.ptr(ws), ws.numel(), _lib.ptr(iters)),
                        "problem_iters")
+            _lib.check(lib.lqp_boxqp_problem_status(ctypes.c_void_p(stream), dt, B, n, m, _lib.ptr(ws), ws.numel(), _lib.ptr(pstatus)),
+                       "problem_status")
     if split_wait:
         if while_running is not None:
             while_running(dict(x=x, u=u, lams=lams, nus=nus, rho_out=rho_out.view(B, 1, 1)), int(stats.linsolve_used))
@@ -629,7 +710,7 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
                                           ctypes.c_void_p(report.data_ptr()), ctypes.byref(stats))
     return _Outcome(status=st, split_wait=split_wait, stats=stats, hook_error=hook_error, any_bound=any_bound, known=known,
                     report=report, ws=ws, stream=stream, dims=(dt, B, n, m), r=r, rho=rho, rho_mode=ctl.rho_mode,
-                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out, iters=iters)
+                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out, iters=iters, pstatus=pstatus)
 
 
 def _print_check_trace(out, dev):
@@ -665,6 +746,8 @@ def _solution(out, like, residuals):
     sol = {"x": out.x, "z": out.z, "u": out.u, "lams": out.lams, "nus": out.nus, "rho": rho_ret, "iter": int(stats.iters)}
     if out.iters is not None:            # control['stop'] = 'each': every problem's own count; "iter" is the largest
         sol["iters"] = out.iters
+        sol["status"] = out.pstatus      # (B,) int32: 0 optimal, 1 ended at max_iters, 2 primal infeasible (control['infeasible'])
+    _last_problem_status[(dev.index, out.stream)] = out.pstatus
     if residuals:                        # errors of the last check (the NumPy twin's extra outputs)
         pri, dua = (torch.empty((B,), dtype=like.dtype, device=dev) for _ in range(2))
         with torch.cuda.device(dev):
@@ -677,11 +760,13 @@ def _solution(out, like, residuals):
 
 
 def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residuals=False, check_hook=None, mutate=False,
-                   holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False):
+                   holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False, raise_infeasible=False):
     """bounds: (any_lb, any_ub) when the caller KNOWS them (a shard of a larger batch with host-side flags); None: found
     on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
     nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound).
-    Attempt, decide, act on the verdict, in a loop: _forward_attempt runs the library once, _forward_decide holds the rules."""
+    Attempt, decide, act on the verdict, in a loop: _forward_attempt runs the library once, _forward_decide holds the rules.
+    raise_infeasible (the layer with control['infeasible'] = 'raise'): a problem flagged primal infeasible raises InfeasibleQPError
+    once the whole batch is done -- here when the call waited, where the other late errors surface when it did not."""
     check_stop(control, check_hook)
     _lib.require_gpu(Q, p, A, b, lb, ub)
     sync = sync or check_hook is not None             # (the strict global stop is host-driven: one launch per check)
@@ -697,7 +782,8 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
                 if out.stats.mode_used == 3:  # nothing was waited for: the report is read once the stream has passed the call
                     _lib.defer_check("SolveBoxQP.forward", dev, out.report, Q.shape[0], True,
                                      bounds_check=None if out.known else (
-                                         out.any_bound, owner, mutate, lambda _c, seen: _remember_any_bound(holder, owner, seen)))
+                                         out.any_bound, owner, mutate, lambda _c, seen: _remember_any_bound(holder, owner, seen)),
+                                     raise_infeasible=raise_infeasible and out.pstatus is not None)
                 else:                     # (the library waited after all: nothing left to report late)
                     _lib.report_done(out.report)
         else:
@@ -717,10 +803,27 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
         att.control['rho'] = owner['rho'] = 0      # written into the CALLER's dict, as the reference does (:37-38)
     if out.r['verbose']:
         _print_check_trace(out, dev)
-    return _solution(out, p, residuals)
+    sol = _solution(out, p, residuals)
+    if raise_infeasible and out.pstatus is not None and out.stats.mode_used != 3:
+        flagged = (out.pstatus == 2).nonzero().flatten().tolist()      # (the call waited for the solve: this read waits for a copy kernel)
+        if flagged:
+            raise _lib.InfeasibleQPError("SolveBoxQP.forward", flagged)
+    return sol
 
 
 _last_forward = {}
+_last_problem_status = {}
+
+
+def last_problem_status(device):
+    """How every problem of the most recent forward solve on `device`, on the CURRENT stream, ended: a (B,) int32 device tensor --
+    0 optimal, 1 it ended at max_iters without being optimal, 2 flagged primal infeasible (control['infeasible']) -- or None when that
+    solve did not run with control['stop'] = 'each'.  Stream-ordered like the solution itself: reading it on the host waits for the
+    solve.  Valid until the next forward on the same stream, like last_forward_status."""
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return _last_problem_status[(device.index, _lib.current_stream_handle(device))]
 
 
 def last_forward_status(device):
@@ -770,7 +873,7 @@ def _backward_call(fn, args, what, fail, report, dev, B, sync):
         _lib.poll_errors()
     finally:
         if not sync:
-            _lib.defer_check("SolveBoxQP.backward", dev, report, B, False)
+            _lib.defer_check("SolveBoxQP.backward", dev, report, B, False, ignore=getattr(_tls, 'flagged', None))
         else:
             _lib.report_done(report)
 
