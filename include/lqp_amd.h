@@ -130,7 +130,8 @@ typedef struct lqp_boxqp_ctrl {
                                         [16+B..16+2B) per-problem flag bits {1: a lower bound is finite, 2: an upper
                                         bound is finite, 4: its workgroup saw a barrier timeout, 8: its matrix left the
                                         symmetric x-update, 65536 (bit 16, added within ABI 17): flagged primal
-                                        infeasible by lqp_boxqp_forward_detect}.  Valid once the stream has passed the call (an event):
+                                        infeasible by lqp_boxqp_forward_detect / _certify, 131072 (bit 17, added within
+                                        ABI 17): flagged dual infeasible by lqp_boxqp_forward_certify}.  Valid once the stream has passed the call (an event):
                                         ctrl.reserved = 1 callers read it then.  A synchronous call sets every
                                         word to -1 before its first launch and POLLS them (all stored words are >= 0)
                                         instead of synchronising the stream: it returns about a microsecond after the
@@ -363,9 +364,33 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m,
                              void* x, void* z, void* u, void* lams, void* nus, void* rho_out,
                              lqp_boxqp_stats* stats,
                              void* workspace, size_t workspace_bytes, double eps_prim_inf);
+/* ---- dual infeasibility detection (added within ABI 17: new symbols only, no struct and no signature changed) ----------
+ * lqp_boxqp_forward_certify is the same implementation once more (lqp_boxqp_forward_detect is the call with eps_dual_inf = 0)
+ * with a second test at every stopping check of a problem, on the same snapshot: with dx, dq the differences of x and Qs x
+ * (scaled problem; Qs x is formed from the x-update's right-hand side, Q is not read) between this check and the last one,
+ *   N = |dx|_inf,  e1 = |dq|_inf / N,  e2 = ps^T dx / N,  e3 = max_i([lbs_i finite] (-dx_i), [ubs_i finite] dx_i, 0) / N
+ * and the problem is DUAL INFEASIBLE -- its objective is unbounded below on its feasible set -- iff N > 0, e1 <= eps_dual_inf,
+ * e2 <= -eps_dual_inf and e3 <= eps_dual_inf: OSQP's certificate with differences taken check to check, except that As dx is
+ * not tested (the x-update solves the equality-constrained system: As x = bs holds at every iteration to rounding).  Order in a
+ * check: optimal, primal infeasible, dual infeasible.  A flagged problem stops like an optimal one with the iterate of that
+ * check; lqp_boxqp_problem_status says 3 and bit 17 of its flag word in ctrl.host_report is set.
+ * Either threshold is 0 (that certificate is off) or finite and inside (0, 1), and at least one is not 0; the other refusals
+ * are lqp_boxqp_forward_detect's (reserved2 bit 3 required, no check_hook, no bit 0): LQP_ERR_INVALID before anything is
+ * touched.  lqp_boxqp_forward_certify_workspace_bytes is the size with both certificates on: the forward's layout, unchanged,
+ * and behind it two snapshots of 4 n + m values and four words each per problem (with eps_dual_inf = 0 the size and the layout
+ * of lqp_boxqp_forward_detect are enough, and are what is used).  The rho = 0 one-shot ignores both thresholds.              */
+size_t lqp_boxqp_forward_certify_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_certify(void* stream, int dtype, int B, int n, int m,
+                              const void* Q, const void* p, const void* A, const void* b,
+                              const void* lb, const void* ub,
+                              const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                              void* x, void* z, void* u, void* lams, void* nus, void* rho_out,
+                              lqp_boxqp_stats* stats,
+                              void* workspace, size_t workspace_bytes, double eps_prim_inf, double eps_dual_inf);
 /* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
  * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
- * optimal, 2 primal infeasible -- B int32 on the DEVICE.  Enqueued on `stream`, nothing is waited for.                       */
+ * optimal, 2 primal infeasible, 3 dual infeasible (lqp_boxqp_forward_certify) -- B int32 on the DEVICE.  Enqueued on `stream`,
+ * nothing is waited for.                                                                                                     */
 int lqp_boxqp_problem_status(void* stream, int dtype, int B, int n, int m,
                              const void* workspace, size_t workspace_bytes, int32_t* status_out);
 

@@ -73,6 +73,10 @@ SYMBOLS = {
     "lqp_boxqp_forward_detect": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
                                          ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P,
                                          ctypes.POINTER(BoxQPStats), _P, c_size_t, c_double]),
+    "lqp_boxqp_forward_certify_workspace_bytes": (c_size_t, [c_int] * 4),     # (added within ABI 17)
+    "lqp_boxqp_forward_certify": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
+                                          ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P,
+                                          ctypes.POINTER(BoxQPStats), _P, c_size_t, c_double, c_double]),
     "lqp_boxqp_problem_status": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "lqp_boxqp_forward_finish": (c_int, [_P, c_int, c_int, c_int, _P, ctypes.POINTER(BoxQPStats)]),
     "lqp_boxqp_forward_layout": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 4),
@@ -251,7 +255,7 @@ def stream_ptr(device):
 # ---- deferred error reporting for calls that did not synchronise with the host -----------------
 class _Pending:
     """status / LU-info words of an un-synchronised call, copied to pinned memory on the call's stream"""
-    __slots__ = ("what", "event", "status", "info", "bounds_check", "keep", "flags", "raise_infeasible", "ignore")
+    __slots__ = ("what", "event", "status", "info", "bounds_check", "keep", "flags", "raise_infeasible", "raise_unbounded", "ignore")
 
     def __init__(self, what, event, status, info, bounds_check=None):
         self.what, self.event, self.status, self.info, self.bounds_check = what, event, status, info, bounds_check
@@ -307,7 +311,15 @@ RP_LB, RP_UB, RP_TIMEOUT, RP_NOTSPD = 1, 2, 4, 8
 RP_INFEAS = 1 << 16          # the problem was flagged primal infeasible (control['infeasible'], lqp_boxqp_forward_detect)
 
 
-class InfeasibleQPError(RuntimeError):
+RP_UNBOUNDED = 1 << 17       # the problem was flagged dual infeasible (control['unbounded'], lqp_boxqp_forward_certify)
+
+
+class CertifiedQPError(RuntimeError):
+    """a certificate of the layer's forward says that problems of the batch have no solution: the base of InfeasibleQPError and
+    UnboundedQPError.  ``indices``: their batch indices, a sorted list."""
+
+
+class InfeasibleQPError(CertifiedQPError):
     """control['infeasible'] = 'raise': the layer's forward flagged problems primal infeasible -- {A x = b} and [lb, ub] do not meet.
     ``indices``: their batch indices, a sorted list."""
 
@@ -317,18 +329,30 @@ class InfeasibleQPError(RuntimeError):
                          "cannot be met inside the box (control['infeasible'] = 'flag' returns their status instead of raising)")
 
 
+class UnboundedQPError(CertifiedQPError):
+    """control['unbounded'] = 'raise': the layer's forward flagged problems dual infeasible -- the objective is unbounded below on
+    {A x = b, lb <= x <= ub}.  ``indices``: their batch indices, a sorted list."""
+
+    def __init__(self, what, indices):
+        self.indices = sorted(int(i) for i in indices)
+        super().__init__(f"lqp_py_amd.{what}: dual infeasible (unbounded) problem(s) at batch index {self.indices}: the objective "
+                         "falls without bound along a direction the box and the equality constraints leave open "
+                         "(control['unbounded'] = 'flag' returns their status instead of raising)")
+
+
 def host_report(words):
     """Pinned int32 buffer the kernels of an un-synchronised call report into (no device-to-host copy: the forward's / the
     backward's last kernel stores the words straight into host memory).  Word 0 starts as -1 = "nothing arrived"."""
     return _pinned(words)        # (the library sets every word to -1 before its first launch)
 
 
-def defer_check(what, device, report, B, forward, bounds_check=None, raise_infeasible=False, ignore=None):
+def defer_check(what, device, report, B, forward, bounds_check=None, raise_infeasible=False, ignore=None, raise_unbounded=False):
     """Queue the report of an un-synchronised call: `report` is the pinned buffer given to the library as host_report
     (forward: 16 status words | B info words | B flag words; backward: B info words).
     bounds_check = (assumed, control, mutate, remember): the call was enqueued ASSUMING that the batch holds some /
     no finite bound; status words 12 / 13 hold what the setup kernel found.
-    raise_infeasible: bit 16 of a problem's flag word (flagged primal infeasible) raises InfeasibleQPError.  ignore: a (B,) bool
+    raise_infeasible: bit 16 of a problem's flag word (flagged primal infeasible) raises InfeasibleQPError; raise_unbounded: bit 17
+    (flagged dual infeasible) raises UnboundedQPError, behind the primal one.  ignore: a (B,) bool
     device tensor -- info words of these problems are not errors (the backward of a batch that holds flagged problems)."""
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream(device))
@@ -337,7 +361,7 @@ def defer_check(what, device, report, B, forward, bounds_check=None, raise_infea
                      report[ST_WORDS:ST_WORDS + B] if forward else report[:B], bounds_check)
         p.keep = (report,)
         p.flags = report[ST_WORDS + B:ST_WORDS + 2 * B] if forward else None
-        p.raise_infeasible, p.ignore = bool(raise_infeasible), ignore
+        p.raise_infeasible, p.raise_unbounded, p.ignore = bool(raise_infeasible), bool(raise_unbounded), ignore
         _pending.append(p)
         backlog = len(_pending)
     if backlog > 64:
@@ -403,6 +427,8 @@ def poll_errors(block=False):
             raise RuntimeError(f"lqp_py_amd.{p.what}: in-kernel grid barrier timed out")
         if p.raise_infeasible and (flags & RP_INFEAS):
             raise InfeasibleQPError(p.what, (flags_each & RP_INFEAS).nonzero()[0].tolist())
+        if p.raise_unbounded and (flags & RP_UNBOUNDED):
+            raise UnboundedQPError(p.what, (flags_each & RP_UNBOUNDED).nonzero()[0].tolist())
 
 
 _ws_cache = {}

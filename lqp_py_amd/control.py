@@ -24,6 +24,12 @@ stopping check of a problem; it needs ``stop='each'`` and refuses
 (2), and their gradient rows are zero.  ``torch_solve_box_qp`` never raises
 for it: its dict holds ``"status"`` whenever ``stop='each'``.
 ``eps_prim_inf`` (default 1e-4, inside (0, 1)) is the certificate's threshold.
+
+``unbounded`` (absent or None: off | 'raise' | 'flag') turns on dual
+infeasibility detection -- the objective is unbounded below on the feasible
+set -- the same way, independent of ``infeasible`` (either key or both):
+``lqp_py_amd.UnboundedQPError`` under 'raise', status 3 and zero gradient rows
+under 'flag'.  ``eps_dual_inf`` (default 1e-4, inside (0, 1)) is its threshold.
 """
 
 

@@ -536,6 +536,7 @@ template <typename T> struct FwdLayout {
     int* pstat_area;                // [B][PS_WORDS]: per-problem stopping (FwdParams::pstat points here when ctrl.reserved2 bit 3 asks for it)
     void* snap_area;                // [B][snap_stride]: the infeasibility certificate's snapshots, BEHIND `bytes` (lqp_boxqp_forward_detect alone)
     size_t detect_bytes;            // ... and the size that holds them
+    size_t certify_bytes;           // ... and with the dual certificate's x and Qs x in every slot (lqp_boxqp_forward_certify; the same start)
 };
 // the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
 // by ADDRESS: an entry goes when another forward runs on the address; memory that was freed and handed out again without a forward in
@@ -589,6 +590,9 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     c.off = L.bytes;                // (nothing in front of it moves, and lqp_boxqp_forward_workspace_bytes says what it said)
     L.snap_area = c.take<T>((size_t)B * snap_stride(n, m));
     L.detect_bytes = c.off + kAlign;
+    c.off = L.bytes;
+    c.take<T>((size_t)B * snap_stride(n, m, true));
+    L.certify_bytes = c.off + kAlign;
     return L;
 }
 
@@ -820,9 +824,11 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     plan.loop_nt = hot512 ? 512 : 1024;
     plan.loop_fn = k_admm_loop<T, false, false, 1024>;
     plan.tail_fn = k_admm_loop<T, false, true, 1024>;        // same code, own name: continuation launches
+    const bool dual = each && P.snap != nullptr && P.eps_dinf > 0;      // (control['unbounded']: ... and the dual certificate beside it)
     const bool detect = each && P.snap != nullptr;      // (control['infeasible']: the EACH instances with the certificate in their check)
     if (each) { plan.loop_fn = k_admm_loop_each<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, false, true, 1024, false>; }
     if (detect) { plan.loop_fn = k_admm_loop_each_detect<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each_detect<T, false, true, 1024, false>; }
+    if (dual) { plan.loop_fn = k_admm_loop_each_certify<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each_certify<T, false, true, 1024, false>; }
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
     //  separate gated kernels, and the continuation kernel's LDS does not have to hold an LU panel)
@@ -833,6 +839,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         if (resident) { plan.loop_fn = k_admm_loop<T, true, false, 1024>; plan.tail_fn = k_admm_loop<T, true, true, 1024>; }
         if (resident && each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, false>; }
         if (resident && detect) { plan.loop_fn = k_admm_loop_each_detect<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each_detect<T, true, true, 1024, false>; }
+        if (resident && dual) { plan.loop_fn = k_admm_loop_each_certify<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each_certify<T, true, true, 1024, false>; }
         if (hot512) plan.loop_fn = k_admm_loop<T, true, false, 512>;
         if (spd) {
             P.sym_rl = sym_resident_lds_blocks(n, m, P.Ks);
@@ -843,6 +850,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             plan.tail_fn = k_admm_loop<T, true, true, 1024, true>;
             if (each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, true>; }
             if (detect) { plan.loop_fn = k_admm_loop_each_detect<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each_detect<T, true, true, 1024, true>; }
+            if (dual) { plan.loop_fn = k_admm_loop_each_certify<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each_certify<T, true, true, 1024, true>; }
             // optional 512-thread first launch (8 elements per thread, 12 register-resident blocks).  Measured at
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
@@ -953,7 +961,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
         if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
             const int small_lds = small_loop_lds_bytes(m);
-            if (detect ? fits(d, k_admm_loop_small_each_detect<>, 256, small_lds, B) : each ? fits(d, k_admm_loop_small_each<>, 256, small_lds, B) : fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
+            if (dual ? fits(d, k_admm_loop_small_each_certify<>, 256, small_lds, B) : detect ? fits(d, k_admm_loop_small_each_detect<>, 256, small_lds, B) : each ? fits(d, k_admm_loop_small_each<>, 256, small_lds, B) : fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
         }
         // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
         // (ctrl.reserved2 bit 0: the caller will read the corrected H from the workspace afterwards -- lqp_boxqp_unroll_backward --
@@ -1104,7 +1112,8 @@ void launch_hot(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, c
             hipLaunchKernelGGL(plan.split_fn, dim3((absent & 1) ? B : shared_grid(B, plan.kind_wg)), dim3(plan.split_nt), plan.split_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_SMALL:
-            if (plan.each && P.snap) hipLaunchKernelGGL(k_admm_loop_small_each_detect<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            if (plan.each && P.snap && P.eps_dinf > 0) hipLaunchKernelGGL(k_admm_loop_small_each_certify<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            else if (plan.each && P.snap) hipLaunchKernelGGL(k_admm_loop_small_each_detect<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             else if (plan.each) hipLaunchKernelGGL(k_admm_loop_small_each<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             else hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             return;
@@ -1430,9 +1439,11 @@ template <typename T>
 int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
-                 int retry = 0, const double eps_prim_inf = 0.0) {      // (eps_prim_inf > 0: lqp_boxqp_forward_detect)
+                 int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0) {
+    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    if (ws_bytes < (eps_prim_inf > 0.0 ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
+    const bool certify = eps_prim_inf > 0.0 || eps_dual_inf > 0.0;
+    if (ws_bytes < (eps_dual_inf > 0.0 ? L.certify_bytes : certify ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
@@ -1445,7 +1456,10 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         if (ctl->reserved2 & 8) {
             if (ctl->check_hook) return LQP_ERR_INVALID;
             P.pstat = L.pstat_area;
-            if (eps_prim_inf > 0.0) { P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m); P.eps_pinf = (T)eps_prim_inf; }
+            if (certify) {
+                P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m, eps_dual_inf > 0.0);
+                P.eps_pinf = (T)eps_prim_inf; P.eps_dinf = (T)eps_dual_inf;
+            }
         }
         each_ws_note(ws, P.pstat != nullptr);
         P.host_report = (int*)ctl->host_report;
@@ -2189,11 +2203,11 @@ size_t lqp_boxqp_forward_detect_workspace_bytes(int dtype, int B, int n, int m) 
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).detect_bytes; });
 }
 
-// lqp_boxqp_forward (eps_prim_inf = 0: no detection) and lqp_boxqp_forward_detect
+// lqp_boxqp_forward (both thresholds 0: no detection), lqp_boxqp_forward_detect (eps_dual_inf = 0) and lqp_boxqp_forward_certify
 static int forward_entry(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
                          const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
-                         void* workspace, size_t workspace_bytes, const double eps_prim_inf) {
+                         void* workspace, size_t workspace_bytes, const double eps_prim_inf, const double eps_dual_inf) {
     if (bad_dims(dtype, B, n, m) || !Q || !p || !lb || !ub || !ctrl || !x || !z || !u || !lams || !rho_out || !workspace)
         return LQP_ERR_INVALID;
     if (m > 0 && (!A || !b || !nus)) return LQP_ERR_INVALID;
@@ -2208,7 +2222,7 @@ static int forward_entry(void* stream, int dtype, int B, int n, int m, const voi
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)
     return by_dtype(dtype, [&](auto t) {
-        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf);
+        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf);
     });
 }
 
@@ -2217,7 +2231,7 @@ int lqp_boxqp_forward(void* stream, int dtype, int B, int n, int m, const void* 
                       void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
                       void* workspace, size_t workspace_bytes) {
     return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
-                         workspace_bytes, 0.0);
+                         workspace_bytes, 0.0, 0.0);
 }
 
 int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
@@ -2229,7 +2243,25 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const
     if (!(eps_prim_inf > 0.0 && eps_prim_inf < 1.0)) return LQP_ERR_INVALID;
     if (!ctrl || !(ctrl->reserved2 & 8) || (ctrl->reserved2 & 1) || ctrl->check_hook) return LQP_ERR_INVALID;
     return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
-                         workspace_bytes, eps_prim_inf);
+                         workspace_bytes, eps_prim_inf, 0.0);
+}
+
+size_t lqp_boxqp_forward_certify_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).certify_bytes; });
+}
+
+int lqp_boxqp_forward_certify(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                              const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                              void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
+                              void* workspace, size_t workspace_bytes, double eps_prim_inf, double eps_dual_inf) {
+    // refused before anything is touched, as lqp_boxqp_forward_detect does: a threshold that is neither 0 (off) nor inside (0, 1)
+    // (NaN fails every comparison), both off, no per-problem stop, a check hook, the factor kept for the unroll sweep
+    const auto ok = [](double e) { return e == 0.0 || (e > 0.0 && e < 1.0); };
+    if (!ok(eps_prim_inf) || !ok(eps_dual_inf) || (eps_prim_inf == 0.0 && eps_dual_inf == 0.0)) return LQP_ERR_INVALID;
+    if (!ctrl || !(ctrl->reserved2 & 8) || (ctrl->reserved2 & 1) || ctrl->check_hook) return LQP_ERR_INVALID;
+    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
+                         workspace_bytes, eps_prim_inf, eps_dual_inf);
 }
 
 int lqp_boxqp_forward_finish(void* stream, int B, int max_iters, int check_solved, const void* host_report,

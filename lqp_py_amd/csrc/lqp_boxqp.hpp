@@ -27,7 +27,8 @@ enum { PS_DONE = 0, PS_FINAL = 1, PS_RESUME = 2, PS_NFACTOR = 3, PS_WORDS = 4 };
 // host report (lqp_boxqp_ctrl.host_report): [ST_WORDS status words as workgroup 0 of the forward's last kernel sees them |
 // B info words | B flag words], written straight into pinned host memory by that kernel
 enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
-       RP_INFEAS = 1 << 16 };     // control['infeasible']: the problem was flagged primal infeasible (each_stop)
+       RP_INFEAS = 1 << 16,       // control['infeasible']: the problem was flagged primal infeasible (each_stop)
+       RP_UNBOUNDED = 1 << 17 };  // control['unbounded']: the problem was flagged dual infeasible (each_stop)
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -112,15 +113,17 @@ template <typename T> struct FwdParams {
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
     T* snap;                 // B * snap_stride: control['infeasible'] (stop = 'each' only) -- the certificate's snapshots, or null = no detection
     size_t snap_stride;
-    T eps_pinf;              // control['eps_prim_inf']
+    T eps_pinf;              // control['eps_prim_inf']; 0: the primal certificate is off (lqp_boxqp_forward_certify with the dual one alone)
+    T eps_dinf;              // control['eps_dual_inf']; 0: no dual certificate (control['unbounded'] absent) -- the slots then end behind nu
 };
 // control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
 // number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split_each:
 // bit-identical iterates, at most one hand-off apart) write the same values and never a slot somebody still reads.
-// A slot: [rho it was taken at | mark = iteration + 1 (0: none, k_snap_init) | - | - | y (n) | g (n) | nu (m)]
+// A slot: [rho it was taken at | mark = iteration + 1 (0: none, k_snap_init) | - | - | y (n) | g (n) | nu (m)], and behind nu, with the dual
+// certificate alone (control['unbounded'], `dual`): [x (n) | qx (n)], qx = Qs x -- see dinf_elem
 enum { SN_RHO = 0, SN_MARK = 1, SN_HEAD = 4 };
-__host__ __device__ inline size_t snap_slot_len(int n, int m) { return (size_t)round_up(SN_HEAD + 2 * n + m, 4); }
-__host__ __device__ inline size_t snap_stride(int n, int m) { return 2 * snap_slot_len(n, m); }
+__host__ __device__ inline size_t snap_slot_len(int n, int m, bool dual = false) { return (size_t)round_up(SN_HEAD + 2 * n + m + (dual ? 2 * n : 0), 4); }
+__host__ __device__ inline size_t snap_stride(int n, int m, bool dual = false) { return 2 * snap_slot_len(n, m, dual); }
 
 // vector block of problem b: [ps | lbs | ubs | D | z | u | x | As (m*n) | bs | E | nu | cv | Tm (m*n) | s0]
 // (cv, Tm, s0: constant term c, T = G S^-1 and S^-1 b of the symmetric-inverse path, lqp_spd.hpp)
@@ -1479,13 +1482,14 @@ __device__ __forceinline__ bool loop_all_optimal(const FwdParams<T>& P, unsigned
 // largest; the count of stopped problems goes behind the RETURNED maximum, and whoever makes it B has therefore seen every maximum
 // land before it raises ST_DONE
 // why = 1: optimal; 2: flagged primal infeasible (control['infeasible']) -- also bit RP_INFEAS of the problem's flag word, which the
-// forward's last kernel reports as it stands
+// forward's last kernel reports as it stands; 3: flagged dual infeasible (control['unbounded']), bit RP_UNBOUNDED
 template <typename T>
 __device__ __forceinline__ void each_stop(const FwdParams<T>& P, const int b, const int it, const int why = 1) {
     int* ps_ = P.pstat + (size_t)b * PS_WORDS;
     ps_[PS_FINAL] = it;
     ps_[PS_DONE] = why;
     if (why == 2) P.bflags[b] |= RP_INFEAS;
+    if (why == 3) P.bflags[b] |= RP_UNBOUNDED;
     const int r1 = atomicMax(P.status + ST_FINAL_ITER, it);
     asm volatile("s_waitcnt vmcnt(0)" :: "v"(r1) : "memory");
     const int nd = __hip_atomic_fetch_add(P.status + ST_NDONE, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1500,7 +1504,7 @@ __device__ __forceinline__ void each_stop(const FwdParams<T>& P, const int b, co
 // of this problem changes y's scale: the check behind it only refreshes).  Composed like the other steps: infeas_view (which slots,
 // valid?), infeas_elem per element the caller owns, infeas_nu per equality row, infeas_decide on the four reduced numbers
 // {N, |dg|_inf, largest |dy_i| on an infinite bound, the sum}, infeas_mark by one thread.  All of it on check iterations only.
-template <typename T> struct InfeasView { const T* prev; T* next; int n; bool valid; };
+template <typename T> struct InfeasView { const T* prev; T* next; int n; bool valid; int xo; };      // xo: where a slot's x lies, 0 = no dual certificate
 template <typename T>
 __device__ __forceinline__ InfeasView<T> infeas_view(const FwdParams<T>& P, const int b, const int it, const T rho) {
     T* base = P.snap + (size_t)b * P.snap_stride;
@@ -1508,7 +1512,7 @@ __device__ __forceinline__ InfeasView<T> infeas_view(const FwdParams<T>& P, cons
     const int c = it / P.check_solved;
     const T* prev = base + (size_t)((c + 1) & 1) * len;
     const bool valid = it >= P.check_solved && prev[SN_MARK] == T(it - P.check_solved + 1) && prev[SN_RHO] == rho;
-    return {prev, base + (size_t)(c & 1) * len, P.n, valid};
+    return {prev, base + (size_t)(c & 1) * len, P.n, valid, P.eps_dinf > T(0) ? SN_HEAD + 2 * P.n + P.m : 0};
 }
 template <typename T>
 __device__ __forceinline__ void infeas_elem(T (&ia)[4], const InfeasView<T>& S, const int i, const T y, const T g, const T lb,
@@ -1542,23 +1546,63 @@ __device__ __forceinline__ void infeas_mark(const InfeasView<T>& S, const int it
 }
 template <typename T>
 __device__ __forceinline__ bool infeas_decide(const FwdParams<T>& P, const InfeasView<T>& S, const T (&iv)[4]) {
-    if (!S.valid) return false;
+    if (!S.valid || !(P.eps_pinf > T(0))) return false;
     const T N = iv[0];
     if (!(N > T(0))) return false;
     if (iv[2] > P.eps_pinf * N) return false;                 // (c2 = +inf)
     return iv[1] / N <= P.eps_pinf && iv[3] / N <= -P.eps_pinf;
 }
-// {max, max, max, sum} over the workgroup (NWV waves; red: NWV * 8 + 8 words, as wg_max_n), the same numbers in every thread
+// ---- control['unbounded'] (P.eps_dinf > 0; S.xo != 0): the dual infeasibility certificate at the same check, on the same snapshot ----
+// dx = x - x_prev, dq = Qs x - Qs x_prev (qx as the check forms it, from the right-hand side); N = |dx|_inf, e1 = |dq|_inf / N,
+// e2 = ps^T dx / N, e3 = max_i([lbs_i finite] (-dx_i), [ubs_i finite] dx_i, 0) / N.  Dual infeasible iff N > 0, e1 <= eps, e2 <= -eps and
+// e3 <= eps: dx has Qs dx = 0 and ps^T dx < 0 and lies in the recession cone of the box.  As dx is not tested: the x-update solves the
+// equality-constrained system, As x = bs at every iteration.  da: {N, |dq|_inf, cone violation, ps^T dx} -- {max, max, max,
+// sum} like the primal four.  Without the dual certificate neither array is loaded or stored.
+template <typename T>
+__device__ __forceinline__ void dinf_elem(T (&da)[4], const InfeasView<T>& S, const int i, const T x, const T qx, const T psi,
+                                          const T lb, const T ub) {
+    if (S.xo) {
+        const T px = S.prev[S.xo + i], pq = S.prev[S.xo + S.n + i];
+        S.next[S.xo + i] = x;
+        S.next[S.xo + S.n + i] = qx;
+        if (S.valid) {
+            const T dx = x - px;
+            da[0] = tmax(da[0], tabs(dx));
+            da[1] = tmax(da[1], tabs(qx - pq));
+            if (tabs(lb) <= std::numeric_limits<T>::max()) da[2] = tmax(da[2], -dx);
+            if (tabs(ub) <= std::numeric_limits<T>::max()) da[2] = tmax(da[2], dx);
+            da[3] += psi * dx;
+        }
+    }
+}
+template <typename T>
+__device__ __forceinline__ bool dinf_decide(const FwdParams<T>& P, const InfeasView<T>& S, const T (&dv)[4]) {
+    if (!S.valid || !S.xo) return false;
+    const T N = dv[0];
+    if (!(N > T(0))) return false;
+    return dv[1] / N <= P.eps_dinf && dv[3] / N <= -P.eps_dinf && dv[2] / N <= P.eps_dinf;
+}
+// {max, max, max, sum} over the workgroup (NWV waves; red: NWV * 8 + 8 words, as wg_max_n), the same numbers in every thread; `dual`
+// (uniform): the dual certificate's four ride in the same pair of barriers, words 4 .. 7 of a wave's eight
 template <typename T, int NWV>
-__device__ __forceinline__ void infeas_reduce(T (&ia)[4], T* red) {
+__device__ __forceinline__ void infeas_reduce(T (&ia)[4], T (&da)[4], const bool dual, T* red) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < 3; ++q) ia[q] = wave_max(ia[q]);
     ia[3] = wave_sum(ia[3]);
+    if (dual) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) da[q] = wave_max(da[q]);
+        da[3] = wave_sum(da[3]);
+    }
     __syncthreads();
     if (lane == 0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) red[w * 8 + q] = ia[q];
+        if (dual) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) red[w * 8 + 4 + q] = da[q];
+        }
     }
     __syncthreads();
 #pragma unroll
@@ -1568,16 +1612,28 @@ __device__ __forceinline__ void infeas_reduce(T (&ia)[4], T* red) {
         for (int ww = 1; ww < NWV; ++ww) r = q < 3 ? tmax(r, red[ww * 8 + q]) : r + red[ww * 8 + q];
         ia[q] = r;
     }
+    if (dual) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            T r = red[4 + q];
+#pragma unroll 1
+            for (int ww = 1; ww < NWV; ++ww) r = q < 3 ? tmax(r, red[ww * 8 + 4 + q]) : r + red[ww * 8 + 4 + q];
+            da[q] = r;
+        }
+    }
 }
 // the rest of the step behind the element pass (every thread of the workgroup, uniform): equality rows, reduction, decision, mark.
-// nus / bs: the duals of this check and the scaled right-hand side, wherever the caller holds them
+// nus / bs: the duals of this check and the scaled right-hand side, wherever the caller holds them.  -> 0 neither, 2 primal infeasible
+// (tested first), 3 dual infeasible: each_stop's `why`
 template <typename T, int NT>
-__device__ __forceinline__ bool infeas_finish(const FwdParams<T>& P, const InfeasView<T>& S, T (&ia)[4], const T* nus,
-                                              const T* bs, const int it, const T rho, T* red) {
+// dual (uniform; a constant in the DETECT / CERTIFY instances, S.xo != 0 in the split loop): the dual certificate's four numbers too
+__device__ __forceinline__ int infeas_finish(const FwdParams<T>& P, const InfeasView<T>& S, T (&ia)[4], T (&da)[4], const bool dual,
+                                             const T* nus, const T* bs, const int it, const T rho, T* red) {
     for (int r = threadIdx.x; r < P.m; r += NT) infeas_nu(ia, S, r, nus[r], bs[r]);
-    infeas_reduce<T, NT / 64>(ia, red);
+    infeas_reduce<T, NT / 64>(ia, da, dual, red);
     if (threadIdx.x == 0) infeas_mark(S, it, rho);
-    return infeas_decide(P, S, ia);
+    if (infeas_decide(P, S, ia)) return 2;
+    return dual && dinf_decide(P, S, da) ? 3 : 0;
 }
 // ---------------------------------------------------------------------------
 // The ADMM loop (:235-313).  RES: resident head of the factor stream (registers + LDS); SYM: symmetric-inverse
@@ -1600,7 +1656,7 @@ __device__ __forceinline__ bool infeas_finish(const FwdParams<T>& P, const Infea
 // stops at the first check at which IT is optimal (its workgroup stores the iterate, marks pstat[b] and returns), it adapts rho at
 // an event iff its own `wants && trig` of the last check say so, and nothing crosses workgroups: no grid_wait, no arrival word,
 // no decision from the counters.  A launch begins by reading pstat[b].done and leaves at once when it is set.
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false, bool DETECT = false>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem);
 // does the adaptive-rho event at iteration seg0 change this problem's rho?  The reference's decision over the whole batch, from the
@@ -1649,7 +1705,9 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
 }
 // DETECT (EACH only; control['infeasible']): the certificate at every check (infeas_view ...), instances of their own: inside the one body
 // its registers cost the plain EACH kernels 3 % of their time
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false, bool DETECT = false>
+// DUAL (DETECT only; control['unbounded']): the dual certificate too, instances of their own again (k_admm_loop_each_certify): under a
+// run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
+template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
                                                const int prev_slot,      // slot of the last check before it0, -1: none / known not done
@@ -1660,13 +1718,14 @@ __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int 
         // this problem stopped in an earlier launch: its iterate is not touched again
         if (__builtin_amdgcn_readfirstlane(P.pstat[(size_t)blockIdx.x * PS_WORDS + PS_DONE])) return;
     }
-    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH, DETECT>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH, DETECT, DUAL>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH, bool DETECT>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH, bool DETECT, bool DUAL>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
     static_assert(!DETECT || EACH, "the infeasibility certificate is part of a problem's own stopping check");
+    static_assert(!DUAL || DETECT, "the dual certificate shares the primal one's snapshot and reduction");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
     int b = blockIdx.x, part_id = 0;
     if constexpr (NP == 2) { if (!shared_map((int)blockIdx.x, P.B, 2, b, part_id)) return; }
@@ -1838,7 +1897,8 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
 #pragma unroll
         for (int q = 0; q < 6; ++q) mx[q] = T(0);
         T ia[4] = {T(0), T(0), T(0), T(0)};                      // (DETECT: the certificate's terms, see infeas_view)
-        InfeasView<T> isv = {nullptr, nullptr, n, false};
+        T da[4] = {T(0), T(0), T(0), T(0)};                      // (... and the dual certificate's, see dinf_elem)
+        InfeasView<T> isv = {nullptr, nullptr, n, false, 0};
         if constexpr (DETECT) { if (check) isv = infeas_view(P, b, it, rho); }
         // ||Q x / D||_inf of the check (:299) without touching Q: the x-update solved (Qs + rho I) x + As^T nu = w
         // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu.  It only feeds a tolerance SCALE.
@@ -1937,7 +1997,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                         T qx = v[i] - rho * xi;
                         for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + i] * nus_l[q];
                         mx[5] = tmax(mx[5], tabs(qx / di));
-                        if constexpr (DETECT) infeas_elem(ia, isv, i, rho * un, qx + s, lb[i], ub[i]);
+                        if constexpr (DETECT) { infeas_elem(ia, isv, i, rho * un, qx + s, lb[i], ub[i]); if constexpr (DUAL) dinf_elem(da, isv, i, xi, qx, ps[i], lb[i], ub[i]); }
                     }
                     wn = -ps[i] + rho * (zn - un);           // next iteration's right-hand side
                 }
@@ -1983,7 +2043,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     T qx = -ps[i] + rho * (zp - ui) - rho * xi;
                     for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + i] * nul[q];
                     mx[5] = tmax(mx[5], tabs(qx / di));
-                    if constexpr (DETECT) infeas_elem(ia, isv, i, rho * un, qx + s, lb[i], ub[i]);
+                    if constexpr (DETECT) { infeas_elem(ia, isv, i, rho * un, qx + s, lb[i], ub[i]); if constexpr (DUAL) dinf_elem(da, isv, i, xi, qx, ps[i], lb[i], ub[i]); }
                 }
             }
         }
@@ -2016,14 +2076,14 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     if (!solved) atomicAdd(ct + CT_NOTOPT, 1u);
                 }
                 ++slot;
-                bool flagged = false;                        // control['infeasible']: primal infeasible at this check (optimal comes first)
-                if constexpr (DETECT) flagged = infeas_finish<T, NT>(P, isv, ia, SYM ? bs + m : v + n, bs, it, rho, red) && !solved;
+                int flagged = 0;                             // control['infeasible'] / ['unbounded']: 2 primal, 3 dual infeasible at this check (optimal comes first)
+                if constexpr (DETECT) { flagged = infeas_finish<T, NT>(P, isv, ia, da, DUAL, SYM ? bs + m : v + n, bs, it, rho, red); if (solved) flagged = 0; }
                 if (solved || flagged) {
                     // leave with the state of iteration `it`: the iterate first, then the words that say so
                     __syncthreads();
                     store_state();
                     if (tid == 0) {
-                        each_stop(P, b, it, flagged ? 2 : 1);
+                        each_stop(P, b, it, flagged ? flagged : 1);
                     }
                     return;
                 }
@@ -2127,6 +2187,13 @@ __global__ __launch_bounds__(NT) void k_admm_loop_each_detect(const FwdParams<T>
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_body<T, RES, TAIL, NT, SYM, 1, true, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
+// ... and with the dual certificate beside it (control['unbounded']; DUAL)
+template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
+__global__ __launch_bounds__(NT) void k_admm_loop_each_certify(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
+                                                               const int prev_slot, const int persistent) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_body<T, RES, TAIL, NT, SYM, 1, true, true, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+}
 
 // all problems optimal at the check held in `slot` (iteration `it_check`)?  -> DONE
 template <int LQP_ANY = 0>      // (a template only so that the split build can place its one instance: tools/gen_split_build.py)
@@ -2209,13 +2276,13 @@ __global__ void k_copy_iters(const int* __restrict__ pstat, int* __restrict__ ou
     if (b < B) out[b] = pstat[(size_t)b * PS_WORDS + PS_FINAL];
 }
 // how every problem of a control['stop'] = 'each' solve ended (lqp_boxqp_problem_status): 0 optimal, 1 out of iterations, 2 flagged
-// primal infeasible
+// primal infeasible, 3 flagged dual infeasible
 template <int LQP_ANY = 0>
 __global__ void k_copy_pstatus(const int* __restrict__ pstat, int* __restrict__ out, const int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) {
         const int d = pstat[(size_t)b * PS_WORDS + PS_DONE];
-        out[b] = d == 1 ? 0 : (d == 2 ? 2 : 1);
+        out[b] = d == 1 ? 0 : (d == 2 || d == 3 ? d : 1);
     }
 }
 // control['infeasible']: no problem has a snapshot yet -- the marks of both slots (infeas_view), at the head of every attempt

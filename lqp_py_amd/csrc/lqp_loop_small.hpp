@@ -18,7 +18,8 @@ __host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 +
 // EACH (control['stop'] = 'each'): the problem's own verdict ends its workgroup; no arrival word, no grid_wait
 // DETECT (EACH only; control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
 // check iterations, and the certificate's registers in it cost the plain EACH kernel 12 % of its time
-template <bool EACH, bool DETECT = false>
+// DUAL (DETECT only; control['unbounded']): the dual certificate too, k_admm_loop_small_each_certify
+template <bool EACH, bool DETECT = false, bool DUAL = false>
 __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                      char* smem) {
     typedef float T;
@@ -31,7 +32,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
     }
     if (it0 >= it1) return;
     bool each_done = false;
-    int each_why = 1;                   // (DETECT) 2: the problem stopped because it was flagged primal infeasible
+    int each_why = 1;                   // (DETECT) 2 / 3: the problem stopped because it was flagged primal / dual infeasible
     int final_it = it1 - 1;
     T* const wv = (T*)smem;
     T* const yv = wv + 128;
@@ -107,7 +108,8 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
 #pragma unroll
         for (int q = 0; q < 6; ++q) mx[q] = T(0);
         T ia[4] = {T(0), T(0), T(0), T(0)};                      // (DETECT: the certificate's terms, see infeas_view)
-        InfeasView<T> isv = {nullptr, nullptr, n, false};
+        T da[4] = {T(0), T(0), T(0), T(0)};                      // (... and the dual certificate's, see dinf_elem)
+        InfeasView<T> isv = {nullptr, nullptr, n, false, 0};
         if constexpr (DETECT) { if (check) isv = infeas_view(P, b, it, rho); }
         if (live) {
             const T wi = wv[e];
@@ -119,7 +121,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
                 T qx = wi - rho * xi;
                 for (int q = 0; q < m; ++q) qx -= V.As[(size_t)q * n + e] * nus_l[q];
                 admm_step_norms<false>(mx, sp, xi, di, rho, qx);
-                if constexpr (DETECT) infeas_elem(ia, isv, e, rho * sp.un, qx + sp.s, lbi, ubi);
+                if constexpr (DETECT) { infeas_elem(ia, isv, e, rho * sp.un, qx + sp.s, lbi, ubi); if constexpr (DUAL) dinf_elem(da, isv, e, xi, qx, psi, lbi, ubi); }
             }
         }
         __syncthreads();                                         // (everybody has read w and y)
@@ -136,8 +138,8 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
                 }
                 ++slot;
                 if constexpr (DETECT) {
-                    const bool flagged = infeas_finish<T, NT>(P, isv, ia, nus_l, V.bs, it, rho, red) && !ck.solved;
-                    if (flagged) { each_done = true; each_why = 2; final_it = it; break; }
+                    const int flagged = infeas_finish<T, NT>(P, isv, ia, da, DUAL, nus_l, V.bs, it, rho, red);
+                    if (flagged && !ck.solved) { each_done = true; each_why = flagged; final_it = it; break; }
                 }
                 if (ck.solved) { each_done = true; final_it = it; break; }      // (uniform: every thread holds the reduced norms)
             } else {
@@ -185,6 +187,12 @@ __global__ __launch_bounds__(256) void k_admm_loop_small_each_detect(const FwdPa
                                                                      const int ctr_base) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_small_body<true, true>(P, it0, it1, ctr_base, smem);
+}
+template <int LQP_ANY = 0>
+__global__ __launch_bounds__(256) void k_admm_loop_small_each_certify(const FwdParams<float> P, const int it0, const int it1,
+                                                                      const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_small_body<true, true, true>(P, it0, it1, ctr_base, smem);
 }
 
 }  // namespace lqp

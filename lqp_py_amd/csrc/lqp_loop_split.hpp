@@ -388,7 +388,8 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
 #pragma unroll
         for (int q = 0; q < 6; ++q) mx[q] = T(0);
         T ia[4] = {T(0), T(0), T(0), T(0)};                   // (EACH, control['infeasible']: the certificate's terms, see infeas_view)
-        InfeasView<T> isv = {nullptr, nullptr, n, false};
+        T da[4] = {T(0), T(0), T(0), T(0)};                   // (... and the dual certificate's, control['unbounded'], see dinf_elem)
+        InfeasView<T> isv = {nullptr, nullptr, n, false, 0};
         if constexpr (COLD && EACH) { if (check && P.snap) isv = infeas_view(P, b, it, rho); }
         if (tid < Nps) {
             const int i = tid;
@@ -405,7 +406,7 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
                         for (int q = 0; q < m; ++q) qx -= Asl[(size_t)q * Nps + i] * nus_l[q];
                         admm_step_norms<false>(mx, sp, xi, D[i], rho, qx);
                         // (every workgroup of the problem stores the same values into the same slot, see snap_stride)
-                        if constexpr (EACH) { if (P.snap) infeas_elem(ia, isv, i, rho * un, qx + sp.s, lb[i], ub[i]); }
+                        if constexpr (EACH) { if (P.snap) { infeas_elem(ia, isv, i, rho * un, qx + sp.s, lb[i], ub[i]); dinf_elem(da, isv, i, xi, qx, ps[i], lb[i], ub[i]); } }
                     }
                 }
             }
@@ -448,7 +449,8 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
                     __syncthreads();
                     int why = flags[4];                       // 1: optimal
                     if (P.snap) {
-                        if (infeas_finish<T, NT>(P, isv, ia, nus_l, bs, it, rho, red) && !why) why = 2;      // flagged primal infeasible
+                        const int flagged = infeas_finish<T, NT>(P, isv, ia, da, isv.xo != 0, nus_l, bs, it, rho, red);      // 2 / 3: primal / dual infeasible
+                        if (!why) why = flagged;
                     }
                     if (why) {
                         // leave with the state of iteration `it`: the iterate first, then the words that say so

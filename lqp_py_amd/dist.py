@@ -27,6 +27,8 @@ pass the same value, like every other setting.
 detection) travel the same way and are allowed only where ``'each'`` is:
 every shard flags its own problems (``'raise'``: ``InfeasibleQPError.indices``
 are indices into the rank's shard), no exchange is needed.
+``control['unbounded']`` / ``control['eps_dual_inf']`` (dual infeasibility
+detection, ``UnboundedQPError``) likewise.
 ``dl_dQ`` is never gathered.
 """
 import torch

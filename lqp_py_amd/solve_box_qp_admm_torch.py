@@ -91,9 +91,15 @@ class SolveBoxQPLayer(torch.autograd.Function):
         sol = _forward_solve(Q, p, A, b, lb, ub, control, bounds=control.get('_global_bounds'), sync=sync,
                              check_hook=control.get('_check_hook'), mutate=True,
                              holder=control.get('_holder') or getattr(_tls, 'holder', None), while_running=while_running,
-                             raise_infeasible=control.get('infeasible') == 'raise')
-        # control['infeasible'] = 'flag': the rows of a flagged problem are zero in every gradient (masked on the device, no host sync)
-        ctx.flagged = (sol['status'] == 2) if control.get('infeasible') == 'flag' and sol.get('status') is not None else None
+                             raise_infeasible=control.get('infeasible') == 'raise', raise_unbounded=control.get('unbounded') == 'raise')
+        # control['infeasible'] / control['unbounded'] = 'flag': the rows of a flagged problem (status 2 / 3) are zero in every gradient
+        # (one mask, made on the device, no host sync)
+        ctx.flagged = None
+        if sol.get('status') is not None:
+            for key, code in (('infeasible', 2), ('unbounded', 3)):
+                if control.get(key) == 'flag':
+                    hit = sol['status'] == code
+                    ctx.flagged = hit if ctx.flagged is None else ctx.flagged | hit
         ctx.rho = sol['rho']
         st_ = sol['_stats']
         ctx.bound_flags = (bool(st_['any_lb']), bool(st_['any_ub'])) if st_['any_lb'] >= 0 else None     # (pipelined: not known)
@@ -210,7 +216,17 @@ def torch_solve_box_qp(Q, p, A, b, lb, ub, control):
     certificate of {A x = b} and [lb, ub] not meeting -- OSQP's test; the rule is in DESIGN.md section 7.  A flagged problem stops
     like an optimal one, x, z, u hold its iterate of that check.  This function never raises for it: with stop='each', detection on
     or off, the dict holds "status", a (B,) int32 device tensor -- 0 optimal, 1 ended at max_iters without being optimal, 2 primal
-    infeasible.  The layer raises lqp_py_amd.InfeasibleQPError ('raise') or zeroes the gradient rows of flagged problems ('flag')."""
+    infeasible, 3 dual infeasible.  The layer raises lqp_py_amd.InfeasibleQPError ('raise') or zeroes the gradient rows of flagged
+    problems ('flag').
+
+    control['unbounded'] (extension; absent or None: off | 'raise' | 'flag') with control['eps_dual_inf'] (default 1e-4, inside
+    (0, 1)): dual infeasibility detection -- the objective is unbounded below on the feasible set (a Q that is only positive
+    semi-definite, a bound that is infinite on one side, p pointing down a null direction of Q that the box and A leave open) --
+    under the same conditions and independent of control['infeasible']: either key alone or both.  At every check of a problem the
+    differences dx, d(Qs x) against the check before (same rho) are tested as OSQP's certificate: Qs dx = 0, ps^T dx < 0, dx inside
+    the recession cone of the box (As dx is not tested: the x-update keeps As x = bs).  Optimal is tested
+    first, then primal, then dual infeasible.  A flagged problem stops like an optimal one with its iterate of that check, "status"
+    says 3; the layer raises lqp_py_amd.UnboundedQPError ('raise') or zeroes its gradient rows ('flag')."""
     check_stop(control)
     if control.get('unroll', False):
         # autograd through the loop (:328-329 returns the bare x); see lqp_py_amd/unrolled.py
@@ -396,9 +412,12 @@ def resolve_control(control, n_x):
     check = g('check_solved', max(round((n_x ** 0.5) / 10) * 10, 1))
     ar_iter = max(round(g('adaptive_rho_iter', 100) / check) * check, 1)
     infeasible, eps_prim_inf = check_infeasible(control)
+    unbounded, eps_dual_inf = check_infeasible(control, 'unbounded', 'eps_dual_inf')
     return dict(
         infeasible=infeasible,                   # extension: None | 'raise' | 'flag' -- primal infeasibility detection (stop='each' only)
         eps_prim_inf=eps_prim_inf,               # ... and its threshold, inside (0, 1)
+        unbounded=unbounded,                     # extension: None | 'raise' | 'flag' -- dual infeasibility detection (stop='each' only)
+        eps_dual_inf=eps_dual_inf,               # ... and its threshold, inside (0, 1)
         max_iters=g('max_iters', 10_000),
         eps_abs=max(g('eps_abs', 1e-3), 1e-12),
         eps_rel=max(g('eps_rel', 1e-3), 1e-12),
@@ -435,34 +454,37 @@ def check_alpha(control):
     return a
 
 
-def check_infeasible(control):
-    """control['infeasible'] and control['eps_prim_inf'] -> (None | 'raise' | 'flag', eps as a float).  Raises at the call, before any
-    launch; the one place that holds this rule (check_stop comes here).  Detection lives in the per-problem stop: the key needs
-    stop='each' and cannot be combined with unroll=True."""
-    mode = control.get('infeasible')
+def check_infeasible(control, key='infeasible', eps_key='eps_prim_inf'):
+    """control['infeasible'] and control['eps_prim_inf'] -- or, the same rule, control['unbounded'] and control['eps_dual_inf'] --
+    -> (None | 'raise' | 'flag', eps as a float).  Raises at the call, before any launch; the one place that holds this rule
+    (check_stop comes here for both pairs).  Detection lives in the per-problem stop: the key needs stop='each' and cannot be combined
+    with unroll=True."""
+    mode = control.get(key)
     if mode is not None and not (isinstance(mode, str) and mode in ('raise', 'flag')):
-        _bad("control['infeasible'] must be None, 'raise' or 'flag'")
-    eps = control.get('eps_prim_inf', 1e-4)
+        _bad(f"control['{key}'] must be None, 'raise' or 'flag'")
+    eps = control.get(eps_key, 1e-4)
     if eps.__class__ is not float:
         if isinstance(eps, bool) or not (isinstance(eps, numbers.Real) or (torch.is_tensor(eps) and eps.numel() == 1)):
-            _bad("control['eps_prim_inf'] must be a number (or a one-element tensor) inside (0, 1)")
+            _bad(f"control['{eps_key}'] must be a number (or a one-element tensor) inside (0, 1)")
         eps = float(eps)
     if not 0.0 < eps < 1.0:                       # (NaN fails both comparisons)
-        _bad("control['eps_prim_inf'] must be inside (0, 1)")
+        _bad(f"control['{eps_key}'] must be inside (0, 1)")
     if mode is not None:
         if control.get('stop', 'all') != 'each':
-            _bad("control['infeasible'] needs control['stop'] = 'each': the certificate is part of a problem's own stopping check")
+            _bad(f"control['{key}'] needs control['stop'] = 'each': the certificate is part of a problem's own stopping check")
         if control.get('unroll', False):
-            _bad("control['infeasible'] cannot be combined with unroll=True: the tape has one length")
+            _bad(f"control['{key}'] cannot be combined with unroll=True: the tape has one length")
     return mode, eps
 
 
 def check_stop(control, check_hook=None):
     """control['stop'] and what it cannot be combined with; -> True for 'each'.  Raises at the call, before any launch.  The one place
     that holds these rules: torch_solve_box_qp, _forward_solve, lqp_py_amd.dist and lqp_py_amd.unrolled all come here (and, through
-    it, to check_alpha and check_infeasible: control['alpha'] and control['infeasible'] are refused at the same places)."""
+    it, to check_alpha and check_infeasible: control['alpha'], control['infeasible'] and control['unbounded'] are refused at the same
+    places)."""
     check_alpha(control)
     check_infeasible(control)
+    check_infeasible(control, 'unbounded', 'eps_dual_inf')
     stop = control.get('stop', 'all')
     if not isinstance(stop, str) or stop not in ('all', 'each'):
         _bad("control['stop'] must be 'all' or 'each'")
@@ -672,11 +694,15 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
     x, addresses, views = _output_block(B, n, m, p.dtype, dev)
     # control['infeasible'] (with stop='each' alone, check_stop): the entry point with the certificate, and its larger workspace -- the
     # forward's layout with the snapshots behind it.  Key absent: the entry point and the size there always were
+    # control['unbounded'], alone or with it: the certifying entry point (either threshold 0 = off) and the workspace whose snapshots
+    # hold x and Qs x too
     detect = each and r['infeasible'] is not None
-    nbytes = _ws_bytes.get((dt, B, n, m, detect))
+    certify = each and r['unbounded'] is not None
+    nbytes = _ws_bytes.get((dt, B, n, m, detect, certify))
     if nbytes is None:
-        size_of = lib.lqp_boxqp_forward_detect_workspace_bytes if detect else lib.lqp_boxqp_forward_workspace_bytes
-        nbytes = _ws_bytes[(dt, B, n, m, detect)] = size_of(dt, B, n, m)
+        size_of = (lib.lqp_boxqp_forward_certify_workspace_bytes if certify else
+                   lib.lqp_boxqp_forward_detect_workspace_bytes if detect else lib.lqp_boxqp_forward_workspace_bytes)
+        nbytes = _ws_bytes[(dt, B, n, m, detect, certify)] = size_of(dt, B, n, m)
     stream = _lib.current_stream_handle(dev)
     ws = private_ws if private_ws is not None else _lib.workspace(dev, nbytes, "fwd", stream)
     hook_c = hook_error = None
@@ -688,12 +714,15 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
             ctypes.byref(ctl), _lib.ptr(rho_tensor), *addresses,
             ctypes.byref(stats), _lib.ptr(ws), ws.numel())
     with _lib.on_device(dev):
-        st = lib.lqp_boxqp_forward_detect(*args, float(r['eps_prim_inf'])) if detect else lib.lqp_boxqp_forward(*args)
+        if certify:
+            st = lib.lqp_boxqp_forward_certify(*args, float(r['eps_prim_inf']) if detect else 0.0, float(r['eps_dual_inf']))
+        else:
+            st = lib.lqp_boxqp_forward_detect(*args, float(r['eps_prim_inf'])) if detect else lib.lqp_boxqp_forward(*args)
     split_wait = st == 0 and stats.mode_used == 4
     z, u, lams, nus, rho_out = views()
     iters = pstatus = None
     if each and st == 0:
-        # the per-problem iteration counts, and how every problem ended (0 optimal, 1 out of iterations, 2 primal infeasible): two copy
+        # the per-problem iteration counts, and how every problem ended (0 optimal, 1 out of iterations, 2 primal, 3 dual infeasible): two copy
         # kernels behind the solve on its stream, into device tensors -- no host wait
         iters = torch.empty((B,), dtype=torch.int32, device=dev)
         pstatus = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -746,7 +775,7 @@ def _solution(out, like, residuals):
     sol = {"x": out.x, "z": out.z, "u": out.u, "lams": out.lams, "nus": out.nus, "rho": rho_ret, "iter": int(stats.iters)}
     if out.iters is not None:            # control['stop'] = 'each': every problem's own count; "iter" is the largest
         sol["iters"] = out.iters
-        sol["status"] = out.pstatus      # (B,) int32: 0 optimal, 1 ended at max_iters, 2 primal infeasible (control['infeasible'])
+        sol["status"] = out.pstatus      # (B,) int32: 0 optimal, 1 ended at max_iters, 2 primal infeasible (control['infeasible']), 3 dual infeasible (control['unbounded'])
     _last_problem_status[(dev.index, out.stream)] = out.pstatus
     if residuals:                        # errors of the last check (the NumPy twin's extra outputs)
         pri, dua = (torch.empty((B,), dtype=like.dtype, device=dev) for _ in range(2))
@@ -760,13 +789,16 @@ def _solution(out, like, residuals):
 
 
 def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residuals=False, check_hook=None, mutate=False,
-                   holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False, raise_infeasible=False):
+                   holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False, raise_infeasible=False,
+                   raise_unbounded=False):
     """bounds: (any_lb, any_ub) when the caller KNOWS them (a shard of a larger batch with host-side flags); None: found
     on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
     nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound).
     Attempt, decide, act on the verdict, in a loop: _forward_attempt runs the library once, _forward_decide holds the rules.
     raise_infeasible (the layer with control['infeasible'] = 'raise'): a problem flagged primal infeasible raises InfeasibleQPError
-    once the whole batch is done -- here when the call waited, where the other late errors surface when it did not."""
+    once the whole batch is done -- here when the call waited, where the other late errors surface when it did not.
+    raise_unbounded (control['unbounded'] = 'raise'): the same for a problem flagged dual infeasible, UnboundedQPError, behind the
+    primal one."""
     check_stop(control, check_hook)
     _lib.require_gpu(Q, p, A, b, lb, ub)
     sync = sync or check_hook is not None             # (the strict global stop is host-driven: one launch per check)
@@ -783,7 +815,8 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
                     _lib.defer_check("SolveBoxQP.forward", dev, out.report, Q.shape[0], True,
                                      bounds_check=None if out.known else (
                                          out.any_bound, owner, mutate, lambda _c, seen: _remember_any_bound(holder, owner, seen)),
-                                     raise_infeasible=raise_infeasible and out.pstatus is not None)
+                                     raise_infeasible=raise_infeasible and out.pstatus is not None,
+                                     raise_unbounded=raise_unbounded and out.pstatus is not None)
                 else:                     # (the library waited after all: nothing left to report late)
                     _lib.report_done(out.report)
         else:
@@ -804,10 +837,12 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
     if out.r['verbose']:
         _print_check_trace(out, dev)
     sol = _solution(out, p, residuals)
-    if raise_infeasible and out.pstatus is not None and out.stats.mode_used != 3:
-        flagged = (out.pstatus == 2).nonzero().flatten().tolist()      # (the call waited for the solve: this read waits for a copy kernel)
-        if flagged:
-            raise _lib.InfeasibleQPError("SolveBoxQP.forward", flagged)
+    if (raise_infeasible or raise_unbounded) and out.pstatus is not None and out.stats.mode_used != 3:
+        ended = out.pstatus.tolist()          # (the call waited for the solve: this read waits for a copy kernel)
+        for wanted, code, error in ((raise_infeasible, 2, _lib.InfeasibleQPError), (raise_unbounded, 3, _lib.UnboundedQPError)):
+            flagged = [i for i, e in enumerate(ended) if e == code]
+            if wanted and flagged:
+                raise error("SolveBoxQP.forward", flagged)
     return sol
 
 
@@ -817,7 +852,8 @@ _last_problem_status = {}
 
 def last_problem_status(device):
     """How every problem of the most recent forward solve on `device`, on the CURRENT stream, ended: a (B,) int32 device tensor --
-    0 optimal, 1 it ended at max_iters without being optimal, 2 flagged primal infeasible (control['infeasible']) -- or None when that
+    0 optimal, 1 it ended at max_iters without being optimal, 2 flagged primal infeasible (control['infeasible']), 3 flagged dual
+    infeasible (control['unbounded']) -- or None when that
     solve did not run with control['stop'] = 'each'.  Stream-ordered like the solution itself: reading it on the host waits for the
     solve.  Valid until the next forward on the same stream, like last_forward_status."""
     device = torch.device(device)

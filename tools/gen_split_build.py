@@ -35,6 +35,8 @@ GROUPS = [
     ("split_b", lambda n: "k_admm_loop_split<" in n),
     ("split_each_b", lambda n: re.search(r"k_admm_loop_split_each<(3|4|8), 512, false, 2>|k_admm_loop_split_each<\d, 512, false, 4>", n)),
     ("split_each_a", lambda n: "k_admm_loop_split_each<" in n),
+    ("loop_each_certify_tail", lambda n: re.search(r"k_admm_loop_each_certify<\w+, \w+, true,", n)),
+    ("loop_each_certify_hot", lambda n: "k_admm_loop_each_certify<" in n),
     ("loop_each_detect_tail", lambda n: re.search(r"k_admm_loop_each_detect<\w+, \w+, true,", n)),
     ("loop_each_detect_hot", lambda n: "k_admm_loop_each_detect<" in n),
     ("loop_each_tail", lambda n: re.search(r"k_admm_loop_each<\w+, \w+, true,", n)),
@@ -94,6 +96,7 @@ EXTRA = [
     "void lqp::k_snap_init<double>(double*, unsigned long, int)",
     "void lqp::k_admm_loop_small_each<0>(lqp::FwdParams<float>, int, int, int)",
     "void lqp::k_admm_loop_small_each_detect<0>(lqp::FwdParams<float>, int, int, int)",
+    "void lqp::k_admm_loop_small_each_certify<0>(lqp::FwdParams<float>, int, int, int)",
     "void lqp::k_debug_chol_solve<2>(float const*, int const*, float const*, float*, int, int, int)",
     "void lqp::k_debug_chol_solve<4>(float const*, int const*, float const*, float*, int, int, int)",
     "void lqp::k_debug_chol_factor<false>(float*, int const*, int*, int, int, int)",
@@ -109,6 +112,11 @@ EXTRA = [
 ] + [
     # ... and the same eight with the infeasibility certificate in their check (control['infeasible'])
     f"void lqp::k_admm_loop_each_detect<{t}, {res}, {tail}, 1024, {sym}>(lqp::FwdParams<{t}>, int, int, int, int, int)"
+    for tail in ("false", "true")
+    for t, res, sym in (("double", "false", "false"), ("float", "false", "false"), ("float", "true", "false"), ("float", "true", "true"))
+] + [
+    # ... and with the dual certificate beside it (control['unbounded'])
+    f"void lqp::k_admm_loop_each_certify<{t}, {res}, {tail}, 1024, {sym}>(lqp::FwdParams<{t}>, int, int, int, int, int)"
     for tail in ("false", "true")
     for t, res, sym in (("double", "false", "false"), ("float", "false", "false"), ("float", "true", "false"), ("float", "true", "true"))
 ]

@@ -1,5 +1,6 @@
-"""What primal infeasibility detection (control['infeasible']) costs on problems that are feasible: the split row's shape (n = 130,
-m = 1) at B = 128 with control['stop'] = 'each', eps 1e-5, the key set against the key absent.
+"""What infeasibility detection costs on problems that are feasible: the split row's shape (n = 130, m = 1) at B = 128 with
+control['stop'] = 'each', eps 1e-5, the keys set against the keys absent.  `--keys`: none | flag (control['infeasible'], the primal
+certificate) | unbounded (control['unbounded'], the dual one) | both.
 
 For each of the two: the iteration count, the time of the loop kernels (the library's per-class device events, synchronous
 forwards) and the forward's time between two device events, `--rounds` times after a warm-up.  One JSON line each; run the script
@@ -7,6 +8,7 @@ several times and compare the difference with the spread one setting shows again
 
     python tools/gpu_infeas.py
     python tools/gpu_infeas.py --keys none --tree /path/to/another/checkout     # key absent on another build: A/B
+    python tools/gpu_infeas.py --keys none unbounded both --n 600               # the dual certificate, alone and with the primal one
 """
 import argparse
 import json
@@ -35,7 +37,7 @@ B, n = args.batch, args.n
 data = [[t.to(dev) for t in create_qp_data(n, B, seed=s)] for s in range(3)]
 
 for key in args.keys:
-    extra = {} if key == "none" else dict(infeasible=key)
+    extra = {"none": {}, "unbounded": dict(unbounded='flag'), "both": dict(infeasible='flag', unbounded='flag')}.get(key, dict(infeasible=key))
     ctl = L.box_qp_control(eps_abs=1e-5, eps_rel=1e-5, verbose=False, stop='each', **extra)
     for i in range(5):
         sol = L.torch_solve_box_qp(*data[i % len(data)], dict(ctl))
@@ -60,6 +62,7 @@ for key in args.keys:
     status = sol.get("status")
     print(json.dumps(dict(tag=args.tag, infeasible=key, B=B, n=n, iters=sol["iter"], loop_kind=st["loop_kind"],
                           loop_workgroups_per_qp=st["loop_workgroups_per_qp"],
-                          flagged=None if status is None else int((status == 2).sum()),
+                          checks=sol["iter"] // int(ctl.get("check_solved") or max(round((n ** 0.5) / 10) * 10, 1)) + 1,
+                          flagged=None if status is None else int((status >= 2).sum()),
                           loop_us=round(pr["admm_loop"][0] / args.reps * 1e3, 2),
                           forward_us=dict(median=round(fwd[len(fwd) // 2], 1), min=round(fwd[0], 1), max=round(fwd[-1], 1)))), flush=True)
