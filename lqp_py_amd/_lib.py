@@ -131,9 +131,9 @@ def build_library(force=False, verbose=False):
 
     Default: the split build -- the host translation unit (csrc/lqp_amd.hip with `extern template` declarations of every
     kernel instance, csrc/split/lqp_extern.inc) and one translation unit per group of kernel instances
-    (csrc/split/lqp_tu_*.hip), compiled in parallel and linked; same headers and flags, hence the same code per kernel
-    as the single-source build (LQP_UNITY_BUILD=1: one hipcc command, ~3.5 minutes of serial code generation).  The
-    lists are generated from a built library's kernel names by tools/gen_split_build.py."""
+    (csrc/split/lqp_tu_*.hip: 27 units, 173 instances), compiled in parallel and linked; same headers and flags, hence
+    the same code per kernel as the single-source build (LQP_UNITY_BUILD=1: one hipcc command, ~3.5 minutes of serial
+    code generation).  The lists are written by tools/gen_split_build.py from the manifest of kernel instances in it."""
     split_dir = os.path.join(CSRC, "split")
     tus = sorted(f for f in os.listdir(split_dir) if f.endswith(".hip")) if os.path.isdir(split_dir) else []
     unity = bool(os.environ.get("LQP_UNITY_BUILD")) or not tus

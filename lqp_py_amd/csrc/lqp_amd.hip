@@ -597,34 +597,55 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
 }
 
 // ---- the tier plan: what one attempt at a forward solve will launch, decided before its first launch ----
-// Ks -> the instance of the resident sweep on NP workgroups per matrix (four: Ks = 7, 8 only) and of the two-workgroup loop
 inline int spd_prep_lds_bytes(const int Ks) { return (2 * 64 * SPD_LS + 2 * LQP_NW + 64 * Ks) * 4; }      // (k_spd_prep)
 typedef void (*SweepFn)(const FwdParams<float>, const int*);
 typedef void (*SplitFn)(const FwdParams<float>, const int, const int, const int);
+// How a solve stops, derived ONCE (loop_stop); every loop family has an instance per kind, and nothing but its selector below chooses one.
+// The batch as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
+// infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']: P.eps_dinf > 0)
+enum LoopStop { STOP_ALL, STOP_EACH, STOP_DETECT, STOP_CERTIFY };
+inline LoopStop loop_stop(const bool each, const bool snapshots, const bool dual) { return !each ? STOP_ALL : !snapshots ? STOP_EACH : dual ? STOP_CERTIFY : STOP_DETECT; }
+template <typename T> LoopStop loop_stop(const FwdParams<T>& P) { return loop_stop(P.pstat != nullptr, P.snap != nullptr, P.eps_dinf > 0); }
+// Ks -> f(the KS of its instance) on NP workgroups per problem: two have 3 .. 6 as they are; then 7; everything else is 8
+template <int KS> using KsTag = std::integral_constant<int, KS>;
+template <int NP, typename F> auto by_ks(const int Ks, F f) -> decltype(f(KsTag<8>())) {
+    if constexpr (NP == 2) switch (Ks) { case 3: return f(KsTag<3>()); case 4: return f(KsTag<4>()); case 5: return f(KsTag<5>()); case 6: return f(KsTag<6>()); default: break; }
+    return Ks == 7 ? f(KsTag<7>()) : f(KsTag<8>());
+}
 template <int NP> SweepFn spd_resident_fn(const int Ks, const bool f16) {
-#if LQP_PIV_MFMA
-#define LQP_KS_CASE(KS) case KS: return f16 ? k_spd_resident<KS, NP, true> : k_spd_resident<KS, NP, false>
-#else
-#define LQP_KS_CASE(KS) case KS: return k_spd_resident<KS, NP, false>
-#endif
-    if constexpr (NP == 2) switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
-    switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
-#undef LQP_KS_CASE
+    return by_ks<NP>(Ks, [&](auto ks) -> SweepFn {
+        if constexpr (LQP_PIV_MFMA != 0) if (f16) return k_spd_resident<decltype(ks)::value, NP, true>;
+        return k_spd_resident<decltype(ks)::value, NP, false>;
+    });
 }
-template <int NP> SplitFn loop_split_each_fn(const int Ks) {
-#define LQP_KS_CASE(KS) case KS: return k_admm_loop_split_each<KS, 512, false, NP>
-    if constexpr (NP == 2) switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
-    switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
-#undef LQP_KS_CASE
+// the split loop (its per-problem form takes the certificates from P.snap and P.eps_dinf itself: one instance for the three kinds)
+template <int NP> SplitFn loop_split_fn(const LoopStop stop, const int Ks, const bool dbg) {
+    if constexpr (NP == 2) if (stop == STOP_ALL && dbg && (Ks < 3 || Ks > 7)) return k_admm_loop_split<8, 512, true, 2>;
+    return by_ks<NP>(Ks, [&](auto ks) -> SplitFn { return stop == STOP_ALL ? k_admm_loop_split<decltype(ks)::value, 512, false, NP> : k_admm_loop_split_each<decltype(ks)::value, 512, false, NP>; });
 }
-template <int NP> SplitFn loop_split_fn(const int Ks, const bool dbg) {
-#define LQP_KS_CASE(KS) case KS: return k_admm_loop_split<KS, 512, false, NP>
-    if constexpr (NP == 2) {
-        switch (Ks) { LQP_KS_CASE(3); LQP_KS_CASE(4); LQP_KS_CASE(5); LQP_KS_CASE(6); default: break; }
-        if (Ks != 7 && dbg) return k_admm_loop_split<8, 512, true, 2>;
+inline SplitFn small_loop_kernel(const LoopStop stop) {
+    switch (stop) {
+        case STOP_EACH:    return k_admm_loop_small_each<>;
+        case STOP_DETECT:  return k_admm_loop_small_each_detect<>;
+        case STOP_CERTIFY: return k_admm_loop_small_each_certify<>;
+        default:           return k_admm_loop_small<>;
     }
-    switch (Ks) { LQP_KS_CASE(7); default: LQP_KS_CASE(8); }
-#undef LQP_KS_CASE
+}
+// the one-workgroup loop, first launch and continuation (same code, own name), 1024 threads.  One column per (RES, SYM): float64 has
+// the first alone, and the symmetric path keeps its blocks on chip whatever `resident` says
+template <typename T> using LoopFn = void (*)(const FwdParams<T>, int, int, int, int, int);
+template <typename T> struct LoopPair { LoopFn<T> hot, tail; };
+template <typename T, bool RES, bool SYM> LoopPair<T> loop_column(const LoopStop stop) {
+    switch (stop) {
+        case STOP_EACH:    return {k_admm_loop_each<T, RES, false, 1024, SYM>,         k_admm_loop_each<T, RES, true, 1024, SYM>};
+        case STOP_DETECT:  return {k_admm_loop_each_detect<T, RES, false, 1024, SYM>,  k_admm_loop_each_detect<T, RES, true, 1024, SYM>};
+        case STOP_CERTIFY: return {k_admm_loop_each_certify<T, RES, false, 1024, SYM>, k_admm_loop_each_certify<T, RES, true, 1024, SYM>};
+        default:           return {k_admm_loop<T, RES, false, 1024, SYM>,              k_admm_loop<T, RES, true, 1024, SYM>};
+    }
+}
+template <typename T> LoopPair<T> loop_kernels(const LoopStop stop, const bool resident, const bool sym) {
+    if constexpr (sizeof(T) == 4) { if (sym) return loop_column<T, true, true>(stop); if (resident) return loop_column<T, true, false>(stop); }
+    return loop_column<T, false, false>(stop);
 }
 
 // the kernel of the first (hot) launch of the persistent mode
@@ -639,7 +660,6 @@ enum LoopKind {
 constexpr int kMaxChecksPerLaunch = kRing / 4;
 
 template <typename T> struct FwdPlan {
-    typedef void (*LoopFn)(const FwdParams<T>, int, int, int, int, int);
     int retry = 0;                      // forward_impl's retry bits of this attempt
     bool solo = false;                  // (retry bit 2: nothing shared between workgroups)
     int dbg_loop_absent = 0;            // LQP_DBG_LOOP_ABSENT
@@ -658,14 +678,15 @@ template <typename T> struct FwdPlan {
     // the loop
     LoopKind kind = LOOP_ONE;
     int kind_lds = 0;                   // LDS of LOOP_SMALL / LOOP_DENSE / LOOP_DENSE_W
+    SplitFn small_fn = nullptr;         // LOOP_SMALL
     int kind_wg = 1;                    // workgroups per problem of the hot launch
     int densew_tpr = 0;
     bool loop_split_seg = false;        // mode 1: k_admm_loop_split per check segment, its pairs taking turns on the chip
-    LoopFn loop_fn = nullptr; int loop_nt = 1024, loop_lds = 0;     // hot launch of LOOP_ONE, every launch of mode 1
-    LoopFn tail_fn = nullptr; int tail_lds = 0;                     // continuation launches (LQP_NT threads)
+    LoopFn<T> loop_fn = nullptr; int loop_nt = 1024, loop_lds = 0;     // hot launch of LOOP_ONE, every launch of mode 1
+    LoopFn<T> tail_fn = nullptr; int tail_lds = 0;                     // continuation launches (LQP_NT threads)
     SplitFn split_fn = nullptr; int split_nt = 512, split_lds = 0;  // LOOP_SPLIT and loop_split_seg
     int mode = 0;                       // 2: persistent loop kernel, 1: one launch per check segment
-    bool each = false;                  // ctrl.reserved2 bit 3: every problem stops and adapts rho as a batch of one (P.pstat)
+    LoopStop stop = STOP_ALL;           // which instance of every loop family runs (loop_stop)
     bool inkernel_refactor = false;     // the continuation kernel refactorises at its adaptive-rho events itself
     // the scheduler
     bool up_front = false;              // run_planned: the whole schedule enqueued before anything is waited for
@@ -677,38 +698,13 @@ template <typename T> struct FwdPlan {
     int factor_launches = 0, loop_workgroups = 1;
 };
 
-// Every decision of an attempt and every ensure_lds / occupancy query; launches nothing.  Writes the fields of P that are decisions.
-// retry: bit 0 -- the symmetric x-update gave the solve up (not symmetric / not positive definite in f32): pivoted LU;
-//        bit 1 -- a pair of the turn-taking two-workgroup loop (split_seg) waited for its partner in vain: the one-workgroup loop
-//        bit 2 -- a kernel that shares its problems between workgroups gave up waiting (bounded spins: something else holds the
-//                 CUs -- another stream, another process, RCCL): nothing shared this time -- one workgroup per matrix in every
-//                 factorisation, host-launched check segments instead of the persistent loop with its grid barrier
-template <typename T>
-int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
+// ---- x-update linear algebra: pivoted LU of the KKT matrix, or the symmetric inverse (lqp_spd.hpp) ----
+template <typename T> int plan_xupdate(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
     const int B = P.B, n = P.n, m = P.m;
-    const bool force_lu = (retry & 1) != 0;
-    const bool solo = (retry & 4) != 0;
-    plan = FwdPlan<T>();
-    plan.retry = retry; plan.solo = solo;
-    // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
-    // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
-    const bool each = P.pstat != nullptr;
-    plan.each = each;
-    plan.dbg_loop_absent = k.dbg_loop_absent;
-    P.xcd_local = k.xcd_local != 0 ? 1 : 0;
-    P.dbg_qpass = k.dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
-    P.dbg = g_lu_dbg;
-    P.dbg_setup = nullptr;
-    if (g_lu_dbg && k.dbg_setup) { P.dbg_setup = g_lu_dbg; P.dbg = nullptr; }
-    const int check = P.check_solved;
-    const int max_iters = ctl->max_iters;
-    const int ar_iter = P.ar_iter;
-
-    // ---- x-update linear algebra: pivoted LU of the KKT matrix, or the symmetric inverse (lqp_spd.hpp) ----
+    const bool force_lu = (plan.retry & 1) != 0, solo = plan.solo;
     bool spd = false;
     if constexpr (sizeof(T) == 4) {
-        int want = ctl->linsolve;
-        if (want == 0) want = k.linsolve;
+        const int want = ctl->linsolve != 0 ? ctl->linsolve : k.linsolve;
         const bool rho_pos = !(ctl->rho_mode == 1 && !(ctl->rho_value > 0.0));
         // (512 < n <= 1024: the sweep parks its panel in the M area, see wg_spd_sweep_big)
         spd = !force_lu && want != 1 && rho_pos && P.Ks <= SPD_BIGK && m <= SPD_MAXM &&
@@ -717,8 +713,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // fit the 160 KB of LDS: large n with many equality rows (n > 960 at m >= 8, ...) stays on the LU path
         spd = spd && spd_factor_lds_bytes(m, P.Ks) <= 160 * 1024 && sym_loop_lds_bytes(n, m, P.Ks, 0) <= 160 * 1024;
     }
-    plan.spd = spd;
-    P.spd = spd ? 1 : 0;
+    plan.spd = spd; P.spd = spd ? 1 : 0;
     // (the LU path too: its refactorisations form (D Q) D again from Q and the scaling vector -- assemble_kkt_rows -- instead of
     //  reading a stored copy the setup kernel would have to write: 128 MB per batch at n = 500)
     P.qs_lazy = k.qs_lazy ? 1 : 0;
@@ -726,8 +721,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     // symmetric path with fewer problems than half the CUs: share each matrix between SPD_NP workgroups
     const bool share = (k.spd_split < 0 ? (B * SPD_NP <= d.cus ? 1 : 0) : k.spd_split) != 0 && !solo;
     plan.spd_pivot_tasks = k.spd_ptasks;
-    bool spd_split = spd && P.Ks >= 3 && P.Ks <= SPD_MAXK && share &&
-                     (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS;     // room for W, W^T in the M area
+    bool spd_split = spd && P.Ks >= 3 && P.Ks <= SPD_MAXK && share && (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS;     // room for W, W^T in the M area
     // More matrices than half the CUs (BASELINE configs[4]: 1024 per GPU): the resident sweep all the same, its pairs taking turns
     // on the chip as the loop's do (FwdParams::split_seg) -- partners are neighbours in dispatch order on one XCD (shared_map), so a
     // workgroup that waits for its partner waits for a CU that a COMPLETE earlier pair is about to leave.  Round 4 measured this
@@ -735,17 +729,13 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     // turn is 0.28 ms and needs no pass over Q in front (k_spd_prep: 0.44 ms at B = 1024).
     bool spd_turns = false;
 #if LQP_PIV_MFMA
-    if (spd && !spd_split && !solo && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && k.spd_turns != 0 &&
-        k.spd_resident != 0 && k.spd_f16 != 0 && k.spd_split != 0 &&
-        (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) && (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS && B * SPD_NP > d.cus) {
-        spd_turns = true; spd_split = true;
-    }
+    if (spd && !spd_split && !solo && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && k.spd_turns != 0 && k.spd_resident != 0 && k.spd_f16 != 0 &&
+        k.spd_split != 0 && (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) && (size_t)P.Np * P.Np >= 2 * 64 * SPD_LS && B * SPD_NP > d.cus)
+        spd_turns = spd_split = true;
 #endif
     const bool spd_big_split = spd && P.Ks > SPD_MAXK && share;
     // ... and, with the exchange buffer in the M area and the step flags behind the loop's granules, in ONE launch
-    bool spd_resident = spd_split && P.xchg && P.Ks >= SPLIT_MINK &&
-                        (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) &&
-                        k.spd_resident != 0;
+    bool spd_resident = spd_split && P.xchg && P.Ks >= SPLIT_MINK && (size_t)P.Np * P.Np >= rs2_xb_floats(P.Ks) && k.spd_resident != 0;
     if constexpr (sizeof(T) == 4) {
         if (spd_resident) {
             // workgroups per matrix of the resident sweep: 2, or 4 for batches up to a quarter of the CUs
@@ -773,8 +763,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     P.piv_cols = k.piv_cols != 0 ? 1 : 0;
     P.rho_late = (spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late) ? 1 : 0;
     // ... and above 512 rows on two workgroups per matrix: the sums k_spd_begin leaves are turned into rho by k_spd_rho_big
-    plan.rho_late_big = spd_big_split && !spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late != 0 &&
-                        (size_t)P.Np * P.Np >= (size_t)(2 * P.Ks + 1) * LQP_BLK;
+    plan.rho_late_big = spd_big_split && !spd_resident && (!P.scale || P.qs_lazy) && ctl->rho_mode == 0 && k.rho_late != 0 && (size_t)P.Np * P.Np >= (size_t)(2 * P.Ks + 1) * LQP_BLK;
     if (plan.rho_late_big) P.rho_late = 1;
     // two pivot steps per pass over the tiles (wg_spd_sweep_big, phases bits 2 .. 4): pivot + Y of step k | its update on
     // block column k + 1 alone | pivot + Y' of step k + 1 | ONE read-modify-write of every other tile with both products
@@ -810,25 +799,22 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             if (!rc && (spd_big_split || spd_split)) rc = ensure_lds((const void*)k_spd_end<>, lds);
         }
     }
-    if (rc) return rc;
+    return rc;
+}
 
-    // ---- the loop kernels ----
+// ---- the loop kernels, and whether one persistent launch can hold all their workgroups ----
+template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
+    const int B = P.B, n = P.n, m = P.m, check = P.check_solved;
+    const bool spd = plan.spd, each = plan.stop != STOP_ALL;
     // hot (first) launch: optional 512-thread build (256 VGPRs per thread: 16 register-resident blocks instead
     // of 8).  Measured SLOWER at B=128 n=500 (2.03 ms vs 1.54 ms; 1.76 ms with a 6-deep ring and 4 spills):
     // 8 waves hide the per-block dependent chain worse than 16, which costs more than the 8 extra resident
     // blocks save.  Kept selectable (LQP_LOOP512=1) for re-measurement; continuation launches always use 1024.
-    const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && k.resident != 0 &&
-                          loop_lds_bytes<T>(n, m, P.Np, true) <= 160 * 1024;
+    const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && k.resident != 0 && loop_lds_bytes<T>(n, m, P.Np, true) <= 160 * 1024;
     const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0 && !each;
-    plan.loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident);
-    plan.loop_nt = hot512 ? 512 : 1024;
-    plan.loop_fn = k_admm_loop<T, false, false, 1024>;
-    plan.tail_fn = k_admm_loop<T, false, true, 1024>;        // same code, own name: continuation launches
-    const bool dual = each && P.snap != nullptr && P.eps_dinf > 0;      // (control['unbounded']: ... and the dual certificate beside it)
-    const bool detect = each && P.snap != nullptr;      // (control['infeasible']: the EACH instances with the certificate in their check)
-    if (each) { plan.loop_fn = k_admm_loop_each<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, false, true, 1024, false>; }
-    if (detect) { plan.loop_fn = k_admm_loop_each_detect<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each_detect<T, false, true, 1024, false>; }
-    if (dual) { plan.loop_fn = k_admm_loop_each_certify<T, false, false, 1024, false>; plan.tail_fn = k_admm_loop_each_certify<T, false, true, 1024, false>; }
+    plan.loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident); plan.loop_nt = hot512 ? 512 : 1024;
+    const LoopPair<T> fns = loop_kernels<T>(plan.stop, resident, spd);
+    plan.loop_fn = fns.hot; plan.tail_fn = fns.tail;
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
     //  separate gated kernels, and the continuation kernel's LDS does not have to hold an LU panel)
@@ -836,21 +822,11 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     //  separate gated kernels each one cost four launches that do nothing when the solve is over: rho update, LU, pack, tail)
     plan.inkernel_refactor = P.N <= 1024;
     if constexpr (sizeof(T) == 4) {
-        if (resident) { plan.loop_fn = k_admm_loop<T, true, false, 1024>; plan.tail_fn = k_admm_loop<T, true, true, 1024>; }
-        if (resident && each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, false>; }
-        if (resident && detect) { plan.loop_fn = k_admm_loop_each_detect<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each_detect<T, true, true, 1024, false>; }
-        if (resident && dual) { plan.loop_fn = k_admm_loop_each_certify<T, true, false, 1024, false>; plan.tail_fn = k_admm_loop_each_certify<T, true, true, 1024, false>; }
-        if (hot512) plan.loop_fn = k_admm_loop<T, true, false, 512>;
+        if (hot512 && !spd) plan.loop_fn = k_admm_loop<T, true, false, 512>;
         if (spd) {
             P.sym_rl = sym_resident_lds_blocks(n, m, P.Ks);
-            plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl);
+            plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl); plan.loop_nt = 1024;
             plan.tail_lds = std::max(plan.loop_lds, spd_factor_lds_bytes(m, P.Ks));      // the tail refactorises in-kernel
-            plan.loop_nt = 1024;
-            plan.loop_fn = k_admm_loop<T, true, false, 1024, true>;
-            plan.tail_fn = k_admm_loop<T, true, true, 1024, true>;
-            if (each) { plan.loop_fn = k_admm_loop_each<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each<T, true, true, 1024, true>; }
-            if (detect) { plan.loop_fn = k_admm_loop_each_detect<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each_detect<T, true, true, 1024, true>; }
-            if (dual) { plan.loop_fn = k_admm_loop_each_certify<T, true, false, 1024, true>; plan.tail_fn = k_admm_loop_each_certify<T, true, true, 1024, true>; }
             // optional 512-thread first launch (8 elements per thread, 12 register-resident blocks).  Measured at
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
@@ -858,33 +834,26 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             if (k.sym512 && !each) {
                 P.sym_rl_hot = sym_resident_lds_blocks(n, m, P.Ks, resident_regs<512>(), 8);
                 plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl_hot, 8);
-                plan.loop_nt = 512;
-                plan.loop_fn = k_admm_loop<T, true, false, 512, true>;
+                plan.loop_nt = 512; plan.loop_fn = k_admm_loop<T, true, false, 512, true>;
             }
         }
     }
-    rc = ensure_lds((const void*)plan.loop_fn, plan.loop_lds);
-    if (rc) return rc;
+    if (const int rc = ensure_lds((const void*)plan.loop_fn, plan.loop_lds)) return rc;
     if (!spd) {
         plan.tail_lds = plan.loop_lds;
-        if (P.N <= 1024) {
-            plan.tail_lds = std::max(plan.tail_lds, LuLds<T, (sizeof(T) == 4 ? 16 : 8)>(round_up(P.N, 64)).total);
-            plan.tail_lds = std::max(plan.tail_lds, (int)pack_lds_bytes<T>());
-        }
+        if (P.N <= 1024) plan.tail_lds = std::max({plan.tail_lds, LuLds<T, (sizeof(T) == 4 ? 16 : 8)>(round_up(P.N, 64)).total, (int)pack_lds_bytes<T>()});
     }
-    rc = ensure_lds((const void*)plan.tail_fn, plan.tail_lds);
-    if (rc) return rc;
+    if (const int rc = ensure_lds((const void*)plan.tail_fn, plan.tail_lds)) return rc;
 
     // ---- launch mode ----
     int mode = ctl->launch_mode;
     if (mode == 0) mode = k.launch_mode;            // auto: persistent when every workgroup is resident
-    if (ctl->check_hook || solo) mode = 1;          // the hook sits between the check segments | no grid barrier
+    if (ctl->check_hook || plan.solo) mode = 1;          // the hook sits between the check segments | no grid barrier
     if (mode == 2) {
         // the grid barrier needs EVERY workgroup resident -- of the hot kernel and of the continuation kernel
         // (own block size and LDS footprint): take the smaller of the two answers
         int per_cu = 0, per_cu_tail = 0;
-        if (!blocks_per_cu(&per_cu, plan.loop_fn, plan.loop_nt, plan.loop_lds, d.dev) ||
-            !blocks_per_cu(&per_cu_tail, plan.tail_fn, LQP_NT, plan.tail_lds, d.dev))
+        if (!blocks_per_cu(&per_cu, plan.loop_fn, plan.loop_nt, plan.loop_lds, d.dev) || !blocks_per_cu(&per_cu_tail, plan.tail_fn, LQP_NT, plan.tail_lds, d.dev))
             return LQP_ERR_HIP;
         per_cu = std::min(per_cu, per_cu_tail);
         if (per_cu < 1 || B > d.cus * per_cu) mode = 1;     // not every workgroup resident: no grid barrier
@@ -893,13 +862,19 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // registers (split_seg below) -- one launch per check segment then beats the persistent launch (B = 256, n = 500: loop
         // 0.82 -> 0.42 ms, step 1.87 -> 1.60 ms; B = 192: 1.63 -> 1.51).  Only when the caller left the mode to the library.
         if constexpr (sizeof(T) == 4) {
-            if (mode == 2 && ctl->launch_mode == 0 && k.launch_mode == 2 && spd && P.xchg && 2 * B > d.cus &&
-                P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && k.loop_split != 0 &&
-                k.loop_split_seg != 0 && !ctl->check_hook)
+            if (mode == 2 && ctl->launch_mode == 0 && k.launch_mode == 2 && spd && P.xchg && 2 * B > d.cus && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK &&
+                check >= 4 && k.loop_split != 0 && k.loop_split_seg != 0 && !ctl->check_hook)
                 mode = 1;
         }
     }
     plan.mode = mode;
+    return LQP_OK;
+}
+
+// ---- the kernel of the hot launch (plan.kind) and of the check segments of mode 1 (plan.loop_split_seg) ----
+template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
+    const int B = P.B, n = P.n, m = P.m, check = P.check_solved, mode = plan.mode, retry = plan.retry;
+    const bool spd = plan.spd, solo = plan.solo, each = plan.stop != STOP_ALL;
     if constexpr (sizeof(T) == 4) {
         // two workgroups per QP for the first (hot) launch: symmetric path, persistent mode, 2 B workgroups resident
         if (spd && mode == 2 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && k.loop_split != 0) {
@@ -910,12 +885,12 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
             // four workgroups per QP (one column pair each) when the batch leaves room for them: B <= #CUs / 4
             if (P.Ks >= 7 && 4 * B <= d.cus && k.loop_split4 != 0) {
                 plan.split_lds = split_loop_lds_bytes<512, 4>(P.Ks, m);
-                plan.split_fn = each ? loop_split_each_fn<4>(P.Ks) : loop_split_fn<4>(P.Ks, false);
+                plan.split_fn = loop_split_fn<4>(plan.stop, P.Ks, false);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 4))) loop_np = 4;
             }
             if (loop_np != 4) {
                 plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-                plan.split_fn = each ? loop_split_each_fn<2>(P.Ks) : loop_split_fn<2>(P.Ks, g_lu_dbg != nullptr);
+                plan.split_fn = loop_split_fn<2>(plan.stop, P.Ks, g_lu_dbg != nullptr);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 2))) loop_np = 2;
             }
             if (loop_np > 1) { plan.kind = LOOP_SPLIT; plan.kind_wg = loop_np; }
@@ -934,7 +909,7 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         if (spd && mode == 1 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 &&
             k.loop_split != 0 && k.loop_split_seg != 0 && !(retry & 2) && !solo && 2 * B > d.cus) {
             plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-            plan.split_fn = each ? loop_split_each_fn<2>(P.Ks) : loop_split_fn<2>(P.Ks, false);
+            plan.split_fn = loop_split_fn<2>(plan.stop, P.Ks, false);
             plan.loop_split_seg = fits(d, plan.split_fn, plan.split_nt, plan.split_lds, 0);
         }
     }
@@ -961,7 +936,8 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
         if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
             const int small_lds = small_loop_lds_bytes(m);
-            if (dual ? fits(d, k_admm_loop_small_each_certify<>, 256, small_lds, B) : detect ? fits(d, k_admm_loop_small_each_detect<>, 256, small_lds, B) : each ? fits(d, k_admm_loop_small_each<>, 256, small_lds, B) : fits(d, k_admm_loop_small<>, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
+            plan.small_fn = small_loop_kernel(plan.stop);
+            if (fits(d, plan.small_fn, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
         }
         // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
         // (ctrl.reserved2 bit 0: the caller will read the corrected H from the workspace afterwards -- lqp_boxqp_unroll_backward --
@@ -970,10 +946,14 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
         //  back -- from two turns of the chip on; below that k_spd_end on every CU at once is faster: B = 256 1.39 against 1.53 ms
         //  per step, B = 512 2.69 against 2.59)
         const bool seg_eq = plan.loop_split_seg && B >= 2 * d.cus;
-        P.eq_in_loop = ((plan.kind == LOOP_SPLIT || seg_eq) && spd_resident && m > 0 && !(ctl->reserved2 & 1) && k.eq_in_loop) ? 1 : 0;
+        P.eq_in_loop = ((plan.kind == LOOP_SPLIT || seg_eq) && plan.spd_resident && m > 0 && !(ctl->reserved2 & 1) && k.eq_in_loop) ? 1 : 0;
     }
+}
 
-    // ---- the scheduler ----
+// ---- the scheduler ----
+template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, FwdPlan<T>& plan) {
+    const int max_iters = ctl->max_iters, ar_iter = P.ar_iter;
+    const bool spd = plan.spd, each = plan.stop != STOP_ALL;
     // no-host-sync plan (ctrl.reserved == 1, persistent launches): enqueue the WHOLE schedule.
     // Every kernel exits at once when the device-side DONE flag is up, the refactor chains are
     // gated on device, so nothing needs the host; errors are read later by the caller
@@ -981,9 +961,8 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     // A synchronous call (the default: the reference's semantics) enqueues the same schedule and then waits for the report
     // the last kernel stores into the caller's pinned memory (wait_report) -- not for the stream.
     int n_events = 0;
-    if (ctl->adaptive_rho)
-        for (int a = ar_iter; a < max_iters && a < ctl->adaptive_rho_max_iter; a += ar_iter) ++n_events;
-    plan.up_front = (ctl->reserved >= 1 || k.sync_plan != 0) && mode == 2 && n_events <= k.nosync_max_events;
+    for (int a = ar_iter; ctl->adaptive_rho && a < max_iters && a < ctl->adaptive_rho_max_iter; a += ar_iter) ++n_events;
+    plan.up_front = (ctl->reserved >= 1 || k.sync_plan != 0) && plan.mode == 2 && n_events <= k.nosync_max_events;
     // (round 6) the two-workgroup loop does not stop at the first iteration at which rho MAY be adapted: it looks at the
     // counters of the check before and only hands over to the continuation kernel when the event changes something
     // (FwdParams::hot_past).  Its range is the whole solve; the continuation launch is enqueued from the first event
@@ -1000,8 +979,31 @@ int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, co
     // (each: workgroups leave the last launch at different times -- workgroup 0 cannot report the status block from inside it)
     plan.tail_epilogue = k.tail_epilogue != 0 && !each;
     plan.spec_launches = k.spec_launches;
-    plan.factor_launches = spd ? (spd_big_split ? 2 * P.Ks + 2 : spd_split ? (spd_resident ? 3 : P.Ks + 2) : 1) : 2;
+    plan.factor_launches = spd ? (plan.spd_big_split ? 2 * P.Ks + 2 : plan.spd_split ? (plan.spd_resident ? 3 : P.Ks + 2) : 1) : 2;
     plan.loop_workgroups = plan.loop_split_seg ? 2 : plan.kind_wg;      // (what the loop's launches put on a problem)
+}
+
+// Every decision of an attempt and every ensure_lds / occupancy query; launches nothing.  Writes the fields of P that are decisions.
+// retry: bit 0 -- the symmetric x-update gave the solve up (not symmetric / not positive definite in f32): pivoted LU;
+//        bit 1 -- a pair of the turn-taking two-workgroup loop (split_seg) waited for its partner in vain: the one-workgroup loop
+//        bit 2 -- a kernel that shares its problems between workgroups gave up waiting (bounded spins: something else holds the
+//                 CUs -- another stream, another process, RCCL): nothing shared this time -- one workgroup per matrix in every
+//                 factorisation, host-launched check segments instead of the persistent loop with its grid barrier
+template <typename T> int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
+    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0;
+    // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
+    // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
+    plan.stop = loop_stop(P);
+    plan.dbg_loop_absent = k.dbg_loop_absent;
+    P.xcd_local = k.xcd_local != 0 ? 1 : 0;
+    P.dbg_qpass = k.dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
+    P.dbg = g_lu_dbg; P.dbg_setup = nullptr;
+    if (g_lu_dbg && k.dbg_setup) { P.dbg_setup = g_lu_dbg; P.dbg = nullptr; }
+    int rc = plan_xupdate(P, ctl, k, d, plan);
+    if (!rc) rc = plan_loop_kernels(P, ctl, k, d, plan);
+    if (rc) return rc;
+    plan_hot_kind(P, ctl, k, d, plan);
+    plan_scheduler(P, ctl, k, plan);
     return LQP_OK;
 }
 
@@ -1112,10 +1114,7 @@ void launch_hot(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, c
             hipLaunchKernelGGL(plan.split_fn, dim3((absent & 1) ? B : shared_grid(B, plan.kind_wg)), dim3(plan.split_nt), plan.split_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_SMALL:
-            if (plan.each && P.snap && P.eps_dinf > 0) hipLaunchKernelGGL(k_admm_loop_small_each_certify<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
-            else if (plan.each && P.snap) hipLaunchKernelGGL(k_admm_loop_small_each_detect<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
-            else if (plan.each) hipLaunchKernelGGL(k_admm_loop_small_each<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
-            else hipLaunchKernelGGL(k_admm_loop_small<>, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
+            hipLaunchKernelGGL(plan.small_fn, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_NP2:
             hipLaunchKernelGGL(k_admm_loop_np2<>, dim3((absent & 8) ? B : shared_grid(B, 2)), dim3(1024), plan.loop_lds, st, P, 0, e, ctr_base, -1, 1);
@@ -1442,8 +1441,8 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
                  int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0) {
     // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    const bool certify = eps_prim_inf > 0.0 || eps_dual_inf > 0.0;
-    if (ws_bytes < (eps_dual_inf > 0.0 ? L.certify_bytes : certify ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
+    const LoopStop asked = loop_stop(true, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);      // (under stop = 'each')
+    if (ws_bytes < (asked == STOP_CERTIFY ? L.certify_bytes : asked == STOP_DETECT ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
@@ -1456,8 +1455,8 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         if (ctl->reserved2 & 8) {
             if (ctl->check_hook) return LQP_ERR_INVALID;
             P.pstat = L.pstat_area;
-            if (certify) {
-                P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m, eps_dual_inf > 0.0);
+            if (asked != STOP_EACH) {
+                P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m, asked == STOP_CERTIFY);
                 P.eps_pinf = (T)eps_prim_inf; P.eps_dinf = (T)eps_dual_inf;
             }
         }

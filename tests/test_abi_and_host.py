@@ -333,9 +333,9 @@ def test_bench_dump_outputs_writes_a_fixed_sample(tmp_path):
     assert np.array_equal(got["x_local"], x[:64].numpy()) and np.array_equal(got["x_all"], x.double().numpy())
 
 
-def _kernel_resources():
+def _kernel_resources(path=None):
     """{demangled kernel name: (vgprs, spilled vgprs, scratch bytes)} from the code-object metadata of the built library
-    (every translation unit of the split build carries its own code object)."""
+    (every translation unit of the split build carries its own code object), or of one object file of its build."""
     import shutil
     import subprocess
     import tempfile
@@ -345,7 +345,7 @@ def _kernel_resources():
     _lib.build_library()
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        shutil.copy(_lib.LIB_PATH, os.path.join(tmp, "lib.so"))
+        shutil.copy(path or _lib.LIB_PATH, os.path.join(tmp, "lib.so"))
         subprocess.run([objdump, "--offloading", "lib.so"], cwd=tmp, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         for f in sorted(os.listdir(tmp)):
             if "gfx950" not in f:
@@ -401,6 +401,44 @@ def test_register_budgets_of_the_hot_kernels():
         assert res[k][1] <= spill and res[k][2] <= scratch, (k, res[k])
     for k, (vg, _, _) in res.items():
         assert vg <= 256, (k, vg)
+
+
+HOST_UNIT_KERNELS = {"k_debug_spin", "k_debug_xcd"}       # the two kernels written in csrc/lqp_amd.hip itself
+
+
+def _manifest():
+    """tools/gen_split_build.py as a module: its manifest says which kernel instances the library contains"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_split_build", os.path.join(REPO, "tools", "gen_split_build.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+def test_split_build_lists_are_what_the_generator_writes():
+    """csrc/split/ is generated from the manifest in tools/gen_split_build.py and never edited: --check writes nothing and
+    fails when a committed file differs from what the generator would write."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_split_build.py"), "--check"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+def test_host_unit_holds_only_the_debug_kernels():
+    """The host translation unit of the split build sees every kernel instance as an `extern template`; one that the host
+    code names and the manifest lacks would be compiled here instead, silently and on one thread.  Its device code object
+    defines exactly the two kernels written in csrc/lqp_amd.hip itself."""
+    _lib.build_library()
+    obj = os.path.join(_lib.CSRC, "build", "lqp_amd.o")
+    if not os.path.exists(obj):
+        pytest.skip("no csrc/build/lqp_amd.o: the library was built from a single source (LQP_UNITY_BUILD)")
+    assert set(_kernel_resources(obj)) == HOST_UNIT_KERNELS
+
+
+def test_library_holds_the_instances_of_the_manifest():
+    """The kernels of the built library are the manifest's instances and the host unit's two: none missing, none besides."""
+    built, want = set(_kernel_resources()), set(_manifest().instances()) | HOST_UNIT_KERNELS
+    assert built == want, (sorted(built - want), sorted(want - built))
 
 
 def test_report_buffer_quarantine():

@@ -1,25 +1,24 @@
 #!/usr/bin/env python3
 """Split build of the HIP library: one translation unit per group of kernels, compiled in parallel.
 
-The library is ONE source (csrc/lqp_amd.hip) whose ~80 kernel instances take ~3.5 minutes of single-threaded device
-code generation.  Every kernel is a template, so the host code can be compiled with `extern template` declarations
-(no device code at all) while each group's translation unit instantiates its share explicitly -- same headers, same
-flags, the same code per kernel as the single-source build.
+Every kernel is a template, so the host code (csrc/lqp_amd.hip) is compiled with `extern template` declarations of every
+instance (no device code of theirs at all) while each group's translation unit instantiates its share explicitly -- same
+headers, same flags, the same code per kernel as the single-source build (LQP_UNITY_BUILD=1).
 
-    python tools/gen_split_build.py            # (re)writes csrc/split/*.inc / *.hip from the BUILT library's kernel list
+KERNELS below is the manifest: every kernel instance the library contains.  An instance the host code names that is missing
+here would be compiled into the host translation unit silently; tests/test_abi_and_host.py fails on that.
 
-Run it after a single-source build (LQP_UNITY_BUILD=1) whenever kernel instances were added or removed; an instance
-that is missing from the lists is simply compiled in the host translation unit (slower, still correct).
+    python tools/gen_split_build.py            # (re)writes csrc/split/*.inc / *.hip
+    python tools/gen_split_build.py --out DIR  # ... somewhere else
+    python tools/gen_split_build.py --check    # writes nothing; exit status 1 when csrc/split/ is not what it would write
 """
+import argparse
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, "lqp_py_amd", "csrc")
-OUT = os.path.join(CSRC, "split")
+OUT = os.path.join(REPO, "lqp_py_amd", "csrc", "split")
 
 # group -> predicate on the demangled name; first match wins.  Balanced by measured compile time (seconds at -O3).
 GROUPS = [
@@ -52,153 +51,138 @@ GROUPS = [
     ("misc", lambda n: True),
 ]
 
-
-# instances that are not in the built library yet (added since the last single-source build)
-EXTRA = [
-    "void lqp::k_bwd_gather_rhs<float>(lqp::BwdParams<float>)",
-    "void lqp::k_bwd_gather_rhs<double>(lqp::BwdParams<double>)",
-    "void lqp::k_report_info<0>(int const*, int*, int)",
-    "void lqp::k_admm_loop_dense_w<float>(lqp::FwdParams<float>, int, int, int, int)",
-    "void lqp::k_admm_loop_dense_w<double>(lqp::FwdParams<double>, int, int, int, int)",
-    "void lqp::k_admm_loop_dense<float>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_admm_loop_dense<double>(lqp::FwdParams<double>, int, int, int)",
-    "void lqp::k_lu_inverse<float, false>(float const*, unsigned long, int, int, int const*, int, float*, unsigned long, int, int const*)",
-    "void lqp::k_lu_inverse<float, true>(float const*, unsigned long, int, int, int const*, int, float*, unsigned long, int, int const*)",
-    "void lqp::k_lu_inverse<double, false>(double const*, unsigned long, int, int, int const*, int, double*, unsigned long, int, int const*)",
-    "void lqp::k_lu_factor2<float, 32>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, unsigned long long*, unsigned long, unsigned int, unsigned long long*, int, int)",
-    "void lqp::k_lu_factor2<double, 16>(double*, int, int, unsigned long, int*, int, int*, int const*, int const*, unsigned long long*, unsigned long, unsigned int, unsigned long long*, int, int)",
-    "void lqp::k_lu_factor_wide<float>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, int*, unsigned long, unsigned int, int, unsigned long long*)",
-    "void lqp::k_lu_factor_wide<double>(double*, int, int, unsigned long, int*, int, int*, int const*, int const*, int*, unsigned long, unsigned int, int, unsigned long long*)",
-    "void lqp::k_lu_factor_big<float>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*)",
-    "void lqp::k_lu_factor_big<double>(double*, int, int, unsigned long, int*, int, int*, int const*, int const*)",
-    "void lqp::k_unroll_sweep<1>(lqp::FwdParams<float>, lqp::UnrollParams)",
-    "void lqp::k_unroll_sweep<16>(lqp::FwdParams<float>, lqp::UnrollParams)",
-    "void lqp::k_unroll_outer<0>(float const*, float const*, float*, int, int)",
-    "void lqp::k_unroll_sweep_split<8, 1>(lqp::FwdParams<float>, lqp::UnrollParams, unsigned int)",
-    "void lqp::k_unroll_sweep_split<8, 16>(lqp::FwdParams<float>, lqp::UnrollParams, unsigned int)",
-    "void lqp::k_unroll_sweep_split<7, 16>(lqp::FwdParams<float>, lqp::UnrollParams, unsigned int)",
-    "void lqp::k_unroll_sweep_split<6, 16>(lqp::FwdParams<float>, lqp::UnrollParams, unsigned int)",
-    "void lqp::k_unroll_sweep_split<5, 16>(lqp::FwdParams<float>, lqp::UnrollParams, unsigned int)",
-    "void lqp::k_unroll_scale_colmax<0>(float const*, int, float*, int*, int*)",
-    "void lqp::k_unroll_scale_grad<0>(float const*, float const*, float const*, float*, int, float*)",
-    "void lqp::k_unroll_scale_vectors<0>(lqp::ScaleVecParams)",
-    "void lqp::k_unroll_scale_scatter<0>(float const*, float const*, int const*, int const*, float const*, float*, int)",
-    "void lqp::k_admm_loop_small<0>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_admm_loop_split<3, 512, false, 2>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_admm_loop_split<4, 512, false, 2>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_spd_inverse<1>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_inverse<2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_inverse_dense<1>(float const*, float*, float*, int*, int, int, float*)",
-    "void lqp::k_spd_inverse_dense<2>(float const*, float*, float*, int*, int, int, float*)",
-    "void lqp::k_copy_iters<0>(int const*, int*, int)",
-    "void lqp::k_copy_pstatus<0>(int const*, int*, int)",
-    "void lqp::k_snap_init<float>(float*, unsigned long, int)",
-    "void lqp::k_snap_init<double>(double*, unsigned long, int)",
-    "void lqp::k_admm_loop_small_each<0>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_admm_loop_small_each_detect<0>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_admm_loop_small_each_certify<0>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_debug_chol_solve<2>(float const*, int const*, float const*, float*, int, int, int)",
-    "void lqp::k_debug_chol_solve<4>(float const*, int const*, float const*, float*, int, int, int)",
-    "void lqp::k_debug_chol_factor<false>(float*, int const*, int*, int, int, int)",
-    "void lqp::k_debug_chol_factor<true>(float*, int const*, int*, int, int, int)",
-] + [
-    f"void lqp::k_admm_loop_split_each<{ks}, 512, false, {np_}>(lqp::FwdParams<float>, int, int, int)"
-    for ks, np_ in ((3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4))
-] + [
-    # control['stop'] = 'each': the one-workgroup loop, hot and continuation (LU f64 | LU f32 | LU f32 resident | symmetric)
-    f"void lqp::k_admm_loop_each<{t}, {res}, {tail}, 1024, {sym}>(lqp::FwdParams<{t}>, int, int, int, int, int)"
-    for tail in ("false", "true")
-    for t, res, sym in (("double", "false", "false"), ("float", "false", "false"), ("float", "true", "false"), ("float", "true", "true"))
-] + [
-    # ... and the same eight with the infeasibility certificate in their check (control['infeasible'])
-    f"void lqp::k_admm_loop_each_detect<{t}, {res}, {tail}, 1024, {sym}>(lqp::FwdParams<{t}>, int, int, int, int, int)"
-    for tail in ("false", "true")
-    for t, res, sym in (("double", "false", "false"), ("float", "false", "false"), ("float", "true", "false"), ("float", "true", "true"))
-] + [
-    # ... and with the dual certificate beside it (control['unbounded'])
-    f"void lqp::k_admm_loop_each_certify<{t}, {res}, {tail}, 1024, {sym}>(lqp::FwdParams<{t}>, int, int, int, int, int)"
-    for tail in ("false", "true")
-    for t, res, sym in (("double", "false", "false"), ("float", "false", "false"), ("float", "true", "false"), ("float", "true", "true"))
+# ---- the manifest: (kernel, parameter signature, template-argument tuples).  {0} in a signature is the first template argument ----
+BOTH, F32, ZERO = [("double",), ("float",)], [("float",)], [(0,)]
+FP, BP, ULP = "lqp::FwdParams<{0}>", "lqp::BwdParams<{0}>", "lqp::UnrollLuParams<{0}>"
+FPF, BPF = "lqp::FwdParams<float>", "lqp::BwdParams<float>"
+KS_NP = [(3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4)]      # Ks, workgroups per problem (four: Ks = 7, 8 only)
+SPLIT = [(ks, 512, False, np_) for ks, np_ in KS_NP]
+# the one-workgroup loop, hot and continuation: LU f64 | LU f32 | LU f32 resident | symmetric
+LOOP = [(t, res, tail, 1024, sym) for tail in (False, True)
+        for t, res, sym in (("double", False, False), ("float", False, False), ("float", True, False), ("float", True, True))]
+LOOP_SIG = FP + ", int, int, int, int, int"
+LU_SIG = "{0}*, int, int, unsigned long, int*, int, int*, int const*"
+WIDE_SIG = LU_SIG + ", int const*, int*, unsigned long, unsigned int, int, unsigned long long*"
+KERNELS = [
+    # the ADMM loops (lqp_boxqp.hpp, lqp_loop_split.hpp, lqp_loop_small.hpp, lqp_dense.hpp)
+    ("k_admm_loop", LOOP_SIG, LOOP + [("float", True, False, 512, False), ("float", True, False, 512, True)]),
+    ("k_admm_loop_each", LOOP_SIG, LOOP),                      # control['stop'] = 'each'
+    ("k_admm_loop_each_detect", LOOP_SIG, LOOP),               # ... with the infeasibility certificate (control['infeasible'])
+    ("k_admm_loop_each_certify", LOOP_SIG, LOOP),              # ... and the dual certificate beside it (control['unbounded'])
+    ("k_admm_loop_split", FPF + ", int, int, int", SPLIT + [(8, 512, True, 2)]),
+    ("k_admm_loop_split_each", FPF + ", int, int, int", SPLIT),
+    ("k_admm_loop_small", FPF + ", int, int, int", ZERO),
+    ("k_admm_loop_small_each", FPF + ", int, int, int", ZERO),
+    ("k_admm_loop_small_each_detect", FPF + ", int, int, int", ZERO),
+    ("k_admm_loop_small_each_certify", FPF + ", int, int, int", ZERO),
+    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", ZERO),
+    ("k_admm_loop_dense", FP + ", int, int, int", BOTH),
+    ("k_admm_loop_dense_w", FP + ", int, int, int, int", BOTH),
+    # the symmetric x-update (lqp_spd.hpp)
+    ("k_spd_resident", FPF + ", int const*", [(ks, np_, f16) for ks, np_ in KS_NP for f16 in (False, True)]),
+    ("k_spd_prep", FPF, ZERO),
+    ("k_spd_rho_big", FPF, ZERO),
+    ("k_spd_begin", FPF + ", int const*", ZERO),
+    ("k_spd_end", FPF + ", int const*", ZERO),
+    ("k_spd_step", FPF + ", int const*, int, int", ZERO),
+    ("k_spd_big_step", FPF + ", int const*, int, int", ZERO),
+    ("k_spd_inverse", FPF + ", int const*", [(1,), (2,)]),
+    ("k_spd_inverse_dense", "float const*, float*, float*, int*, int, int, float*", [(1,), (2,)]),
+    ("k_debug_chol_factor", "float*, int const*, int*, int, int, int", [(False,), (True,)]),
+    ("k_debug_chol_solve", "float const*, int const*, float const*, float*, int, int, int", [(2,), (4,)]),
+    # the pivoted LU (lqp_lu.hpp, lqp_lu2.hpp, lqp_lu_big.hpp, lqp_lu_wide.hpp) and what runs on its factor
+    ("k_lu_factor", LU_SIG + ", unsigned long long*, int const*",
+     [("float", pb, mfma, nt) for mfma in (False, True) for pb, nt in ((16, 1024), (16, 512), (32, 512))] +
+     [("float", 8, False, nt) for nt in (1024, 512)] + [("double", pb, True, nt) for pb in (8, 16) for nt in (1024, 512)]),
+    ("k_lu_factor2", LU_SIG + ", int const*, unsigned long long*, unsigned long, unsigned int, unsigned long long*, int, int",
+     [("double", 16), ("float", 32)]),
+    ("k_lu_factor_big", LU_SIG + ", int const*", BOTH),
+    ("k_lu_factor_wide", WIDE_SIG, BOTH),
+    ("k_lu_factor_wide_tall", WIDE_SIG, F32),
+    ("k_lu_inverse", "{0} const*, unsigned long, int, int, int const*, int, {0}*, unsigned long, int, int const*",
+     [("double", False), ("float", False), ("float", True)]),
+    ("k_pack", "{0} const*, int, int, unsigned long, int const*, int, {0}*, unsigned long, int*, int, int, int const*, int const*", BOTH),
+    ("k_packed_solve", "{0} const*, int, int, int, int const*, {0}*, int, unsigned long, int, int, int const*", BOTH),
+    # forward prologue / epilogue and the copies out of the workspace
+    ("k_fwd_setup", FP, BOTH),
+    ("k_fwd_epilogue", FP, BOTH),
+    ("k_rho_update", FP + ", int, int", BOTH),
+    ("k_snap_init", "{0}*, unsigned long, int", BOTH),
+    ("k_check_done", "int*, unsigned int const*, int, int", ZERO),
+    ("k_report_info", "int const*, int*, int", ZERO),
+    ("k_copy_ints", "int const*, int, int*, int, int", [("int",)]),
+    ("k_copy_iters", "int const*, int*, int", ZERO),
+    ("k_copy_pstatus", "int const*, int*, int", ZERO),
+    ("k_copy_trace", "unsigned int const*, float*, int", ZERO),
+    ("k_copy_matrix", "{0} const*, int, unsigned long, {0}*, int, unsigned long, int", BOTH),
+    ("k_copy_residuals", "{0} const*, {0}*, {0}*, int", BOTH),
+    # backward
+    ("k_bwd_chol_solve", BPF, [(r, f16) for r in (0, 4) for f16 in (False, True)]),
+    ("k_bwd_build_chol", BPF, ZERO),
+    ("k_bwd_build", BP, BOTH),
+    ("k_bwd_build_reduced", BP, BOTH),
+    ("k_bwd_gather_rhs", BP, BOTH),
+    ("k_bwd_residual", BP, BOTH),
+    ("k_bwd_epilogue", BP, BOTH),
+    ("k_kkt_build", "{0} const*, {0} const*, {0} const*, {0} const*, int, int, int, {0}*, {0}*, int*", BOTH),
+    ("k_kkt_unpack", "{0} const*, int, int, int, {0}*, {0}*", BOTH),
+    ("k_outer_grads", "{0} const*, {0} const*, {0} const*, {0} const*, int, int, {0}*, {0}*", BOTH),
+    # unroll=True (lqp_unroll.hpp)
+    ("k_unroll_sweep", FPF + ", lqp::UnrollParams", [(1,), (16,)]),
+    ("k_unroll_sweep_split", FPF + ", lqp::UnrollParams, unsigned int", [(5, 16), (6, 16), (7, 16), (8, 16), (8, 1)]),
+    ("k_unroll_sweep_lu", FP + ", " + ULP, BOTH),
+    ("k_unroll_lu_eq", ULP + ", int, int", BOTH),
+    ("k_unroll_outer", "float const*, float const*, float*, int, int", ZERO),
+    ("k_unroll_outer_any", "{0} const*, {0} const*, {0}*, int, int", BOTH),
+    ("k_unroll_scale_colmax", "float const*, int, float*, int*, int*", ZERO),
+    ("k_unroll_scale_grad", "float const*, float const*, float const*, float*, int, float*", ZERO),
+    ("k_unroll_scale_vectors", "lqp::ScaleVecParams", ZERO),
+    ("k_unroll_scale_scatter", "float const*, float const*, int const*, int const*, float const*, float*, int", ZERO),
 ]
 
 
-# instances a built library may still hold that no longer exist in the sources
-DROP = [
-    "void lqp::k_bwd_chol_solve<0>(lqp::BwdParams<float>)",
-    "void lqp::k_bwd_chol_solve<4>(lqp::BwdParams<float>)",
-    "void lqp::k_spd_resident<3, 2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<4, 2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<5, 2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<6, 2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<7, 2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<8, 2>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<7, 4>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_resident<8, 4>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_lu_inverse<float>(float const*, unsigned long, int, int, int const*, int, float*, unsigned long, int, int const*)",
-    "void lqp::k_lu_inverse<double>(double const*, unsigned long, int, int, int const*, int, double*, unsigned long, int, int const*)",
-    "void lqp::k_lu_factor_wide<0>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, int*, unsigned long, unsigned int, int, unsigned long long*)",
-    "void lqp::k_lu_factor_wide<0>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, int*, unsigned long, unsigned int, int)",
-    "void lqp::k_unroll_scale_fro<0>(float const*, float const*, int, float*)",
-    "void lqp::k_admm_loop_lu2<float>(lqp::FwdParams<float>, int, int, int)",
-    "void lqp::k_admm_loop_lu2<double>(lqp::FwdParams<double>, int, int, int)",
-    "void lqp::k_lu_factor<float, 32, true, 1024>(float*, int, int, unsigned long, int*, int, int*, int const*, unsigned long long*, int const*)",
-    "void lqp::k_lu_factor_la<16, 1024>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, unsigned long long*)",
-    "void lqp::k_lu_factor_la<32, 768>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, unsigned long long*)",
-    "void lqp::k_lu_factor2<float, 32>(float*, int, int, unsigned long, int*, int, int*, int const*, int const*, unsigned long long*, unsigned long, unsigned int, unsigned long long*, int)",
-    "void lqp::k_lu_factor2<double, 16>(double*, int, int, unsigned long, int*, int, int*, int const*, int const*, unsigned long long*, unsigned long, unsigned int, unsigned long long*, int)",
-    "void lqp::k_unroll_sweep<0>(lqp::FwdParams<float>, lqp::UnrollParams)",
-    "void lqp::k_lu_factor<float, 32, false, 1024>(float*, int, int, unsigned long, int*, int, int*, int const*, unsigned long long*, int const*)",
-    "void lqp::k_spd_inverse<0>(lqp::FwdParams<float>, int const*)",
-    "void lqp::k_spd_inverse_dense<0>(float const*, float*, float*, int*, int, int, float*)",
-]
+def instances():
+    """{demangled instance name, e.g. 'lqp::k_pack<float>': its parameter list}, every instance of the manifest"""
+    spell = lambda a: str(a).lower() if isinstance(a, bool) else str(a)
+    out = {}
+    for kernel, sig, arg_tuples in KERNELS:
+        for args in arg_tuples:
+            name = f"lqp::{kernel}<{', '.join(map(spell, args))}>"
+            assert name not in out, name
+            out[name] = sig.format(*args)
+    return out
 
 
-def kernel_names(lib):
-    with tempfile.TemporaryDirectory() as tmp:
-        so = os.path.join(tmp, "lib.so")
-        subprocess.run(["cp", lib, so], check=True)
-        subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "--offloading", "lib.so"], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-        names = []
-        for f in sorted(os.listdir(tmp)):
-            if "gfx950" not in f:
-                continue
-            nm = subprocess.run(["nm", "--defined-only", os.path.join(tmp, f)], capture_output=True, text=True, check=True).stdout
-            syms = [ln.split()[2] for ln in nm.splitlines() if len(ln.split()) == 3 and ln.split()[1] == "T"]
-            dem = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True, check=True).stdout
-            names += [d.strip() for d in dem.splitlines() if d.strip()]
-    out = set()
-    for n in names:
-        if n.startswith("lqp::k_"):          # (a library built before these kernels became templates)
-            n = "void " + n.replace("(", "<0>(", 1)
-        if n.startswith("void lqp::"):
-            out.add(n)
-    return sorted((out | set(EXTRA)) - set(DROP))
+def generate():
+    """{file name: content} of csrc/split/"""
+    by_group = {g: [] for g, _ in GROUPS}
+    for n in sorted(f"void {name}({sig})" for name, sig in instances().items()):
+        by_group[next(g for g, pred in GROUPS if pred(n))].append(n)
+    head = "// generated by tools/gen_split_build.py from the manifest of kernel instances in it -- do not edit\n"
+    files = {"lqp_extern.inc": head + "// host translation unit: no kernel of these lists is instantiated here\n" + "".join(
+        f"// ---- {g}\n" + "".join(f"extern template __global__ {n};\n" for n in by_group[g]) for g, _ in GROUPS)}
+    for g, _ in GROUPS:
+        files[f"lqp_tu_{g}.hip"] = head + '#include "../lqp_unroll.hpp"\n' + "".join(f"template __global__ {n};\n" for n in by_group[g])
+    return files, {g: len(v) for g, v in by_group.items()}
 
 
 def main():
-    lib = sys.argv[1] if len(sys.argv) > 1 else os.path.join(CSRC, "liblqp_amd.so")
-    names = kernel_names(lib)
-    os.makedirs(OUT, exist_ok=True)
-    by_group = {g: [] for g, _ in GROUPS}
-    for n in names:
-        for g, pred in GROUPS:
-            if pred(n):
-                by_group[g].append(n)
-                break
-    head = "// generated by tools/gen_split_build.py from the kernel list of a single-source build -- do not edit\n"
-    with open(os.path.join(OUT, "lqp_extern.inc"), "w") as f:
-        f.write(head + "// host translation unit: no kernel of these lists is instantiated here\n")
-        for g, _ in GROUPS:
-            f.write(f"// ---- {g}\n")
-            for n in by_group[g]:
-                f.write("extern template __global__ " + n + ";\n")
-    for g, _ in GROUPS:
-        with open(os.path.join(OUT, f"lqp_tu_{g}.hip"), "w") as f:
-            f.write(head + '#include "../lqp_unroll.hpp"\n')
-            for n in by_group[g]:
-                f.write("template __global__ " + n + ";\n")
-    print({g: len(v) for g, v in by_group.items()}, "kernels:", len(names))
+    ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
+    ap.add_argument("--out", default=OUT, help="directory to write (default: csrc/split)")
+    ap.add_argument("--check", action="store_true", help="write nothing; fail when the directory differs from what would be written")
+    args = ap.parse_args()
+    files, counts = generate()
+    if args.check:
+        have = {f: open(os.path.join(args.out, f)).read() for f in sorted(os.listdir(args.out))} if os.path.isdir(args.out) else {}
+        bad = sorted(f for f in set(files) | set(have) if files.get(f) != have.get(f))
+        if bad:
+            sys.exit(f"{args.out} is not what tools/gen_split_build.py writes: {', '.join(bad)}")
+    else:
+        os.makedirs(args.out, exist_ok=True)
+        for f, text in files.items():
+            with open(os.path.join(args.out, f), "w") as fh:
+                fh.write(text)
+    print(counts, "kernels:", sum(counts.values()), "translation units:", len(GROUPS), "+ the host's")
 
 
 if __name__ == "__main__":
