@@ -1,9 +1,9 @@
 """The cases of control['unbounded'], dual infeasibility detection under control['stop'] = 'each', and their truth (no GPU needed to
 import this module).  tests/test_dinf_table.py checks them on the CPU, tests/test_gpu_dinf.py runs them.
 
-The truth is `solve_certify`: ``infeas_table.solve_detect`` (the oracle's loop on a batch of one with the primal certificate at every
-check) extended by the dual one.  In the SCALED problem, at a check of iteration k, against the snapshot (x, Qs x) of the last check,
-valid iff it is the last check's and rho has not changed since:
+The truth is `solve_certify`: ``oracle.solve_box_qp`` itself on a batch of one with ``infeas_table.Certificates`` as its per-check
+callback, the dual certificate on behind the primal one.  In the SCALED problem, at a check of iteration k, against the snapshot
+(x, Qs x) of the last check, valid iff it is the last check's and rho has not changed since:
 
     dx = x_k - x_prev;  dq = Qs x_k - Qs x_prev;  N = |dx|_inf
     e1 = |dq|_inf / N;  e2 = ps^T dx / N;  e3 = max_i([lbs_i finite] (-dx_i), [ubs_i finite] dx_i, 0) / N
@@ -51,7 +51,7 @@ import infeas_table as IT
 
 EPS = 1e-4           # control['eps_dual_inf'] (and eps_prim_inf) of every row: the defaults
 MARGIN = 2.0
-OPTIMAL, MAXITER, INFEASIBLE, UNBOUNDED = 0, 1, 2, 3
+OPTIMAL, MAXITER, INFEASIBLE, UNBOUNDED = IT.OPTIMAL, IT.MAXITER, IT.INFEASIBLE, IT.UNBOUNDED
 CHECK = 30
 FLAGGED_BY = 90      # float32 rows: the last iteration at which a problem of the table is flagged (the module's docstring says why)
 
@@ -106,10 +106,7 @@ def inputs(row, dtype=torch.float64):
             ub[i, :, 0] = torch.where(d > 0, torch.full_like(d, inf), ub[i, :, 0])
             lb[i, :, 0] = torch.where(d < 0, torch.full_like(d, -inf), lb[i, :, 0])
     for i in row["primal"]:
-        a0 = A[i, 0]
-        hi = float((a0 * torch.where(a0 > 0, ub[i, :, 0], lb[i, :, 0])).sum())
-        lo = float((a0 * torch.where(a0 > 0, lb[i, :, 0], ub[i, :, 0])).sum())
-        b[i, 0, 0] = hi + (hi - lo)
+        IT.out_of_reach(A, b, lb, ub, i, 1.0)
     cast = lambda t: None if t is None else t.to(dtype).contiguous()
     return tuple(cast(t) for t in (Q, p, A, b, lb, ub))
 
@@ -126,152 +123,11 @@ def control(row, problem=None, **extra):
 
 def solve_certify(Q, p, A, b, lb, ub, control, eps_prim_inf=None, eps_dual_inf=None, bounds=None, qx_from_rhs=False):
     """``infeas_table.solve_detect`` with the dual certificate behind the primal one at every check (either threshold None: that
-    certificate is off).  -> solve_detect's dict (status 3: dual infeasible) plus "dchecks": per check (iteration, e1, e2, e3, N,
-    valid), e1 = e2 = e3 = N = None where there was no valid snapshot or N == 0, and "as_dx": |As dx|_inf / N of the same checks."""
-    assert Q.shape[0] == 1
-    B, n = 1, p.shape[1]
-    m = O._ncon(A, 1)
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    has_lb = bool(torch.max(lb) > -O.INF) if bounds is None else bool(bounds[0])
-    has_ub = bool(torch.min(ub) < O.INF) if bounds is None else bool(bounds[1])
-    has_box = has_lb or has_ub
-    c = O.resolve_control(control, n)
-    rho = c.rho
-    if not has_box:
-        rho = 0
-    if c.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, c.beta, has_box)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E_ = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=c.rho_min, max=c.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor = 1
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * c.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = c.adaptive_rho
-    xv = None
-    it = 0
-    status = MAXITER
-    snap = None              # (y, g, nu, rho it was taken at, iteration, x, Qs x)
-    checks, dchecks, as_dx = [], [], []
-    detecting = eps_prim_inf is not None or eps_dual_inf is not None
-    lbs_b = torch.broadcast_to(torch.as_tensor(lbs, dtype=dt), (B, n, 1))
-    ubs_b = torch.broadcast_to(torch.as_tensor(ubs, dtype=dt), (B, n, 1))
-    ps_b = torch.broadcast_to(torch.as_tensor(ps, dtype=dt), (B, n, 1))
-    for it in range(c.max_iters):
-        if (c.adaptive_rho and it % c.adaptive_rho_iter == 0 and 0 < it < c.adaptive_rho_max_iter
-                and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            grow = bool((ratio > c.adaptive_rho_tol).sum() > 0)
-            shrink = bool((ratio < 1 / c.adaptive_rho_tol).sum() > 0)
-            if grow or shrink:
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=c.rho_min, max=c.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        x = xv[:, :n, :]
-        z_old = z
-        z = x + u
-        if has_lb:
-            z = torch.maximum(z, lbs)
-        if has_ub:
-            z = torch.minimum(z, ubs)
-        r = x - z
-        s = rho * (z - z_old)
-        u = u + r
-        if it % c.check_solved == 0:
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * s)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx = torch.matmul(Qs, x)
-            qx_inf = O._inf_norm_cols(qx / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = c.eps_abs + c.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = c.eps_abs + c.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                status = OPTIMAL
-                break
-            if detecting:
-                rho_now = float(torch.as_tensor(rho).reshape(-1)[0])
-                nu = xv[:, n:, :] if m > 0 else torch.zeros(B, 0, 1, dtype=dt)
-                qx_c = qx
-                if qx_from_rhs:
-                    qx_c = rhs[:, :n, :] - rho * x - (torch.matmul(As.transpose(1, 2), nu) if m > 0 else 0)
-                y, g = rho * u, qx_c + s
-                valid = snap is not None and snap[3] == rho_now and snap[4] == it - c.check_solved
-                prev = snap
-                snap = (y.clone(), g.clone(), nu.clone(), rho_now, it, x.clone(), qx_c.clone())
-                if eps_prim_inf is not None:
-                    eps = eps_prim_inf
-                    c1 = c2 = N = None
-                    if valid:
-                        dy, dg, dnu = y - prev[0], g - prev[1], nu - prev[2]
-                        N = float(dy.abs().max())
-                        if N > 0:
-                            c1 = float(dg.abs().max()) / N
-                            bnd = torch.where(dy > 0, ubs_b, lbs_b)
-                            fin = torch.isfinite(bnd)
-                            loose = bool(torch.any(torch.logical_and(~fin, dy.abs() > eps * N)))
-                            tot = float(torch.where(torch.logical_and(fin, dy != 0), bnd * dy, torch.zeros_like(dy)).sum())
-                            if m > 0:
-                                tot += float((torch.broadcast_to(torch.as_tensor(bs, dtype=dt), nu.shape) * dnu).sum())
-                            c2 = float("inf") if loose else tot / N
-                        else:
-                            N = None
-                    checks.append((it, c1, c2, N, valid))
-                    if c1 is not None and c1 <= eps and c2 <= -eps:
-                        status = INFEASIBLE
-                        break
-                if eps_dual_inf is not None:
-                    eps = eps_dual_inf
-                    e1 = e2 = e3 = N = adx = None
-                    if valid:
-                        dx, dq = x - prev[5], qx_c - prev[6]
-                        N = float(dx.abs().max())
-                        if N > 0:
-                            e1 = float(dq.abs().max()) / N
-                            e2 = float((ps_b * dx).sum()) / N
-                            zero = torch.zeros_like(dx)
-                            cone = torch.maximum(torch.where(torch.isfinite(lbs_b), -dx, zero), torch.where(torch.isfinite(ubs_b), dx, zero))
-                            e3 = max(float(cone.max()), 0.0) / N
-                            adx = float(torch.matmul(As, dx).abs().max()) / N if m > 0 else 0.0
-                        else:
-                            N = None
-                    dchecks.append((it, e1, e2, e3, N, valid))
-                    as_dx.append(adx)
-                    if e1 is not None and e1 <= eps and e2 <= -eps and e3 <= eps:
-                        status = UNBOUNDED
-                        break
-    x = D * x
-    z = D * z
-    u = u / D
-    y = u * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E_ if m > 0 else None
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it, "status": status, "checks": checks,
-            "n_factor": n_factor, "dchecks": dchecks, "as_dx": as_dx}
+    certificate is off).  -> solve_detect's dict (status 3: dual infeasible) plus "dchecks" and "as_dx" (``infeas_table.Certificates``)."""
+    cert = IT.Certificates(eps_prim_inf, eps_dual_inf, qx_from_rhs)
+    sol = IT.solve_with(cert, Q, p, A, b, lb, ub, control, bounds)
+    sol.update(dchecks=cert.dchecks, as_dx=cert.as_dx)
+    return sol
 
 
 def solve_row(row, dtype, primal=None, dual=True, qx_from_rhs=False):
@@ -279,12 +135,8 @@ def solve_row(row, dtype, primal=None, dual=True, qx_from_rhs=False):
     primal: the primal certificate too (None: iff the row holds `primal` problems -- the mixed row runs with both keys)"""
     primal = bool(row["primal"]) if primal is None else primal
     qp = inputs(row, dtype)
-    out = []
-    for i in range(row["B"]):
-        one = tuple(None if t is None else t[i:i + 1] for t in qp)
-        out.append(solve_certify(*one, control(row, problem=i), eps_prim_inf=EPS if primal else None, eps_dual_inf=EPS if dual else None,
-                                 bounds=(True, True), qx_from_rhs=qx_from_rhs))
-    return out
+    return [solve_certify(*E.alone(qp, i), control(row, problem=i), eps_prim_inf=EPS if primal else None,
+                          eps_dual_inf=EPS if dual else None, qx_from_rhs=qx_from_rhs, **E.ALONE) for i in range(row["B"])]
 
 
 @functools.lru_cache(maxsize=None)
@@ -301,16 +153,9 @@ def margins(sol, eps=EPS):
     """How far the dual rule is from its verdict over the checks of one solve -> (clear, miss_before, nearest): clear: 1 / miss at the
     detecting check (None: not flagged dual infeasible); miss_before: the miss at the valid check before it (None: there is
     none); nearest: over the checks that did not flag, the smallest miss (inf: never a valid snapshot with N > 0)."""
-    chk = sol["dchecks"]
-    flagged = sol["status"] == UNBOUNDED
-    clear = miss_before = None
-    body = chk[:-1] if flagged else chk
-    if flagged:
-        _, e1, e2, e3, _, _ = chk[-1]
-        clear = 1.0 / max(dual_miss(e1, e2, e3, eps), 1e-300)
-        if len(chk) > 1 and chk[-2][1] is not None:
-            miss_before = dual_miss(*chk[-2][1:4], eps)
-    nearest = min([dual_miss(e1, e2, e3, eps) for _, e1, e2, e3, _, _ in body if e1 is not None] or [float("inf")])
+    miss = lambda e1, e2, e3: dual_miss(e1, e2, e3, eps)
+    last, miss_before, nearest = IT.margins_of(sol["dchecks"], sol["status"] == UNBOUNDED, miss, 5)
+    clear = None if last is None else 1.0 / max(miss(*last), 1e-300)
     return clear, miss_before, nearest
 
 

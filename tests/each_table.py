@@ -84,6 +84,14 @@ def control(row, **extra):
     return O.make_control(**dict(row["control"], **extra))
 
 
+ALONE = dict(bounds=(True, True))      # the bound flags of the whole batch, for a problem solved on its own: every table's are both finite
+
+
+def alone(qp, i):
+    """-> problem i of the inputs `qp` as a batch of one (to be solved with **ALONE)"""
+    return tuple(None if t is None else t[i:i + 1] for t in qp)
+
+
 @functools.lru_cache(maxsize=None)
 def solo(name, dtype):
     """-> the oracle's solution of every problem of the row on its own: a list of B dicts (plus "n_factor"), computed once"""
@@ -91,9 +99,8 @@ def solo(name, dtype):
     qp = inputs(row, dtype)
     out = []
     for i in range(row["B"]):
-        one = tuple(None if t is None else t[i:i + 1] for t in qp)
         trace = {}
-        sol = O.solve_box_qp(*one, control(row), trace=trace, bounds=(True, True))
+        sol = O.solve_box_qp(*alone(qp, i), control(row), trace=trace, **ALONE)
         sol["n_factor"] = trace["n_factor"]
         out.append(sol)
     return out

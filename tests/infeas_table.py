@@ -1,9 +1,9 @@
 """The cases of control['infeasible'], primal infeasibility detection under control['stop'] = 'each', and their truth (no GPU
 needed to import this module).  tests/test_infeas_table.py checks them on the CPU, tests/test_gpu_infeas.py runs them.
 
-The truth is `solve_detect`: the loop of ``oracle.solve_box_qp`` restated for a batch of one (in the manner of
-``relax_table.solve_relaxed``) with the certificate at every check.  In the SCALED problem, after the element-wise update of
-iteration k:
+The truth is `solve_detect`: ``oracle.solve_box_qp`` itself, the one loop the reference-made goldens pin, on a batch of one with
+`Certificates` as its per-check callback (``at_check``).  `Certificates` holds the primal rule below and the dual one that
+tests/dinf_table.py describes.  In the SCALED problem, after the element-wise update of iteration k:
 
     y = rho u_k;  g = Qs x_k + rho (z_k - z_{k-1});  nu = nu_k
 
@@ -12,8 +12,8 @@ against the snapshot (y, g, nu) of the last check, which is valid iff rho has no
     dy, dg, dnu;  N = |dy|_inf;  c1 = |dg|_inf / N;  c2 = (sum_i [ubs_i max(dy_i, 0) + lbs_i min(dy_i, 0)] + bs^T dnu) / N
 
 (a term of an infinite bound counts 0 while |dy_i| <= eps N, else c2 = +inf) and "primal infeasible" iff N > 0, c1 <= eps and
-c2 <= -eps.  Optimal comes first; a flagged problem stops with the iterate of that check.  With detection off it is the oracle,
-bit for bit (test_infeas_table.py).
+c2 <= -eps.  Optimal comes first; a flagged problem stops with the iterate of that check.  With detection off the callback changes
+no bit of the solve (test_infeas_table.py).
 
 A row is a row of ``each_table`` (its inputs, its control) in which chosen problems are made infeasible without assuming what A
 looks like: with lo / hi the smallest / largest value of A_0 x over the box, b_0 = hi + f (hi - lo) -- ``gross``: f = 1,
@@ -33,7 +33,7 @@ import each_table as E
 
 EPS = 1e-4           # control['eps_prim_inf'] of every row (the default)
 MARGIN = 4.0
-OPTIMAL, MAXITER, INFEASIBLE = 0, 1, 2
+OPTIMAL, MAXITER, INFEASIBLE, UNBOUNDED = 0, 1, 2, 3      # (3: the dual certificate, tests/dinf_table.py)
 
 ROWS = {}
 
@@ -47,15 +47,20 @@ def _row(name, base, tier, gross, mild, status, iters, f_mild=0.02, margin=MARGI
     ROWS[name] = row
 
 
+def out_of_reach(A, b, lb, ub, i, f):
+    """moves b_0 of problem i out of reach, in place: b_0 = hi + f (hi - lo), lo / hi the smallest / largest A_0 x over the box"""
+    a0 = A[i, 0]
+    hi = float((a0 * torch.where(a0 > 0, ub[i, :, 0], lb[i, :, 0])).sum())
+    lo = float((a0 * torch.where(a0 > 0, lb[i, :, 0], ub[i, :, 0])).sum())
+    b[i, 0, 0] = hi + f * (hi - lo)
+
+
 def inputs(row, dtype=torch.float64):
     """-> Q, p, A, b, lb, ub: each_table's inputs of the row with b_0 of the `gross` / `mild` problems moved out of reach"""
     Q, p, A, b, lb, ub = E.inputs(row, torch.float64)
     for idx, f in ((row["gross"], 1.0), (row["mild"], row.get("f_mild", 0.02))):
         for i in idx:
-            a0 = A[i, 0]
-            hi = float((a0 * torch.where(a0 > 0, ub[i, :, 0], lb[i, :, 0])).sum())
-            lo = float((a0 * torch.where(a0 > 0, lb[i, :, 0], ub[i, :, 0])).sum())
-            b[i, 0, 0] = hi + f * (hi - lo)
+            out_of_reach(A, b, lb, ub, i, f)
     cast = lambda t: None if t is None else t.to(dtype).contiguous()
     return tuple(cast(t) for t in (Q, p, A, b, lb, ub))
 
@@ -67,131 +72,100 @@ def control(row, problem=None, **extra):
     return O.make_control(**dict(row["control"], **extra))
 
 
+class Certificates:
+    """The primal and the dual infeasibility certificate as the ``at_check`` callback of ``oracle.solve_box_qp`` on a batch of ONE
+    (a threshold of None: that certificate is off; both None: the callback looks at nothing).  It owns the snapshot
+    (y, g, nu, rho, iteration, x, Qs x) of the last check it was called at, which is valid iff that was the check before this one and
+    rho has not changed since, and the records: `checks`, per check (iteration, c1, c2, N, valid) of the primal rule; `dchecks`,
+    per check (iteration, e1, e2, e3, N, valid) of the dual rule (tests/dinf_table.py), and `as_dx`: |As dx|_inf / N of the same
+    checks -- the terms None where there was no valid snapshot or N == 0.  Order in a check: primal infeasible (-> 2), dual
+    infeasible (-> 3).  qx_from_rhs: Qs x is w - rho x - As^T nu, as a kernel that does not touch Q forms it, not the product (the
+    rows' verdicts must not care)."""
+
+    def __init__(self, eps_prim_inf=None, eps_dual_inf=None, qx_from_rhs=False):
+        self.eps_prim_inf, self.eps_dual_inf, self.qx_from_rhs = eps_prim_inf, eps_dual_inf, qx_from_rhs
+        self.snap = None
+        self.checks, self.dchecks, self.as_dx = [], [], []
+
+    def __call__(self, it, st):
+        assert st.B == 1
+        if self.eps_prim_inf is None and self.eps_dual_inf is None:
+            return 0
+        n, m, x, rho = st.n, st.m, st.x, st.rho
+        rho_now = float(torch.as_tensor(rho).reshape(-1)[0])
+        nu = st.xv[:, n:, :] if m > 0 else torch.zeros(1, 0, 1, dtype=x.dtype)
+        qx = st.qx
+        if self.qx_from_rhs:
+            qx = st.rhs[:, :n, :] - rho * x - (torch.matmul(st.As.transpose(1, 2), nu) if m > 0 else 0)
+        y, g = rho * st.u, qx + st.s
+        prev = self.snap
+        valid = prev is not None and prev[3] == rho_now and prev[4] == it - st.check_solved
+        self.snap = (y.clone(), g.clone(), nu.clone(), rho_now, it, x.clone(), qx.clone())
+        if self.eps_prim_inf is not None and self._primal(it, st, valid, prev, y, g, nu):
+            return INFEASIBLE
+        if self.eps_dual_inf is not None and self._dual(it, st, valid, prev, x, qx):
+            return UNBOUNDED
+        return 0
+
+    @staticmethod
+    def _whole(t, like):
+        return torch.broadcast_to(torch.as_tensor(t, dtype=like.dtype), like.shape)
+
+    def _primal(self, it, st, valid, prev, y, g, nu):
+        eps = self.eps_prim_inf
+        c1 = c2 = N = None
+        if valid:
+            dy, dg, dnu = y - prev[0], g - prev[1], nu - prev[2]
+            N = float(dy.abs().max())
+            if N > 0:
+                c1 = float(dg.abs().max()) / N
+                bnd = torch.where(dy > 0, self._whole(st.ubs, dy), self._whole(st.lbs, dy))
+                fin = torch.isfinite(bnd)
+                loose = bool(torch.any(torch.logical_and(~fin, dy.abs() > eps * N)))
+                tot = float(torch.where(torch.logical_and(fin, dy != 0), bnd * dy, torch.zeros_like(dy)).sum())
+                if st.m > 0:
+                    tot += float((self._whole(st.bs, nu) * dnu).sum())
+                c2 = float("inf") if loose else tot / N
+            else:
+                N = None
+        self.checks.append((it, c1, c2, N, valid))
+        return c1 is not None and c1 <= eps and c2 <= -eps
+
+    def _dual(self, it, st, valid, prev, x, qx):
+        eps = self.eps_dual_inf
+        e1 = e2 = e3 = N = adx = None
+        if valid:
+            dx, dq = x - prev[5], qx - prev[6]
+            N = float(dx.abs().max())
+            if N > 0:
+                e1 = float(dq.abs().max()) / N
+                e2 = float((self._whole(st.ps, dx) * dx).sum()) / N
+                zero = torch.zeros_like(dx)
+                cone = torch.maximum(torch.where(torch.isfinite(self._whole(st.lbs, dx)), -dx, zero),
+                                     torch.where(torch.isfinite(self._whole(st.ubs, dx)), dx, zero))
+                e3 = max(float(cone.max()), 0.0) / N
+                adx = float(torch.matmul(st.As, dx).abs().max()) / N if st.m > 0 else 0.0
+            else:
+                N = None
+        self.dchecks.append((it, e1, e2, e3, N, valid))
+        self.as_dx.append(adx)
+        return e1 is not None and e1 <= eps and e2 <= -eps and e3 <= eps
+
+
+def solve_with(cert, Q, p, A, b, lb, ub, control, bounds=None):
+    """``oracle.solve_box_qp`` with the `Certificates` ``cert`` attached -> the oracle's dict plus "status" (0 optimal, 1 out of
+    iterations, 2 primal infeasible, 3 dual infeasible), "n_factor" and the "checks" of cert"""
+    trace = {}
+    sol = O.solve_box_qp(Q, p, A, b, lb, ub, control, trace=trace, bounds=bounds, at_check=cert)
+    sol.update(status=trace["status"], checks=cert.checks, n_factor=trace["n_factor"])
+    return sol
+
+
 def solve_detect(Q, p, A, b, lb, ub, control, eps_prim_inf=None, bounds=None, qx_from_rhs=False):
-    """``oracle.solve_box_qp`` on a batch of ONE with the certificate at every check (eps_prim_inf=None: off, the oracle's bits).
-    -> the oracle's dict plus "status" (0 optimal, 1 out of iterations, 2 primal infeasible) and "checks": per check
-    (iteration, c1, c2, N, valid), c1 = c2 = N = None where there was no valid snapshot or N == 0.  qx_from_rhs: the certificate's
-    Qs x is w - rho x - As^T nu, as a kernel that does not touch Q forms it, not the product (the rows' verdicts must not care)."""
-    assert Q.shape[0] == 1
-    B, n = 1, p.shape[1]
-    m = O._ncon(A, 1)
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    has_lb = bool(torch.max(lb) > -O.INF) if bounds is None else bool(bounds[0])
-    has_ub = bool(torch.min(ub) < O.INF) if bounds is None else bool(bounds[1])
-    has_box = has_lb or has_ub
-    c = O.resolve_control(control, n)
-    rho = c.rho
-    if not has_box:
-        rho = 0
-    if c.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, c.beta, has_box)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E_ = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=c.rho_min, max=c.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor = 1
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * c.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = c.adaptive_rho
-    xv = None
-    it = 0
-    status = MAXITER
-    snap = None              # (y, g, nu, rho it was taken at, iteration)
-    checks = []
-    lbs_b = torch.broadcast_to(torch.as_tensor(lbs, dtype=dt), (B, n, 1))
-    ubs_b = torch.broadcast_to(torch.as_tensor(ubs, dtype=dt), (B, n, 1))
-    for it in range(c.max_iters):
-        if (c.adaptive_rho and it % c.adaptive_rho_iter == 0 and 0 < it < c.adaptive_rho_max_iter
-                and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            grow = bool((ratio > c.adaptive_rho_tol).sum() > 0)
-            shrink = bool((ratio < 1 / c.adaptive_rho_tol).sum() > 0)
-            if grow or shrink:
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=c.rho_min, max=c.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        x = xv[:, :n, :]
-        z_old = z
-        z = x + u
-        if has_lb:
-            z = torch.maximum(z, lbs)
-        if has_ub:
-            z = torch.minimum(z, ubs)
-        r = x - z
-        s = rho * (z - z_old)
-        u = u + r
-        if it % c.check_solved == 0:
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * s)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx = torch.matmul(Qs, x)
-            qx_inf = O._inf_norm_cols(qx / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = c.eps_abs + c.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = c.eps_abs + c.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                status = OPTIMAL
-                break
-            if eps_prim_inf is not None:
-                eps = eps_prim_inf
-                rho_now = float(torch.as_tensor(rho).reshape(-1)[0])
-                nu = xv[:, n:, :] if m > 0 else torch.zeros(B, 0, 1, dtype=dt)
-                qx_c = qx
-                if qx_from_rhs:
-                    qx_c = rhs[:, :n, :] - rho * x - (torch.matmul(As.transpose(1, 2), nu) if m > 0 else 0)
-                y, g = rho * u, qx_c + s
-                valid = snap is not None and snap[3] == rho_now and snap[4] == it - c.check_solved
-                c1 = c2 = N = None
-                if valid:
-                    dy, dg, dnu = y - snap[0], g - snap[1], nu - snap[2]
-                    N = float(dy.abs().max())
-                    if N > 0:
-                        c1 = float(dg.abs().max()) / N
-                        bnd = torch.where(dy > 0, ubs_b, lbs_b)
-                        fin = torch.isfinite(bnd)
-                        loose = bool(torch.any(torch.logical_and(~fin, dy.abs() > eps * N)))
-                        tot = float(torch.where(torch.logical_and(fin, dy != 0), bnd * dy, torch.zeros_like(dy)).sum())
-                        if m > 0:
-                            tot += float((torch.broadcast_to(torch.as_tensor(bs, dtype=dt), nu.shape) * dnu).sum())
-                        c2 = float("inf") if loose else tot / N
-                    else:
-                        N = None
-                checks.append((it, c1, c2, N, valid))
-                snap = (y.clone(), g.clone(), nu.clone(), rho_now, it)
-                if c1 is not None and c1 <= eps and c2 <= -eps:
-                    status = INFEASIBLE
-                    break
-    x = D * x
-    z = D * z
-    u = u / D
-    y = u * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E_ if m > 0 else None
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it, "status": status, "checks": checks,
-            "n_factor": n_factor}
+    """``oracle.solve_box_qp`` on a batch of ONE with the primal certificate at every check (eps_prim_inf=None: off, the oracle's
+    bits).  -> the oracle's dict plus "status" (0 optimal, 1 out of iterations, 2 primal infeasible), "checks" (`Certificates`) and
+    "n_factor"."""
+    return solve_with(Certificates(eps_prim_inf, None, qx_from_rhs), Q, p, A, b, lb, ub, control, bounds)
 
 
 @functools.lru_cache(maxsize=None)
@@ -199,11 +173,23 @@ def truth(name, dtype, detect=True):
     """-> every problem of the row solved by solve_detect as a batch of one (the bound flags of the whole batch: both finite)"""
     row = ROWS[name]
     qp = inputs(row, dtype)
-    out = []
-    for i in range(row["B"]):
-        one = tuple(None if t is None else t[i:i + 1] for t in qp)
-        out.append(solve_detect(*one, control(row, problem=i), eps_prim_inf=EPS if detect else None, bounds=(True, True)))
-    return out
+    return [solve_detect(*E.alone(qp, i), control(row, problem=i), eps_prim_inf=EPS if detect else None, **E.ALONE)
+            for i in range(row["B"])]
+
+
+def margins_of(chk, flagged, miss, valid_at):
+    """What the margins of both rules share, over the records `chk` of one solve, each (iteration, *terms, N, valid) with the
+    validity flag at index `valid_at` -> (the terms of the flagged check, which is the last; None: not flagged,
+    miss_before: miss(*terms) at the valid check before it; None: there is none,
+    nearest: the smallest miss over the checks that did not flag; inf: never a valid snapshot with N > 0)."""
+    terms = lambda c: c[1:valid_at - 1]
+    last = miss_before = None
+    if flagged:
+        last = terms(chk[-1])
+        if len(chk) > 1 and chk[-2][1] is not None:
+            miss_before = miss(*terms(chk[-2]))
+    nearest = min([miss(*terms(c)) for c in (chk[:-1] if flagged else chk) if c[1] is not None] or [float("inf")])
+    return last, miss_before, nearest
 
 
 def margins(sol, eps=EPS):
@@ -213,16 +199,8 @@ def margins(sol, eps=EPS):
     smallest such miss (inf: never a valid snapshot)."""
     def miss(c1, c2):
         return max(c1 / eps, eps / max(-c2, 1e-300))
-    chk = sol["checks"]
-    flagged = sol["status"] == INFEASIBLE
-    clear = miss_before = None
-    body = chk[:-1] if flagged else chk
-    if flagged:
-        _, c1, c2, _, _ = chk[-1]
-        clear = min(eps / max(c1, 1e-300), -c2 / eps)
-        if len(chk) > 1 and chk[-2][1] is not None:
-            miss_before = miss(chk[-2][1], chk[-2][2])
-    nearest = min([miss(c1, c2) for _, c1, c2, _, _ in body if c1 is not None] or [float("inf")])
+    last, miss_before, nearest = margins_of(sol["checks"], sol["status"] == INFEASIBLE, miss, 4)
+    clear = None if last is None else min(eps / max(last[0], 1e-300), -last[1] / eps)
     return clear, miss_before, nearest
 
 

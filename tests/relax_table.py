@@ -1,13 +1,13 @@
 """The cases of control['alpha'], the over-relaxed ADMM step, and their truth (no GPU needed to import this module).
 tests/test_relax_table.py checks them on the CPU, tests/test_gpu_relax.py runs them.
 
-The truth is `solve_relaxed`: the loop of ``oracle.solve_box_qp`` restated with the relaxed step
+The truth is `solve_relaxed`: ``oracle.solve_box_qp`` itself, the one loop the reference-made goldens pin, with its ``alpha``
+argument -- the relaxed step
 
     xh = alpha x + (1 - alpha) z_prev;  z = clamp(xh + u);  r = x - z;  s = rho (z - z_prev);  u = u + (xh - z)
 
-on the oracle's own ``resolve_control``, ``equilibrate``, ``kkt_matrix`` and ``_inf_norm_cols``; at alpha = 1 it gives the oracle's
-bits (test_relax_table.py).  Everything else of an iteration -- right-hand side, the six norms of a check with x_inf taken from x,
-the rho events, the returned x -- is the oracle's.
+At alpha = 1 the argument changes no bit (test_relax_table.py).  Everything else of an iteration -- right-hand side, the six norms of
+a check with x_inf taken from x, the rho events, the returned x -- does not know about alpha.
 
 The pinned rows are records of ``tier_table.row`` with an ``alpha`` on top, so ``tier_table.inputs / batch / sample / control /
 compare`` apply with their bars: float32 |hip - t64| <= R |t32 - t64| + F scale (R = 4, F = 1e-7), float64 1e-9 scale, where t32 /
@@ -69,96 +69,8 @@ EACH_ROW = "split_n130"
 
 
 def solve_relaxed(Q, p, A, b, lb, ub, control, alpha=1.0, trace=None, bounds=None):
-    """``oracle.solve_box_qp`` with the over-relaxed step; returns the same dict.  trace: n_factor / n_solve / n_check."""
-    B, n = Q.shape[0], p.shape[1]
-    m = O._ncon(A, 1)
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    has_lb = bool(torch.max(lb) > -O.INF) if bounds is None else bool(bounds[0])
-    has_ub = bool(torch.min(ub) < O.INF) if bounds is None else bool(bounds[1])
-    has_box = has_lb or has_ub
-    c = O.resolve_control(control, n)
-    rho = c.rho
-    if not has_box:
-        rho = 0
-    if c.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, c.beta, has_box)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E_ = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=c.rho_min, max=c.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor, n_solve, n_check = 1, 0, 0
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * c.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = c.adaptive_rho
-    xv = None
-    it = 0
-    for it in range(c.max_iters):
-        if (c.adaptive_rho and it % c.adaptive_rho_iter == 0 and 0 < it < c.adaptive_rho_max_iter
-                and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            grow = bool((ratio > c.adaptive_rho_tol).sum() > 0)
-            shrink = bool((ratio < 1 / c.adaptive_rho_tol).sum() > 0)
-            if grow or shrink:
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=c.rho_min, max=c.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        n_solve += 1
-        x = xv[:, :n, :]
-        # ---- the relaxed step ----
-        z_old = z
-        xh = alpha * x + (1 - alpha) * z_old
-        z = xh + u
-        if has_lb:
-            z = torch.maximum(z, lbs)
-        if has_ub:
-            z = torch.minimum(z, ubs)
-        r = x - z
-        s = rho * (z - z_old)
-        u = u + (xh - z)
-        # ---- the oracle's check ----
-        if it % c.check_solved == 0:
-            n_check += 1
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * s)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx_inf = O._inf_norm_cols(torch.matmul(Qs, x) / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = c.eps_abs + c.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = c.eps_abs + c.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                break
-    x = D * x
-    z = D * z
-    u = u / D
-    y = u * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E_ if m > 0 else None
-    if trace is not None:
-        trace.update(n_factor=n_factor, n_solve=n_solve, n_check=n_check)
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it}
+    """``oracle.solve_box_qp`` with the over-relaxed step (its ``alpha`` argument); returns the same dict.  trace: the oracle's."""
+    return O.solve_box_qp(Q, p, A, b, lb, ub, control, trace=trace, bounds=bounds, alpha=alpha)
 
 
 def truth(r, inp, dtype, alpha=None):
@@ -209,8 +121,4 @@ def each_truth(dtype, alpha=ALPHA):
     """Every problem of EACH_ROW solved relaxed as a batch of one (the bound flags of the whole batch: both finite)"""
     row = E.ROWS[EACH_ROW]
     qp = E.inputs(row, dtype)
-    out = []
-    for i in range(row["B"]):
-        one = tuple(None if t is None else t[i:i + 1] for t in qp)
-        out.append(solve_relaxed(*one, E.control(row), alpha=alpha, bounds=(True, True)))
-    return out
+    return [solve_relaxed(*E.alone(qp, i), E.control(row), alpha=alpha, **E.ALONE) for i in range(row["B"])]

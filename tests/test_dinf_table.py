@@ -107,10 +107,10 @@ def test_with_the_dual_threshold_off_it_is_solve_detect_bit_for_bit(table, name,
     qp = T.inputs(row, dtype)
     for eps in (IT.EPS, None) if name == "small_n50" else (IT.EPS,):
         for i in range(row["B"]):
-            one = tuple(None if t is None else t[i:i + 1] for t in qp)
+            one = E.alone(qp, i)
             ctl = T.control(row, problem=i) if table == "infeas" else T.control(row)
-            want = IT.solve_detect(*one, ctl, eps_prim_inf=eps, bounds=(True, True))
-            got = DT.solve_certify(*one, ctl, eps_prim_inf=eps, eps_dual_inf=None, bounds=(True, True))
+            want = IT.solve_detect(*one, ctl, eps_prim_inf=eps, **E.ALONE)
+            got = DT.solve_certify(*one, ctl, eps_prim_inf=eps, eps_dual_inf=None, **E.ALONE)
             assert got["dchecks"] == [] and got["as_dx"] == []
             assert all(got[k] == want[k] for k in ("iter", "status", "checks", "n_factor")), (i, eps)
             assert all(_same(got[k], want[k]) for k in KEYS), (i, eps)
@@ -126,9 +126,8 @@ def test_the_new_key_cannot_change_a_verdict_of_the_existing_tables(table, name)
     assert all(bool(torch.isfinite(t).all()) for t in qp[4:])
     prim = IT.EPS if table == "infeas" else None
     for i in range(row["B"]):
-        one = tuple(None if t is None else t[i:i + 1] for t in qp)
         ctl = T.control(row, problem=i) if table == "infeas" else T.control(row)
-        got = DT.solve_certify(*one, ctl, eps_prim_inf=prim, eps_dual_inf=DT.EPS, bounds=(True, True))
+        got = DT.solve_certify(*E.alone(qp, i), ctl, eps_prim_inf=prim, eps_dual_inf=DT.EPS, **E.ALONE)
         assert all(c[3] > DT.EPS for c in got["dchecks"] if c[4] is not None), (i, got["dchecks"])
         assert got["status"] != DT.UNBOUNDED
         if table == "infeas":

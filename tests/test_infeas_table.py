@@ -25,19 +25,58 @@ NEW = ("lqp_boxqp_forward_detect_workspace_bytes", "lqp_boxqp_forward_detect", "
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("name", ["small_n50", "split_n130_event", "f64_n70_m3"])
 def test_the_restatement_without_detection_is_the_oracle(name, dtype):
-    """every problem of a row (the infeasible ones run out of iterations), bit for bit"""
+    """every problem of a row (the infeasible ones run out of iterations), bit for bit: solve_detect attaches its callback with both
+    thresholds off, the oracle here runs without one"""
     row = IT.ROWS[name]
     qp = IT.inputs(row, dtype)
     off = IT.truth(name, dtype, False)
     for i in range(row["B"]):
-        one = tuple(None if t is None else t[i:i + 1] for t in qp)
-        want = O.solve_box_qp(*one, IT.control(row, problem=i), bounds=(True, True))
+        trace = {}
+        want = O.solve_box_qp(*E.alone(qp, i), IT.control(row, problem=i), trace=trace, **E.ALONE)
         got = off[i]
-        assert got["iter"] == want["iter"] and got["checks"] == []
-        assert got["status"] == (IT.OPTIMAL if want["iter"] < row["control"]["max_iters"] - 1 else IT.MAXITER)
+        assert got["iter"] == want["iter"] and got["checks"] == [] and got["n_factor"] == trace["n_factor"]
+        assert got["status"] == trace["status"] == (IT.OPTIMAL if want["iter"] < row["control"]["max_iters"] - 1 else IT.MAXITER)
         for k in KEYS:
             a, b = got[k], want[k]
             assert (a is None and b is None) or torch.equal(torch.as_tensor(a), torch.as_tensor(b)), (i, k)
+
+
+def test_the_oracle_refuses_a_per_check_callback_next_to_a_check_hook():
+    qp = E.inputs(E.ROWS["chunk_n20"], torch.float64)
+    with pytest.raises(ValueError, match="at_check"):
+        O.solve_box_qp(*qp, E.control(E.ROWS["chunk_n20"]), check_hook=lambda counts, k: None, at_check=lambda it, state: 0)
+
+
+def test_a_callback_that_never_flags_changes_no_bit():
+    """through an adaptive-rho event, in both dtypes; it is called at every check that was not optimal, and at no other"""
+    name = "split_n130_event"
+    row = E.ROWS[name]
+    check = O.resolve_control(E.control(row), row["n"]).check_solved
+    for dtype in (torch.float32, torch.float64):
+        qp = E.inputs(row, dtype)
+        plain = E.solo(name, dtype)
+        assert [s["n_factor"] > 1 for s in plain] == row["adapts"] and any(row["adapts"])
+        for i in range(row["B"]):
+            seen, trace = [], {}
+            got = O.solve_box_qp(*E.alone(qp, i), E.control(row), trace=trace, at_check=lambda it, state: seen.append(it) or 0, **E.ALONE)
+            assert got["iter"] == plain[i]["iter"] == row["iters"][i] and trace["n_factor"] == plain[i]["n_factor"]
+            assert trace["status"] == 0 and seen == list(range(0, got["iter"], check)), (i, seen)      # (the last check is the optimal one)
+            for k in KEYS:
+                assert (got[k] is None and plain[i][k] is None) or torch.equal(torch.as_tensor(got[k]), torch.as_tensor(plain[i][k])), (i, k)
+
+
+def test_the_trace_says_how_a_solve_ended():
+    """0: it stopped by itself; 1: it ran to max_iters - 1 -- the row that has both"""
+    row = E.ROWS["chunk_n20"]
+    qp = E.inputs(row, row["dtype"])
+    last = row["control"]["max_iters"] - 1
+    status = []
+    for i in range(row["B"]):
+        trace = {}
+        sol = O.solve_box_qp(*E.alone(qp, i), E.control(row), trace=trace, **E.ALONE)
+        assert sol["iter"] == row["iters"][i] and "status" not in sol
+        status.append(trace["status"])
+    assert status == [1 if it == last else 0 for it in row["iters"]] and set(status) == {0, 1}
 
 
 @pytest.mark.parametrize("name", ROWS)
@@ -64,8 +103,8 @@ def test_every_verdict_stands_clear_of_the_threshold(name, form):
     row = IT.ROWS[name]
     if form == "rhs":
         qp = IT.inputs(row, torch.float32)
-        sols = [[IT.solve_detect(*tuple(None if t is None else t[i:i + 1] for t in qp), IT.control(row, problem=i), eps_prim_inf=IT.EPS,
-                                 bounds=(True, True), qx_from_rhs=True) for i in range(row["B"])]]
+        sols = [[IT.solve_detect(*E.alone(qp, i), IT.control(row, problem=i), eps_prim_inf=IT.EPS, qx_from_rhs=True, **E.ALONE)
+                 for i in range(row["B"])]]
     else:
         sols = [IT.truth(name, torch.float32), IT.truth(name, torch.float64)]
     for t in sols:

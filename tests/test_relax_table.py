@@ -24,6 +24,7 @@ KEYS = ("x", "z", "u", "lams", "nus", "rho")
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("case", list(RT.STOPS))
 def test_the_restatement_at_alpha_one_is_the_oracle(case, dtype):
+    """alpha = 1.0 passed to the oracle (solve_relaxed) against the argument absent, bit for bit"""
     n, B, seed = case
     qp = O.create_qp_data(n, B, seed=seed, dtype=dtype)
     want = O.solve_box_qp(*qp, O.make_control(**RT.STOP_CONTROL))
