@@ -4,7 +4,6 @@
 #include <type_traits>
 #include "lqp_common.hpp"
 #include "lqp_lu.hpp"
-#include "lqp_lu_big.hpp"
 #include "lqp_lu2.hpp"
 #include "lqp_lu_wide.hpp"
 #include "lqp_trsv.hpp"
@@ -789,7 +788,7 @@ __global__ __launch_bounds__(LU2_NT) void k_lu_factor2(T* __restrict__ Mall, con
                          scr + (size_t)b * scr_stride, epoch, xlocal_ok != 0, (dbg && me == 0) ? dbg + (size_t)b * 16 : nullptr);
 }
 
-// 1024 < N <= 2048: two panel rows per thread; to 4096 in float32: four (lqp_lu_big.hpp)
+// 1024 < N <= 2048: two panel rows per thread; to 4096 in float32: four (wg_lu_factor with R > 1; no debug counters)
 template <typename T>
 __global__ __launch_bounds__(LQP_NT) void k_lu_factor_big(T* __restrict__ Mall, const int N, const int ld,
                                                           const size_t mstride, int* __restrict__ piv,
@@ -803,12 +802,12 @@ __global__ __launch_bounds__(LQP_NT) void k_lu_factor_big(T* __restrict__ Mall, 
     // (N is the launch's size, the LDS layout follows it: a smaller Nvec[b] runs on the same form)
     if constexpr (sizeof(T) == 4) {
         if (N > 2048) {           // 2048 < N <= 4096: four rows per thread, panels of 4 columns (2 * 4 * N floats of LDS)
-            wg_lu_factor_big<T, 4, true, 4>(Mall + (size_t)b * mstride, Nvec ? Nvec[b] : N, ld, piv + (size_t)b * pstride, info + b, smem);
+            wg_lu_factor<T, 4, true, LQP_NT, 4>(Mall + (size_t)b * mstride, Nvec ? Nvec[b] : N, ld, piv + (size_t)b * pstride, info + b, smem, nullptr);
             return;
         }
     }
-    wg_lu_factor_big<T, lu_big_panel<T>(), true, 2>(Mall + (size_t)b * mstride, Nvec ? Nvec[b] : N, ld,
-                                                               piv + (size_t)b * pstride, info + b, smem);
+    wg_lu_factor<T, lu_big_panel<T>(), true, LQP_NT, 2>(Mall + (size_t)b * mstride, Nvec ? Nvec[b] : N, ld,
+                                                        piv + (size_t)b * pstride, info + b, smem, nullptr);
 }
 
 template <typename T>

@@ -4,13 +4,16 @@
 // lqp_py/solve_box_qp_admm_torch.py:215,254 and lqp_py/lu_layer.py:10,31.
 //
 // Right-looking, panel width PB:
-//   1. panel  : thread r keeps row k0+r of the panel in registers; per column
-//               a wave max-|.| search (DPP inside 16-lane rows; first index
+//   1. panel  : thread t keeps the rows k0 + t + q * STRIDE, q < R, of the
+//               panel in registers (R = 1 up to N = 1024: k_lu_factor; 2 and
+//               4 above: k_lu_factor_big; 8 and 16 on four waves: the
+//               several-workgroup kernels of lqp_lu_wide.hpp); per column a
+//               wave max-|.| search (DPP inside 16-lane rows; first index
 //               wins ties, as isamax), the pivot row is broadcast through
-//               LDS, rank-1 update in registers;
-//   2. swaps  : the PB row interchanges are composed into one gather map and
-//               applied to the columns left and right of the panel, one
-//               thread per column;
+//               LDS, rank-1 update in registers (lu_panel_columns);
+//   2. swaps  : the PB row interchanges are composed into one gather map
+//               (lu_panel_store) and applied to the columns left and right
+//               of the panel, a thread per column (lu_interchange_column);
 //   3. U12    : the same threads solve L11 * U12 = (P A)12 in registers;
 //   4. update : A22 -= L21 * U12 with L21^T and U12 staged in LDS: MFMA
 //               32x32x2 f32 tiles (C tile prefetched one tile ahead and used
@@ -29,7 +32,7 @@ template <typename T, int PB> struct LuLds {
         up = o;   o += PB * Mpad * (int)sizeof(T);
         l11 = o;  o += round_up(PB * (PB + 1) * (int)sizeof(T), 32);
         rowp = o; o += 2 * LQP_NW * PB * (int)sizeof(T);       // candidate pivot rows [parity][wave][PB]
-        rowj = o; o += round_up(2 * PB * (int)sizeof(T), 32);  // row at the diagonal position [parity][PB]
+        rowj = o; o += round_up(2 * PB * (int)sizeof(T), 32);  // (not used; the slot keeps the layout the host sizes)
         wval = o; o += round_up(2 * LQP_NW * (int)sizeof(T), 32);
         wrcp = o; o += round_up(2 * LQP_NW * (int)sizeof(T), 32);
         widx = o; o += round_up(2 * LQP_NW * 4, 32);
@@ -173,128 +176,311 @@ template <typename T> struct PanelLds {
     T* rowP; T* wval; T* wrcp; int* widx; int* wtid; int* pidx; int* cnt;
 };
 
-// The PB columns of one panel.  `sync` is the barrier among the waves that hold panel rows: the whole
-// workgroup (plain variant) or the panel group only (lookahead variant, the other waves are busy with
-// the previous panel's trailing update).
-template <typename T, int PB, typename SYNC>
-__device__ __forceinline__ void lu_panel_columns(V4<T> (&row4)[PB / 4], int& curpos, bool& done, const bool wact,
-                                                 const int pb, const int k0, const int r, const PanelLds<T>& S,
-                                                 SYNC&& sync) {
+// ---- the panel's rows, R per thread: row q of thread t is relative row t + q * STRIDE -------------------------------------
+// `live`: this thread holds panel rows at all (the kernels whose panel runs on some of their waves only pass tid < STRIDE).
+// A full panel (pb == PB) moves in 16-byte pieces: element by element every lane asked for its line PB times.
+template <typename T, int PB, int R, int STRIDE>
+__device__ __forceinline__ void lu_panel_load(V4<T> (&row4)[R][PB / 4], int (&curpos)[R], bool (&done)[R],
+                                              const T* A, const int ld, const int k0, const int pb,
+                                              const int M, const bool live) {
     typedef V4<T> vec;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T* const rowP = S.rowP; T* const wval = S.wval; T* const wrcp = S.wrcp;
-    int* const widx = S.widx; int* const wtid = S.wtid; int* const pidx = S.pidx; int* const cnt = S.cnt;
-                // ---- unblocked panel factorisation, one column at a time ----
-                // Rows never move between threads: thread r keeps the row it loaded, `curpos` is the
-                // position LAPACK's explicit interchanges would have moved that row to, `done` marks
-                // rows already used as pivots.  Per column: wave arg-max of |a_rj| over the live rows
-                // (ties: smallest position, as isamax), each wave's winner publishes its row, ONE
-                // barrier, cross-wave arg-max, branch-free rank-1 update against the broadcast pivot
-                // row.  The publish buffers alternate with the column parity, so column j+1 never
-                // overwrites what a slow wave still reads for column j.
-    #pragma unroll
-                for (int j = 0; j < PB; ++j) {
-                    if (j < pb) {
-                        const int par = j & 1;
-                        T* cand = rowP + par * (LQP_NW * PB);
-                        T* wv = wval + par * LQP_NW;
-                        int* wi = widx + par * LQP_NW;
-                        int* wt = wtid + par * LQP_NW;
-                        T* wr = wrcp + par * LQP_NW;
-                        if (wact) {
-                            const T aj = row4[j >> 2].v[j & 3];
-                            const T key = done ? T(-1) : tabs(aj);
-                            T myrcp = T(1) / aj;                 // independent of the arg-max chain below
-                            asm volatile("" : "+v"(myrcp));      // keep it out of the winner-only branch
-                            T bw; int lb;
-                            wave_argmax(key, bw, lb);
-                            const unsigned long long tied = __ballot(key == bw);
-                            if (__popcll(tied) > 1) {                            // rare: smallest position wins
-                                int cp = (key == bw) ? curpos : 0x7fffffff;
-                                cp = row16_min_i32(cp);
-                                cp = min(min(__builtin_amdgcn_readlane(cp, 0), __builtin_amdgcn_readlane(cp, 16)),
-                                         min(__builtin_amdgcn_readlane(cp, 32), __builtin_amdgcn_readlane(cp, 48)));
-                                lb = __ffsll((unsigned long long)__ballot(key == bw && curpos == cp)) - 1;
-                            }
-                            if (lane == lb) {
-                                wv[w] = bw;
-                                wr[w] = myrcp;
-                                wi[w] = curpos;
-                                wt[w] = r;
-    #pragma unroll
-                                for (int q = 0; q < PB / 4; ++q) *(vec*)(cand + w * PB + 4 * q) = row4[q];
-                            }
-                        } else if (lane == 0) {
-                            wv[w] = T(-2);                                       // can never win
-                        }
-                        sync();
-                        if (wact) {
-                            // cross-wave arg-max: lane l looks at wave (l & 15)'s winner
-                            const T cv = wv[lane & 15];
-                            const int ci = wi[lane & 15];
-                            const int ct = wt[lane & 15];
-                            const T best = row16_max(cv);
-                            const unsigned long long tied = __ballot(cv == best) & 0xFFFFull;
-                            int ww = __ffsll(tied) - 1;
-                            if (__popcll(tied) > 1) {
-                                const int cp = row16_min_i32((cv == best) ? ci : 0x7fffffff);
-                                ww = __ffsll((unsigned long long)__ballot(cv == best && ci == cp) & 0xFFFFull) - 1;
-                            }
-                            const int pivpos = __builtin_amdgcn_readlane(ci, ww);    // pivot row's position before the swap
-                            const int bi = __builtin_amdgcn_readlane(ct, ww);        // thread that owns the pivot row
-                            // the whole pivot row, 16 B per LDS read, all reads independent
-                            const T* rowPc = cand + ww * PB;
-                            vec pr[PB / 4];
-    #pragma unroll
-                            for (int q = j >> 2; q < PB / 4; ++q) pr[q] = *(const vec*)(rowPc + 4 * q);
-                            const T rinv = wr[ww];
-                            if (r == bi) {
-                                pidx[j] = pivpos;      // pivots / info go to global memory once per panel
-                                if (!(best > T(0)) && cnt[1] == 0) cnt[1] = k0 + j + 1;
-                                curpos = j;
-                                done = true;
-                            } else if (curpos == j) {
-                                curpos = pivpos;       // the row that sat on the diagonal takes the pivot's old place
-                            }
-                            // branch-free elimination: finished rows (and a zero pivot column, as getf2) use l = 0
-                            const bool upd = !done && (best > T(0));
-                            const T aj = row4[j >> 2].v[j & 3];
-                            const T l = upd ? aj * rinv : T(0);
-                            row4[j >> 2].v[j & 3] = upd ? l : aj;
-    #pragma unroll
-                            for (int c = j + 1; c < PB; ++c)
-                                row4[c >> 2].v[c & 3] -= l * pr[c >> 2].v[c & 3];
-                        }
-                    }
-                }
-
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        curpos[q] = (int)threadIdx.x + q * STRIDE;      // LAPACK position of this row
+        done[q] = !(live && curpos[q] < M);             // already a pivot row (or no row at all)
+    }
+    if (pb == PB) {
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const T* rp = A + (size_t)(k0 + (int)threadIdx.x + q * STRIDE) * ld + k0;
+#pragma unroll
+            for (int v = 0; v < PB / 4; ++v) {
+                if (!done[q]) row4[q][v] = *(const vec*)(rp + 4 * v);
+                else { row4[q][v].v[0] = row4[q][v].v[1] = row4[q][v].v[2] = row4[q][v].v[3] = T(0); }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < R; ++q) {
+            const T* rp = A + (size_t)(k0 + (int)threadIdx.x + q * STRIDE) * ld + k0;
+#pragma unroll
+            for (int c = 0; c < PB; ++c) row4[q][c >> 2].v[c & 3] = (!done[q] && c < pb) ? rp[c] : T(0);
+        }
+    }
 }
 
+// The PB columns of one panel: unblocked factorisation, one column at a time.
+// Rows never move between threads: a thread keeps the rows it loaded, `curpos` is the position LAPACK's explicit
+// interchanges would have moved a row to, `done` marks rows already used as pivots.  Per column: the thread's best live
+// row, wave arg-max of |a_rj| (ties: smallest position, as isamax), each wave's winner publishes its row, ONE barrier
+// of the whole workgroup, cross-wave arg-max, branch-free rank-1 update against the broadcast pivot row.  Factoring goes
+// on past a zero pivot (l = 0, as getf2); the first one is noted in cnt[1].  The publish buffers alternate with the
+// column parity, so column j+1 never overwrites what a slow wave still reads for column j.
+template <typename T, int PB, int R, int STRIDE>
+__device__ __forceinline__ void lu_panel_columns(V4<T> (&row4)[R][PB / 4], int (&curpos)[R], bool (&done)[R],
+                                                 const bool wact, const int pb, const int k0, const PanelLds<T>& S) {
+    typedef V4<T> vec;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    T* const rowP = S.rowP; T* const wval = S.wval; T* const wrcp = S.wrcp;
+    int* const widx = S.widx; int* const wtid = S.wtid; int* const pidx = S.pidx; int* const cnt = S.cnt;
+#pragma unroll
+    for (int j = 0; j < PB; ++j) {
+        if (j < pb) {
+            const int par = j & 1;
+            T* cand = rowP + par * (LQP_NW * PB);
+            T* wv = wval + par * LQP_NW;
+            int* wi = widx + par * LQP_NW;
+            int* wt = wtid + par * LQP_NW;
+            T* wr = wrcp + par * LQP_NW;
+            if (wact) {
+                // this thread's best live row: largest |a_rj|, ties to the smaller position
+                T aj = row4[0][j >> 2].v[j & 3];
+                T key = done[0] ? T(-1) : tabs(aj);
+                int cp = curpos[0], qs = 0;
+#pragma unroll
+                for (int q = 1; q < R; ++q) {
+                    const T a = row4[q][j >> 2].v[j & 3];
+                    const T kq = done[q] ? T(-1) : tabs(a);
+                    const bool better = kq > key || (kq == key && kq >= T(0) && curpos[q] < cp);
+                    if (better) { key = kq; aj = a; cp = curpos[q]; qs = q; }
+                }
+                T myrcp = T(1) / aj;                 // independent of the arg-max chain below
+                asm volatile("" : "+v"(myrcp));      // keep it out of the winner-only branch
+                T bw; int lb;
+                wave_argmax(key, bw, lb);
+                const unsigned long long tied = __ballot(key == bw);
+                if (__popcll(tied) > 1) {                            // rare: smallest position wins
+                    int c2 = (key == bw) ? cp : 0x7fffffff;
+                    c2 = row16_min_i32(c2);
+                    c2 = min(min(__builtin_amdgcn_readlane(c2, 0), __builtin_amdgcn_readlane(c2, 16)),
+                             min(__builtin_amdgcn_readlane(c2, 32), __builtin_amdgcn_readlane(c2, 48)));
+                    lb = __ffsll((unsigned long long)__ballot(key == bw && cp == c2)) - 1;
+                }
+                if (lane == lb) {
+                    wv[w] = bw;
+                    wr[w] = myrcp;
+                    wi[w] = cp;
+                    wt[w] = tid + qs * STRIDE;
+#pragma unroll
+                    for (int q4 = 0; q4 < PB / 4; ++q4) {
+                        vec o = row4[0][q4];
+#pragma unroll
+                        for (int q = 1; q < R; ++q)
+                            if (qs == q) o = row4[q][q4];
+                        *(vec*)(cand + w * PB + 4 * q4) = o;
+                    }
+                }
+            } else if (lane == 0) {
+                wv[w] = T(-2);                                       // can never win
+            }
+            __syncthreads();
+            if (wact) {
+                // cross-wave arg-max: lane l looks at wave (l & 15)'s winner
+                const T cv = wv[lane & 15];
+                const int ci = wi[lane & 15];
+                const int ct = wt[lane & 15];
+                const T best = row16_max(cv);
+                const unsigned long long tied = __ballot(cv == best) & 0xFFFFull;
+                int ww = __ffsll(tied) - 1;
+                if (__popcll(tied) > 1) {
+                    const int c2 = row16_min_i32((cv == best) ? ci : 0x7fffffff);
+                    ww = __ffsll((unsigned long long)__ballot(cv == best && ci == c2) & 0xFFFFull) - 1;
+                }
+                const int pivpos = __builtin_amdgcn_readlane(ci, ww);    // pivot row's position before the swap
+                const int bi = __builtin_amdgcn_readlane(ct, ww);        // (thread + q * STRIDE) that owns the pivot row
+                // the whole pivot row, 16 B per LDS read, all reads independent
+                const T* rowPc = cand + ww * PB;
+                vec pr[PB / 4];
+#pragma unroll
+                for (int q4 = j >> 2; q4 < PB / 4; ++q4) pr[q4] = *(const vec*)(rowPc + 4 * q4);
+                const T rinv = wr[ww];
+#pragma unroll
+                for (int q = 0; q < R; ++q) {
+                    if (tid + q * STRIDE == bi) {
+                        pidx[j] = pivpos;      // pivots / info go to global memory once per panel
+                        if (!(best > T(0)) && cnt[1] == 0) cnt[1] = k0 + j + 1;
+                        curpos[q] = j;
+                        done[q] = true;
+                    } else if (curpos[q] == j) {
+                        curpos[q] = pivpos;    // the row that sat on the diagonal takes the pivot's old place
+                    }
+                    // branch-free elimination: finished rows (and a zero pivot column, as getf2) use l = 0
+                    const bool upd = !done[q] && (best > T(0));
+                    const T a = row4[q][j >> 2].v[j & 3];
+                    const T l = upd ? a * rinv : T(0);
+                    row4[q][j >> 2].v[j & 3] = upd ? l : a;
+#pragma unroll
+                    for (int c = j + 1; c < PB; ++c)
+                        row4[q][c >> 2].v[c & 3] -= l * pr[c >> 2].v[c & 3];
+                }
+            }
+        }
+    }
+}
+
+// Write the factored panel back at its final position; stage L11 and L21^T in LDS; note the gather map of the
+// interchanges: src (position -> original relative row) and the displaced top rows that ended below the panel top
+// (xsrc -> xdst, *cnt of them; their sources are always < pb).
+template <typename T, int PB, int R, int STRIDE>
+__device__ __forceinline__ void lu_panel_store(const V4<T> (&row4)[R][PB / 4], const int (&curpos)[R],
+                                               T* A, const int ld, const int k0, const int pb, const int M,
+                                               const bool live, T* L11, T* LT, const int Mpad,
+                                               int* src, int* xdst, int* xsrc,
+                                               int* cnt) {
+    typedef V4<T> vec;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        const int r = (int)threadIdx.x + q * STRIDE;
+        if (live && r < M) {
+            const int cp = curpos[q];
+            T* wp = A + (size_t)(k0 + cp) * ld + k0;
+            if (pb == PB) {
+#pragma unroll
+                for (int v = 0; v < PB / 4; ++v) *(vec*)(wp + 4 * v) = row4[q][v];
+            } else {
+#pragma unroll
+                for (int c = 0; c < PB; ++c)
+                    if (c < pb) wp[c] = row4[q][c >> 2].v[c & 3];
+            }
+            if (cp < pb) {
+#pragma unroll
+                for (int c = 0; c < PB; ++c) L11[cp * (PB + 1) + c] = row4[q][c >> 2].v[c & 3];
+            } else {
+#pragma unroll
+                for (int c = 0; c < PB; ++c) LT[c * Mpad + (cp - pb)] = row4[q][c >> 2].v[c & 3];
+            }
+            src[cp] = r;
+            if (cp >= pb && cp != r) {
+                const int e = atomicAdd(cnt, 1);
+                xdst[e] = cp;
+                xsrc[e] = r;
+            }
+        }
+    }
+}
+
+// does the panel move any row at all?  (wave-uniform)
+template <int PB> __device__ __forceinline__ bool lu_any_interchange(const int* src, const int pb, const int ne) {
+    bool any = ne > 0;
+#pragma unroll
+    for (int j = 0; j < PB; ++j)
+        if (j < pb && __builtin_amdgcn_readfirstlane(src[j]) != j) any = true;
+    return any;
+}
+
+// One column left (`right` false) or right of the panel, Ac = its element in row k0: apply the panel's interchanges and, right
+// of the panel, solve L11 * U12 = (P A)12 for the column.  `top` holds the column's new top rows; `stage()` is the caller's store
+// of them into its own U12 layout for the trailing update.  It runs BEFORE the rows go back to global memory: the barrier in
+// front of the trailing update waits for the LDS stores only, and behind a queue of float64 global stores they arrived late.
+template <typename T, int PB, typename STAGE>
+__device__ __forceinline__ void lu_interchange_column(T* Ac, const int ld, const bool right, const int pb,
+                                                      const int ne, const int* src,
+                                                      const int* xsrc, const int* xdst,
+                                                      const T* L11, T (&top)[PB], STAGE&& stage) {
+    // (1) new top rows: sources anywhere in the panel rows
+#pragma unroll
+    for (int j = 0; j < PB; ++j)
+        top[j] = (j < pb) ? Ac[(size_t)__builtin_amdgcn_readfirstlane(src[j]) * ld] : T(0);
+    // (2) displaced top rows go down, at most 8 at a time (their sources are original top rows, which are only
+    //     overwritten in step (4); ne <= pb, so panels of up to 8 columns take one trip)
+    constexpr int G = PB < 8 ? PB : 8;
+    for (int q0 = 0; q0 < ne; q0 += G) {
+        T ext[G];
+#pragma unroll
+        for (int q = 0; q < G; ++q)
+            ext[q] = (q0 + q < ne) ? Ac[(size_t)__builtin_amdgcn_readfirstlane(xsrc[q0 + q]) * ld] : T(0);
+#pragma unroll
+        for (int q = 0; q < G; ++q)
+            if (q0 + q < ne) Ac[(size_t)__builtin_amdgcn_readfirstlane(xdst[q0 + q]) * ld] = ext[q];
+    }
+    // (3) U12 column: forward substitution with the unit-lower L11
+    if (right) {
+#pragma unroll
+        for (int j = 0; j < PB; ++j) {
+#pragma unroll
+            for (int i = j + 1; i < PB; ++i) top[i] -= L11[i * (PB + 1) + j] * top[j];
+        }
+        stage();
+    }
+    // (4) store the new top rows
+#pragma unroll
+    for (int j = 0; j < PB; ++j)
+        if (j < pb && (right || __builtin_amdgcn_readfirstlane(src[j]) != j)) Ac[(size_t)j * ld] = top[j];
+}
+
+// Trailing update on the vector unit: 8 x 4 tiles of A22 per thread.
+template <typename T, int PB, int NT>
+__device__ __forceinline__ void lu_trailing_valu(T* __restrict__ A22, const int ld, const int M2,
+                                                 const T* __restrict__ LT, const T* __restrict__ UP, const int Mpad) {
+    typedef V4<T> vec;
+    const int tj_n = (M2 + 3) >> 2, ti_n = (M2 + 7) >> 3;
+    for (int t = threadIdx.x; t < ti_n * tj_n; t += NT) {
+        const int ti = t / tj_n, tj = t - ti * tj_n;
+        const int i0 = ti << 3, j0 = tj << 2;
+        T acc[8][4];
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = T(0);
+#pragma unroll 4
+        for (int k = 0; k < PB; ++k) {
+            const vec a0 = *(const vec*)(LT + k * Mpad + i0);
+            const vec a1 = *(const vec*)(LT + k * Mpad + i0 + 4);
+            const vec b0 = *(const vec*)(UP + k * Mpad + j0);
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    acc[a][b] += a0.v[a] * b0.v[b];
+                    acc[a + 4][b] += a1.v[a] * b0.v[b];
+                }
+        }
+        const bool fullj = j0 + 3 < M2;
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            if (i0 + a < M2) {
+                T* p = A22 + (size_t)(i0 + a) * ld + j0;
+                if (fullj) {
+                    vec c = *(const vec*)p;
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) c.v[b] -= acc[a][b];
+                    *(vec*)p = c;
+                } else {
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (j0 + b < M2) p[b] -= acc[a][b];
+                }
+            }
+        }
+    }
+}
+
+// One workgroup of NT threads (512 or 1024) factors one matrix, R panel rows per thread: rows per panel N - k0 <= R * NT.
+// R = 1 is the tuned kernel of N <= 1024; R = 2 takes 1024 < N <= 2048 and R = 4 float32 to 4096 (k_lu_factor_big: the
+// matrix stays in global memory, 16 MB at N = 2048, and panels are lu_big_panel() or 4 columns wide so that L21^T and U12
+// still fit in LDS).
 // dbg (optional): 4 cycle counters per workgroup: panel, swaps+U12, trailing update, total
-// NT = threads in the workgroup (512 or 1024); rows per panel N - k0 <= NT and columns N - PB <= NT
-template <typename T, int PB, bool USE_MFMA, int NT>
+template <typename T, int PB, bool USE_MFMA, int NT, int R = 1>
 __device__ __forceinline__ void wg_lu_factor(T* __restrict__ A, const int N, const int ld, int* __restrict__ ipiv,
                                              int* __restrict__ info, char* __restrict__ smem,
                                              unsigned long long* __restrict__ dbg) {
-    const int Mpad = round_up(N, 64);
+    // (N may come out of a per-problem size table, and then the LDS layout and every c * Mpad of the staging stores sit in vector
+    //  registers across the whole factorisation.  A 1024-thread workgroup has 128 of them per thread and none to spare: float64
+    //  with 16-column panels spills more than its ceiling in tests/test_abi_and_host.py without this.  512 threads have 256.)
+    const int Mpad = NT == 1024 ? __builtin_amdgcn_readfirstlane(round_up(N, 64)) : round_up(N, 64);
     const LuLds<T, PB> L(Mpad);
     T* LT = (T*)(smem + L.lt);
     T* UP = (T*)(smem + L.up);
     T* L11 = (T*)(smem + L.l11);
-    T* rowP = (T*)(smem + L.rowp);
-    T* rowJ = (T*)(smem + L.rowj);
     T* wval = (T*)(smem + L.wval);
-    T* wrcp = (T*)(smem + L.wrcp);
-    int* widx = (int*)(smem + L.widx);
-    int* wtid = (int*)(smem + L.wtid);
     int* pidx = (int*)(smem + L.pidx);
     int* src = (int*)(smem + L.src);
     int* xdst = (int*)(smem + L.xdst);
     int* xsrc = (int*)(smem + L.xsrc);
     int* cnt = (int*)(smem + L.cnt);
+    const PanelLds<T> S{(T*)(smem + L.rowp), wval, (T*)(smem + L.wrcp), (int*)(smem + L.widx), (int*)(smem + L.wtid), pidx, cnt};
 
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    typedef V4<T> vec;
+    const int tid = threadIdx.x;
     const int wbase = __builtin_amdgcn_readfirstlane(tid & ~63);     // first row handled by this wave
     if (tid == 0) cnt[1] = 0;       // first zero pivot (1-based) seen by this factorisation, 0 = none
     if (tid < 2 * LQP_NW) wval[tid] = T(-2);     // slots of waves that do not exist (NT < 1024) never win
@@ -305,108 +491,38 @@ __device__ __forceinline__ void wg_lu_factor(T* __restrict__ A, const int N, con
         const int pb = (N - k0 < PB) ? (N - k0) : PB;
         const int M = N - k0;
         const int M2 = M - pb;
-        const int r = tid;
-        const bool act = r < M;
         if (dbg) t0 = clock64();
         {
-            // this thread's panel row as PB/4 four-wide vectors: row element c = row4[c >> 2].v[c & 3]
-            vec row4[PB / 4];
-            int curpos = r;             // LAPACK position of this thread's row
-            bool done = !act;           // already a pivot row (or no row at all)
-            const bool wact = wbase < M;   // this wave holds rows of the panel (loop-invariant, wave-uniform)
-            // ---- load this thread's panel row ----
-            if (pb == PB) {
-#pragma unroll
-                for (int q = 0; q < PB / 4; ++q) {
-                    if (act) row4[q] = *(const vec*)(A + (size_t)(k0 + r) * ld + k0 + 4 * q);
-                    else { row4[q].v[0] = row4[q].v[1] = row4[q].v[2] = row4[q].v[3] = T(0); }
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < PB; ++c)
-                    row4[c >> 2].v[c & 3] = (act && c < pb) ? A[(size_t)(k0 + r) * ld + k0 + c] : T(0);
-            }
+            // this thread's panel rows as PB/4 four-wide vectors: element c of row q = row4[q][c >> 2].v[c & 3]
+            V4<T> row4[R][PB / 4];
+            int curpos[R];
+            bool done[R];
+            const bool wact = wbase < M;   // this wave holds rows of the panel (wave-uniform)
+            lu_panel_load<T, PB, R, NT>(row4, curpos, done, A, ld, k0, pb, M, true);
             if (tid == 0) *cnt = 0;
-
-            // ---- unblocked panel factorisation, one column at a time (barrier = whole workgroup) ----
-            {
-                const PanelLds<T> S{rowP, wval, wrcp, widx, wtid, pidx, cnt};
-                lu_panel_columns<T, PB>(row4, curpos, done, wact, pb, k0, r, S, [] { __syncthreads(); });
-            }
-
-            // ---- write the factored panel back at its final position; stage L11 and L21^T in LDS ----
-            if (act) {
-                if (pb == PB) {
-#pragma unroll
-                    for (int q = 0; q < PB / 4; ++q)
-                        *(vec*)(A + (size_t)(k0 + curpos) * ld + k0 + 4 * q) = row4[q];
-                } else {
-#pragma unroll
-                    for (int c = 0; c < PB; ++c)
-                        if (c < pb) A[(size_t)(k0 + curpos) * ld + k0 + c] = row4[c >> 2].v[c & 3];
-                }
-                if (curpos < pb) {
-#pragma unroll
-                    for (int c = 0; c < PB; ++c) L11[curpos * (PB + 1) + c] = row4[c >> 2].v[c & 3];
-                } else {
-#pragma unroll
-                    for (int c = 0; c < PB; ++c) LT[c * Mpad + (curpos - pb)] = row4[c >> 2].v[c & 3];
-                }
-                src[curpos] = r;                        // position -> original (relative) row
-                // a displaced top row that ended below the panel top (its source is always < pb)
-                if (curpos >= pb && curpos != r) {
-                    const int q = atomicAdd(cnt, 1);
-                    xdst[q] = curpos;
-                    xsrc[q] = r;
-                }
-            }
+            lu_panel_columns<T, PB, R, NT>(row4, curpos, done, wact, pb, k0, S);
+            lu_panel_store<T, PB, R, NT>(row4, curpos, A, ld, k0, pb, M, true, L11, LT, Mpad, src, xdst, xsrc, cnt);
         }
         __syncthreads();
         if (tid < pb) ipiv[k0 + tid] = k0 + pidx[tid] + 1;
         if (dbg) { const unsigned long long t1 = clock64(); t_panel += t1 - t0; t0 = t1; }
         const int ne = __builtin_amdgcn_readfirstlane(*cnt);
-        bool anyswap = ne > 0;
-#pragma unroll
-        for (int j = 0; j < PB; ++j)
-            if (j < pb && __builtin_amdgcn_readfirstlane(src[j]) != j) anyswap = true;
+        const bool anyswap = lu_any_interchange<PB>(src, pb, ne);
 
-        // ---- apply the interchanges left and right of the panel; U12 = L11^-1 (PA)12 ----
-        if (tid < N - pb) {
-            const bool right = tid >= k0;
-            const int col = right ? tid + pb : tid;
+        // ---- apply the interchanges left and right of the panel; U12 = L11^-1 (PA)12: one column at a time per thread ----
+        for (int cc = tid; cc < N - pb; cc += NT) {
+            const bool right = cc >= k0;
+            const int col = right ? cc + pb : cc;
             if (right || anyswap) {
-                T* Ac = A + (size_t)k0 * ld + col;
                 T top[PB];
-                // (1) new top rows: sources anywhere in the panel rows
-#pragma unroll
-                for (int j = 0; j < PB; ++j)
-                    top[j] = (j < pb) ? Ac[(size_t)__builtin_amdgcn_readfirstlane(src[j]) * ld] : T(0);
-                // (2) displaced top rows go down, 8 at a time (their sources are original
-                //     top rows, which are only overwritten in step (4))
-                for (int q0 = 0; q0 < ne; q0 += 8) {
-                    T ext[8];
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        ext[q] = (q0 + q < ne) ? Ac[(size_t)__builtin_amdgcn_readfirstlane(xsrc[q0 + q]) * ld] : T(0);
-#pragma unroll
-                    for (int q = 0; q < 8; ++q)
-                        if (q0 + q < ne) Ac[(size_t)__builtin_amdgcn_readfirstlane(xdst[q0 + q]) * ld] = ext[q];
-                }
-                // (3) U12 column: forward substitution with the unit-lower L11
-                if (right) {
-#pragma unroll
-                    for (int j = 0; j < PB; ++j) {
-#pragma unroll
-                        for (int i = j + 1; i < PB; ++i) top[i] -= L11[i * (PB + 1) + j] * top[j];
-                    }
+                lu_interchange_column<T, PB>(A + (size_t)k0 * ld + col, ld, right, pb, ne, src, xsrc, xdst, L11, top, [&] {
 #pragma unroll
                     for (int j = 0; j < PB; ++j) UP[j * Mpad + (col - k0 - pb)] = top[j];
-                }
-                // (4) store the new top rows
-#pragma unroll
-                for (int j = 0; j < PB; ++j)
-                    if (j < pb && (right || __builtin_amdgcn_readfirstlane(src[j]) != j)) Ac[(size_t)j * ld] = top[j];
+                });
             }
+            // (N - pb <= NT at R = 1, one trip: said to the compiler, since a loop counter and its bound kept live across the
+            //  column step put float64 with 16-column panels on 1024 threads over its spill ceiling in tests/test_abi_and_host.py)
+            if constexpr (R == 1) break;
         }
         __syncthreads();
         if (dbg) { const unsigned long long t1 = clock64(); t_swap += t1 - t0; t0 = t1; }
@@ -419,46 +535,7 @@ __device__ __forceinline__ void wg_lu_factor(T* __restrict__ A, const int N, con
             } else if constexpr (USE_MFMA) {
                 lu_trailing_mfma_f64<PB, NT>((double*)A22, ld, M2, (const double*)LT, (const double*)UP, Mpad);
             } else {
-                const int tj_n = (M2 + 3) >> 2, ti_n = (M2 + 7) >> 3;
-                for (int t = tid; t < ti_n * tj_n; t += NT) {
-                    const int ti = t / tj_n, tj = t - ti * tj_n;
-                    const int i0 = ti << 3, j0 = tj << 2;
-                    T acc[8][4];
-#pragma unroll
-                    for (int a = 0; a < 8; ++a)
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) acc[a][b] = T(0);
-#pragma unroll 4
-                    for (int k = 0; k < PB; ++k) {
-                        const vec a0 = *(const vec*)(LT + k * Mpad + i0);
-                        const vec a1 = *(const vec*)(LT + k * Mpad + i0 + 4);
-                        const vec b0 = *(const vec*)(UP + k * Mpad + j0);
-#pragma unroll
-                        for (int a = 0; a < 4; ++a)
-#pragma unroll
-                            for (int b = 0; b < 4; ++b) {
-                                acc[a][b] += a0.v[a] * b0.v[b];
-                                acc[a + 4][b] += a1.v[a] * b0.v[b];
-                            }
-                    }
-                    const bool fullj = j0 + 3 < M2;
-#pragma unroll
-                    for (int a = 0; a < 8; ++a) {
-                        if (i0 + a < M2) {
-                            T* p = A22 + (size_t)(i0 + a) * ld + j0;
-                            if (fullj) {
-                                vec c = *(const vec*)p;
-#pragma unroll
-                                for (int b = 0; b < 4; ++b) c.v[b] -= acc[a][b];
-                                *(vec*)p = c;
-                            } else {
-#pragma unroll
-                                for (int b = 0; b < 4; ++b)
-                                    if (j0 + b < M2) p[b] -= acc[a][b];
-                            }
-                        }
-                    }
-                }
+                lu_trailing_valu<T, PB, NT>(A22, ld, M2, LT, UP, Mpad);
             }
         }
         __syncthreads();
@@ -469,6 +546,9 @@ __device__ __forceinline__ void wg_lu_factor(T* __restrict__ A, const int N, con
         dbg[0] = t_panel; dbg[1] = t_swap; dbg[2] = t_trail; dbg[3] = clock64() - t_begin;
     }
 }
+
+// panel width of the R > 1 forms (and of the several-workgroup kernels of lqp_lu_wide.hpp): 2 * PB * Mpad elements of LDS
+template <typename T> __host__ __device__ constexpr int lu_big_panel() { return sizeof(T) == 4 ? 8 : 4; }
 
 // (A look-ahead variant inside ONE workgroup -- waves 0-7 factoring panel k+1 while waves 8-15 ran panel k's trailing update -- was
 //  measured no faster in rounds 1-2 and is gone from the sources; the look-ahead that pays runs on two CUs: lqp_lu2.hpp.)

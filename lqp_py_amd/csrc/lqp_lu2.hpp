@@ -368,10 +368,6 @@ __device__ __forceinline__ void lu2_tile_finish(const Lu2Tile<T, PB>& t, T* __re
     }
 }
 
-template <typename T> struct Panel2Lds {
-    T* rowP; T* wval; T* wrcp; int* widx; int* wtid; int* pidx; int* cnt;
-};
-
 // The PB columns of one panel on LU2_PW waves: row a = relative row t and -- TWO: panels of more than 256 rows -- row b =
 // t + 256.  Same per-element arithmetic and the same pivot rule as lu_panel_columns (max |.|, ties to the smallest position).
 // Every wave of the workgroup calls it (the barrier per column is the workgroup's); waves >= LU2_PW only synchronise.
@@ -379,7 +375,7 @@ template <typename T> struct Panel2Lds {
 // knows them).
 template <typename T, int PB, bool TWO>
 __device__ __forceinline__ void lu2_panel_columns(V4<T> (&ra)[PB / 4], V4<T> (&rb)[PB / 4], int& posa, int& posb, bool& donea,
-                                                  bool& doneb, const int pb, const int k0, const Panel2Lds<T>& S) {
+                                                  bool& doneb, const int pb, const int k0, const PanelLds<T>& S) {
     typedef V4<T> vec;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const bool pw = w < LU2_PW;
@@ -595,8 +591,8 @@ __device__ __forceinline__ void wg_lu_factor2(T* __restrict__ A, const int N, co
     int* pxdst = (int*)(smem + L.pxdst);
     int* pxsrc = (int*)(smem + L.pxsrc);
     int* cnt = (int*)(smem + L.cnt);
-    const Panel2Lds<T> S{(T*)(smem + L.rowp), (T*)(smem + L.wval), (T*)(smem + L.wrcp), (int*)(smem + L.widx),
-                         (int*)(smem + L.wtid), pidx, cnt};
+    const PanelLds<T> S{(T*)(smem + L.rowp), (T*)(smem + L.wval), (T*)(smem + L.wrcp), (int*)(smem + L.widx),
+                        (int*)(smem + L.wtid), pidx, cnt};
     const int tid = threadIdx.x;
     const int nblk = (N + PB - 1) / PB;
     int* const msg_base = (int*)(scr + 8);

@@ -1,19 +1,18 @@
 // Pivoted LU above the one-row-per-thread tier (1024 < N <= 2048; float32 to 4096: k_lu_factor_wide_tall) on SEVERAL workgroups per matrix, for batches that leave the
-// chip idle (B = 8, n = 1500: the one-workgroup kernel of lqp_lu_big.hpp streams the trailing matrix through ONE CU 188 times --
+// chip idle (B = 8, n = 1500: the one-workgroup kernel k_lu_factor_big streams the trailing matrix through ONE CU 188 times --
 // 25 ms per factorisation, 34 of the 47 ms of a forward + backward step).  Same right-looking algorithm, LAPACK layout and pivot
-// rule (replaces torch.linalg.lu_factor at lqp_py/solve_box_qp_admm_torch.py:215,254, lqp_py/lu_layer.py:10,31), float32.
+// rule (replaces torch.linalg.lu_factor at lqp_py/solve_box_qp_admm_torch.py:215,254, lqp_py/lu_layer.py:10,31), float32 and float64.
 //
 // Columns are dealt out in tiles of 32 (one 128-B line per row): tile g belongs to workgroup g % W for the whole factorisation,
 // and NOBODY else ever reads or writes those columns of the matrix -- the owner brings them up to date, factors the panels that
-// lie in them (PB = 8 columns, two rows per thread, the code of the one-workgroup kernel), applies the interchanges to them when
-// they are left of the panel.  What crosses between workgroups is the factored panel alone: L21^T (PB x M2), L11, the gather map
+// lie in them (PB = 8 | 4 columns, R rows per thread of four waves: lu_panel_load / _columns / _store of lqp_lu.hpp), applies the interchanges to them when
+// they are left of the panel (lu_interchange_column, the same file).  What crosses between workgroups is the factored panel alone: L21^T (PB x M2), L11, the gather map
 // of the interchanges -- a message in a two-slot ring in global memory, written through (sc1 stores), one tagged `go` word per
 // slot, read with sc1 loads (MI355X_MICROARCH R1: the form of lqp_lu2.hpp).  No barrier between the workgroups: a consumer
 // waits for the message of panel k, the publisher of panel k waits until every workgroup has taken message k - 2 out of the slot
 // it is about to overwrite (one progress word per workgroup).  All W B workgroups must be resident (the host checks).
 #pragma once
 #include "lqp_lu2.hpp"
-#include "lqp_lu_big.hpp"
 
 namespace lqp {
 
@@ -51,7 +50,7 @@ __device__ __forceinline__ void wg_lu_factor_wide(T* __restrict__ Mall, const in
                                                   const int* __restrict__ gate, const int* __restrict__ Nvec,
                                                   int* __restrict__ scr_all, const size_t scr_stride, const unsigned int epoch,
                                                   const int B, unsigned long long* __restrict__ dbg, char* __restrict__ smem) {
-    constexpr int NT = LQP_NT, TW = luw_tw<T>(), NV = PB / 4;
+    constexpr int NT = LQP_NT, TW = luw_tw<T>();
     constexpr int NTP = 256;                  // the panel: waves 0..3, R rows per thread (sixteen waves with two rows each share four SIMDs:
                                               // 7 k cycles per column; four waves alone on theirs: see DESIGN.md)
     static_assert(PB <= luw_pb<T>() && PB % 4 == 0, "the message slots are sized for the widest panel");
@@ -66,16 +65,13 @@ __device__ __forceinline__ void wg_lu_factor_wide(T* __restrict__ Mall, const in
     T* LT = (T*)(smem + L.lt);
     T* UPt = (T*)(smem + L.up);                           // [own tile slot][PB][32]
     T* L11 = (T*)(smem + L.l11);
-    T* rowP = (T*)(smem + L.rowp);
     T* wval = (T*)(smem + L.wval);
-    T* wrcp = (T*)(smem + L.wrcp);
-    int* widx = (int*)(smem + L.widx);
-    int* wtid = (int*)(smem + L.wtid);
     int* pidx = (int*)(smem + L.pidx);
     int* src = (int*)(smem + L.src);
     int* xdst = (int*)(smem + L.xdst);
     int* xsrc = (int*)(smem + L.xsrc);
     int* cnt = (int*)(smem + L.cnt);                      // [0] interchange count | [1] first zero pivot | [2] failed | [3] ne of the message
+    const PanelLds<T> S{(T*)(smem + L.rowp), wval, (T*)(smem + L.wrcp), (int*)(smem + L.widx), (int*)(smem + L.wtid), pidx, cnt};
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     typedef V4<T> vec;
     const int wbase = __builtin_amdgcn_readfirstlane(tid & ~63);
@@ -107,68 +103,16 @@ __device__ __forceinline__ void wg_lu_factor_wide(T* __restrict__ Mall, const in
         int ne = 0;
         if (dbg_on) dts = clock64();
         if (y == owner) {
-            // ---- the panel: my own columns, two rows per thread (the one-workgroup kernel's code) ----
+            // ---- the panel: my own columns, R rows per thread of waves 0..3 (the one-workgroup kernel's code) ----
             {
                 vec row4[R][PB / 4];
                 int curpos[R];
                 bool done[R];
-                const bool wact = wbase < M && tid < NTP;
-#pragma unroll
-                for (int q = 0; q < R; ++q) {
-                    const int r = tid + q * NTP;
-                    const bool act = r < M && tid < NTP;
-                    curpos[q] = r;
-                    done[q] = !act;
-                    // (a full panel is two 16-B pieces of a row, 32-B aligned: element by element every lane asked for its line
-                    //  eight times -- 2 MB of requests per panel through one CU, 30 k of the panel's 70 k cycles)
-                    if (pb == PB) {
-                        const vec* rp = (const vec*)(A + (size_t)(k0 + (act ? r : 0)) * ld + k0);
-#pragma unroll
-                        for (int v = 0; v < NV; ++v) {
-                            const vec a = rp[v];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) row4[q][v].v[e] = act ? a.v[e] : T(0);
-                        }
-                    } else {
-#pragma unroll
-                        for (int c = 0; c < PB; ++c)
-                            row4[q][c >> 2].v[c & 3] = (act && c < pb) ? A[(size_t)(k0 + r) * ld + k0 + c] : T(0);
-                    }
-                }
+                const bool pw = tid < NTP;
+                lu_panel_load<T, PB, R, NTP>(row4, curpos, done, A, ld, k0, pb, M, pw);
                 if (tid == 0) *cnt = 0;
-                {
-                    const PanelLds<T> S{rowP, wval, wrcp, widx, wtid, pidx, cnt};
-                    lu_panel_columns_r<T, PB, R, NTP>(row4, curpos, done, wact, pb, k0, S);
-                }
-#pragma unroll
-                for (int q = 0; q < R; ++q) {
-                    const int r = tid + q * NTP;
-                    if (r < M && tid < NTP) {
-                        const int cp = curpos[q];
-                        if (pb == PB) {
-                            vec* wp = (vec*)(A + (size_t)(k0 + cp) * ld + k0);
-#pragma unroll
-                            for (int v = 0; v < NV; ++v) wp[v] = row4[q][v];
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < PB; ++c)
-                                if (c < pb) A[(size_t)(k0 + cp) * ld + k0 + c] = row4[q][c >> 2].v[c & 3];
-                        }
-                        if (cp < pb) {
-#pragma unroll
-                            for (int c = 0; c < PB; ++c) L11[cp * (PB + 1) + c] = row4[q][c >> 2].v[c & 3];
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < PB; ++c) LT[c * Mpad + (cp - pb)] = row4[q][c >> 2].v[c & 3];
-                        }
-                        src[cp] = r;
-                        if (cp >= pb && cp != r) {
-                            const int e = atomicAdd(cnt, 1);
-                            xdst[e] = cp;
-                            xsrc[e] = r;
-                        }
-                    }
-                }
+                lu_panel_columns<T, PB, R, NTP>(row4, curpos, done, wbase < M && pw, pb, k0, S);
+                lu_panel_store<T, PB, R, NTP>(row4, curpos, A, ld, k0, pb, M, pw, L11, LT, Mpad, src, xdst, xsrc, cnt);
             }
             __syncthreads();
             if (tid < pb) ipiv[k0 + tid] = k0 + pidx[tid] + 1;
@@ -235,10 +179,7 @@ __device__ __forceinline__ void wg_lu_factor_wide(T* __restrict__ Mall, const in
             LUW_STAMP(4);
         }
         __syncthreads();
-        bool anyswap = ne > 0;
-#pragma unroll
-        for (int j = 0; j < PB; ++j)
-            if (j < pb && __builtin_amdgcn_readfirstlane(src[j]) != j) anyswap = true;
+        const bool anyswap = lu_any_interchange<PB>(src, pb, ne);
 
         // ---- my tiles: interchanges left and right of the panel, U12 = L11^-1 (P A)12 (a column per thread, 32 tiles at a time) ----
         const int ntile = (N + TW - 1) / TW;
@@ -247,30 +188,11 @@ __device__ __forceinline__ void wg_lu_factor_wide(T* __restrict__ Mall, const in
             if (col >= N || (col >= k0 && col < k0 + pb)) continue;
             const bool right = col >= k0 + pb;
             if (!right && !anyswap) continue;
-            T* Ac = A + (size_t)k0 * ld + col;
             T top[PB];
-#pragma unroll
-            for (int j = 0; j < PB; ++j) top[j] = (j < pb) ? Ac[(size_t)src[j] * ld] : T(0);
-            {
-                T ext[PB];
-#pragma unroll
-                for (int e = 0; e < PB; ++e) ext[e] = (e < ne) ? Ac[(size_t)xsrc[e] * ld] : T(0);
-#pragma unroll
-                for (int e = 0; e < PB; ++e)
-                    if (e < ne) Ac[(size_t)xdst[e] * ld] = ext[e];
-            }
-            if (right) {
-#pragma unroll
-                for (int j = 0; j < PB; ++j) {
-#pragma unroll
-                    for (int i = j + 1; i < PB; ++i) top[i] -= L11[i * (PB + 1) + j] * top[j];
-                }
+            lu_interchange_column<T, PB>(A + (size_t)k0 * ld + col, ld, right, pb, ne, src, xsrc, xdst, L11, top, [&] {
 #pragma unroll
                 for (int j = 0; j < PB; ++j) UPt[(q * PB + j) * TW + (tid % TW)] = top[j];
-            }
-#pragma unroll
-            for (int j = 0; j < PB; ++j)
-                if (j < pb && (right || src[j] != j)) Ac[(size_t)j * ld] = top[j];
+            });
         }
         __syncthreads();
         LUW_STAMP(5);

@@ -1,6 +1,7 @@
 """Exact inputs for the pivoted-LU kernels, as data (no GPU needed to import this module): matrices with a PLANTED factorisation
 whose every intermediate is exactly representable in float32, so that any correct partial-pivoting LU -- LAPACK's, and each of
-the five kernel families of csrc/lqp_lu.hpp, lqp_lu2.hpp, lqp_lu_big.hpp, lqp_lu_wide.hpp (and its tall form) -- returns the
+the five kernel families of csrc/lqp_lu.hpp (one panel row per thread, and several: k_lu_factor_big), lqp_lu2.hpp,
+lqp_lu_wide.hpp (and its tall form) -- returns the
 planted factor and pivots BIT FOR BIT, in float32 and in float64, whatever the order of its sums.  tests/test_gpu_lu_exact.py runs
 every row on the GPU under torch.equal; tests/test_lu_table.py proves the table on the CPU first (LAPACK returns the plant, the
 plain getf2 below agrees, P A' = L U in integers, the rows cover every panel kind and tie class per kernel family, and a wrong
@@ -86,8 +87,8 @@ def select(N, B, dtype, env=None, cus=256):
 
 def holder(rel, ntp):
     """Who holds relative panel row `rel` (numpy arrays welcome): thread, register slot, lane, 16-lane row, wave -- one row per
-    thread in lqp_lu.hpp (ntp = the workgroup), rows t + q * 256 in the panel waves of lqp_lu2.hpp and lqp_lu_wide.hpp, rows
-    t + q * 1024 in lqp_lu_big.hpp."""
+    thread in k_lu_factor (ntp = the workgroup), rows t + q * 256 in the panel waves of lqp_lu2.hpp and lqp_lu_wide.hpp, rows
+    t + q * 1024 in k_lu_factor_big."""
     t = rel % ntp
     return dict(thread=t, slot=rel // ntp, lane=t % 64, row16=(t % 64) // 16, wave=t // 64)
 
@@ -430,7 +431,7 @@ def explain(r, LU, piv):
 # the rows
 EXPECT_ONLY = "the instantiations of the one-workgroup kernel write the same four counters: that THIS one ran rests on expect_kernel"
 COUNTERS = "the cycle counters of lqp_debug_set_lu_counters tell this family's launch from the others"
-BIG_NONE = "lqp_lu_big.hpp writes no counters: none written, and a size only it takes"
+BIG_NONE = "k_lu_factor_big writes no counters: none written, and a size only it takes"
 
 
 def row(name, N, kernel, dtype="f32", B=1, env=None, zero=None, first_kind=0, why=None):

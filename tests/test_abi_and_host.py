@@ -397,6 +397,18 @@ def test_register_budgets_of_the_hot_kernels():
                 "lqp::k_admm_loop_dense_w<float>": (9, 40), "lqp::k_admm_loop_dense_w<double>": (0, 0),
                 "lqp::k_unroll_sweep_split<8, 1>": (0, 0), "lqp::k_unroll_sweep_split<8, 16>": (0, 0), "lqp::k_unroll_sweep_split<7, 16>": (0, 0),
                 "lqp::k_unroll_scale_grad<0>": (0, 0), "lqp::k_unroll_scale_vectors<0>": (0, 0), "lqp::k_lu_inverse<float, true>": (0, 0)}
+    # the one-workgroup pivoted LU, every instance (wg_lu_factor with one panel row per thread; with two and four: k_lu_factor_big),
+    # at the numbers of the build before the families came to share one panel routine and one interchange step: nothing spilled
+    # but in float64 with 16-column panels on 1024 threads (row and pivot row are 64 of its 128 registers), and the 96 B of the
+    # float32 k_lu_factor_big that holds both of its forms
+    for inst in ("float, 16, true, 1024", "float, 16, true, 512", "float, 32, true, 512", "float, 16, false, 1024", "float, 16, false, 512",
+                 "float, 32, false, 512", "float, 8, false, 1024", "float, 8, false, 512", "double, 8, true, 1024", "double, 8, true, 512",
+                 "double, 16, true, 512"):
+        ceilings[f"lqp::k_lu_factor<{inst}>"] = (0, 0)
+    ceilings["lqp::k_lu_factor<double, 16, true, 1024>"] = (24, 68)
+    ceilings["lqp::k_lu_factor_big<float>"] = (0, 96)
+    ceilings["lqp::k_lu_factor_big<double>"] = (0, 0)
+    assert sum(k.startswith("lqp::k_lu_factor<") for k in res) == sum(k.startswith("lqp::k_lu_factor<") for k in ceilings) == 12
     for k, (spill, scratch) in ceilings.items():
         assert res[k][1] <= spill and res[k][2] <= scratch, (k, res[k])
     for k, (vg, _, _) in res.items():

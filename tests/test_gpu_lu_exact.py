@@ -8,7 +8,8 @@ Singular rows: the factorisation goes on past the zero pivot as getf2 does (the 
 raises with the planted FIRST zero column, the same message from every kernel family.
 
 That the kernel a row names ran: the cycle counters of lqp_debug_set_lu_counters tell the launch shapes apart -- four words per
-matrix from lqp_lu.hpp, sixteen from lqp_lu2.hpp and lqp_lu_wide.hpp (eight used by the latter), none from lqp_lu_big.hpp; which
+matrix from k_lu_factor (lqp_lu.hpp), sixteen from lqp_lu2.hpp and lqp_lu_wide.hpp (eight used by the latter), none from
+k_lu_factor_big (the same body with several panel rows per thread, given no counter block); which
 instantiation of the one-workgroup kernel ran rests on expect_kernel (tests/test_lu_table.py checks it against the restated
 selection), see each row's `why`.
 
@@ -56,7 +57,7 @@ def _raw_factor(A):
     _lib.check(st, "lu_factor")
     c = dbg.cpu()
     if not bool(c.any()):
-        shape = "none"                                   # lqp_lu_big.hpp
+        shape = "none"                                   # k_lu_factor_big
     elif bool(c[4 * B:].any()):
         shape = "sixteen" if all(int(c[16 * b + 7]) > 0 for b in range(B)) else "?"       # lqp_lu2.hpp | lqp_lu_wide.hpp: [7] total
     else:

@@ -90,7 +90,7 @@ KERNELS = [
     ("k_spd_inverse_dense", "float const*, float*, float*, int*, int, int, float*", [(1,), (2,)]),
     ("k_debug_chol_factor", "float*, int const*, int*, int, int, int", [(False,), (True,)]),
     ("k_debug_chol_solve", "float const*, int const*, float const*, float*, int, int, int", [(2,), (4,)]),
-    # the pivoted LU (lqp_lu.hpp, lqp_lu2.hpp, lqp_lu_big.hpp, lqp_lu_wide.hpp) and what runs on its factor
+    # the pivoted LU (lqp_lu.hpp: one workgroup, one or several panel rows per thread; lqp_lu2.hpp; lqp_lu_wide.hpp) and what runs on its factor
     ("k_lu_factor", LU_SIG + ", unsigned long long*, int const*",
      [("float", pb, mfma, nt) for mfma in (False, True) for pb, nt in ((16, 1024), (16, 512), (32, 512))] +
      [("float", 8, False, nt) for nt in (1024, 512)] + [("double", pb, True, nt) for pb in (8, 16) for nt in (1024, 512)]),
