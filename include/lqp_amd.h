@@ -387,6 +387,53 @@ int lqp_boxqp_forward_certify(void* stream, int dtype, int B, int n, int m,
                               void* x, void* z, void* u, void* lams, void* nus, void* rho_out,
                               lqp_boxqp_stats* stats,
                               void* workspace, size_t workspace_bytes, double eps_prim_inf, double eps_dual_inf);
+/* ---- an L1 term in the objective (added within ABI 17: new symbols only, no struct and no signature changed) ---------------
+ *   min 0.5 x'Qx + p'x + sum_i w_i |x_i - c_i|   s.t.  A x = b,  lb <= x <= ub,     w >= 0 and c finite, (B,n,1) like p
+ * (turnover / transaction cost around yesterday's holdings c).  lqp_boxqp_forward_l1 is the same implementation once more with
+ * another z-update: in the scaled space of the loop (x = D xs) the data are ws = D w, cs = c / D, and with v = xh + u (xh as in
+ * lqp_boxqp_forward, over-relaxation included), t = ws / rho (the rho of this iteration) and d = v - cs
+ *   S = v - t if d > t,  v + t if d < -t,  cs otherwise;     z = min(max(S, lbs), ubs)
+ * -- soft-threshold around cs, then clamp.  x-update, factorisations, stopping rule, rho adaptation: unchanged; w = 0 gives
+ * lqp_boxqp_forward's x, z, u bit for bit.  The solve always iterates: bounds that are all infinite are an ordinary case, the
+ * rho = 0 one-shot does not exist here (rho_mode 1 with rho_value <= 0: LQP_ERR_INVALID), ctrl.any_lb / any_ub are not read.
+ * Every loop kernel family has instances with this step (the small loop, the split loop on two and four workgroups, the
+ * streaming loop on one and two) except the dense LU tiers, whose problems run the streaming loop's LU branch.
+ * Two more outputs, (B,n,1) in the solve's dtype, from the step evaluated once more at the returned iterate (v = zs + us, in the
+ * scaled space, where an element on the kink has zs == cs exactly):
+ *   side   sign(S - cs): +1 / -1 off the kink, 0 exactly on the kink set K (the "otherwise" branch with t > 0)
+ *   u_box  (S - clamp(S)) / D -- S - zs with the clamp taken again at this v, so exactly zero unless the element is clamped:
+ *          the box's share of the dual u; lams is built from IT here, lams = [relu(-rho u_box); relu(rho u_box)] -- the
+ *          rest of u is the L1 term's multiplier.
+ * Refused with LQP_ERR_INVALID before anything is touched: a null w, c, side or u_box, ctrl.reserved2 bit 3 (per-problem
+ * stopping) or bit 0 (the factor kept for the unroll sweep), a check_hook.  A weight that is negative or not finite, and a
+ * rho of a problem (rho_mode 2: an entry of rho_in) that is not positive and finite, is found
+ * on the device: the problem's outputs are NaN, bit 18 (262144) of its flag word in ctrl.host_report is set, and a call that
+ * waits returns LQP_ERR_INVALID with stats.fail_index naming it.  lqp_boxqp_forward_l1_workspace_bytes: the forward's layout,
+ * unchanged, and behind it 3 n values per problem (ws, cs, t), written by a kernel of the call before any loop kernel runs.   */
+size_t lqp_boxqp_forward_l1_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_l1(void* stream, int dtype, int B, int n, int m,
+                         const void* Q, const void* p, const void* A, const void* b,
+                         const void* lb, const void* ub, const void* w, const void* c,
+                         const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                         void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* side, void* u_box,
+                         lqp_boxqp_stats* stats,
+                         void* workspace, size_t workspace_bytes);
+/* Its backward needs no factorisation of its own: an element on the kink behaves like one whose two bounds are both c_i, a
+ * thresholded free element like p_i shifted by side_i w_i.  Two element-wise kernels around lqp_boxqp_backward_fp, which runs
+ * unchanged on (dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, rho):
+ *   lqp_boxqp_l1_effective_box   K = (side == 0):  lb_e = K ? c : lb,  ub_e = K ? c : ub,  u_e = K ? u : u_box,
+ *                                lams_e = [relu(-rho u_e); relu(rho u_e)] (B,2n,1); rho_mode 1 = rho_value, 2 = rho_in (B)
+ *   lqp_boxqp_l1_finish_grads    dlb = K ? 0 : dlb_e,  dub = K ? 0 : dub_e,  dc = K ? dlb_e + dub_e : 0,  dw = side * dp;
+ *                                any of dlb, dub, dc, dw may be NULL = skip, dlb / dub may be dlb_e / dub_e themselves.
+ * dQ, dp, dA, db are lqp_boxqp_backward_fp's.  All (B,n,1) in `dtype`; enqueued on `stream`, nothing is waited for.          */
+int lqp_boxqp_l1_effective_box(void* stream, int dtype, int B, int n,
+                               const void* side, const void* u, const void* u_box,
+                               const void* lb, const void* ub, const void* c,
+                               int rho_mode, double rho_value, const void* rho_in,
+                               void* lb_e, void* ub_e, void* u_e, void* lams_e);
+int lqp_boxqp_l1_finish_grads(void* stream, int dtype, int B, int n,
+                              const void* side, const void* dp, const void* dlb_e, const void* dub_e,
+                              void* dlb, void* dub, void* dc, void* dw);
 /* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
  * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
  * optimal, 2 primal infeasible, 3 dual infeasible (lqp_boxqp_forward_certify) -- B int32 on the DEVICE.  Enqueued on `stream`,

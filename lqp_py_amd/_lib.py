@@ -77,6 +77,12 @@ SYMBOLS = {
     "lqp_boxqp_forward_certify": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
                                           ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P,
                                           ctypes.POINTER(BoxQPStats), _P, c_size_t, c_double, c_double]),
+    "lqp_boxqp_forward_l1_workspace_bytes": (c_size_t, [c_int] * 4),          # (added within ABI 17)
+    "lqp_boxqp_forward_l1": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                     ctypes.POINTER(BoxQPCtrl), _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                     ctypes.POINTER(BoxQPStats), _P, c_size_t]),
+    "lqp_boxqp_l1_effective_box": (c_int, [_P, c_int, c_int, c_int] + [_P] * 6 + [c_int, c_double, _P] + [_P] * 4),
+    "lqp_boxqp_l1_finish_grads": (c_int, [_P, c_int, c_int, c_int] + [_P] * 8),
     "lqp_boxqp_problem_status": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "lqp_boxqp_forward_finish": (c_int, [_P, c_int, c_int, c_int, _P, ctypes.POINTER(BoxQPStats)]),
     "lqp_boxqp_forward_layout": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 4),
@@ -131,7 +137,7 @@ def build_library(force=False, verbose=False):
 
     Default: the split build -- the host translation unit (csrc/lqp_amd.hip with `extern template` declarations of every
     kernel instance, csrc/split/lqp_extern.inc) and one translation unit per group of kernel instances
-    (csrc/split/lqp_tu_*.hip: 27 units, 173 instances), compiled in parallel and linked; same headers and flags, hence
+    (csrc/split/lqp_tu_*.hip: 33 units, 199 instances), compiled in parallel and linked; same headers and flags, hence
     the same code per kernel as the single-source build (LQP_UNITY_BUILD=1: one hipcc command, ~3.5 minutes of serial
     code generation).  The lists are written by tools/gen_split_build.py from the manifest of kernel instances in it."""
     split_dir = os.path.join(CSRC, "split")
@@ -312,6 +318,7 @@ RP_INFEAS = 1 << 16          # the problem was flagged primal infeasible (contro
 
 
 RP_UNBOUNDED = 1 << 17       # the problem was flagged dual infeasible (control['unbounded'], lqp_boxqp_forward_certify)
+RP_L1_INPUT = 1 << 18        # a weight of the problem is negative or not finite, or its rho not positive (lqp_boxqp_forward_l1)
 
 
 class CertifiedQPError(RuntimeError):
@@ -425,6 +432,9 @@ def poll_errors(block=False):
                                f"zero pivot for batch index {int(bad[0])}; the matrix is singular")
         if status5:
             raise RuntimeError(f"lqp_py_amd.{p.what}: in-kernel grid barrier timed out")
+        if flags & RP_L1_INPUT:
+            raise RuntimeError(f"lqp_py_amd.{p.what} (reported late: the call did not synchronise): w must be finite and >= 0, and rho positive and finite "
+                               f"(batch index {int((flags_each & RP_L1_INPUT).nonzero()[0][0])}); the outputs are NaN")
         if p.raise_infeasible and (flags & RP_INFEAS):
             raise InfeasibleQPError(p.what, (flags_each & RP_INFEAS).nonzero()[0].tolist())
         if p.raise_unbounded and (flags & RP_UNBOUNDED):

@@ -513,6 +513,14 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
         lu_timeout = lu_timeout || rv[ST_WORDS + i] == -7;          // (a multi-workgroup LU never met its partner)
         flags_or |= rv[ST_WORDS + B + i];
     }
+    if (flags_or & RP_L1_INPUT) {
+        // lqp_boxqp_forward_l1: a weight that is negative or not finite, a rho that is not positive (k_l1_setup).  First: what such
+        // data do to a factorisation (a negative rho leaves the symmetric x-update, a NaN makes a zero pivot) is no finding of its own
+        memset(stats, 0, sizeof(*stats));
+        stats->fail_index = -1;
+        for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & RP_L1_INPUT) stats->fail_index = i;
+        return LQP_ERR_INVALID;
+    }
     if (lu_timeout && stats->linsolve_used != 2) return LQP_ERR_TIMEOUT;
     if (fail_index >= 0 && stats->linsolve_used == 2) return LQP_RETRY_LU;
     if (fail_index >= 0) {
@@ -537,6 +545,8 @@ template <typename T> struct FwdLayout {
     void* snap_area;                // [B][snap_stride]: the infeasibility certificate's snapshots, BEHIND `bytes` (lqp_boxqp_forward_detect alone)
     size_t detect_bytes;            // ... and the size that holds them
     size_t certify_bytes;           // ... and with the dual certificate's x and Qs x in every slot (lqp_boxqp_forward_certify; the same start)
+    void* l1_area;                  // [B][l1_stride]: ws, cs, t of lqp_boxqp_forward_l1, BEHIND `bytes` too (the same start: never together with the snapshots)
+    size_t l1_bytes;                // ... and the size that holds them
 };
 // the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
 // by ADDRESS: an entry goes when another forward runs on the address; memory that was freed and handed out again without a forward in
@@ -593,6 +603,9 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     c.off = L.bytes;
     c.take<T>((size_t)B * snap_stride(n, m, true));
     L.certify_bytes = c.off + kAlign;
+    c.off = L.bytes;
+    L.l1_area = c.take<T>((size_t)B * l1_stride(n));
+    L.l1_bytes = c.off + kAlign;
     return L;
 }
 
@@ -605,7 +618,9 @@ typedef void (*SplitFn)(const FwdParams<float>, const int, const int, const int)
 // infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']: P.eps_dinf > 0)
 enum LoopStop { STOP_ALL, STOP_EACH, STOP_DETECT, STOP_CERTIFY };
 inline LoopStop loop_stop(const bool each, const bool snapshots, const bool dual) { return !each ? STOP_ALL : !snapshots ? STOP_EACH : dual ? STOP_CERTIFY : STOP_DETECT; }
-template <typename T> LoopStop loop_stop(const FwdParams<T>& P) { return loop_stop(P.pstat != nullptr, P.snap != nullptr, P.eps_dinf > 0); }
+// (FwdParams::snap shares its storage with the L1 area, FwdParams::l1v: whoever asks for the snapshots asks here)
+template <typename T> bool has_snapshots(const FwdParams<T>& P) { return P.snap != nullptr && !P.l1; }
+template <typename T> LoopStop loop_stop(const FwdParams<T>& P) { return loop_stop(P.pstat != nullptr, has_snapshots(P), P.eps_dinf > 0); }
 // Ks -> f(the KS of its instance) on NP workgroups per problem: two have 3 .. 6 as they are; then 7; everything else is 8
 template <int KS> using KsTag = std::integral_constant<int, KS>;
 template <int NP, typename F> auto by_ks(const int Ks, F f) -> decltype(f(KsTag<8>())) {
@@ -647,6 +662,21 @@ template <typename T> LoopPair<T> loop_kernels(const LoopStop stop, const bool r
     if constexpr (sizeof(T) == 4) { if (sym) return loop_column<T, true, true>(stop); if (resident) return loop_column<T, true, false>(stop); }
     return loop_column<T, false, false>(stop);
 }
+// ... and the same families with the L1 step (lqp_boxqp_forward_l1: FwdParams::l1; the batch stops as one, STOP_ALL)
+// the extra arguments of lqp_boxqp_forward_l1
+struct L1Args { const void *w, *c; void *side, *u_box; };
+template <typename T> bool with_l1(const FwdParams<T>& P) { return P.l1 != 0; }
+template <typename T> LoopPair<T> loop_kernels_l1(const bool resident, const bool sym) {
+    if constexpr (sizeof(T) == 4) {
+        if (sym) return {k_admm_loop_l1<T, true, false, 1024, true>, k_admm_loop_l1<T, true, true, 1024, true>};
+        if (resident) return {k_admm_loop_l1<T, true, false, 1024, false>, k_admm_loop_l1<T, true, true, 1024, false>};
+    }
+    return {k_admm_loop_l1<T, false, false, 1024, false>, k_admm_loop_l1<T, false, true, 1024, false>};
+}
+// (no DBG instance: with the debug counters set -- lqp_debug_set_lu_counters -- an L1 solve runs the same kernels and records no split-loop phases)
+template <int NP> SplitFn loop_split_fn_l1(const int Ks) {
+    return by_ks<NP>(Ks, [&](auto ks) -> SplitFn { return k_admm_loop_split_l1<decltype(ks)::value, 512, false, NP>; });
+}
 
 // the kernel of the first (hot) launch of the persistent mode
 enum LoopKind {
@@ -679,6 +709,9 @@ template <typename T> struct FwdPlan {
     LoopKind kind = LOOP_ONE;
     int kind_lds = 0;                   // LDS of LOOP_SMALL / LOOP_DENSE / LOOP_DENSE_W
     SplitFn small_fn = nullptr;         // LOOP_SMALL
+    LoopFn<float> np2_fn = nullptr;     // LOOP_NP2
+    bool l1 = false;                    // lqp_boxqp_forward_l1: every loop kernel is its StepL1 instance, the epilogue k_fwd_epilogue_l1
+    L1Args l1a = {nullptr, nullptr, nullptr, nullptr};      // ... and what k_l1_setup reads, k_fwd_epilogue_l1 writes
     int kind_wg = 1;                    // workgroups per problem of the hot launch
     int densew_tpr = 0;
     bool loop_split_seg = false;        // mode 1: k_admm_loop_split per check segment, its pairs taking turns on the chip
@@ -811,9 +844,11 @@ template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctr
     // 8 waves hide the per-block dependent chain worse than 16, which costs more than the 8 extra resident
     // blocks save.  Kept selectable (LQP_LOOP512=1) for re-measurement; continuation launches always use 1024.
     const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && k.resident != 0 && loop_lds_bytes<T>(n, m, P.Np, true) <= 160 * 1024;
-    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0 && !each;
+    // (the measurement-only 512-thread builds have no L1 instance)
+    const bool l1 = plan.l1;
+    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0 && !each && !l1;
     plan.loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident); plan.loop_nt = hot512 ? 512 : 1024;
-    const LoopPair<T> fns = loop_kernels<T>(plan.stop, resident, spd);
+    const LoopPair<T> fns = l1 ? loop_kernels_l1<T>(resident, spd) : loop_kernels<T>(plan.stop, resident, spd);
     plan.loop_fn = fns.hot; plan.tail_fn = fns.tail;
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
@@ -831,7 +866,7 @@ template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctr
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
             // blocks show, the product is bound by the un-overlapped sum of its resident and streamed phases.
-            if (k.sym512 && !each) {
+            if (k.sym512 && !each && !l1) {
                 P.sym_rl_hot = sym_resident_lds_blocks(n, m, P.Ks, resident_regs<512>(), 8);
                 plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl_hot, 8);
                 plan.loop_nt = 512; plan.loop_fn = k_admm_loop<T, true, false, 512, true>;
@@ -874,7 +909,7 @@ template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctr
 // ---- the kernel of the hot launch (plan.kind) and of the check segments of mode 1 (plan.loop_split_seg) ----
 template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
     const int B = P.B, n = P.n, m = P.m, check = P.check_solved, mode = plan.mode, retry = plan.retry;
-    const bool spd = plan.spd, solo = plan.solo, each = plan.stop != STOP_ALL;
+    const bool spd = plan.spd, solo = plan.solo, each = plan.stop != STOP_ALL, l1 = plan.l1;
     if constexpr (sizeof(T) == 4) {
         // two workgroups per QP for the first (hot) launch: symmetric path, persistent mode, 2 B workgroups resident
         if (spd && mode == 2 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && k.loop_split != 0) {
@@ -885,12 +920,12 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
             // four workgroups per QP (one column pair each) when the batch leaves room for them: B <= #CUs / 4
             if (P.Ks >= 7 && 4 * B <= d.cus && k.loop_split4 != 0) {
                 plan.split_lds = split_loop_lds_bytes<512, 4>(P.Ks, m);
-                plan.split_fn = loop_split_fn<4>(plan.stop, P.Ks, false);
+                plan.split_fn = l1 ? loop_split_fn_l1<4>(P.Ks) : loop_split_fn<4>(plan.stop, P.Ks, false);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 4))) loop_np = 4;
             }
             if (loop_np != 4) {
                 plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-                plan.split_fn = loop_split_fn<2>(plan.stop, P.Ks, g_lu_dbg != nullptr);
+                plan.split_fn = l1 ? loop_split_fn_l1<2>(P.Ks) : loop_split_fn<2>(plan.stop, P.Ks, g_lu_dbg != nullptr);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 2))) loop_np = 2;
             }
             if (loop_np > 1) { plan.kind = LOOP_SPLIT; plan.kind_wg = loop_np; }
@@ -898,8 +933,9 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
         // above 512 rows (BASELINE configs[3]: n = 1000): the streaming loop of the symmetric path with TWO workgroups per problem, each
         // streaming one range of whole block columns of H (admm_loop_body_from, NP == 2): twice the registers and LDS under the same
         // matrix (16 % -> 32 % of it on chip), half the stream per CU -- one CU alone pulls 58 GB/s, 29 us per iteration at n = 1000
+        plan.np2_fn = l1 ? k_admm_loop_np2_l1<> : k_admm_loop_np2<>;
         if (spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && plan.loop_nt == 1024 && k.loop_np2 != 0 && !solo && !each &&
-            !(retry & 2) && fits(d, k_admm_loop_np2<>, 1024, plan.loop_lds, shared_grid(B, 2))) {
+            !(retry & 2) && fits(d, plan.np2_fn, 1024, plan.loop_lds, shared_grid(B, 2))) {
             plan.kind = LOOP_NP2; plan.kind_wg = 2;
         }
         // ... and for batches LARGER than half the CUs (BASELINE configs[4]: 1024 per GPU), where the loop runs one launch per
@@ -909,13 +945,15 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
         if (spd && mode == 1 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 &&
             k.loop_split != 0 && k.loop_split_seg != 0 && !(retry & 2) && !solo && 2 * B > d.cus) {
             plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-            plan.split_fn = loop_split_fn<2>(plan.stop, P.Ks, false);
+            plan.split_fn = l1 ? loop_split_fn_l1<2>(P.Ks) : loop_split_fn<2>(plan.stop, P.Ks, false);
             plan.loop_split_seg = fits(d, plan.split_fn, plan.split_nt, plan.split_lds, 0);
         }
     }
     // LU tier, persistent mode, n <= 256, 2 B workgroups resident: the explicit inverse of the KKT matrix in the registers of two
     // workgroups per problem (lqp_dense.hpp) -- float64, many equality rows, non-symmetric Q, control['linsolve'] = 'lu'
-    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0 && !each) {
+    // (L1: the dense tiers have no StepL1 instance -- their problems run the streaming LU body, the plan's default, which holds
+    //  every size, dtype and m; an inverse in registers pays off least where the element-wise step grows)
+    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0 && !each && !l1) {
         const int dense_lds = dense_loop_lds_bytes<T>(m);
         if (lu_inverse_lds_bytes<T>(P.Np) <= 160 * 1024 && fits(d, k_admm_loop_dense<T>, DENSE_NT, dense_lds, shared_grid(B, 2))) {
             plan.kind = LOOP_DENSE; plan.kind_lds = dense_lds; plan.kind_wg = 2;
@@ -923,7 +961,7 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
     }
     // ... and for batches that leave most of the chip idle, any n the inverse kernel takes: W workgroups per problem, each with its
     // rows of the inverse in registers (k_admm_loop_dense_w): a matrix-vector product spreads over CUs, triangular solves do not
-    if (!spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && !each && lu_inverse_fits<T>(P.Np) &&
+    if (!spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && !each && !l1 && lu_inverse_fits<T>(P.Np) &&
         (size_t)P.dnx_words >= densew_xchg_words<T>(n)) {
         const int densew_lds = densew_lds_bytes<T>(n, m);
         const int tpr = densew_tpr(n, densew_cpt<T>());
@@ -936,7 +974,7 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
         // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
         if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
             const int small_lds = small_loop_lds_bytes(m);
-            plan.small_fn = small_loop_kernel(plan.stop);
+            plan.small_fn = l1 ? k_admm_loop_small_l1<> : small_loop_kernel(plan.stop);
             if (fits(d, plan.small_fn, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
         }
         // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
@@ -977,7 +1015,8 @@ template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl*
     // is over ~5 launches that leave at once -- which is why the automatic rho (it practically never adapts) gets none.
     plan.hot_rounds = (ctl->rho_mode != 0 && !each) ? k.hot_rounds : 0;
     // (each: workgroups leave the last launch at different times -- workgroup 0 cannot report the status block from inside it)
-    plan.tail_epilogue = k.tail_epilogue != 0 && !each;
+    // (L1: the epilogue takes two more outputs, a launch of its own)
+    plan.tail_epilogue = k.tail_epilogue != 0 && !each && !plan.l1;
     plan.spec_launches = k.spec_launches;
     plan.factor_launches = spd ? (plan.spd_big_split ? 2 * P.Ks + 2 : plan.spd_split ? (plan.spd_resident ? 3 : P.Ks + 2) : 1) : 2;
     plan.loop_workgroups = plan.loop_split_seg ? 2 : plan.kind_wg;      // (what the loop's launches put on a problem)
@@ -990,10 +1029,12 @@ template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl*
 //                 CUs -- another stream, another process, RCCL): nothing shared this time -- one workgroup per matrix in every
 //                 factorisation, host-launched check segments instead of the persistent loop with its grid barrier
 template <typename T> int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
-    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0;
+    const L1Args l1a = plan.l1a;
+    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0; plan.l1a = l1a;
     // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
     // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
     plan.stop = loop_stop(P);
+    plan.l1 = with_l1(P);
     plan.dbg_loop_absent = k.dbg_loop_absent;
     P.xcd_local = k.xcd_local != 0 ? 1 : 0;
     P.dbg_qpass = k.dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
@@ -1101,6 +1142,11 @@ int enqueue_prologue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pl
         if (rc) return rc;
         ++n_launch;
     }
+    if (plan.l1) {      // ws, cs: behind whoever wrote the scaling vector (the setup kernel, or the resident sweep it defers to)
+        ProfScope ps(st, PC_SETUP);
+        hipLaunchKernelGGL(k_l1_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.l1a.w, (const T*)plan.l1a.c);
+        ++n_launch;
+    }
     return LQP_OK;
 }
 
@@ -1117,7 +1163,7 @@ void launch_hot(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan, c
             hipLaunchKernelGGL(plan.small_fn, dim3(B), dim3(256), plan.kind_lds, st, P, 0, e, ctr_base);
             return;
         case LOOP_NP2:
-            hipLaunchKernelGGL(k_admm_loop_np2<>, dim3((absent & 8) ? B : shared_grid(B, 2)), dim3(1024), plan.loop_lds, st, P, 0, e, ctr_base, -1, 1);
+            hipLaunchKernelGGL(plan.np2_fn, dim3((absent & 8) ? B : shared_grid(B, 2)), dim3(1024), plan.loop_lds, st, P, 0, e, ctr_base, -1, 1);
             return;
         default: break;
     }
@@ -1250,7 +1296,8 @@ Attempt run_planned(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
     }
     if (!epilogue_done) {
         ProfScope ps(st, PC_EPILOGUE);
-        hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
+        if (plan.l1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
+          else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
         ++n_launch;
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
@@ -1362,7 +1409,8 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         // the epilogue only reads state: run it now so that the common case (converged in this chunk)
         // pays no host round trip between the loop and its outputs; a later chunk simply re-runs it
         { ProfScope ps(st, PC_EPILOGUE);
-          hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P); }
+          if (plan.l1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
+          else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P); }
         ++n_launch;
         // (with a host report the epilogue has left status and info words in pinned host memory: one wait, no copies)
         if (!P.host_report) HIP_OK(hipMemcpyAsync(h_status, P.status, sizeof(h_status), hipMemcpyDeviceToHost, st));
@@ -1417,6 +1465,17 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         chunk_cap = std::min(chunk_cap * 2, 64);
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
+    if (plan.l1) {
+        // a weight that is negative or not finite (k_l1_setup marks the problem's flag word; the epilogue has reported it)
+        std::vector<int> fl(B);
+        if (P.host_report) for (int i = 0; i < B; ++i) fl[i] = ((const volatile int*)P.host_report)[ST_WORDS + B + i];
+        else { HIP_OK(hipMemcpyAsync(fl.data(), P.bflags, sizeof(int) * B, hipMemcpyDeviceToHost, st)); HIP_OK(hipStreamSynchronize(st)); }
+        for (int i = 0; i < B; ++i)
+            if (fl[i] & RP_L1_INPUT) {
+                if (stats) { memset(stats, 0, sizeof(*stats)); stats->fail_index = i; }
+                return LQP_ERR_INVALID;
+            }
+    }
     if (stats) {
         fill_stats(stats, plan, mode, n_launch);
         solve_stats(stats, h_status, max_iters, check);
@@ -1438,13 +1497,14 @@ template <typename T>
 int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
-                 int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0) {
-    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify)
+                 int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const L1Args* l1 = nullptr) {
+    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; l1: lqp_boxqp_forward_l1)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
     const LoopStop asked = loop_stop(true, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);      // (under stop = 'each')
-    if (ws_bytes < (asked == STOP_CERTIFY ? L.certify_bytes : asked == STOP_DETECT ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
+    if (ws_bytes < (l1 ? L.l1_bytes : asked == STOP_CERTIFY ? L.certify_bytes : asked == STOP_DETECT ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
+        if (l1) { P.l1 = 1; P.l1v = (T*)L.l1_area; }
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
         P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in; P.beta_in = (const T*)ctl->beta_in;
         P.x = (T*)x; P.z = (T*)z; P.u = (T*)u; P.lams = (T*)lams; P.nus = (T*)nus; P.rho_out = (T*)rho_out;
@@ -1483,10 +1543,11 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         if (retry & 4) one_wg_lu.enter();
         FwdParams<T> P = L.P;
         FwdPlan<T> plan;
+        if (l1) plan.l1a = *l1;
         int rc = plan_forward(P, ctl, retry, k, d, plan);
         if (rc) return rc;
         int n_launch = 0;
-        if (P.snap) { hipLaunchKernelGGL(k_snap_init<T>, dim3((2 * B + 255) / 256), dim3(256), 0, st, P.snap, P.snap_stride, B); ++n_launch; }
+        if (has_snapshots(P)) { hipLaunchKernelGGL(k_snap_init<T>, dim3((2 * B + 255) / 256), dim3(256), 0, st, P.snap, P.snap_stride, B); ++n_launch; }
         rc = enqueue_prologue(st, P, plan, n_launch);
         if (rc) return rc;
         const Attempt a = plan.up_front ? run_planned(st, P, plan, ctl, stats, n_launch) : run_chunked(st, P, plan, ctl, stats, n_launch);
@@ -2206,7 +2267,8 @@ size_t lqp_boxqp_forward_detect_workspace_bytes(int dtype, int B, int n, int m) 
 static int forward_entry(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
                          const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
-                         void* workspace, size_t workspace_bytes, const double eps_prim_inf, const double eps_dual_inf) {
+                         void* workspace, size_t workspace_bytes, const double eps_prim_inf, const double eps_dual_inf,
+                         const L1Args* l1 = nullptr) {
     if (bad_dims(dtype, B, n, m) || !Q || !p || !lb || !ub || !ctrl || !x || !z || !u || !lams || !rho_out || !workspace)
         return LQP_ERR_INVALID;
     if (m > 0 && (!A || !b || !nus)) return LQP_ERR_INVALID;
@@ -2221,7 +2283,7 @@ static int forward_entry(void* stream, int dtype, int B, int n, int m, const voi
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)
     return by_dtype(dtype, [&](auto t) {
-        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf);
+        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf, l1);
     });
 }
 
@@ -2243,6 +2305,57 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const
     if (!ctrl || !(ctrl->reserved2 & 8) || (ctrl->reserved2 & 1) || ctrl->check_hook) return LQP_ERR_INVALID;
     return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
                          workspace_bytes, eps_prim_inf, 0.0);
+}
+
+size_t lqp_boxqp_forward_l1_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).l1_bytes; });
+}
+
+int lqp_boxqp_forward_l1(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                         const void* b, const void* lb, const void* ub, const void* w, const void* c, const lqp_boxqp_ctrl* ctrl,
+                         const void* rho_in, void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* side, void* u_box,
+                         lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
+    // refused before anything is touched: a null pointer, the per-problem stop (no L1 instance of its kernels), a check hook, the
+    // factor kept for the unroll sweep (its tape replays the plain step), and the rho = 0 one-shot -- the L1 solve always iterates,
+    // whatever the bounds: all of them infinite is an ordinary case here
+    if (!w || !c || !side || !u_box) return LQP_ERR_INVALID;
+    if (!ctrl || (ctrl->reserved2 & (8 | 1)) || ctrl->check_hook) return LQP_ERR_INVALID;
+    if (ctrl->rho_mode == 1 && !(ctrl->rho_value > 0.0)) return LQP_ERR_INVALID;
+    const L1Args l1 = {w, c, side, u_box};
+    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
+                         workspace_bytes, 0.0, 0.0, &l1);
+}
+
+// the two element-wise kernels around lqp_boxqp_backward_fp in the backward of lqp_boxqp_forward_l1 (csrc/lqp_boxqp.hpp)
+int lqp_boxqp_l1_effective_box(void* stream, int dtype, int B, int n, const void* side, const void* u, const void* u_box,
+                               const void* lb, const void* ub, const void* c, int rho_mode, double rho_value, const void* rho_in,
+                               void* lb_e, void* ub_e, void* u_e, void* lams_e) {
+    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
+    if (!side || !u || !u_box || !lb || !ub || !c || !lb_e || !ub_e || !u_e || !lams_e || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
+    const size_t total = (size_t)B * n;
+    by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_l1_effective_box<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)side,
+                           (const T*)u, (const T*)u_box, (const T*)lb, (const T*)ub, (const T*)c, rho_mode == 2 ? (const T*)rho_in : nullptr,
+                           (T)rho_value, n, total, (T*)lb_e, (T*)ub_e, (T*)u_e, (T*)lams_e);
+        return 0;
+    });
+    return last_error();
+}
+
+int lqp_boxqp_l1_finish_grads(void* stream, int dtype, int B, int n, const void* side, const void* dp, const void* dlb_e,
+                              const void* dub_e, void* dlb, void* dub, void* dc, void* dw) {
+    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
+    if (!side || !dp || !dlb_e || !dub_e) return LQP_ERR_INVALID;
+    const size_t total = (size_t)B * n;
+    by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_l1_finish_grads<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)side,
+                           (const T*)dp, (const T*)dlb_e, (const T*)dub_e, total, (T*)dlb, (T*)dub, (T*)dc, (T*)dw);
+        return 0;
+    });
+    return last_error();
 }
 
 size_t lqp_boxqp_forward_certify_workspace_bytes(int dtype, int B, int n, int m) {

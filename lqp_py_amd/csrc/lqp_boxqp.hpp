@@ -27,7 +27,8 @@ enum { PS_DONE = 0, PS_FINAL = 1, PS_RESUME = 2, PS_NFACTOR = 3, PS_WORDS = 4 };
 // B info words | B flag words], written straight into pinned host memory by that kernel
 enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
        RP_INFEAS = 1 << 16,       // control['infeasible']: the problem was flagged primal infeasible (each_stop)
-       RP_UNBOUNDED = 1 << 17 };  // control['unbounded']: the problem was flagged dual infeasible (each_stop)
+       RP_UNBOUNDED = 1 << 17,    // control['unbounded']: the problem was flagged dual infeasible (each_stop)
+       RP_L1_INPUT = 1 << 18 };   // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_l1_setup); its outputs are NaN
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -109,11 +110,21 @@ template <typename T> struct FwdParams {
     T eps_abs, eps_rel, rho_value, rho_min, rho_max, ar_tol, ar_inv_tol, ar_thr, beta_value;
     T alpha, alpha_c;         // over-relaxation factor (control['alpha']; 1 = the reference's plain step) and 1 - alpha, see admm_relax
     int relax;                // 1: alpha != 1
+    int l1;                   // 1: lqp_boxqp_forward_l1 -- the objective carries sum_i w_i |x_i - c_i| and `snap` is the L1 area (in the alignment gap in front of the pointer: no offset moves)
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
+    union {
     T* snap;                 // B * snap_stride: control['infeasible'] (stop = 'each' only) -- the certificate's snapshots, or null = no detection
+    T* l1v;                  // l1 (never together with the snapshots, and at their place in the workspace): B * l1_stride(n), per problem
+    };                       //   [ws = D w | cs = c / D | t = ws / rho of the running segment]; k_l1_setup writes ws, cs
     size_t snap_stride;
     T eps_pinf;              // control['eps_prim_inf']; 0: the primal certificate is off (lqp_boxqp_forward_certify with the dual one alone)
     T eps_dinf;              // control['eps_dual_inf']; 0: no dual certificate (control['unbounded'] absent) -- the slots then end behind nu
+};
+__host__ __device__ inline size_t l1_stride(int n) { return (size_t)3 * round_up(n, 8); }
+// the scaled L1 data of problem b
+template <typename T> struct L1View {
+    T *ws, *cs, *t;
+    __device__ L1View(T* base, int n) { ws = base; cs = ws + round_up(n, 8); t = cs + round_up(n, 8); }
 };
 // control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
 // number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split_each:
@@ -1329,8 +1340,17 @@ __host__ __device__ inline int sym_resident_lds_blocks(int n, int m, int Ks, int
 // block -- no device-to-host copy behind the solve (a 1.4 us blit kernel + a boundary).  Words other workgroups of the SAME
 // launch may still write (ST_NOTSPD, ST_TIMEOUT of an in-kernel refactorisation) are therefore also kept per problem
 // (RP_NOTSPD / RP_TIMEOUT in the writer's own flag word).
-template <typename T>
-__device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b) {
+// L1 (lqp_boxqp_forward_l1): the soft threshold once more at the returned iterate, in the scaled space where the kink is exact
+// (z == cs by assignment): v = z + u, S = l1_shrink(v, ws / rho, cs).  side = sign(S - cs), 0 exactly on the kink set (the threshold
+// branch was taken and t > 0); u_box = (S - clamp(S)) / D -- S - z with the clamp taken again, so that it is exactly zero unless
+// the element is clamped (the stored z is the clamp of the last iteration's v, one rounding away from this one) -- the box's share
+// of the dual, and lams are built from it; the rest of u is the L1 term's multiplier.
+template <typename T> __device__ __forceinline__ T l1_shrink(const T v, const T t, const T c) {
+    const T d = v - c;
+    return d > t ? v - t : (d < -t ? v + t : c);
+}
+template <typename T, bool L1 = false>
+__device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T* __restrict__ l1_side = nullptr, T* __restrict__ l1_ubox = nullptr) {
     const int n = P.n, m = P.m, tid = threadIdx.x, nt = blockDim.x;
     VecView<T> V(P.vecs + (size_t)b * P.vstride, n, m);
     const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
@@ -1339,7 +1359,8 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b) {
     const int info_b = P.info[b];
     const int notspd = __hip_atomic_load(P.status + ST_NOTSPD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool bad = info_b != 0 || notspd != 0 || tmo != 0;
+    bool bad = info_b != 0 || notspd != 0 || tmo != 0;
+    if constexpr (L1) bad = bad || (P.bflags[b] & RP_L1_INPUT) != 0;
     const T poison = bad ? T(__builtin_nanf("")) : T(0);
     for (int i = tid; i < n; i += nt) {
         const T d = V.D[i];
@@ -1347,7 +1368,17 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b) {
         P.x[(size_t)b * n + i] = xo;
         P.z[(size_t)b * n + i] = zo;
         P.u[(size_t)b * n + i] = uo;
-        const T y = uo * rho;
+        T y = uo * rho;
+        if constexpr (L1) {
+            const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
+            const T zs = V.z[i], v = zs + V.u[i], t = W.ws[i] / rho, cs = W.cs[i], dd = v - cs;
+            const bool kink = t > T(0) && !(dd > t) && !(dd < -t);
+            const T S = l1_shrink(v, t, cs);
+            const T ubx = (S - tmin(tmax(S, V.lbs[i]), V.ubs[i])) / d + poison;      // (S - z with z = clamp(S): exactly zero off the bounds)
+            l1_side[(size_t)b * n + i] = (kink ? T(0) : (dd < T(0) ? T(-1) : T(1))) + poison;
+            l1_ubox[(size_t)b * n + i] = ubx;
+            y = ubx * rho;
+        }
         P.lams[(size_t)b * 2 * n + i] = (-y > T(0)) ? -y : T(0);
         P.lams[(size_t)b * 2 * n + n + i] = (y > T(0)) ? y : T(0);
     }
@@ -1422,6 +1453,36 @@ __device__ __forceinline__ AdmmStep<T> admm_step_tag(const FwdParams<T>& P, cons
                                                      const T rho) {
     if constexpr (TAG::kind == 2) return admm_step(P, xi, zp, ui, lb, ub, rho);
     else return admm_step_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho);
+}
+// The step with an L1 term w |x - c| in the objective (lqp_boxqp_forward_l1): the prox of the two separable terms is "soft-threshold
+// around cs, then clamp", t = ws / rho with the rho of this iteration; r, s, u are the lines of admm_step_as.  The branch form of
+// l1_shrink returns v itself at t = 0: w = 0 gives the plain step's bits.  A compile-time tag beside the relaxation's (StepBox: the
+// kernels there always were, not one instruction of theirs knows about this; StepL1: instances of their own), never a run-time flag.
+struct StepBox { static constexpr bool l1 = false; };
+struct StepL1 { static constexpr bool l1 = true; };
+// what a thread of the streaming loop keeps of the L1 data (nothing at all in a StepBox instance)
+template <typename T, bool ON> struct L1Own {};
+template <typename T> struct L1Own<T, true> { T t0 = T(0), c0 = T(0); const T *t = nullptr, *cs = nullptr; };
+template <bool RELAX, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_l1_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                       const T rho, const T t, const T cs) {
+    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
+    const T zn = tmin(tmax(l1_shrink(xh + ui, t, cs), lb), ub);
+    const T r = xi - zn;
+    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
+}
+template <typename TAG, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_l1_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                        const T rho, const T t, const T cs) {
+    if constexpr (TAG::kind == 2) {
+        if (P.relax) {
+            asm volatile("");
+            return admm_step_l1_as<true>(P, xi, zp, ui, lb, ub, rho, t, cs);
+        }
+        return admm_step_l1_as<false>(P, xi, zp, ui, lb, ub, rho, t, cs);
+    } else {
+        return admm_step_l1_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, t, cs);
+    }
 }
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
 // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu without touching Q -- it only feeds a tolerance SCALE; the
@@ -1655,7 +1716,7 @@ __device__ __forceinline__ int infeas_finish(const FwdParams<T>& P, const Infeas
 // stops at the first check at which IT is optimal (its workgroup stores the iterate, marks pstat[b] and returns), it adapts rho at
 // an event iff its own `wants && trig` of the last check say so, and nothing crosses workgroups: no grid_wait, no arrival word,
 // no decision from the counters.  A launch begins by reading pstat[b].done and leaves at once when it is set.
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false, typename STEP = StepBox>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem);
 // does the adaptive-rho event at iteration seg0 change this problem's rho?  The reference's decision over the whole batch, from the
@@ -1706,7 +1767,8 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
 // its registers cost the plain EACH kernels 3 % of their time
 // DUAL (DETECT only; control['unbounded']): the dual certificate too, instances of their own again (k_admm_loop_each_certify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false>
+// STEP (StepBox | StepL1): the element-wise step, see admm_step_l1_as -- lqp_boxqp_forward_l1's kernels are instances of their own
+template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false, typename STEP = StepBox>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
                                                const int prev_slot,      // slot of the last check before it0, -1: none / known not done
@@ -1717,15 +1779,16 @@ __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int 
         // this problem stopped in an earlier launch: its iterate is not touched again
         if (__builtin_amdgcn_readfirstlane(P.pstat[(size_t)blockIdx.x * PS_WORDS + PS_DONE])) return;
     }
-    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH, DETECT, DUAL>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH, DETECT, DUAL, STEP>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH, bool DETECT, bool DUAL>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH, bool DETECT, bool DUAL, typename STEP>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
     static_assert(!DETECT || EACH, "the infeasibility certificate is part of a problem's own stopping check");
     static_assert(!DUAL || DETECT, "the dual certificate shares the primal one's snapshot and reduction");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
+    static_assert(!STEP::l1 || !EACH, "the L1 step has no per-problem form (lqp_boxqp_forward_l1 refuses control['stop'] = 'each')");
     int b = blockIdx.x, part_id = 0;
     if constexpr (NP == 2) { if (!shared_map((int)blockIdx.x, P.B, 2, b, part_id)) return; }
     const bool lead = part_id == 0;                          // (the workgroup that reports and writes state)
@@ -1869,6 +1932,16 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         z[i] = V.z[i]; u[i] = V.u[i]; ps[i] = V.ps[i]; lb[i] = V.lbs[i]; ub[i] = V.ubs[i]; D[i] = V.D[i];
     }
     for (int r = tid; r < m; r += NT) bs[r] = V.bs[r];
+    // StepL1: t = ws / rho with this segment's rho (a division per element and rho, none per iteration).  A thread keeps t and cs of
+    // its first element in registers; those of its further elements (n > NT only) come from the workspace, where it stores their t
+    // itself here -- nothing is stored for the first (both workgroups of a shared problem would write the same values)
+    L1Own<T, STEP::l1> l1o;
+    if constexpr (STEP::l1) {
+        const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
+        for (int i = tid + NT; i < n; i += NT) W.t[i] = W.ws[i] / rho;
+        if (tid < n) { l1o.t0 = W.ws[tid] / rho; l1o.c0 = W.cs[tid]; }
+        l1o.t = W.t; l1o.cs = W.cs;
+    }
     if constexpr (SYM) {
         for (int i = tid; i < Nps; i += NT) cvl[i] = (i < n && m > 0) ? V.cv[i] : T(0);
         if constexpr (NP == 2) {       // (every slot / column sum of the range is written by every product; zeroed once all the same)
@@ -1980,6 +2053,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     const T ui = u[i];
                     const T xh = admm_relax(xi, zp, P);      // (the lines of admm_step)
                     T zn = xh + ui;
+                    if constexpr (STEP::l1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
                     zn = tmin(tmax(zn, lb[i]), ub[i]);     // (:273-276; an infinite bound is a no-op)
                     const T r = xi - zn;
                     const T s = rho * (zn - zp);
@@ -2026,6 +2100,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 const T ui = u[i];
                 const T xh = admm_relax(xi, zp, P);          // (the lines of admm_step)
                 T zn = xh + ui;
+                if constexpr (STEP::l1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
                 zn = tmin(tmax(zn, lb[i]), ub[i]);
                 const T r = xi - zn;
                 const T s = rho * (zn - zp);
@@ -2157,6 +2232,14 @@ __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P
     admm_loop_body<float, true, false, 1024, true, 2>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
 
+// ... and with the L1 step (lqp_boxqp_forward_l1)
+template <int LQP_ANY = 0>
+__global__ __launch_bounds__(1024) void k_admm_loop_np2_l1(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
+                                                           const int prev_slot, const int persistent) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_body<float, true, false, 1024, true, 2, false, false, false, StepL1>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+}
+
 // persistent & 4 (continuation launches): this is the forward's LAST launch -- it ends with the epilogue (fwd_finish)
 template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
 __global__ __launch_bounds__(NT) void k_admm_loop(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
@@ -2169,6 +2252,15 @@ __global__ __launch_bounds__(NT) void k_admm_loop(const FwdParams<T> P, const in
             fwd_finish(P, blockIdx.x);
         }
     }
+}
+
+// lqp_boxqp_forward_l1: the same loop with the L1 step (StepL1).  Never the forward's last launch: its epilogue takes two more
+// outputs and is a launch of its own (k_fwd_epilogue_l1)
+template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
+__global__ __launch_bounds__(NT) void k_admm_loop_l1(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
+                                                     const int prev_slot, const int persistent) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_body<T, RES, TAIL, NT, SYM, 1, false, false, false, StepL1>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
 
 // control['stop'] = 'each': the same loop, every problem on its own (admm_loop_body_from, EACH).  Never the forward's last launch:
@@ -2305,6 +2397,29 @@ __global__ void k_copy_residuals(const T* __restrict__ scal, T* __restrict__ pri
 template <typename T>
 __global__ __launch_bounds__(256) void k_fwd_epilogue(const FwdParams<T> P) {
     fwd_finish(P, blockIdx.x);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void k_fwd_epilogue_l1(const FwdParams<T> P, T* __restrict__ side, T* __restrict__ u_box) {
+    fwd_finish<T, true>(P, blockIdx.x, side, u_box);
+}
+// lqp_boxqp_forward_l1, behind the prologue (the scaling vector exists whichever kernel made it): ws = D w, cs = c / D next to
+// lbs / ubs' problem, and the input checks that need the data -- a weight that is negative or not finite, or a rho of the problem
+// (a per-problem rho_in among them) that is not positive and finite: t = ws / rho would be no threshold -- mark the problem
+// (RP_L1_INPUT: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
+template <typename T>
+__global__ __launch_bounds__(256) void k_l1_setup(const FwdParams<T> P, const T* __restrict__ w, const T* __restrict__ c) {
+    const int b = blockIdx.x, n = P.n, tid = threadIdx.x;
+    VecView<T> V(P.vecs + (size_t)b * P.vstride, n, P.m);
+    const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
+    const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
+    bool badw = !(rho > T(0) && rho < T(INFINITY));
+    for (int i = tid; i < n; i += 256) {
+        const T wi = w[(size_t)b * n + i], di = V.D[i];
+        badw |= !(wi >= T(0) && wi < T(INFINITY));            // (NaN fails the first comparison)
+        W.ws[i] = di * wi;
+        W.cs[i] = c[(size_t)b * n + i] / di;
+    }
+    if (__syncthreads_or(badw ? 1 : 0) && tid == 0) P.bflags[b] |= RP_L1_INPUT;
 }
 
 // ---------------------------------------------------------------------------
@@ -3081,6 +3196,45 @@ __global__ __launch_bounds__(256) void k_bwd_gather_rhs(const BwdParams<T> P) {
 
 // the info words of a factorisation into the caller's pinned host memory (LU form of the backward: they are final behind the LU, a
 // synchronous caller that polls them returns while pack, solves and epilogue still run)
+// ---------------------------------------------------------------------------
+// backward of lqp_boxqp_forward_l1: two element-wise kernels around lqp_boxqp_backward_fp, which runs unchanged in between.
+// An element on the kink (side == 0) behaves like one whose two bounds are both c; a thresholded free element like p shifted by
+// side * w.  So: the effective box (lb_e, ub_e) = K ? (c, c) : (lb, ub) with the dual u_e = K ? u : u_box and its lams ...
+// ---------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_l1_effective_box(const T* __restrict__ side, const T* __restrict__ u, const T* __restrict__ ubox,
+                                                          const T* __restrict__ lb, const T* __restrict__ ub, const T* __restrict__ c,
+                                                          const T* __restrict__ rho_in, const T rho_value, const int n, const size_t total,
+                                                          T* __restrict__ lb_e, T* __restrict__ ub_e, T* __restrict__ u_e,
+                                                          T* __restrict__ lams_e) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / n, e = i - b * n;
+    const bool K = side[i] == T(0);
+    const T ue = K ? u[i] : ubox[i];
+    lb_e[i] = K ? c[i] : lb[i];
+    ub_e[i] = K ? c[i] : ub[i];
+    u_e[i] = ue;
+    const T y = (rho_in ? rho_in[b] : rho_value) * ue;
+    lams_e[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
+    lams_e[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+}
+// ... and what the effective box's gradients mean for the eight inputs: on K both bounds were c (dc = dlb_e + dub_e, nothing for
+// lb and ub), elsewhere they were the bounds; dw = side * dp.  Outputs may be null; dlb / dub may be dlb_e / dub_e themselves.
+template <typename T>
+__global__ __launch_bounds__(256) void k_l1_finish_grads(const T* __restrict__ side, const T* __restrict__ dp, const T* dlb_e, const T* dub_e,
+                                                         const size_t total, T* dlb, T* dub, T* __restrict__ dc, T* __restrict__ dw) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const T s = side[i];
+    const bool K = s == T(0);
+    const T gl = dlb_e[i], gu = dub_e[i];
+    if (dlb) dlb[i] = K ? T(0) : gl;
+    if (dub) dub[i] = K ? T(0) : gu;
+    if (dc) dc[i] = K ? gl + gu : T(0);
+    if (dw) dw[i] = s * dp[i];
+}
+
 template <int LQP_ANY = 0>
 __global__ void k_report_info(const int* __restrict__ info, int* __restrict__ host_report, const int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

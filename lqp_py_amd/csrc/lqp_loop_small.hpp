@@ -19,7 +19,8 @@ __host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 +
 // DETECT (EACH only; control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
 // check iterations, and the certificate's registers in it cost the plain EACH kernel 12 % of its time
 // DUAL (DETECT only; control['unbounded']): the dual certificate too, k_admm_loop_small_each_certify
-template <bool EACH, bool DETECT = false, bool DUAL = false>
+// STEP (StepBox | StepL1): the element-wise step; StepL1 (lqp_boxqp_forward_l1, k_admm_loop_small_l1) keeps t = ws / rho and cs beside lb / ub
+template <bool EACH, bool DETECT = false, bool DUAL = false, typename STEP = StepBox>
 __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                      char* smem) {
     typedef float T;
@@ -74,6 +75,12 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
     T zi = live ? V.z[e] : T(0), ui = live ? V.u[e] : T(0);
     const T psi = live ? V.ps[e] : T(0), lbi = live ? V.lbs[e] : T(0), ubi = live ? V.ubs[e] : T(0);
     const T di = live ? V.D[e] : T(1), cvi = (live && m > 0) ? V.cv[e] : T(0);
+    T l1t = T(0), l1c = T(0);           // (StepL1; rho is this launch's: an adaptive-rho event ends it)
+    if constexpr (STEP::l1) {
+        static_assert(!EACH, "the L1 step has no per-problem form");
+        const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
+        if (live) { l1t = W.ws[e] / rho; l1c = W.cs[e]; }
+    }
     T xi = T(0);
     if (tid < 128) { wv[tid] = live ? -psi + rho * (zi - ui) : T(0); }
     __syncthreads();
@@ -114,7 +121,9 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
         if (live) {
             const T wi = wv[e];
             xi = cvi - yv[e];
-            const AdmmStep<T> sp = admm_step(P, xi, zi, ui, lbi, ubi, rho);
+            AdmmStep<T> sp;
+            if constexpr (STEP::l1) sp = admm_step_l1_tag<RelaxDyn>(P, xi, zi, ui, lbi, ubi, rho, l1t, l1c);
+            else sp = admm_step(P, xi, zi, ui, lbi, ubi, rho);
             zi = sp.zn;
             ui = sp.un;
             if (check) {
@@ -175,6 +184,11 @@ template <int LQP_ANY = 0>      // (a template only so that the split build can 
 __global__ __launch_bounds__(256) void k_admm_loop_small(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_small_body<false>(P, it0, it1, ctr_base, smem);
+}
+template <int LQP_ANY = 0>
+__global__ __launch_bounds__(256) void k_admm_loop_small_l1(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_small_body<false, false, false, StepL1>(P, it0, it1, ctr_base, smem);
 }
 template <int LQP_ANY = 0>
 __global__ __launch_bounds__(256) void k_admm_loop_small_each(const FwdParams<float> P, const int it0, const int it1,

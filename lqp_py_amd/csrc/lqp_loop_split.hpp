@@ -43,7 +43,9 @@ template <int NT, int NP = 2> __host__ __device__ inline int split_loop_lds_byte
 // compiled out).  Optimal -> the lead workgroup stores the iterate and marks pstat[b], every workgroup of the problem returns.  The hot
 // launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop_each) takes the problem's own decision.
 // (P by value: a reference to the kernel's parameter block costs the default's instances registers)
-template <int KS, int NT, bool DBG, int NP, bool EACH>
+// STEP (StepBox | StepL1): the element-wise step of every iteration form below.  StepL1 (lqp_boxqp_forward_l1, k_admm_loop_split_l1): thread i
+// keeps t = ws_i / rho and cs_i in two registers beside its element -- rho is this launch's, an event that changes it ends the launch
+template <int KS, int NT, bool DBG, int NP, bool EACH, typename STEP = StepBox>
 __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, int it0, const int it1, int ctr_base, char* smem) {
     typedef float T;
     if (P.hot_resume) {            // (a later round of the hot loop: it goes on where the round before stopped)
@@ -129,6 +131,12 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         yrow[i] = T(0);                                       // rows / columns of the partner stay zero
     }
     for (int r = tid; r < m; r += NT) bs[r] = V.bs[r];
+    T l1t = T(0), l1c = T(0);
+    if constexpr (STEP::l1) {
+        static_assert(!EACH && NT >= KS * LQP_NB, "the L1 step: one element per thread, no per-problem form");
+        const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
+        if (tid < n) { l1t = W.ws[tid] / rho; l1c = W.cs[tid]; }
+    }
     for (int i = tid; i < m * Nps; i += NT) { const int q = i / Nps, e = i - q * Nps; Asl[i] = e < n ? V.As[(size_t)q * n + e] : T(0); }
     for (int i = tid; i < NWV * Nps; i += NT) part[i] = T(0);
     if (tid < 8) flags[tid] = 0;
@@ -394,7 +402,9 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         if (tid < Nps) {
             const int i = tid;
             xs[i] = xi;
-            const AdmmStep<T> sp = admm_step_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho);
+            AdmmStep<T> sp;
+            if constexpr (STEP::l1) sp = admm_step_l1_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho, l1t, l1c);
+            else sp = admm_step_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho);
             const T zn = sp.zn, un = sp.un;
             const bool in = i < n;
             if (in) { z[i] = zn; u[i] = un; }
@@ -569,6 +579,11 @@ template <int KS, int NT, bool DBG = false, int NP = 2>
 __global__ __launch_bounds__(NT) void k_admm_loop_split(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
     admm_loop_split_body<KS, NT, DBG, NP, false>(P, it0, it1, ctr_base, smem);
+}
+template <int KS, int NT, bool DBG = false, int NP = 2>
+__global__ __launch_bounds__(NT) void k_admm_loop_split_l1(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
+    extern __shared__ __attribute__((aligned(32))) char smem[];
+    admm_loop_split_body<KS, NT, DBG, NP, false, StepL1>(P, it0, it1, ctr_base, smem);
 }
 template <int KS, int NT, bool DBG = false, int NP = 2>
 __global__ __launch_bounds__(NT) void k_admm_loop_split_each(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {

@@ -22,6 +22,13 @@ OUT = os.path.join(REPO, "lqp_py_amd", "csrc", "split")
 
 # group -> predicate on the demangled name; first match wins.  Balanced by measured compile time (seconds at -O3).
 GROUPS = [
+    # the instances with the L1 step (lqp_boxqp_forward_l1), grouped as their plain twins are
+    ("split_l1_c", lambda n: re.search(r"k_admm_loop_split_l1<(3|4), 512, false, 2>", n)),
+    ("split_l1_a", lambda n: re.search(r"k_admm_loop_split_l1<(5|6|7), 512, false, 2>", n)),
+    ("split_l1_b", lambda n: "k_admm_loop_split_l1<" in n),
+    ("loop_l1_tail", lambda n: re.search(r"k_admm_loop_l1<\w+, \w+, true,", n)),
+    ("loop_l1_hot", lambda n: "k_admm_loop_l1<" in n),
+    ("l1", lambda n: re.search(r"k_admm_loop_np2_l1<|k_admm_loop_small_l1<|k_fwd_epilogue_l1<|k_l1_", n)),
     ("bwd_f", lambda n: re.search(r"k_bwd_chol_solve<\d, true>", n)),
     ("resident_f", lambda n: re.search(r"k_spd_resident<8, 2, true>", n)),
     ("resident_g", lambda n: re.search(r"k_spd_resident<(5|6|7), 2, true>", n)),
@@ -76,6 +83,10 @@ KERNELS = [
     ("k_admm_loop_small_each_detect", FPF + ", int, int, int", ZERO),
     ("k_admm_loop_small_each_certify", FPF + ", int, int, int", ZERO),
     ("k_admm_loop_np2", FPF + ", int, int, int, int, int", ZERO),
+    ("k_admm_loop_l1", LOOP_SIG, LOOP),                        # lqp_boxqp_forward_l1: the L1 step (StepL1) in every family but the dense tiers
+    ("k_admm_loop_split_l1", FPF + ", int, int, int", SPLIT),
+    ("k_admm_loop_small_l1", FPF + ", int, int, int", ZERO),
+    ("k_admm_loop_np2_l1", FPF + ", int, int, int, int, int", ZERO),
     ("k_admm_loop_dense", FP + ", int, int, int", BOTH),
     ("k_admm_loop_dense_w", FP + ", int, int, int, int", BOTH),
     # the symmetric x-update (lqp_spd.hpp)
@@ -106,6 +117,10 @@ KERNELS = [
     # forward prologue / epilogue and the copies out of the workspace
     ("k_fwd_setup", FP, BOTH),
     ("k_fwd_epilogue", FP, BOTH),
+    ("k_fwd_epilogue_l1", FP + ", {0}*, {0}*", BOTH),
+    ("k_l1_setup", FP + ", {0} const*, {0} const*", BOTH),
+    ("k_l1_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
+    ("k_l1_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_rho_update", FP + ", int, int", BOTH),
     ("k_snap_init", "{0}*, unsigned long, int", BOTH),
     ("k_check_done", "int*, unsigned int const*, int, int", ZERO),
