@@ -537,6 +537,27 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
+// The form of a solve's loop kernels, derived ONCE (loop_form): the run-time twin of the Form tags (lqp_boxqp.hpp).  Every loop family
+// has an instance per form it supports (family_has_form), and nothing but its selector below chooses one.
+// The batch stops as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
+// infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']:
+// P.eps_dinf > 0) | the L1 step (lqp_boxqp_forward_l1: P.l1, whose area shares its storage with the snapshots; the batch stops as one)
+enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1 };
+inline LoopForm loop_form(const bool l1, const bool each, const bool snapshots, const bool dual) {
+    return l1 ? FORM_L1 : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
+}
+inline bool form_each(const LoopForm form) { return form == FORM_EACH || form == FORM_DETECT || form == FORM_CERTIFY; }
+inline bool form_snapshots(const LoopForm form) { return form == FORM_DETECT || form == FORM_CERTIFY; }
+template <typename T> LoopForm loop_form(const FwdParams<T>& P) { return loop_form(P.l1 != 0, P.pstat != nullptr, P.snap != nullptr, P.eps_dinf > 0); }
+template <typename F> auto by_form(const LoopForm form, F f) -> decltype(f(FormAll())) {
+    switch (form) {
+        case FORM_EACH:    return f(FormEach());
+        case FORM_DETECT:  return f(FormDetect());
+        case FORM_CERTIFY: return f(FormCertify());
+        case FORM_L1:      return f(FormL1());
+        default:           return f(FormAll());
+    }
+}
 template <typename T> struct FwdLayout {
     FwdParams<T> P;
     size_t bytes;
@@ -547,6 +568,9 @@ template <typename T> struct FwdLayout {
     size_t certify_bytes;           // ... and with the dual certificate's x and Qs x in every slot (lqp_boxqp_forward_certify; the same start)
     void* l1_area;                  // [B][l1_stride]: ws, cs, t of lqp_boxqp_forward_l1, BEHIND `bytes` too (the same start: never together with the snapshots)
     size_t l1_bytes;                // ... and the size that holds them
+    size_t bytes_for(const LoopForm form) const {      // the workspace a solve of this form needs
+        return form == FORM_L1 ? l1_bytes : form == FORM_CERTIFY ? certify_bytes : form == FORM_DETECT ? detect_bytes : bytes;
+    }
 };
 // the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
 // by ADDRESS: an entry goes when another forward runs on the address; memory that was freed and handed out again without a forward in
@@ -613,14 +637,24 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
 inline int spd_prep_lds_bytes(const int Ks) { return (2 * 64 * SPD_LS + 2 * LQP_NW + 64 * Ks) * 4; }      // (k_spd_prep)
 typedef void (*SweepFn)(const FwdParams<float>, const int*);
 typedef void (*SplitFn)(const FwdParams<float>, const int, const int, const int);
-// How a solve stops, derived ONCE (loop_stop); every loop family has an instance per kind, and nothing but its selector below chooses one.
-// The batch as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
-// infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']: P.eps_dinf > 0)
-enum LoopStop { STOP_ALL, STOP_EACH, STOP_DETECT, STOP_CERTIFY };
-inline LoopStop loop_stop(const bool each, const bool snapshots, const bool dual) { return !each ? STOP_ALL : !snapshots ? STOP_EACH : dual ? STOP_CERTIFY : STOP_DETECT; }
-// (FwdParams::snap shares its storage with the L1 area, FwdParams::l1v: whoever asks for the snapshots asks here)
-template <typename T> bool has_snapshots(const FwdParams<T>& P) { return P.snap != nullptr && !P.l1; }
-template <typename T> LoopStop loop_stop(const FwdParams<T>& P) { return loop_stop(P.pstat != nullptr, has_snapshots(P), P.eps_dinf > 0); }
+// the kernel of the first (hot) launch of the persistent mode
+enum LoopKind {
+    LOOP_ONE,           // k_admm_loop: one workgroup per problem
+    LOOP_SPLIT,         // k_admm_loop_split: two (four) workgroups per problem, the matrix in their registers
+    LOOP_SMALL,         // k_admm_loop_small: n <= 128, 256 threads per problem
+    LOOP_NP2,           // k_admm_loop_np2: above 512 rows, the streaming loop on two workgroups per problem
+    LOOP_DENSE,         // k_admm_loop_dense: LU tier, n <= 256, the explicit inverse in the registers of two workgroups
+    LOOP_DENSE_W        // k_admm_loop_dense_w: LU tier, W workgroups per problem
+};
+// Which family runs which form -- the ONE place that says so.  A family without the form of a solve is not planned: its problems run
+// the one-workgroup loop, which holds every form, size, dtype and m.
+inline bool family_has_form(const LoopKind kind, const LoopForm form) {
+    switch (kind) {
+        case LOOP_ONE: case LOOP_SMALL: case LOOP_SPLIT: return true;      // (the split loop's FormEach serves FormDetect and FormCertify)
+        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1;
+        default: return form == FORM_ALL;                                  // (the dense tiers)
+    }
+}
 // Ks -> f(the KS of its instance) on NP workgroups per problem: two have 3 .. 6 as they are; then 7; everything else is 8
 template <int KS> using KsTag = std::integral_constant<int, KS>;
 template <int NP, typename F> auto by_ks(const int Ks, F f) -> decltype(f(KsTag<8>())) {
@@ -633,60 +667,37 @@ template <int NP> SweepFn spd_resident_fn(const int Ks, const bool f16) {
         return k_spd_resident<decltype(ks)::value, NP, false>;
     });
 }
-// the split loop (its per-problem form takes the certificates from P.snap and P.eps_dinf itself: one instance for the three kinds)
-template <int NP> SplitFn loop_split_fn(const LoopStop stop, const int Ks, const bool dbg) {
-    if constexpr (NP == 2) if (stop == STOP_ALL && dbg && (Ks < 3 || Ks > 7)) return k_admm_loop_split<8, 512, true, 2>;
-    return by_ks<NP>(Ks, [&](auto ks) -> SplitFn { return stop == STOP_ALL ? k_admm_loop_split<decltype(ks)::value, 512, false, NP> : k_admm_loop_split_each<decltype(ks)::value, 512, false, NP>; });
+// the split loop (FormEach serves FormDetect and FormCertify: it takes the certificates from P.snap and P.eps_dinf itself)
+// (the DBG instance is FormAll's alone: with the debug counters set -- lqp_debug_set_lu_counters -- any other form runs the same kernels
+//  and records no split-loop phases)
+template <int NP> SplitFn loop_split_fn(const LoopForm form, const int Ks, const bool dbg) {
+    if constexpr (NP == 2) if (form == FORM_ALL && dbg && (Ks < 3 || Ks > 7)) return k_admm_loop_split<8, 512, true, 2, FormAll>;
+    return by_form(form, [&](auto f) {
+        using FORM = typename std::conditional<decltype(f)::detect, FormEach, decltype(f)>::type;
+        return by_ks<NP>(Ks, [&](auto ks) -> SplitFn { return k_admm_loop_split<decltype(ks)::value, 512, false, NP, FORM>; });
+    });
 }
-inline SplitFn small_loop_kernel(const LoopStop stop) {
-    switch (stop) {
-        case STOP_EACH:    return k_admm_loop_small_each<>;
-        case STOP_DETECT:  return k_admm_loop_small_each_detect<>;
-        case STOP_CERTIFY: return k_admm_loop_small_each_certify<>;
-        default:           return k_admm_loop_small<>;
-    }
+inline SplitFn small_loop_kernel(const LoopForm form) {
+    return by_form(form, [](auto f) -> SplitFn { return k_admm_loop_small<decltype(f)>; });
 }
 // the one-workgroup loop, first launch and continuation (same code, own name), 1024 threads.  One column per (RES, SYM): float64 has
 // the first alone, and the symmetric path keeps its blocks on chip whatever `resident` says
 template <typename T> using LoopFn = void (*)(const FwdParams<T>, int, int, int, int, int);
 template <typename T> struct LoopPair { LoopFn<T> hot, tail; };
-template <typename T, bool RES, bool SYM> LoopPair<T> loop_column(const LoopStop stop) {
-    switch (stop) {
-        case STOP_EACH:    return {k_admm_loop_each<T, RES, false, 1024, SYM>,         k_admm_loop_each<T, RES, true, 1024, SYM>};
-        case STOP_DETECT:  return {k_admm_loop_each_detect<T, RES, false, 1024, SYM>,  k_admm_loop_each_detect<T, RES, true, 1024, SYM>};
-        case STOP_CERTIFY: return {k_admm_loop_each_certify<T, RES, false, 1024, SYM>, k_admm_loop_each_certify<T, RES, true, 1024, SYM>};
-        default:           return {k_admm_loop<T, RES, false, 1024, SYM>,              k_admm_loop<T, RES, true, 1024, SYM>};
-    }
+template <typename T> LoopPair<T> loop_kernels(const LoopForm form, const bool resident, const bool sym) {
+    return by_form(form, [&](auto f) -> LoopPair<T> {
+        using FORM = decltype(f);
+        if constexpr (sizeof(T) == 4) {
+            if (sym) return {k_admm_loop<T, true, false, 1024, true, FORM>, k_admm_loop<T, true, true, 1024, true, FORM>};
+            if (resident) return {k_admm_loop<T, true, false, 1024, false, FORM>, k_admm_loop<T, true, true, 1024, false, FORM>};
+        }
+        return {k_admm_loop<T, false, false, 1024, false, FORM>, k_admm_loop<T, false, true, 1024, false, FORM>};
+    });
 }
-template <typename T> LoopPair<T> loop_kernels(const LoopStop stop, const bool resident, const bool sym) {
-    if constexpr (sizeof(T) == 4) { if (sym) return loop_column<T, true, true>(stop); if (resident) return loop_column<T, true, false>(stop); }
-    return loop_column<T, false, false>(stop);
-}
-// ... and the same families with the L1 step (lqp_boxqp_forward_l1: FwdParams::l1; the batch stops as one, STOP_ALL)
+inline LoopFn<float> np2_kernel(const LoopForm form) { return form == FORM_L1 ? k_admm_loop_np2<FormL1> : k_admm_loop_np2<FormAll>; }
 // the extra arguments of lqp_boxqp_forward_l1
 struct L1Args { const void *w, *c; void *side, *u_box; };
-template <typename T> bool with_l1(const FwdParams<T>& P) { return P.l1 != 0; }
-template <typename T> LoopPair<T> loop_kernels_l1(const bool resident, const bool sym) {
-    if constexpr (sizeof(T) == 4) {
-        if (sym) return {k_admm_loop_l1<T, true, false, 1024, true>, k_admm_loop_l1<T, true, true, 1024, true>};
-        if (resident) return {k_admm_loop_l1<T, true, false, 1024, false>, k_admm_loop_l1<T, true, true, 1024, false>};
-    }
-    return {k_admm_loop_l1<T, false, false, 1024, false>, k_admm_loop_l1<T, false, true, 1024, false>};
-}
-// (no DBG instance: with the debug counters set -- lqp_debug_set_lu_counters -- an L1 solve runs the same kernels and records no split-loop phases)
-template <int NP> SplitFn loop_split_fn_l1(const int Ks) {
-    return by_ks<NP>(Ks, [&](auto ks) -> SplitFn { return k_admm_loop_split_l1<decltype(ks)::value, 512, false, NP>; });
-}
 
-// the kernel of the first (hot) launch of the persistent mode
-enum LoopKind {
-    LOOP_ONE,           // k_admm_loop: one workgroup per problem
-    LOOP_SPLIT,         // k_admm_loop_split: two (four) workgroups per problem, the matrix in their registers
-    LOOP_SMALL,         // k_admm_loop_small: n <= 128, 256 threads per problem
-    LOOP_NP2,           // k_admm_loop_np2: above 512 rows, the streaming loop on two workgroups per problem
-    LOOP_DENSE,         // k_admm_loop_dense: LU tier, n <= 256, the explicit inverse in the registers of two workgroups
-    LOOP_DENSE_W        // k_admm_loop_dense_w: LU tier, W workgroups per problem
-};
 constexpr int kMaxChecksPerLaunch = kRing / 4;
 
 template <typename T> struct FwdPlan {
@@ -710,8 +721,7 @@ template <typename T> struct FwdPlan {
     int kind_lds = 0;                   // LDS of LOOP_SMALL / LOOP_DENSE / LOOP_DENSE_W
     SplitFn small_fn = nullptr;         // LOOP_SMALL
     LoopFn<float> np2_fn = nullptr;     // LOOP_NP2
-    bool l1 = false;                    // lqp_boxqp_forward_l1: every loop kernel is its StepL1 instance, the epilogue k_fwd_epilogue_l1
-    L1Args l1a = {nullptr, nullptr, nullptr, nullptr};      // ... and what k_l1_setup reads, k_fwd_epilogue_l1 writes
+    L1Args l1a = {nullptr, nullptr, nullptr, nullptr};      // FORM_L1: what k_l1_setup reads, k_fwd_epilogue_l1 (the epilogue of that form) writes
     int kind_wg = 1;                    // workgroups per problem of the hot launch
     int densew_tpr = 0;
     bool loop_split_seg = false;        // mode 1: k_admm_loop_split per check segment, its pairs taking turns on the chip
@@ -719,7 +729,7 @@ template <typename T> struct FwdPlan {
     LoopFn<T> tail_fn = nullptr; int tail_lds = 0;                     // continuation launches (LQP_NT threads)
     SplitFn split_fn = nullptr; int split_nt = 512, split_lds = 0;  // LOOP_SPLIT and loop_split_seg
     int mode = 0;                       // 2: persistent loop kernel, 1: one launch per check segment
-    LoopStop stop = STOP_ALL;           // which instance of every loop family runs (loop_stop)
+    LoopForm form = FORM_ALL;           // which instance of every loop family runs (loop_form)
     bool inkernel_refactor = false;     // the continuation kernel refactorises at its adaptive-rho events itself
     // the scheduler
     bool up_front = false;              // run_planned: the whole schedule enqueued before anything is waited for
@@ -838,17 +848,16 @@ template <typename T> int plan_xupdate(FwdParams<T>& P, const lqp_boxqp_ctrl* ct
 // ---- the loop kernels, and whether one persistent launch can hold all their workgroups ----
 template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
     const int B = P.B, n = P.n, m = P.m, check = P.check_solved;
-    const bool spd = plan.spd, each = plan.stop != STOP_ALL;
+    const bool spd = plan.spd, plain = plan.form == FORM_ALL;
     // hot (first) launch: optional 512-thread build (256 VGPRs per thread: 16 register-resident blocks instead
     // of 8).  Measured SLOWER at B=128 n=500 (2.03 ms vs 1.54 ms; 1.76 ms with a 6-deep ring and 4 spills):
     // 8 waves hide the per-block dependent chain worse than 16, which costs more than the 8 extra resident
     // blocks save.  Kept selectable (LQP_LOOP512=1) for re-measurement; continuation launches always use 1024.
     const bool resident = loop_resident_ok<1024>(P.K, sizeof(T)) && k.resident != 0 && loop_lds_bytes<T>(n, m, P.Np, true) <= 160 * 1024;
-    // (the measurement-only 512-thread builds have no L1 instance)
-    const bool l1 = plan.l1;
-    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0 && !each && !l1;
+    // (the measurement-only 512-thread builds have the plain form alone)
+    const bool hot512 = resident && loop_resident_ok<512>(P.K, sizeof(T)) && k.loop512 != 0 && plain;
     plan.loop_lds = loop_lds_bytes<T>(n, m, P.Np, resident); plan.loop_nt = hot512 ? 512 : 1024;
-    const LoopPair<T> fns = l1 ? loop_kernels_l1<T>(resident, spd) : loop_kernels<T>(plan.stop, resident, spd);
+    const LoopPair<T> fns = loop_kernels<T>(plan.form, resident, spd);
     plan.loop_fn = fns.hot; plan.tail_fn = fns.tail;
     // the continuation kernel also runs LU + pack (in-kernel adaptive-rho refactor): LDS = max of the three
     // (above 1024 rows the LU kernel is the two-rows-per-thread one, launched on its own: refactorisations go through the
@@ -857,7 +866,7 @@ template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctr
     //  separate gated kernels each one cost four launches that do nothing when the solve is over: rho update, LU, pack, tail)
     plan.inkernel_refactor = P.N <= 1024;
     if constexpr (sizeof(T) == 4) {
-        if (hot512 && !spd) plan.loop_fn = k_admm_loop<T, true, false, 512>;
+        if (hot512 && !spd) plan.loop_fn = k_admm_loop<T, true, false, 512, false, FormAll>;
         if (spd) {
             P.sym_rl = sym_resident_lds_blocks(n, m, P.Ks);
             plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl); plan.loop_nt = 1024;
@@ -866,10 +875,10 @@ template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctr
             // B=128 n=500: 0.96-0.99 ms with an 8-deep ring (26 spilled VGPRs), 0.87 ms with a 6-deep one, against
             // 0.885 ms for the 1024-thread kernel: neither the halved instruction count nor the fewer streamed
             // blocks show, the product is bound by the un-overlapped sum of its resident and streamed phases.
-            if (k.sym512 && !each && !l1) {
+            if (k.sym512 && plain) {
                 P.sym_rl_hot = sym_resident_lds_blocks(n, m, P.Ks, resident_regs<512>(), 8);
                 plan.loop_lds = sym_loop_lds_bytes(n, m, P.Ks, P.sym_rl_hot, 8);
-                plan.loop_nt = 512; plan.loop_fn = k_admm_loop<T, true, false, 512, true>;
+                plan.loop_nt = 512; plan.loop_fn = k_admm_loop<T, true, false, 512, true, FormAll>;
             }
         }
     }
@@ -909,7 +918,8 @@ template <typename T> int plan_loop_kernels(FwdParams<T>& P, const lqp_boxqp_ctr
 // ---- the kernel of the hot launch (plan.kind) and of the check segments of mode 1 (plan.loop_split_seg) ----
 template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
     const int B = P.B, n = P.n, m = P.m, check = P.check_solved, mode = plan.mode, retry = plan.retry;
-    const bool spd = plan.spd, solo = plan.solo, each = plan.stop != STOP_ALL, l1 = plan.l1;
+    const bool spd = plan.spd, solo = plan.solo;
+    const LoopForm form = plan.form;
     if constexpr (sizeof(T) == 4) {
         // two workgroups per QP for the first (hot) launch: symmetric path, persistent mode, 2 B workgroups resident
         if (spd && mode == 2 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 && k.loop_split != 0) {
@@ -920,12 +930,12 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
             // four workgroups per QP (one column pair each) when the batch leaves room for them: B <= #CUs / 4
             if (P.Ks >= 7 && 4 * B <= d.cus && k.loop_split4 != 0) {
                 plan.split_lds = split_loop_lds_bytes<512, 4>(P.Ks, m);
-                plan.split_fn = l1 ? loop_split_fn_l1<4>(P.Ks) : loop_split_fn<4>(plan.stop, P.Ks, false);
+                plan.split_fn = loop_split_fn<4>(form, P.Ks, false);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 4))) loop_np = 4;
             }
             if (loop_np != 4) {
                 plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-                plan.split_fn = l1 ? loop_split_fn_l1<2>(P.Ks) : loop_split_fn<2>(plan.stop, P.Ks, g_lu_dbg != nullptr);
+                plan.split_fn = loop_split_fn<2>(form, P.Ks, g_lu_dbg != nullptr);
                 if (fits(d, plan.split_fn, plan.split_nt, plan.split_lds, shared_grid(B, 2))) loop_np = 2;
             }
             if (loop_np > 1) { plan.kind = LOOP_SPLIT; plan.kind_wg = loop_np; }
@@ -933,10 +943,10 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
         // above 512 rows (BASELINE configs[3]: n = 1000): the streaming loop of the symmetric path with TWO workgroups per problem, each
         // streaming one range of whole block columns of H (admm_loop_body_from, NP == 2): twice the registers and LDS under the same
         // matrix (16 % -> 32 % of it on chip), half the stream per CU -- one CU alone pulls 58 GB/s, 29 us per iteration at n = 1000
-        plan.np2_fn = l1 ? k_admm_loop_np2_l1<> : k_admm_loop_np2<>;
-        if (spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && plan.loop_nt == 1024 && k.loop_np2 != 0 && !solo && !each &&
-            !(retry & 2) && fits(d, plan.np2_fn, 1024, plan.loop_lds, shared_grid(B, 2))) {
-            plan.kind = LOOP_NP2; plan.kind_wg = 2;
+        if (family_has_form(LOOP_NP2, form) && spd && mode == 2 && P.xchg && P.Ks > SPD_MAXK && P.Ks <= SPD_BIGK && plan.loop_nt == 1024 &&
+            k.loop_np2 != 0 && !solo && !(retry & 2)) {
+            plan.np2_fn = np2_kernel(form);
+            if (fits(d, plan.np2_fn, 1024, plan.loop_lds, shared_grid(B, 2))) { plan.kind = LOOP_NP2; plan.kind_wg = 2; }
         }
         // ... and for batches LARGER than half the CUs (BASELINE configs[4]: 1024 per GPU), where the loop runs one launch per
         // check segment anyway: the same kernel, its pairs taking turns on the chip (FwdParams::split_seg) -- a pair holds its
@@ -945,15 +955,14 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
         if (spd && mode == 1 && P.xchg && P.Ks >= SPLIT_MINK && P.Ks <= SPD_MAXK && check >= 4 &&
             k.loop_split != 0 && k.loop_split_seg != 0 && !(retry & 2) && !solo && 2 * B > d.cus) {
             plan.split_lds = split_loop_lds_bytes<512>(P.Ks, m);
-            plan.split_fn = l1 ? loop_split_fn_l1<2>(P.Ks) : loop_split_fn<2>(plan.stop, P.Ks, false);
+            plan.split_fn = loop_split_fn<2>(form, P.Ks, false);
             plan.loop_split_seg = fits(d, plan.split_fn, plan.split_nt, plan.split_lds, 0);
         }
     }
     // LU tier, persistent mode, n <= 256, 2 B workgroups resident: the explicit inverse of the KKT matrix in the registers of two
     // workgroups per problem (lqp_dense.hpp) -- float64, many equality rows, non-symmetric Q, control['linsolve'] = 'lu'
-    // (L1: the dense tiers have no StepL1 instance -- their problems run the streaming LU body, the plan's default, which holds
-    //  every size, dtype and m; an inverse in registers pays off least where the element-wise step grows)
-    if (!spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0 && !each && !l1) {
+    // (the plain form alone, family_has_form: an inverse in registers pays off least where the element-wise step grows)
+    if (family_has_form(LOOP_DENSE, form) && !spd && mode == 2 && P.dnx && n <= DENSE_NMAX && k.loop_dense != 0) {
         const int dense_lds = dense_loop_lds_bytes<T>(m);
         if (lu_inverse_lds_bytes<T>(P.Np) <= 160 * 1024 && fits(d, k_admm_loop_dense<T>, DENSE_NT, dense_lds, shared_grid(B, 2))) {
             plan.kind = LOOP_DENSE; plan.kind_lds = dense_lds; plan.kind_wg = 2;
@@ -961,7 +970,7 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
     }
     // ... and for batches that leave most of the chip idle, any n the inverse kernel takes: W workgroups per problem, each with its
     // rows of the inverse in registers (k_admm_loop_dense_w): a matrix-vector product spreads over CUs, triangular solves do not
-    if (!spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && !each && !l1 && lu_inverse_fits<T>(P.Np) &&
+    if (family_has_form(LOOP_DENSE_W, form) && !spd && mode == 2 && P.dnx && plan.kind != LOOP_DENSE && n > DENSE_NMAX && k.loop_dense_w != 0 && lu_inverse_fits<T>(P.Np) &&
         (size_t)P.dnx_words >= densew_xchg_words<T>(n)) {
         const int densew_lds = densew_lds_bytes<T>(n, m);
         const int tpr = densew_tpr(n, densew_cpt<T>());
@@ -974,7 +983,7 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
         // small problems (n <= 128, e.g. BASELINE configs[1]): 256 threads per QP, the full matrix in registers (k_admm_loop_small)
         if (spd && mode == 2 && plan.kind != LOOP_SPLIT && P.Ks <= 2 && k.loop_small != 0) {
             const int small_lds = small_loop_lds_bytes(m);
-            plan.small_fn = l1 ? k_admm_loop_small_l1<> : small_loop_kernel(plan.stop);
+            plan.small_fn = small_loop_kernel(form);
             if (fits(d, plan.small_fn, 256, small_lds, B)) { plan.kind = LOOP_SMALL; plan.kind_lds = small_lds; }
         }
         // the equality correction of the first factorisation moves into that kernel (its blocks are in registers there)
@@ -991,7 +1000,7 @@ template <typename T> void plan_hot_kind(FwdParams<T>& P, const lqp_boxqp_ctrl* 
 // ---- the scheduler ----
 template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const Knobs& k, FwdPlan<T>& plan) {
     const int max_iters = ctl->max_iters, ar_iter = P.ar_iter;
-    const bool spd = plan.spd, each = plan.stop != STOP_ALL;
+    const bool spd = plan.spd, each = form_each(plan.form);
     // no-host-sync plan (ctrl.reserved == 1, persistent launches): enqueue the WHOLE schedule.
     // Every kernel exits at once when the device-side DONE flag is up, the refactor chains are
     // gated on device, so nothing needs the host; errors are read later by the caller
@@ -1016,7 +1025,7 @@ template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl*
     plan.hot_rounds = (ctl->rho_mode != 0 && !each) ? k.hot_rounds : 0;
     // (each: workgroups leave the last launch at different times -- workgroup 0 cannot report the status block from inside it)
     // (L1: the epilogue takes two more outputs, a launch of its own)
-    plan.tail_epilogue = k.tail_epilogue != 0 && !each && !plan.l1;
+    plan.tail_epilogue = k.tail_epilogue != 0 && plan.form == FORM_ALL;
     plan.spec_launches = k.spec_launches;
     plan.factor_launches = spd ? (plan.spd_big_split ? 2 * P.Ks + 2 : plan.spd_split ? (plan.spd_resident ? 3 : P.Ks + 2) : 1) : 2;
     plan.loop_workgroups = plan.loop_split_seg ? 2 : plan.kind_wg;      // (what the loop's launches put on a problem)
@@ -1033,8 +1042,7 @@ template <typename T> int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ct
     plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0; plan.l1a = l1a;
     // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
     // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
-    plan.stop = loop_stop(P);
-    plan.l1 = with_l1(P);
+    plan.form = loop_form(P);
     plan.dbg_loop_absent = k.dbg_loop_absent;
     P.xcd_local = k.xcd_local != 0 ? 1 : 0;
     P.dbg_qpass = k.dbg_qpass;      // (bit 0: the second half of the debug buffer; bits 8..: the wave whose stamps the resident sweep records)
@@ -1142,7 +1150,7 @@ int enqueue_prologue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pl
         if (rc) return rc;
         ++n_launch;
     }
-    if (plan.l1) {      // ws, cs: behind whoever wrote the scaling vector (the setup kernel, or the resident sweep it defers to)
+    if (plan.form == FORM_L1) {      // ws, cs: behind whoever wrote the scaling vector (the setup kernel, or the resident sweep it defers to)
         ProfScope ps(st, PC_SETUP);
         hipLaunchKernelGGL(k_l1_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.l1a.w, (const T*)plan.l1a.c);
         ++n_launch;
@@ -1296,7 +1304,7 @@ Attempt run_planned(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
     }
     if (!epilogue_done) {
         ProfScope ps(st, PC_EPILOGUE);
-        if (plan.l1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
+        if (plan.form == FORM_L1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
           else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
         ++n_launch;
     }
@@ -1409,7 +1417,7 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         // the epilogue only reads state: run it now so that the common case (converged in this chunk)
         // pays no host round trip between the loop and its outputs; a later chunk simply re-runs it
         { ProfScope ps(st, PC_EPILOGUE);
-          if (plan.l1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
+          if (plan.form == FORM_L1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
           else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P); }
         ++n_launch;
         // (with a host report the epilogue has left status and info words in pinned host memory: one wait, no copies)
@@ -1465,7 +1473,7 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         chunk_cap = std::min(chunk_cap * 2, 64);
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
-    if (plan.l1) {
+    if (plan.form == FORM_L1) {
         // a weight that is negative or not finite (k_l1_setup marks the problem's flag word; the epilogue has reported it)
         std::vector<int> fl(B);
         if (P.host_report) for (int i = 0; i < B; ++i) fl[i] = ((const volatile int*)P.host_report)[ST_WORDS + B + i];
@@ -1500,11 +1508,11 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
                  int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const L1Args* l1 = nullptr) {
     // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; l1: lqp_boxqp_forward_l1)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    const LoopStop asked = loop_stop(true, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);      // (under stop = 'each')
-    if (ws_bytes < (l1 ? L.l1_bytes : asked == STOP_CERTIFY ? L.certify_bytes : asked == STOP_DETECT ? L.detect_bytes : L.bytes)) return LQP_ERR_WORKSPACE;
+    const LoopForm asked = loop_form(l1 != nullptr, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
+    if (ws_bytes < L.bytes_for(asked)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
-        if (l1) { P.l1 = 1; P.l1v = (T*)L.l1_area; }
+        if (asked == FORM_L1) { P.l1 = 1; P.l1v = (T*)L.l1_area; }
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
         P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in; P.beta_in = (const T*)ctl->beta_in;
         P.x = (T*)x; P.z = (T*)z; P.u = (T*)u; P.lams = (T*)lams; P.nus = (T*)nus; P.rho_out = (T*)rho_out;
@@ -1515,8 +1523,8 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         if (ctl->reserved2 & 8) {
             if (ctl->check_hook) return LQP_ERR_INVALID;
             P.pstat = L.pstat_area;
-            if (asked != STOP_EACH) {
-                P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m, asked == STOP_CERTIFY);
+            if (form_snapshots(asked)) {
+                P.snap = (T*)L.snap_area; P.snap_stride = snap_stride(n, m, asked == FORM_CERTIFY);
                 P.eps_pinf = (T)eps_prim_inf; P.eps_dinf = (T)eps_dual_inf;
             }
         }
@@ -1547,7 +1555,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         int rc = plan_forward(P, ctl, retry, k, d, plan);
         if (rc) return rc;
         int n_launch = 0;
-        if (has_snapshots(P)) { hipLaunchKernelGGL(k_snap_init<T>, dim3((2 * B + 255) / 256), dim3(256), 0, st, P.snap, P.snap_stride, B); ++n_launch; }
+        if (form_snapshots(plan.form)) { hipLaunchKernelGGL(k_snap_init<T>, dim3((2 * B + 255) / 256), dim3(256), 0, st, P.snap, P.snap_stride, B); ++n_launch; }
         rc = enqueue_prologue(st, P, plan, n_launch);
         if (rc) return rc;
         const Attempt a = plan.up_front ? run_planned(st, P, plan, ctl, stats, n_launch) : run_chunked(st, P, plan, ctl, stats, n_launch);
@@ -2260,7 +2268,7 @@ size_t lqp_boxqp_forward_workspace_bytes(int dtype, int B, int n, int m) {
 
 size_t lqp_boxqp_forward_detect_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).detect_bytes; });
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_DETECT); });
 }
 
 // lqp_boxqp_forward (both thresholds 0: no detection), lqp_boxqp_forward_detect (eps_dual_inf = 0) and lqp_boxqp_forward_certify
@@ -2309,7 +2317,7 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const
 
 size_t lqp_boxqp_forward_l1_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).l1_bytes; });
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_L1); });
 }
 
 int lqp_boxqp_forward_l1(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
@@ -2360,7 +2368,7 @@ int lqp_boxqp_l1_finish_grads(void* stream, int dtype, int B, int n, const void*
 
 size_t lqp_boxqp_forward_certify_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
-    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).certify_bytes; });
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_CERTIFY); });
 }
 
 int lqp_boxqp_forward_certify(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,

@@ -127,7 +127,7 @@ template <typename T> struct L1View {
     __device__ L1View(T* base, int n) { ws = base; cs = ws + round_up(n, 8); t = cs + round_up(n, 8); }
 };
 // control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
-// number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split_each:
+// number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split, FormEach:
 // bit-identical iterates, at most one hand-off apart) write the same values and never a slot somebody still reads.
 // A slot: [rho it was taken at | mark = iteration + 1 (0: none, k_snap_init) | - | - | y (n) | g (n) | nu (m)], and behind nu, with the dual
 // certificate alone (control['unbounded'], `dual`): [x (n) | qx (n)], qx = Qs x -- see dinf_elem
@@ -1456,11 +1456,21 @@ __device__ __forceinline__ AdmmStep<T> admm_step_tag(const FwdParams<T>& P, cons
 }
 // The step with an L1 term w |x - c| in the objective (lqp_boxqp_forward_l1): the prox of the two separable terms is "soft-threshold
 // around cs, then clamp", t = ws / rho with the rho of this iteration; r, s, u are the lines of admm_step_as.  The branch form of
-// l1_shrink returns v itself at t = 0: w = 0 gives the plain step's bits.  A compile-time tag beside the relaxation's (StepBox: the
-// kernels there always were, not one instruction of theirs knows about this; StepL1: instances of their own), never a run-time flag.
-struct StepBox { static constexpr bool l1 = false; };
-struct StepL1 { static constexpr bool l1 = true; };
-// what a thread of the streaming loop keeps of the L1 data (nothing at all in a StepBox instance)
+// l1_shrink returns v itself at t = 0: w = 0 gives the plain step's bits.  A compile-time choice (Form*::l1 below), never a run-time flag.
+//
+// The FORM of a loop kernel: the five ways a solve runs its loop, one tag each -- every loop family (admm_loop_body, admm_loop_small_body,
+// admm_loop_split_body) has an instance per form it supports, named by the tag (k_admm_loop<..., lqp::FormEach>), and the host's
+// LoopForm / by_form (lqp_amd.hip) is the run-time twin.  A combination that is no form cannot be written.
+//   each:   control['stop'] = 'each' -- every problem stops and adapts rho as a batch of one
+//   detect: ... with the primal infeasibility certificate at every check (control['infeasible'])
+//   dual:   ... and the dual certificate beside it (control['unbounded'])
+//   l1:     lqp_boxqp_forward_l1 -- the element-wise step with the L1 term; the batch stops as one
+struct FormAll     { static constexpr bool each = false, detect = false, dual = false, l1 = false; };
+struct FormEach    { static constexpr bool each = true,  detect = false, dual = false, l1 = false; };
+struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false, l1 = false; };
+struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true,  l1 = false; };
+struct FormL1      { static constexpr bool each = false, detect = false, dual = false, l1 = true; };
+// what a thread of the streaming loop keeps of the L1 data (nothing at all in an instance without the L1 step)
 template <typename T, bool ON> struct L1Own {};
 template <typename T> struct L1Own<T, true> { T t0 = T(0), c0 = T(0); const T *t = nullptr, *cs = nullptr; };
 template <bool RELAX, typename T>
@@ -1716,7 +1726,7 @@ __device__ __forceinline__ int infeas_finish(const FwdParams<T>& P, const Infeas
 // stops at the first check at which IT is optimal (its workgroup stores the iterate, marks pstat[b] and returns), it adapts rho at
 // an event iff its own `wants && trig` of the last check say so, and nothing crosses workgroups: no grid_wait, no arrival word,
 // no decision from the counters.  A launch begins by reading pstat[b].done and leaves at once when it is set.
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false, typename STEP = StepBox>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem);
 // does the adaptive-rho event at iteration seg0 change this problem's rho?  The reference's decision over the whole batch, from the
@@ -1763,32 +1773,31 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
     loop_event_count<T, EACH>(P, b, seg0);
     return rho_;
 }
-// DETECT (EACH only; control['infeasible']): the certificate at every check (infeas_view ...), instances of their own: inside the one body
+// FORM (FormAll ... FormL1), read as EACH, DETECT, DUAL and L1 below:
+// DETECT (control['infeasible']): the certificate at every check (infeas_view ...), instances of their own: inside the one body
 // its registers cost the plain EACH kernels 3 % of their time
-// DUAL (DETECT only; control['unbounded']): the dual certificate too, instances of their own again (k_admm_loop_each_certify): under a
+// DUAL (control['unbounded']): the dual certificate too, instances of their own again (FormCertify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
-// STEP (StepBox | StepL1): the element-wise step, see admm_step_l1_as -- lqp_boxqp_forward_l1's kernels are instances of their own
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false, int NP = 1, bool EACH = false, bool DETECT = false, bool DUAL = false, typename STEP = StepBox>
+// L1: the element-wise step, see admm_step_l1_as -- lqp_boxqp_forward_l1's kernels are instances of their own
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
                                                const int prev_slot,      // slot of the last check before it0, -1: none / known not done
                                                const int persistent, char* smem) {
     // every problem stopped at an earlier check -> nothing to do (break at :312)
     if (__hip_atomic_load(P.status + ST_DONE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    if constexpr (EACH) {
+    if constexpr (FORM::each) {
         // this problem stopped in an earlier launch: its iterate is not touched again
         if (__builtin_amdgcn_readfirstlane(P.pstat[(size_t)blockIdx.x * PS_WORDS + PS_DONE])) return;
     }
-    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, EACH, DETECT, DUAL, STEP>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+    admm_loop_body_from<T, RES, TAIL, NT, SYM, NP, FORM>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
-template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, bool EACH, bool DETECT, bool DUAL, typename STEP>
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
+    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1;      // (static: never a lambda's capture)
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
-    static_assert(!DETECT || EACH, "the infeasibility certificate is part of a problem's own stopping check");
-    static_assert(!DUAL || DETECT, "the dual certificate shares the primal one's snapshot and reduction");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
-    static_assert(!STEP::l1 || !EACH, "the L1 step has no per-problem form (lqp_boxqp_forward_l1 refuses control['stop'] = 'each')");
     int b = blockIdx.x, part_id = 0;
     if constexpr (NP == 2) { if (!shared_map((int)blockIdx.x, P.B, 2, b, part_id)) return; }
     const bool lead = part_id == 0;                          // (the workgroup that reports and writes state)
@@ -1932,11 +1941,11 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         z[i] = V.z[i]; u[i] = V.u[i]; ps[i] = V.ps[i]; lb[i] = V.lbs[i]; ub[i] = V.ubs[i]; D[i] = V.D[i];
     }
     for (int r = tid; r < m; r += NT) bs[r] = V.bs[r];
-    // StepL1: t = ws / rho with this segment's rho (a division per element and rho, none per iteration).  A thread keeps t and cs of
+    // L1: t = ws / rho with this segment's rho (a division per element and rho, none per iteration).  A thread keeps t and cs of
     // its first element in registers; those of its further elements (n > NT only) come from the workspace, where it stores their t
     // itself here -- nothing is stored for the first (both workgroups of a shared problem would write the same values)
-    L1Own<T, STEP::l1> l1o;
-    if constexpr (STEP::l1) {
+    L1Own<T, L1> l1o;
+    if constexpr (L1) {
         const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
         for (int i = tid + NT; i < n; i += NT) W.t[i] = W.ws[i] / rho;
         if (tid < n) { l1o.t0 = W.ws[tid] / rho; l1o.c0 = W.cs[tid]; }
@@ -2053,7 +2062,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     const T ui = u[i];
                     const T xh = admm_relax(xi, zp, P);      // (the lines of admm_step)
                     T zn = xh + ui;
-                    if constexpr (STEP::l1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
+                    if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
                     zn = tmin(tmax(zn, lb[i]), ub[i]);     // (:273-276; an infinite bound is a no-op)
                     const T r = xi - zn;
                     const T s = rho * (zn - zp);
@@ -2100,7 +2109,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 const T ui = u[i];
                 const T xh = admm_relax(xi, zp, P);          // (the lines of admm_step)
                 T zn = xh + ui;
-                if constexpr (STEP::l1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
+                if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
                 zn = tmin(tmax(zn, lb[i]), ub[i]);
                 const T r = xi - zn;
                 const T s = rho * (zn - zp);
@@ -2224,66 +2233,28 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
     __syncthreads();
   }
 }
-// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2)
-template <int LQP_ANY = 0>
+// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1
+template <typename FORM>
 __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                         const int prev_slot, const int persistent) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<float, true, false, 1024, true, 2>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+    admm_loop_body<float, true, false, 1024, true, 2, FORM>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
 
-// ... and with the L1 step (lqp_boxqp_forward_l1)
-template <int LQP_ANY = 0>
-__global__ __launch_bounds__(1024) void k_admm_loop_np2_l1(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
-                                                           const int prev_slot, const int persistent) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<float, true, false, 1024, true, 2, false, false, false, StepL1>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
-}
-
-// persistent & 4 (continuation launches): this is the forward's LAST launch -- it ends with the epilogue (fwd_finish)
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
+// The one-workgroup loop in every form.  persistent & 4 (continuation launches, FormAll): this is the forward's LAST launch -- it ends
+// with the epilogue (fwd_finish).  No other form ever is the last launch: under stop = 'each' the workgroups leave at different times,
+// and the L1 epilogue takes two more outputs (k_fwd_epilogue_l1) -- a launch of its own for both.
+template <typename T, bool RES, bool TAIL, int NT, bool SYM, typename FORM>
 __global__ __launch_bounds__(NT) void k_admm_loop(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
-                                                      const int prev_slot, const int persistent) {
+                                                  const int prev_slot, const int persistent) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<T, RES, TAIL, NT, SYM>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
-    if constexpr (TAIL) {
+    admm_loop_body<T, RES, TAIL, NT, SYM, 1, FORM>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
+    if constexpr (TAIL && std::is_same<FORM, FormAll>::value) {
         if (persistent & 4) {
             __syncthreads();                   // (the state the loop left in global memory: written by other threads)
             fwd_finish(P, blockIdx.x);
         }
     }
-}
-
-// lqp_boxqp_forward_l1: the same loop with the L1 step (StepL1).  Never the forward's last launch: its epilogue takes two more
-// outputs and is a launch of its own (k_fwd_epilogue_l1)
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
-__global__ __launch_bounds__(NT) void k_admm_loop_l1(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
-                                                     const int prev_slot, const int persistent) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<T, RES, TAIL, NT, SYM, 1, false, false, false, StepL1>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
-}
-
-// control['stop'] = 'each': the same loop, every problem on its own (admm_loop_body_from, EACH).  Never the forward's last launch:
-// its workgroups leave at different times, so the epilogue is a launch of its own.
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
-__global__ __launch_bounds__(NT) void k_admm_loop_each(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
-                                                       const int prev_slot, const int persistent) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<T, RES, TAIL, NT, SYM, 1, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
-}
-// ... with the infeasibility certificate at every check (control['infeasible']; DETECT)
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
-__global__ __launch_bounds__(NT) void k_admm_loop_each_detect(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
-                                                              const int prev_slot, const int persistent) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<T, RES, TAIL, NT, SYM, 1, true, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
-}
-// ... and with the dual certificate beside it (control['unbounded']; DUAL)
-template <typename T, bool RES, bool TAIL, int NT, bool SYM = false>
-__global__ __launch_bounds__(NT) void k_admm_loop_each_certify(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
-                                                               const int prev_slot, const int persistent) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_body<T, RES, TAIL, NT, SYM, 1, true, true, true>(P, it0, it1, ctr_base, prev_slot, persistent, smem);
 }
 
 // all problems optimal at the check held in `slot` (iteration `it_check`)?  -> DONE

@@ -1,4 +1,4 @@
-// The ADMM loop of the symmetric path for n <= 128: k_admm_loop_small and, for control['stop'] = 'each', k_admm_loop_small_each
+// The ADMM loop of the symmetric path for n <= 128: k_admm_loop_small, an instance per form (FormAll ... FormL1)
 #pragma once
 #include "lqp_boxqp.hpp"
 
@@ -15,14 +15,16 @@ namespace lqp {
 // LDS: w[128] | y[128] | nus[m] | red[4 * 8 + 8]
 // ---------------------------------------------------------------------------
 __host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 + (m > 0 ? m : 1) + 4 * 8 + 8 + 8) * 4; }
+// FORM (FormAll ... FormL1), read as EACH, DETECT, DUAL and L1 below:
 // EACH (control['stop'] = 'each'): the problem's own verdict ends its workgroup; no arrival word, no grid_wait
-// DETECT (EACH only; control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
+// DETECT (control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
 // check iterations, and the certificate's registers in it cost the plain EACH kernel 12 % of its time
-// DUAL (DETECT only; control['unbounded']): the dual certificate too, k_admm_loop_small_each_certify
-// STEP (StepBox | StepL1): the element-wise step; StepL1 (lqp_boxqp_forward_l1, k_admm_loop_small_l1) keeps t = ws / rho and cs beside lb / ub
-template <bool EACH, bool DETECT = false, bool DUAL = false, typename STEP = StepBox>
+// DUAL (control['unbounded']): the dual certificate too
+// L1 (lqp_boxqp_forward_l1): the element-wise step with the L1 term; keeps t = ws / rho and cs beside lb / ub
+template <typename FORM>
 __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                      char* smem) {
+    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1;      // (static: never a lambda's capture)
     typedef float T;
     constexpr int NT = 256;
     const int b = blockIdx.x, n = P.n, m = P.m, Ks = P.Ks;
@@ -75,9 +77,8 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
     T zi = live ? V.z[e] : T(0), ui = live ? V.u[e] : T(0);
     const T psi = live ? V.ps[e] : T(0), lbi = live ? V.lbs[e] : T(0), ubi = live ? V.ubs[e] : T(0);
     const T di = live ? V.D[e] : T(1), cvi = (live && m > 0) ? V.cv[e] : T(0);
-    T l1t = T(0), l1c = T(0);           // (StepL1; rho is this launch's: an adaptive-rho event ends it)
-    if constexpr (STEP::l1) {
-        static_assert(!EACH, "the L1 step has no per-problem form");
+    T l1t = T(0), l1c = T(0);           // (L1; rho is this launch's: an adaptive-rho event ends it)
+    if constexpr (L1) {
         const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
         if (live) { l1t = W.ws[e] / rho; l1c = W.cs[e]; }
     }
@@ -122,7 +123,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
             const T wi = wv[e];
             xi = cvi - yv[e];
             AdmmStep<T> sp;
-            if constexpr (STEP::l1) sp = admm_step_l1_tag<RelaxDyn>(P, xi, zi, ui, lbi, ubi, rho, l1t, l1c);
+            if constexpr (L1) sp = admm_step_l1_tag<RelaxDyn>(P, xi, zi, ui, lbi, ubi, rho, l1t, l1c);
             else sp = admm_step(P, xi, zi, ui, lbi, ubi, rho);
             zi = sp.zn;
             ui = sp.un;
@@ -180,33 +181,10 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
         }
     }
 }
-template <int LQP_ANY = 0>      // (a template only so that the split build can place its one instance: tools/gen_split_build.py)
+template <typename FORM>
 __global__ __launch_bounds__(256) void k_admm_loop_small(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_small_body<false>(P, it0, it1, ctr_base, smem);
-}
-template <int LQP_ANY = 0>
-__global__ __launch_bounds__(256) void k_admm_loop_small_l1(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_small_body<false, false, false, StepL1>(P, it0, it1, ctr_base, smem);
-}
-template <int LQP_ANY = 0>
-__global__ __launch_bounds__(256) void k_admm_loop_small_each(const FwdParams<float> P, const int it0, const int it1,
-                                                              const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_small_body<true>(P, it0, it1, ctr_base, smem);
-}
-template <int LQP_ANY = 0>
-__global__ __launch_bounds__(256) void k_admm_loop_small_each_detect(const FwdParams<float> P, const int it0, const int it1,
-                                                                     const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_small_body<true, true>(P, it0, it1, ctr_base, smem);
-}
-template <int LQP_ANY = 0>
-__global__ __launch_bounds__(256) void k_admm_loop_small_each_certify(const FwdParams<float> P, const int it0, const int it1,
-                                                                      const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_small_body<true, true, true>(P, it0, it1, ctr_base, smem);
+    admm_loop_small_body<FORM>(P, it0, it1, ctr_base, smem);
 }
 
 }  // namespace lqp

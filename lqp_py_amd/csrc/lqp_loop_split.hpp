@@ -1,5 +1,5 @@
-// The ADMM loop of the symmetric path on two or four workgroups per problem, the matrix in their registers: k_admm_loop_split and,
-// for control['stop'] = 'each', k_admm_loop_split_each
+// The ADMM loop of the symmetric path on two or four workgroups per problem, the matrix in their registers: k_admm_loop_split, an
+// instance per form it has (FormAll, FormEach, FormL1)
 #pragma once
 #include "lqp_boxqp.hpp"
 
@@ -41,13 +41,16 @@ template <int NT, int NP = 2> __host__ __device__ inline int split_loop_lds_byte
 // EACH (control['stop'] = 'each'): the partners hold bit-identical iterates and compute the same six norms, so each of them reaches the
 // problem's verdict in the same iteration with no message: no arrival word, no snapshot, no look-back, no verdict in the tags (all
 // compiled out).  Optimal -> the lead workgroup stores the iterate and marks pstat[b], every workgroup of the problem returns.  The hot
-// launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop_each) takes the problem's own decision.
+// launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop, FormEach ...) takes the problem's own decision.
 // (P by value: a reference to the kernel's parameter block costs the default's instances registers)
-// STEP (StepBox | StepL1): the element-wise step of every iteration form below.  StepL1 (lqp_boxqp_forward_l1, k_admm_loop_split_l1): thread i
-// keeps t = ws_i / rho and cs_i in two registers beside its element -- rho is this launch's, an event that changes it ends the launch
-template <int KS, int NT, bool DBG, int NP, bool EACH, typename STEP = StepBox>
+// FORM: FormAll, FormEach (which takes the certificates from P.snap and P.eps_dinf at run time: it serves FormDetect and FormCertify
+// solves too) or FormL1 (lqp_boxqp_forward_l1: the element-wise step of every iteration form below with the L1 term; thread i
+// keeps t = ws_i / rho and cs_i in two registers beside its element -- rho is this launch's, an event that changes it ends the launch)
+template <int KS, int NT, bool DBG, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, int it0, const int it1, int ctr_base, char* smem) {
     typedef float T;
+    static_assert(!FORM::detect, "the split loop's per-problem form reads the certificates at run time: FormEach is its instance");
+    static constexpr bool EACH = FORM::each, L1 = FORM::l1;      // (static: never a lambda's capture -- a generic lambda would take a plain local by reference)
     if (P.hot_resume) {            // (a later round of the hot loop: it goes on where the round before stopped)
         const int r = __builtin_amdgcn_readfirstlane(P.status[ST_RESUME]);
         if (r <= 0) return;
@@ -132,8 +135,8 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
     }
     for (int r = tid; r < m; r += NT) bs[r] = V.bs[r];
     T l1t = T(0), l1c = T(0);
-    if constexpr (STEP::l1) {
-        static_assert(!EACH && NT >= KS * LQP_NB, "the L1 step: one element per thread, no per-problem form");
+    if constexpr (L1) {
+        static_assert(NT >= KS * LQP_NB, "the L1 step: one element per thread");
         const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
         if (tid < n) { l1t = W.ws[tid] / rho; l1c = W.cs[tid]; }
     }
@@ -403,7 +406,7 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
             const int i = tid;
             xs[i] = xi;
             AdmmStep<T> sp;
-            if constexpr (STEP::l1) sp = admm_step_l1_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho, l1t, l1c);
+            if constexpr (L1) sp = admm_step_l1_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho, l1t, l1c);
             else sp = admm_step_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho);
             const T zn = sp.zn, un = sp.un;
             const bool in = i < n;
@@ -575,20 +578,10 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
     }
 #undef LQP_BY_PART
 }
-template <int KS, int NT, bool DBG = false, int NP = 2>
+template <int KS, int NT, bool DBG, int NP, typename FORM>
 __global__ __launch_bounds__(NT) void k_admm_loop_split(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
     extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_split_body<KS, NT, DBG, NP, false>(P, it0, it1, ctr_base, smem);
-}
-template <int KS, int NT, bool DBG = false, int NP = 2>
-__global__ __launch_bounds__(NT) void k_admm_loop_split_l1(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_split_body<KS, NT, DBG, NP, false, StepL1>(P, it0, it1, ctr_base, smem);
-}
-template <int KS, int NT, bool DBG = false, int NP = 2>
-__global__ __launch_bounds__(NT) void k_admm_loop_split_each(const FwdParams<float> P, const int it0, const int it1, const int ctr_base) {
-    extern __shared__ __attribute__((aligned(32))) char smem[];
-    admm_loop_split_body<KS, NT, DBG, NP, true>(P, it0, it1, ctr_base, smem);
+    admm_loop_split_body<KS, NT, DBG, NP, FORM>(P, it0, it1, ctr_base, smem);
 }
 
 }  // namespace lqp

@@ -41,14 +41,14 @@ C_DEV = 0.5
 
 # (tier row, what runs the step there)
 TIERS = [
-    ("small_n31_m1", "k_admm_loop_small_l1"),
-    ("sweep2_n129_m1", "k_admm_loop_split_l1, two workgroups, persistent"),
-    ("sweep4_n511_m0", "k_admm_loop_split_l1, four workgroups"),
-    ("turns_n449_half1", "k_admm_loop_split_l1, one launch per check segment, pairs taking turns"),
-    ("loop_split0_n330", "k_admm_loop_l1: the streaming body's symmetric branch, one workgroup"),
-    ("big_n513_m2", "k_admm_loop_np2_l1: the streaming body's symmetric branch, two workgroups"),
-    ("lu_nonsym_n300", "k_admm_loop_l1: the streaming body's LU branch, float32 (the plain solve takes the dense tier here)"),
-    ("lu1_n300_f64", "k_admm_loop_l1: the streaming body's LU branch, float64, segmented launches"),
+    ("small_n31_m1", "k_admm_loop_small<FormL1>"),
+    ("sweep2_n129_m1", "k_admm_loop_split<.., FormL1>, two workgroups, persistent"),
+    ("sweep4_n511_m0", "k_admm_loop_split<.., FormL1>, four workgroups"),
+    ("turns_n449_half1", "k_admm_loop_split<.., FormL1>, one launch per check segment, pairs taking turns"),
+    ("loop_split0_n330", "k_admm_loop<.., FormL1>: the streaming body's symmetric branch, one workgroup"),
+    ("big_n513_m2", "k_admm_loop_np2<FormL1>: the streaming body's symmetric branch, two workgroups"),
+    ("lu_nonsym_n300", "k_admm_loop<.., FormL1>: the streaming body's LU branch, float32 (the plain solve takes the dense tier here)"),
+    ("lu1_n300_f64", "k_admm_loop<.., FormL1>: the streaming body's LU branch, float64, segmented launches"),
     ("dense_n200_f32", "rerouted: the dense tier has no L1 instance, the streaming LU body runs"),
     ("densew_n257_f64", "rerouted: the W-workgroup dense tier has no L1 instance, the streaming LU body runs"),
     ("mode1_n330", "launch_mode = 1: the streaming body once per check segment"),
@@ -75,7 +75,7 @@ for _name, _what in TIERS:
         ROWS[f"{_name}-K{_K}"] = _row(_name, _K, _what, alpha=ALPHA if _name in RELAXED else 1.0)
 ROWS[f"{EVENT_ROW}-K{K_EVENT}"] = _row(EVENT_ROW, K_EVENT, "hot / tail forms of the split loop around an adaptive-rho event: t changes with rho")
 # above 1024 rows a thread of the streaming body owns a second element: its t comes back from the workspace
-ROWS["wide_n1025_f32-K10"] = _row("wide_n1025_f32", K_FAR, "k_admm_loop_l1, LU branch, n > 1024: the t region of the workspace is read")
+ROWS["wide_n1025_f32-K10"] = _row("wide_n1025_f32", K_FAR, "k_admm_loop<.., FormL1>, LU branch, n > 1024: the t region of the workspace is read")
 ROWS["allinf_n129-K60"] = _row("sweep2_n129_m1", K_NEAR, "every bound infinite: the loop schedule all the same", kind="allinf")
 ROWS["halfw_n330-K60"] = _row("loop_split0_n330", K_NEAR, "w = 0 on half the elements", kind="halfw")
 ROWS["cbound_n31-K60"] = _row("small_n31_m1", K_NEAR, "c_i equals a bound on some elements", kind="cbound")

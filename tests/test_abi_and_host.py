@@ -368,13 +368,13 @@ def test_register_budgets_of_the_hot_kernels():
         per step now and nothing is reloaded inside the loop -- same speed; the look-ahead form,
         round 4, held its tiles with 7 and was no faster: DESIGN.md section 8; its code left the sources in round 5);
       * the other k_spd_resident instances: no spilled VGPR, at most 72 B of scratch (the by-value parameter block of the sweep);
-      * k_admm_loop_split<8,512,false,2>: 132 spilled VGPRs, all in the once-per-launch equality prologue."""
+      * k_admm_loop_split<8,512,false,2,FormAll>: 132 spilled VGPRs, all in the once-per-launch equality prologue."""
     res = _kernel_resources()
     assert len(res) >= 80, len(res)
-    exact_zero = ["lqp::k_admm_loop_split<5, 512, false, 2>",
-                  "lqp::k_admm_loop_split<6, 512, false, 2>",
-                  "lqp::k_admm_loop_split<7, 512, false, 2>", "lqp::k_admm_loop_split<7, 512, false, 4>",
-                  "lqp::k_admm_loop_split<8, 512, false, 4>", "lqp::k_admm_loop_small<0>", "lqp::k_spd_prep<0>",
+    exact_zero = ["lqp::k_admm_loop_split<5, 512, false, 2, lqp::FormAll>",
+                  "lqp::k_admm_loop_split<6, 512, false, 2, lqp::FormAll>",
+                  "lqp::k_admm_loop_split<7, 512, false, 2, lqp::FormAll>", "lqp::k_admm_loop_split<7, 512, false, 4, lqp::FormAll>",
+                  "lqp::k_admm_loop_split<8, 512, false, 4, lqp::FormAll>", "lqp::k_admm_loop_small<lqp::FormAll>", "lqp::k_spd_prep<0>",
                   "lqp::k_bwd_build_chol<0>", "lqp::k_unroll_outer<0>", "lqp::k_pack<float>", "lqp::k_pack<double>",
                   "lqp::k_fwd_setup<double>"]
     for k in exact_zero:
@@ -384,7 +384,7 @@ def test_register_budgets_of_the_hot_kernels():
                 # round 6, the same sweep with two-half operands on the float16 matrix pipe (the instances that run by default)
                 "lqp::k_spd_resident<8, 2, true>": (94, 208), "lqp::k_spd_resident<7, 2, true>": (23, 100), "lqp::k_spd_resident<6, 2, true>": (0, 72), "lqp::k_spd_resident<8, 4, true>": (0, 72),
                 "lqp::k_spd_resident<5, 2, true>": (0, 72), "lqp::k_spd_resident<7, 4, true>": (0, 72), "lqp::k_spd_resident<3, 2, true>": (0, 72), "lqp::k_spd_resident<4, 2, true>": (0, 72),
-                "lqp::k_admm_loop_split<8, 512, false, 2>": (132, 260),
+                "lqp::k_admm_loop_split<8, 512, false, 2, lqp::FormAll>": (132, 260),
                 "lqp::k_bwd_chol_solve<0, false>": (36, 124), "lqp::k_bwd_chol_solve<0, true>": (38, 128), "lqp::k_bwd_chol_solve<4, true>": (38, 132),
                 # round 5, the two-workgroup pivoted LU: nothing spilled in the panel's column steps (the chain); 24 registers around
                 # the hand-off loads of the f32 build

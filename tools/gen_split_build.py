@@ -20,15 +20,22 @@ import sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(REPO, "lqp_py_amd", "csrc", "split")
 
+
+
+def loop(kernel, form, args=""):
+    """predicate: an instance of a loop kernel (the form tag is its last template argument) whose other arguments begin with `args`"""
+    return lambda n: re.search(rf"{kernel}<{args}[^>]*lqp::Form{form}>", n)
+
+
 # group -> predicate on the demangled name; first match wins.  Balanced by measured compile time (seconds at -O3).
 GROUPS = [
     # the instances with the L1 step (lqp_boxqp_forward_l1), grouped as their plain twins are
-    ("split_l1_c", lambda n: re.search(r"k_admm_loop_split_l1<(3|4), 512, false, 2>", n)),
-    ("split_l1_a", lambda n: re.search(r"k_admm_loop_split_l1<(5|6|7), 512, false, 2>", n)),
-    ("split_l1_b", lambda n: "k_admm_loop_split_l1<" in n),
-    ("loop_l1_tail", lambda n: re.search(r"k_admm_loop_l1<\w+, \w+, true,", n)),
-    ("loop_l1_hot", lambda n: "k_admm_loop_l1<" in n),
-    ("l1", lambda n: re.search(r"k_admm_loop_np2_l1<|k_admm_loop_small_l1<|k_fwd_epilogue_l1<|k_l1_", n)),
+    ("split_l1_c", loop("k_admm_loop_split", "L1", r"(3|4), 512, false, 2,")),
+    ("split_l1_a", loop("k_admm_loop_split", "L1", r"(5|6|7), 512, false, 2,")),
+    ("split_l1_b", loop("k_admm_loop_split", "L1")),
+    ("loop_l1_tail", loop("k_admm_loop", "L1", r"\w+, \w+, true,")),
+    ("loop_l1_hot", loop("k_admm_loop", "L1")),
+    ("l1", lambda n: loop("k_admm_loop_np2", "L1")(n) or loop("k_admm_loop_small", "L1")(n) or re.search(r"k_fwd_epilogue_l1<|k_l1_", n)),
     ("bwd_f", lambda n: re.search(r"k_bwd_chol_solve<\d, true>", n)),
     ("resident_f", lambda n: re.search(r"k_spd_resident<8, 2, true>", n)),
     ("resident_g", lambda n: re.search(r"k_spd_resident<(5|6|7), 2, true>", n)),
@@ -36,25 +43,25 @@ GROUPS = [
     ("resident_c", lambda n: re.search(r"k_spd_resident<(3|4), 2(, false)?>", n)),
     ("resident_a", lambda n: re.search(r"k_spd_resident<(5|6|7), 2(, false)?>", n)),
     ("resident_b", lambda n: re.search(r"k_spd_resident<8, 2(, false)?>|k_spd_resident<\d, 4(, false)?>", n)),
-    ("split_c", lambda n: re.search(r"k_admm_loop_split<(3|4), 512, false, 2>", n)),
-    ("split_a", lambda n: re.search(r"k_admm_loop_split<(5|6|7), 512, false, 2>", n)),
-    ("split_b", lambda n: "k_admm_loop_split<" in n),
-    ("split_each_b", lambda n: re.search(r"k_admm_loop_split_each<(3|4|8), 512, false, 2>|k_admm_loop_split_each<\d, 512, false, 4>", n)),
-    ("split_each_a", lambda n: "k_admm_loop_split_each<" in n),
-    ("loop_each_certify_tail", lambda n: re.search(r"k_admm_loop_each_certify<\w+, \w+, true,", n)),
-    ("loop_each_certify_hot", lambda n: "k_admm_loop_each_certify<" in n),
-    ("loop_each_detect_tail", lambda n: re.search(r"k_admm_loop_each_detect<\w+, \w+, true,", n)),
-    ("loop_each_detect_hot", lambda n: "k_admm_loop_each_detect<" in n),
-    ("loop_each_tail", lambda n: re.search(r"k_admm_loop_each<\w+, \w+, true,", n)),
-    ("loop_each_hot", lambda n: "k_admm_loop_each<" in n),
-    ("loop_tail", lambda n: re.search(r"k_admm_loop<\w+, \w+, true,", n)),
-    ("loop_hot", lambda n: "k_admm_loop<" in n),
+    ("split_c", loop("k_admm_loop_split", "All", r"(3|4), 512, false, 2,")),
+    ("split_a", loop("k_admm_loop_split", "All", r"(5|6|7), 512, false, 2,")),
+    ("split_b", loop("k_admm_loop_split", "All")),
+    ("split_each_b", loop("k_admm_loop_split", "Each", r"((3|4|8), 512, false, 2|\d, 512, false, 4),")),
+    ("split_each_a", loop("k_admm_loop_split", "Each")),
+    ("loop_each_certify_tail", loop("k_admm_loop", "Certify", r"\w+, \w+, true,")),
+    ("loop_each_certify_hot", loop("k_admm_loop", "Certify")),
+    ("loop_each_detect_tail", loop("k_admm_loop", "Detect", r"\w+, \w+, true,")),
+    ("loop_each_detect_hot", loop("k_admm_loop", "Detect")),
+    ("loop_each_tail", loop("k_admm_loop", "Each", r"\w+, \w+, true,")),
+    ("loop_each_hot", loop("k_admm_loop", "Each")),
+    ("loop_tail", loop("k_admm_loop", "All", r"\w+, \w+, true,")),
+    ("loop_hot", loop("k_admm_loop", "All")),
     ("dense", lambda n: "k_lu_inverse<" in n or "k_admm_loop_dense" in n),
     ("lu2", lambda n: "k_lu_factor2<" in n),
     ("lu_a", lambda n: re.search(r"k_lu_factor<float, (32|16), true|k_lu_factor_big|k_lu_factor_wide", n)),
     ("lu_b", lambda n: "k_lu_factor<" in n),
     ("spd", lambda n: re.search(r"k_spd_|k_bwd_chol_solve|k_bwd_build_chol|k_debug_chol_solve|k_debug_chol_factor", n)),
-    ("unroll", lambda n: "k_unroll_" in n or "k_admm_loop_small<" in n),
+    ("unroll", lambda n: "k_unroll_" in n or loop("k_admm_loop_small", "All")(n)),
     ("misc", lambda n: True),
 ]
 
@@ -63,30 +70,25 @@ BOTH, F32, ZERO = [("double",), ("float",)], [("float",)], [(0,)]
 FP, BP, ULP = "lqp::FwdParams<{0}>", "lqp::BwdParams<{0}>", "lqp::UnrollLuParams<{0}>"
 FPF, BPF = "lqp::FwdParams<float>", "lqp::BwdParams<float>"
 KS_NP = [(3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4)]      # Ks, workgroups per problem (four: Ks = 7, 8 only)
+# The forms of the loop kernels (the tags of lqp_boxqp.hpp), the last template argument of every instance: the batch stops as one |
+# control['stop'] = 'each' | ... with the infeasibility certificate (control['infeasible']) | ... and the dual certificate beside it
+# (control['unbounded']) | lqp_boxqp_forward_l1: the L1 step
+ALL, EACH, DETECT, CERTIFY, L1 = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify", "L1"))
+FORMS = (ALL, EACH, DETECT, CERTIFY, L1)
 SPLIT = [(ks, 512, False, np_) for ks, np_ in KS_NP]
 # the one-workgroup loop, hot and continuation: LU f64 | LU f32 | LU f32 resident | symmetric
 LOOP = [(t, res, tail, 1024, sym) for tail in (False, True)
         for t, res, sym in (("double", False, False), ("float", False, False), ("float", True, False), ("float", True, True))]
+in_forms = lambda args, forms: [a + (f,) for f in forms for a in args]
 LOOP_SIG = FP + ", int, int, int, int, int"
 LU_SIG = "{0}*, int, int, unsigned long, int*, int, int*, int const*"
 WIDE_SIG = LU_SIG + ", int const*, int*, unsigned long, unsigned int, int, unsigned long long*"
 KERNELS = [
     # the ADMM loops (lqp_boxqp.hpp, lqp_loop_split.hpp, lqp_loop_small.hpp, lqp_dense.hpp)
-    ("k_admm_loop", LOOP_SIG, LOOP + [("float", True, False, 512, False), ("float", True, False, 512, True)]),
-    ("k_admm_loop_each", LOOP_SIG, LOOP),                      # control['stop'] = 'each'
-    ("k_admm_loop_each_detect", LOOP_SIG, LOOP),               # ... with the infeasibility certificate (control['infeasible'])
-    ("k_admm_loop_each_certify", LOOP_SIG, LOOP),              # ... and the dual certificate beside it (control['unbounded'])
-    ("k_admm_loop_split", FPF + ", int, int, int", SPLIT + [(8, 512, True, 2)]),
-    ("k_admm_loop_split_each", FPF + ", int, int, int", SPLIT),
-    ("k_admm_loop_small", FPF + ", int, int, int", ZERO),
-    ("k_admm_loop_small_each", FPF + ", int, int, int", ZERO),
-    ("k_admm_loop_small_each_detect", FPF + ", int, int, int", ZERO),
-    ("k_admm_loop_small_each_certify", FPF + ", int, int, int", ZERO),
-    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", ZERO),
-    ("k_admm_loop_l1", LOOP_SIG, LOOP),                        # lqp_boxqp_forward_l1: the L1 step (StepL1) in every family but the dense tiers
-    ("k_admm_loop_split_l1", FPF + ", int, int, int", SPLIT),
-    ("k_admm_loop_small_l1", FPF + ", int, int, int", ZERO),
-    ("k_admm_loop_np2_l1", FPF + ", int, int, int, int, int", ZERO),
+    ("k_admm_loop", LOOP_SIG, in_forms(LOOP, FORMS) + [("float", True, False, 512, False, ALL), ("float", True, False, 512, True, ALL)]),
+    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH, L1)) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
+    ("k_admm_loop_small", FPF + ", int, int, int", in_forms([()], FORMS)),
+    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL, L1))),
     ("k_admm_loop_dense", FP + ", int, int, int", BOTH),
     ("k_admm_loop_dense_w", FP + ", int, int, int, int", BOTH),
     # the symmetric x-update (lqp_spd.hpp)
