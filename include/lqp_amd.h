@@ -434,6 +434,57 @@ int lqp_boxqp_l1_effective_box(void* stream, int dtype, int B, int n,
 int lqp_boxqp_l1_finish_grads(void* stream, int dtype, int B, int n,
                               const void* side, const void* dp, const void* dlb_e, const void* dub_e,
                               void* dlb, void* dub, void* dc, void* dw);
+/* ---- a soft band in the objective (added within ABI 17: new symbols only, no struct and no signature changed) --------------
+ *   min 0.5 x'Qx + p'x + sum_i [ wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ ]   s.t.  A x = b,  lb <= x <= ub
+ *   wl, wu >= 0 and finite;  lo <= hi, lo finite or -inf, hi finite or +inf;  all four (B,n,1) like p
+ * (soft position limits inside the hard box, a no-cost band, a one-sided hinge, asymmetric costs; lo = hi = c with wl = wu = w is
+ * the L1 term).  lqp_boxqp_forward_soft is the same implementation once more with another z-update: in the scaled space of the
+ * loop the data are wls = D wl, wus = D wu, los = lo / D, his = hi / D, and with v = xh + u (xh as in lqp_boxqp_forward,
+ * over-relaxation included), tl = wls / rho, tu = wus / rho (the rho of this iteration), dh = v - his, dl = v - los
+ *   S = v - tu if dh > tu,  v + tl if dl < -tl,  min(max(v, los), his) otherwise;     z = min(max(S, lbs), ubs)
+ * x-update, factorisations, stopping rule, rho adaptation: unchanged; wl = wu = 0 gives lqp_boxqp_forward's x, z, u bit for bit,
+ * lo = hi with wl = wu gives lqp_boxqp_forward_l1's.  The solve always iterates: bounds that are all infinite are an ordinary
+ * case, the rho = 0 one-shot does not exist here (rho_mode 1 with rho_value <= 0: LQP_ERR_INVALID), ctrl.any_lb / any_ub are not
+ * read.  The same loop kernel families as the L1 term have instances with this step; the dense LU tiers' problems run the
+ * streaming loop's LU branch.
+ * Two more outputs, (B,n,1) in the solve's dtype, from the step evaluated once more at the returned iterate (v = zs + us):
+ *   zone   +2 if dh > tu, -2 if dl < -tl, else +1 if v >= his and tu > 0, else -1 if v <= los and tl > 0, else 0 -- the sloped
+ *          pieces, the kinks hi / lo (zs == his / los exactly there), the inside of the band
+ *   u_box  (S - clamp(S)) / D, exactly zero unless the element is clamped: the box's share of the dual u; lams is built from
+ *          it, lams = [relu(-rho u_box); relu(rho u_box)] -- the rest of u is the band's multiplier, in [-wl, wu] / rho.
+ * Refused with LQP_ERR_INVALID before anything is touched: a null wl, wu, lo, hi, zone or u_box, ctrl.reserved2 bit 3
+ * (per-problem stopping) or bit 0 (the factor kept for the unroll sweep), a check_hook.  A weight that is negative or not finite,
+ * lo > hi, a NaN in lo or hi, and a rho of a problem (rho_mode 2: an entry of rho_in) that is not positive and finite, is found on
+ * the device: the problem's outputs are NaN, bit 19 (524288) of its flag word in ctrl.host_report is set, and a call that waits
+ * returns LQP_ERR_INVALID with stats.fail_index naming it.  lqp_boxqp_forward_soft_workspace_bytes: the forward's layout,
+ * unchanged, and behind it 6 n values per problem (wls, wus, los, his, tl, tu), written by kernels of the call before they are read. */
+size_t lqp_boxqp_forward_soft_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_soft(void* stream, int dtype, int B, int n, int m,
+                           const void* Q, const void* p, const void* A, const void* b,
+                           const void* lb, const void* ub, const void* wl, const void* wu, const void* lo, const void* hi,
+                           const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                           void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* zone, void* u_box,
+                           lqp_boxqp_stats* stats,
+                           void* workspace, size_t workspace_bytes);
+/* Its backward: an element on a kink behaves like one whose two bounds are both that kink, a free element on a sloped piece like
+ * p_i shifted by wu_i / -wl_i.  A kink that lies beyond a hard bound holds nothing -- the bound does (u_box != 0), and the element
+ * is an ordinary clamped one.  Two element-wise kernels around lqp_boxqp_backward_fp, which runs unchanged on
+ * (dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, rho):
+ *   lqp_boxqp_soft_effective_box   Kl = (zone == -1 and u_box == 0), Kh = (zone == +1 and u_box == 0), K = Kl or Kh, kv = Kh ? hi : lo:
+ *                                  lb_e = K ? kv : lb,  ub_e = K ? kv : ub,  u_e = K ? u : u_box,
+ *                                  lams_e = [relu(-rho u_e); relu(rho u_e)] (B,2n,1); rho_mode 1 = rho_value, 2 = rho_in (B)
+ *   lqp_boxqp_soft_finish_grads    dlb = K ? 0 : dlb_e,  dub = K ? 0 : dub_e,  dlo = Kl ? dlb_e + dub_e : 0,  dhi = Kh ? dlb_e + dub_e : 0,
+ *                                  dwu = (zone == +2) ? dp : 0,  dwl = (zone == -2) ? -dp : 0; any of the six outputs may be NULL =
+ *                                  skip, dlb / dub may be dlb_e / dub_e themselves.
+ * dQ, dp, dA, db are lqp_boxqp_backward_fp's.  All (B,n,1) in `dtype`; enqueued on `stream`, nothing is waited for.          */
+int lqp_boxqp_soft_effective_box(void* stream, int dtype, int B, int n,
+                                 const void* zone, const void* u, const void* u_box,
+                                 const void* lb, const void* ub, const void* lo, const void* hi,
+                                 int rho_mode, double rho_value, const void* rho_in,
+                                 void* lb_e, void* ub_e, void* u_e, void* lams_e);
+int lqp_boxqp_soft_finish_grads(void* stream, int dtype, int B, int n,
+                                const void* zone, const void* u_box, const void* dp, const void* dlb_e, const void* dub_e,
+                                void* dlb, void* dub, void* dwl, void* dwu, void* dlo, void* dhi);
 /* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
  * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
  * optimal, 2 primal infeasible, 3 dual infeasible (lqp_boxqp_forward_certify) -- B int32 on the DEVICE.  Enqueued on `stream`,

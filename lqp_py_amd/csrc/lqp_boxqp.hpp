@@ -28,7 +28,8 @@ enum { PS_DONE = 0, PS_FINAL = 1, PS_RESUME = 2, PS_NFACTOR = 3, PS_WORDS = 4 };
 enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
        RP_INFEAS = 1 << 16,       // control['infeasible']: the problem was flagged primal infeasible (each_stop)
        RP_UNBOUNDED = 1 << 17,    // control['unbounded']: the problem was flagged dual infeasible (each_stop)
-       RP_L1_INPUT = 1 << 18 };   // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_l1_setup); its outputs are NaN
+       RP_L1_INPUT = 1 << 18,     // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_l1_setup); its outputs are NaN
+       RP_SOFT_INPUT = 1 << 19 }; // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_soft_setup); its outputs are NaN
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -111,6 +112,7 @@ template <typename T> struct FwdParams {
     T alpha, alpha_c;         // over-relaxation factor (control['alpha']; 1 = the reference's plain step) and 1 - alpha, see admm_relax
     int relax;                // 1: alpha != 1
     int l1;                   // 1: lqp_boxqp_forward_l1 -- the objective carries sum_i w_i |x_i - c_i| and `snap` is the L1 area (in the alignment gap in front of the pointer: no offset moves)
+                              // 2: lqp_boxqp_forward_soft -- it carries sum_i wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ and `l1v` is the soft area (soft_stride, SoftView)
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
     union {
     T* snap;                 // B * snap_stride: control['infeasible'] (stop = 'each' only) -- the certificate's snapshots, or null = no detection
@@ -125,6 +127,16 @@ __host__ __device__ inline size_t l1_stride(int n) { return (size_t)3 * round_up
 template <typename T> struct L1View {
     T *ws, *cs, *t;
     __device__ L1View(T* base, int n) { ws = base; cs = ws + round_up(n, 8); t = cs + round_up(n, 8); }
+};
+// the soft band (lqp_boxqp_forward_soft), at the place of the L1 area: B * soft_stride(n), per problem
+// [wls = D wl | wus = D wu | los = lo / D | his = hi / D | tl = wls / rho | tu = wus / rho of the running segment]; k_soft_setup writes the first four
+__host__ __device__ inline size_t soft_stride(int n) { return (size_t)6 * round_up(n, 8); }
+template <typename T> struct SoftView {
+    T *wls, *wus, *los, *his, *tl, *tu;
+    __device__ SoftView(T* base, int n) {
+        const int s = round_up(n, 8);
+        wls = base; wus = wls + s; los = wus + s; his = los + s; tl = his + s; tu = tl + s;
+    }
 };
 // control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
 // number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split, FormEach:
@@ -1349,7 +1361,13 @@ template <typename T> __device__ __forceinline__ T l1_shrink(const T v, const T 
     const T d = v - c;
     return d > t ? v - t : (d < -t ? v + t : c);
 }
-template <typename T, bool L1 = false>
+// Soft band (lqp_boxqp_forward_soft): the same with soft_prox; zone = +-2 on the sloped pieces, +-1 on the kinks hi / lo (only where the
+// weight of that side is positive: with none the kink is no kink), 0 inside the band; u_box as above.  The outputs take the L1 pair's place.
+template <typename T> __device__ __forceinline__ T soft_prox(const T v, const T tl, const T tu, const T los, const T his) {
+    const T dh = v - his, dl = v - los;
+    return dh > tu ? v - tu : (dl < -tl ? v + tl : tmin(tmax(v, los), his));
+}
+template <typename T, bool L1 = false, bool SOFT = false>
 __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T* __restrict__ l1_side = nullptr, T* __restrict__ l1_ubox = nullptr) {
     const int n = P.n, m = P.m, tid = threadIdx.x, nt = blockDim.x;
     VecView<T> V(P.vecs + (size_t)b * P.vstride, n, m);
@@ -1361,6 +1379,7 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T
     const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     bool bad = info_b != 0 || notspd != 0 || tmo != 0;
     if constexpr (L1) bad = bad || (P.bflags[b] & RP_L1_INPUT) != 0;
+    if constexpr (SOFT) bad = bad || (P.bflags[b] & RP_SOFT_INPUT) != 0;
     const T poison = bad ? T(__builtin_nanf("")) : T(0);
     for (int i = tid; i < n; i += nt) {
         const T d = V.D[i];
@@ -1376,6 +1395,16 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T
             const T S = l1_shrink(v, t, cs);
             const T ubx = (S - tmin(tmax(S, V.lbs[i]), V.ubs[i])) / d + poison;      // (S - z with z = clamp(S): exactly zero off the bounds)
             l1_side[(size_t)b * n + i] = (kink ? T(0) : (dd < T(0) ? T(-1) : T(1))) + poison;
+            l1_ubox[(size_t)b * n + i] = ubx;
+            y = ubx * rho;
+        }
+        if constexpr (SOFT) {
+            const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
+            const T v = V.z[i] + V.u[i], tl = W.wls[i] / rho, tu = W.wus[i] / rho, los = W.los[i], his = W.his[i];
+            const T S = soft_prox(v, tl, tu, los, his);
+            const T zone = (v - his > tu) ? T(2) : (v - los < -tl) ? T(-2) : (v >= his && tu > T(0)) ? T(1) : (v <= los && tl > T(0)) ? T(-1) : T(0);
+            const T ubx = (S - tmin(tmax(S, V.lbs[i]), V.ubs[i])) / d + poison;
+            l1_side[(size_t)b * n + i] = zone + poison;
             l1_ubox[(size_t)b * n + i] = ubx;
             y = ubx * rho;
         }
@@ -1465,14 +1494,25 @@ __device__ __forceinline__ AdmmStep<T> admm_step_tag(const FwdParams<T>& P, cons
 //   detect: ... with the primal infeasibility certificate at every check (control['infeasible'])
 //   dual:   ... and the dual certificate beside it (control['unbounded'])
 //   l1:     lqp_boxqp_forward_l1 -- the element-wise step with the L1 term; the batch stops as one
-struct FormAll     { static constexpr bool each = false, detect = false, dual = false, l1 = false; };
-struct FormEach    { static constexpr bool each = true,  detect = false, dual = false, l1 = false; };
-struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false, l1 = false; };
-struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true,  l1 = false; };
-struct FormL1      { static constexpr bool each = false, detect = false, dual = false, l1 = true; };
+//   soft:   lqp_boxqp_forward_soft -- the element-wise step with the soft band (admm_step_soft_as); the batch stops as one
+struct FormAll     { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = false; };
+struct FormEach    { static constexpr bool each = true,  detect = false, dual = false, l1 = false, soft = false; };
+struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false, l1 = false, soft = false; };
+struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true,  l1 = false, soft = false; };
+struct FormL1      { static constexpr bool each = false, detect = false, dual = false, l1 = true,  soft = false; };
+struct FormSoft    { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = true; };
 // what a thread of the streaming loop keeps of the L1 data (nothing at all in an instance without the L1 step)
 template <typename T, bool ON> struct L1Own {};
 template <typename T> struct L1Own<T, true> { T t0 = T(0), c0 = T(0); const T *t = nullptr, *cs = nullptr; };
+// ... and of the soft band: thresholds and kinks of its first element in registers, those of further elements in the workspace
+template <typename T, bool ON> struct SoftOwn {};
+template <typename T> struct SoftOwn<T, true> {
+    T tl0 = T(0), tu0 = T(0), lo0 = T(0), hi0 = T(0);
+    const T *tl = nullptr, *tu = nullptr, *los = nullptr, *his = nullptr;
+    __device__ __forceinline__ T prox(const T v, const int i, const int tid) const {
+        return i == tid ? soft_prox(v, tl0, tu0, lo0, hi0) : soft_prox(v, tl[i], tu[i], los[i], his[i]);
+    }
+};
 template <bool RELAX, typename T>
 __device__ __forceinline__ AdmmStep<T> admm_step_l1_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
                                                        const T rho, const T t, const T cs) {
@@ -1492,6 +1532,30 @@ __device__ __forceinline__ AdmmStep<T> admm_step_l1_tag(const FwdParams<T>& P, c
         return admm_step_l1_as<false>(P, xi, zp, ui, lb, ub, rho, t, cs);
     } else {
         return admm_step_l1_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, t, cs);
+    }
+}
+// The step with the soft band wl (lo - x)_+ + wu (x - hi)_+ (lqp_boxqp_forward_soft): the prox of the band in the scaled space (soft_prox:
+// two thresholds tl = wls / rho, tu = wus / rho, two kinks los <= his), then the clamp; r, s, u are the lines of admm_step_as.  Zero
+// weights return v itself: the plain step's bits.  los == his with tl == tu is l1_shrink, bit for bit.
+template <bool RELAX, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_soft_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                         const T rho, const T tl, const T tu, const T los, const T his) {
+    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
+    const T zn = tmin(tmax(soft_prox(xh + ui, tl, tu, los, his), lb), ub);
+    const T r = xi - zn;
+    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
+}
+template <typename TAG, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_soft_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                          const T rho, const T tl, const T tu, const T los, const T his) {
+    if constexpr (TAG::kind == 2) {
+        if (P.relax) {
+            asm volatile("");
+            return admm_step_soft_as<true>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
+        }
+        return admm_step_soft_as<false>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
+    } else {
+        return admm_step_soft_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
     }
 }
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
@@ -1773,12 +1837,13 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
     loop_event_count<T, EACH>(P, b, seg0);
     return rho_;
 }
-// FORM (FormAll ... FormL1), read as EACH, DETECT, DUAL and L1 below:
+// FORM (FormAll ... FormSoft), read as EACH, DETECT, DUAL, L1 and SOFT below:
 // DETECT (control['infeasible']): the certificate at every check (infeas_view ...), instances of their own: inside the one body
 // its registers cost the plain EACH kernels 3 % of their time
 // DUAL (control['unbounded']): the dual certificate too, instances of their own again (FormCertify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
 // L1: the element-wise step, see admm_step_l1_as -- lqp_boxqp_forward_l1's kernels are instances of their own
+// SOFT: the same for the soft band, see admm_step_soft_as -- lqp_boxqp_forward_soft's instances
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
@@ -1795,7 +1860,7 @@ __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int 
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
-    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1;      // (static: never a lambda's capture)
+    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1, SOFT = FORM::soft;      // (static: never a lambda's capture)
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
     int b = blockIdx.x, part_id = 0;
@@ -1951,6 +2016,14 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         if (tid < n) { l1o.t0 = W.ws[tid] / rho; l1o.c0 = W.cs[tid]; }
         l1o.t = W.t; l1o.cs = W.cs;
     }
+    // SOFT: the same with two thresholds and two kinks per element
+    SoftOwn<T, SOFT> sfo;
+    if constexpr (SOFT) {
+        const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
+        for (int i = tid + NT; i < n; i += NT) { W.tl[i] = W.wls[i] / rho; W.tu[i] = W.wus[i] / rho; }
+        if (tid < n) { sfo.tl0 = W.wls[tid] / rho; sfo.tu0 = W.wus[tid] / rho; sfo.lo0 = W.los[tid]; sfo.hi0 = W.his[tid]; }
+        sfo.tl = W.tl; sfo.tu = W.tu; sfo.los = W.los; sfo.his = W.his;
+    }
     if constexpr (SYM) {
         for (int i = tid; i < Nps; i += NT) cvl[i] = (i < n && m > 0) ? V.cv[i] : T(0);
         if constexpr (NP == 2) {       // (every slot / column sum of the range is written by every product; zeroed once all the same)
@@ -2063,6 +2136,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     const T xh = admm_relax(xi, zp, P);      // (the lines of admm_step)
                     T zn = xh + ui;
                     if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
+                    if constexpr (SOFT) zn = sfo.prox(zn, i, tid);
                     zn = tmin(tmax(zn, lb[i]), ub[i]);     // (:273-276; an infinite bound is a no-op)
                     const T r = xi - zn;
                     const T s = rho * (zn - zp);
@@ -2110,6 +2184,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 const T xh = admm_relax(xi, zp, P);          // (the lines of admm_step)
                 T zn = xh + ui;
                 if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
+                if constexpr (SOFT) zn = sfo.prox(zn, i, tid);
                 zn = tmin(tmax(zn, lb[i]), ub[i]);
                 const T r = xi - zn;
                 const T s = rho * (zn - zp);
@@ -2233,7 +2308,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
     __syncthreads();
   }
 }
-// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1
+// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft
 template <typename FORM>
 __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                         const int prev_slot, const int persistent) {
@@ -2243,7 +2318,7 @@ __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P
 
 // The one-workgroup loop in every form.  persistent & 4 (continuation launches, FormAll): this is the forward's LAST launch -- it ends
 // with the epilogue (fwd_finish).  No other form ever is the last launch: under stop = 'each' the workgroups leave at different times,
-// and the L1 epilogue takes two more outputs (k_fwd_epilogue_l1) -- a launch of its own for both.
+// and the L1 and soft epilogues take two more outputs (k_fwd_epilogue_l1, k_fwd_epilogue_soft) -- a launch of its own for all.
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, typename FORM>
 __global__ __launch_bounds__(NT) void k_admm_loop(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
                                                   const int prev_slot, const int persistent) {
@@ -2373,6 +2448,10 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_fwd_epilogue_l1(const FwdParams<T> P, T* __restrict__ side, T* __restrict__ u_box) {
     fwd_finish<T, true>(P, blockIdx.x, side, u_box);
 }
+template <typename T>
+__global__ __launch_bounds__(256) void k_fwd_epilogue_soft(const FwdParams<T> P, T* __restrict__ zone, T* __restrict__ u_box) {
+    fwd_finish<T, false, true>(P, blockIdx.x, zone, u_box);
+}
 // lqp_boxqp_forward_l1, behind the prologue (the scaling vector exists whichever kernel made it): ws = D w, cs = c / D next to
 // lbs / ubs' problem, and the input checks that need the data -- a weight that is negative or not finite, or a rho of the problem
 // (a per-problem rho_in among them) that is not positive and finite: t = ws / rho would be no threshold -- mark the problem
@@ -2391,6 +2470,30 @@ __global__ __launch_bounds__(256) void k_l1_setup(const FwdParams<T> P, const T*
         W.cs[i] = c[(size_t)b * n + i] / di;
     }
     if (__syncthreads_or(badw ? 1 : 0) && tid == 0) P.bflags[b] |= RP_L1_INPUT;
+}
+
+// lqp_boxqp_forward_soft, at the same place: wls = D wl, wus = D wu, los = lo / D, his = hi / D (an infinite kink stays infinite), and the
+// input checks that need the data -- a weight that is negative or not finite, lo > hi, a NaN in lo or hi, or a rho of the problem that
+// is not positive and finite -- mark the problem (RP_SOFT_INPUT: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
+template <typename T>
+__global__ __launch_bounds__(256) void k_soft_setup(const FwdParams<T> P, const T* __restrict__ wl, const T* __restrict__ wu,
+                                                    const T* __restrict__ lo, const T* __restrict__ hi) {
+    const int b = blockIdx.x, n = P.n, tid = threadIdx.x;
+    VecView<T> V(P.vecs + (size_t)b * P.vstride, n, P.m);
+    const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
+    const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
+    bool bad = !(rho > T(0) && rho < T(INFINITY));
+    for (int i = tid; i < n; i += 256) {
+        const size_t g = (size_t)b * n + i;
+        const T wli = wl[g], wui = wu[g], loi = lo[g], hii = hi[g], di = V.D[i];
+        bad |= !(wli >= T(0) && wli < T(INFINITY)) || !(wui >= T(0) && wui < T(INFINITY));      // (NaN fails the first comparison)
+        bad |= !(loi <= hii);                                  // (lo > hi, or a NaN in either)
+        W.wls[i] = di * wli;
+        W.wus[i] = di * wui;
+        W.los[i] = loi / di;
+        W.his[i] = hii / di;
+    }
+    if (__syncthreads_or(bad ? 1 : 0) && tid == 0) P.bflags[b] |= RP_SOFT_INPUT;
 }
 
 // ---------------------------------------------------------------------------
@@ -3204,6 +3307,50 @@ __global__ __launch_bounds__(256) void k_l1_finish_grads(const T* __restrict__ s
     if (dub) dub[i] = K ? T(0) : gu;
     if (dc) dc[i] = K ? gl + gu : T(0);
     if (dw) dw[i] = s * dp[i];
+}
+
+// backward of lqp_boxqp_forward_soft, the same recipe with two kink sets: Kl = (zone == -1) rests on lo, Kh = (zone == +1) on hi; both
+// behave like an element whose two bounds are that kink.  A sloped free element (zone == +-2) is p shifted by wu / -wl.  A kink that
+// lies beyond a hard bound holds nothing: the bound does (u_box != 0), and the element is an ordinary clamped one -- not in K.
+template <typename T>
+__global__ __launch_bounds__(256) void k_soft_effective_box(const T* __restrict__ zone, const T* __restrict__ u, const T* __restrict__ ubox,
+                                                            const T* __restrict__ lb, const T* __restrict__ ub, const T* __restrict__ lo,
+                                                            const T* __restrict__ hi, const T* __restrict__ rho_in, const T rho_value,
+                                                            const int n, const size_t total, T* __restrict__ lb_e, T* __restrict__ ub_e,
+                                                            T* __restrict__ u_e, T* __restrict__ lams_e) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / n, e = i - b * n;
+    const T zn = zone[i];
+    const bool held = ubox[i] != T(0);
+    const bool Kl = zn == T(-1) && !held, Kh = zn == T(1) && !held, K = Kl || Kh;
+    const T kv = Kh ? hi[i] : lo[i];
+    const T ue = K ? u[i] : ubox[i];
+    lb_e[i] = K ? kv : lb[i];
+    ub_e[i] = K ? kv : ub[i];
+    u_e[i] = ue;
+    const T y = (rho_in ? rho_in[b] : rho_value) * ue;
+    lams_e[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
+    lams_e[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+}
+// ... and the ten inputs' gradients from the effective box's: on a kink both bounds were the kink (its gradient dlb_e + dub_e, nothing
+// for lb and ub); dwu = dp on zone == +2, dwl = -dp on zone == -2.  Outputs may be null; dlb / dub may be dlb_e / dub_e themselves.
+template <typename T>
+__global__ __launch_bounds__(256) void k_soft_finish_grads(const T* __restrict__ zone, const T* __restrict__ ubox, const T* __restrict__ dp, const T* dlb_e, const T* dub_e,
+                                                           const size_t total, T* dlb, T* dub, T* __restrict__ dwl, T* __restrict__ dwu,
+                                                           T* __restrict__ dlo, T* __restrict__ dhi) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const T zn = zone[i];
+    const bool held = ubox[i] != T(0);
+    const bool Kl = zn == T(-1) && !held, Kh = zn == T(1) && !held, K = Kl || Kh;
+    const T gl = dlb_e[i], gu = dub_e[i], g = dp[i];
+    if (dlb) dlb[i] = K ? T(0) : gl;
+    if (dub) dub[i] = K ? T(0) : gu;
+    if (dlo) dlo[i] = Kl ? gl + gu : T(0);
+    if (dhi) dhi[i] = Kh ? gl + gu : T(0);
+    if (dwu) dwu[i] = zn == T(2) ? g : T(0);
+    if (dwl) dwl[i] = zn == T(-2) ? -g : T(0);
 }
 
 template <int LQP_ANY = 0>

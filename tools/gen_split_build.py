@@ -36,6 +36,13 @@ GROUPS = [
     ("loop_l1_tail", loop("k_admm_loop", "L1", r"\w+, \w+, true,")),
     ("loop_l1_hot", loop("k_admm_loop", "L1")),
     ("l1", lambda n: loop("k_admm_loop_np2", "L1")(n) or loop("k_admm_loop_small", "L1")(n) or re.search(r"k_fwd_epilogue_l1<|k_l1_", n)),
+    # ... and with the soft band's step (lqp_boxqp_forward_soft), the same groups again
+    ("split_soft_c", loop("k_admm_loop_split", "Soft", r"(3|4), 512, false, 2,")),
+    ("split_soft_a", loop("k_admm_loop_split", "Soft", r"(5|6|7), 512, false, 2,")),
+    ("split_soft_b", loop("k_admm_loop_split", "Soft")),
+    ("loop_soft_tail", loop("k_admm_loop", "Soft", r"\w+, \w+, true,")),
+    ("loop_soft_hot", loop("k_admm_loop", "Soft")),
+    ("soft", lambda n: loop("k_admm_loop_np2", "Soft")(n) or loop("k_admm_loop_small", "Soft")(n) or re.search(r"k_fwd_epilogue_soft<|k_soft_", n)),
     ("bwd_f", lambda n: re.search(r"k_bwd_chol_solve<\d, true>", n)),
     ("resident_f", lambda n: re.search(r"k_spd_resident<8, 2, true>", n)),
     ("resident_g", lambda n: re.search(r"k_spd_resident<(5|6|7), 2, true>", n)),
@@ -72,9 +79,9 @@ FPF, BPF = "lqp::FwdParams<float>", "lqp::BwdParams<float>"
 KS_NP = [(3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4)]      # Ks, workgroups per problem (four: Ks = 7, 8 only)
 # The forms of the loop kernels (the tags of lqp_boxqp.hpp), the last template argument of every instance: the batch stops as one |
 # control['stop'] = 'each' | ... with the infeasibility certificate (control['infeasible']) | ... and the dual certificate beside it
-# (control['unbounded']) | lqp_boxqp_forward_l1: the L1 step
-ALL, EACH, DETECT, CERTIFY, L1 = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify", "L1"))
-FORMS = (ALL, EACH, DETECT, CERTIFY, L1)
+# (control['unbounded']) | lqp_boxqp_forward_l1: the L1 step | lqp_boxqp_forward_soft: the soft band's step
+ALL, EACH, DETECT, CERTIFY, L1, SOFT = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify", "L1", "Soft"))
+FORMS = (ALL, EACH, DETECT, CERTIFY, L1, SOFT)
 SPLIT = [(ks, 512, False, np_) for ks, np_ in KS_NP]
 # the one-workgroup loop, hot and continuation: LU f64 | LU f32 | LU f32 resident | symmetric
 LOOP = [(t, res, tail, 1024, sym) for tail in (False, True)
@@ -86,9 +93,9 @@ WIDE_SIG = LU_SIG + ", int const*, int*, unsigned long, unsigned int, int, unsig
 KERNELS = [
     # the ADMM loops (lqp_boxqp.hpp, lqp_loop_split.hpp, lqp_loop_small.hpp, lqp_dense.hpp)
     ("k_admm_loop", LOOP_SIG, in_forms(LOOP, FORMS) + [("float", True, False, 512, False, ALL), ("float", True, False, 512, True, ALL)]),
-    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH, L1)) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
+    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH, L1, SOFT)) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
     ("k_admm_loop_small", FPF + ", int, int, int", in_forms([()], FORMS)),
-    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL, L1))),
+    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL, L1, SOFT))),
     ("k_admm_loop_dense", FP + ", int, int, int", BOTH),
     ("k_admm_loop_dense_w", FP + ", int, int, int, int", BOTH),
     # the symmetric x-update (lqp_spd.hpp)
@@ -123,6 +130,10 @@ KERNELS = [
     ("k_l1_setup", FP + ", {0} const*, {0} const*", BOTH),
     ("k_l1_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_l1_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
+    ("k_fwd_epilogue_soft", FP + ", {0}*, {0}*", BOTH),
+    ("k_soft_setup", FP + ", {0} const*, {0} const*, {0} const*, {0} const*", BOTH),
+    ("k_soft_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
+    ("k_soft_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_rho_update", FP + ", int, int", BOTH),
     ("k_snap_init", "{0}*, unsigned long, int", BOTH),
     ("k_check_done", "int*, unsigned int const*, int, int", ZERO),
