@@ -485,6 +485,66 @@ int lqp_boxqp_soft_effective_box(void* stream, int dtype, int B, int n,
 int lqp_boxqp_soft_finish_grads(void* stream, int dtype, int B, int n,
                                 const void* zone, const void* u_box, const void* dp, const void* dlb_e, const void* dub_e,
                                 void* dlb, void* dub, void* dwl, void* dwu, void* dlo, void* dhi);
+/* ---- a log barrier in the objective (added within ABI 17: new symbols only, no struct and no signature changed) -------------
+ *   min 0.5 x'Qx + p'x - sum_i w_i log(x_i)   s.t.  A x = b,  lb <= x <= ub;     w >= 0 and finite, (B,n,1) like p
+ * (risk budgeting: Q = Sigma, w the budgets; a long-only barrier that keeps holdings off zero; Kelly / log-utility terms).
+ * lqp_boxqp_forward_log is the same implementation once more with another z-update.  In the scaled space of the loop
+ * (x = D xs) the term is -w_i log(xs_i) plus a constant, so the weight takes no D: ws = w; only the equality rows carry E,
+ * the objective has no scalar scale.  With v = xh + u (xh as in lqp_boxqp_forward, over-relaxation included), t = ws / rho
+ * (the rho of this iteration, a true division) and s = sqrt(v v + 4 t):
+ *   S = v              if t == 0     (a branch: w = 0 returns lqp_boxqp_forward's x, z, u bit for bit)
+ *   S = 0.5 (v + s)    if v >= 0
+ *   S = 2 t / (s - v)  if v <  0     (the form without cancellation)
+ *   z = min(max(S, lbs), ubs)
+ * x-update, factorisations, stopping rule, rho adaptation: unchanged.  The solve always iterates: bounds that are all
+ * infinite are an ordinary case, the rho = 0 one-shot does not exist here (rho_mode 1 with rho_value <= 0:
+ * LQP_ERR_INVALID), ctrl.any_lb / any_ub are not read.  The same loop kernel families as the L1 term and the soft band have
+ * instances with this step; the dense LU tiers' problems run the streaming loop's LU branch.
+ * Two more outputs, (B,n,1) in the solve's dtype, from the step evaluated once more at the returned iterate (v = zs + us):
+ *   u_box  the box's share of the dual u: (us + t / zs) / D, i.e. rho u + w / z unscaled and divided by rho, on an element
+ *          where S != clamp(S); exactly zero everywhere else.  (S - zs) / D is NOT the bound's multiplier here: the barrier
+ *          pushes on a clamped element too.  lams = [relu(-rho u_box); relu(rho u_box)].
+ *   curv   w_i / z_i^2 (the unscaled z) where w_i > 0 and u_box_i == 0, else 0: the diagonal of the term's Hessian on the
+ *          free set, for lqp_boxqp_backward_fp_curv.
+ * Refused with LQP_ERR_INVALID before anything is touched: a null w, u_box or curv, ctrl.reserved2 bit 3 (per-problem
+ * stopping) or bit 0 (the factor kept for the unroll sweep), a check_hook.  A weight that is negative or not finite, w_i > 0
+ * with ub_i <= 0 (the domain is empty), and a rho of a problem (rho_mode 2: an entry of rho_in) that is not positive and
+ * finite, is found on the device: the problem's outputs are NaN, bit 20 (1048576) of its flag word in ctrl.host_report is
+ * set, and a call that waits returns LQP_ERR_INVALID with stats.fail_index naming it.
+ * lqp_boxqp_forward_log_workspace_bytes: the forward's layout, unchanged, and behind it 2 n values per problem (ws, t),
+ * written by kernels of the call before they are read. */
+size_t lqp_boxqp_forward_log_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_log(void* stream, int dtype, int B, int n, int m,
+                          const void* Q, const void* p, const void* A, const void* b,
+                          const void* lb, const void* ub, const void* w,
+                          const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* u_box, void* curv,
+                          lqp_boxqp_stats* stats,
+                          void* workspace, size_t workspace_bytes);
+/* lqp_boxqp_backward_fp with a caller's diagonal: curv (B,n,1), non-negative, or NULL.  The free-set system becomes
+ * [[Q_FF + diag(curv_F), A_F^T], [A_F, 0]] (+1e-8 I): curv_i joins the 1e-8 of free variable i in every build (the full
+ * system, the reduced one, the Cholesky form with its equilibration scale) and in the residual of the LU form's refinement
+ * step; entries of clamped variables are not read into the system (their dx is 0).  It is the hook for a smooth separable
+ * term of the objective: the term supplies its prox in the forward and its second derivative here.  NULL or all-zero curv
+ * returns lqp_boxqp_backward_fp's results bit for bit.  There is no prefactor phase with a diagonal: linsolve with
+ * LQP_BWD_PREFACTORED is refused with LQP_ERR_INVALID.  Workspace: lqp_boxqp_backward_fp_workspace_bytes. */
+int lqp_boxqp_backward_fp_curv(void* stream, int dtype, int B, int n, int m,
+                               const void* dl_dz, const void* x, const void* u, const void* lams, const void* nus,
+                               const void* Q, const void* A, const void* lb, const void* ub, const void* curv,
+                               int rho_mode, double rho_value, const void* rho_in,
+                               void* dQ, void* dp, void* dA, void* db, void* dlb, void* dub,
+                               int32_t* fail_index, void* workspace, size_t workspace_bytes, int linsolve, void* host_report);
+/* The backward of lqp_boxqp_forward_log: lqp_boxqp_backward_fp_curv on (dl_dz, x, u_e, lams_e, nus, Q, A, lb, ub, curv, rho)
+ * with the true lb, ub, between two element-wise kernels:
+ *   lqp_boxqp_log_effective_duals  u_e = u_box,  lams_e = [relu(-rho u_e); relu(rho u_e)] (B,2n,1); rho_mode 1 = rho_value,
+ *                                  2 = rho_in (B)
+ *   lqp_boxqp_log_finish_grads     dw_i = -dp_i / z_i where w_i > 0, else 0 (the convention at w_i = 0: the one-sided
+ *                                  derivative is not defined there when x_i <= 0); dw may be NULL = nothing is done.
+ * dQ, dp, dA, db, dlb, dub are the backward's own (a clamped element has dx_i = 0: curv never enters its row).
+ * All (B,n,1) in `dtype`; enqueued on `stream`, nothing is waited for. */
+int lqp_boxqp_log_effective_duals(void* stream, int dtype, int B, int n, const void* u_box,
+                                  int rho_mode, double rho_value, const void* rho_in, void* u_e, void* lams_e);
+int lqp_boxqp_log_finish_grads(void* stream, int dtype, int B, int n, const void* dp, const void* z, const void* w, void* dw);
 /* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
  * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
  * optimal, 2 primal infeasible, 3 dual infeasible (lqp_boxqp_forward_certify) -- B int32 on the DEVICE.  Enqueued on `stream`,

@@ -8,6 +8,7 @@ from .solve_box_qp_admm_torch import (SolveBoxQP, SolveBoxQPLayer, BoxQPTH, torc
                                       torch_qp_int_grads, torch_qp_int_grads_admm, last_problem_status)
 from .solve_box_qp_l1 import SolveBoxQPL1, SolveBoxQPL1Layer, torch_solve_box_qp_l1
 from .solve_box_qp_soft import SolveBoxQPSoft, SolveBoxQPSoftLayer, torch_solve_box_qp_soft
+from .solve_box_qp_log import SolveBoxQPLog, SolveBoxQPLogLayer, torch_solve_box_qp_log
 from ._lib import InfeasibleQPError, UnboundedQPError
 from .lu_layer import TorchLU, TorchLULayer
 from .solve_qp_eqcon_torch import torch_solve_qp_eqcon, torch_solve_qp_eqcon_grad
@@ -41,4 +42,5 @@ __all__ = [
     "solve_qp_uncon", "last_problem_status", "InfeasibleQPError", "UnboundedQPError",
     "SolveBoxQPL1", "SolveBoxQPL1Layer", "torch_solve_box_qp_l1",
     "SolveBoxQPSoft", "SolveBoxQPSoftLayer", "torch_solve_box_qp_soft",
+    "SolveBoxQPLog", "SolveBoxQPLogLayer", "torch_solve_box_qp_log",
 ]

@@ -527,6 +527,12 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
         for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & RP_SOFT_INPUT) stats->fail_index = i;
         return LQP_ERR_INVALID;
     }
+    if (flags_or & RP_LOG_INPUT) {       // lqp_boxqp_forward_log: the same for what k_log_setup flags
+        memset(stats, 0, sizeof(*stats));
+        stats->fail_index = -1;
+        for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & RP_LOG_INPUT) stats->fail_index = i;
+        return LQP_ERR_INVALID;
+    }
     if (lu_timeout && stats->linsolve_used != 2) return LQP_ERR_TIMEOUT;
     if (fail_index >= 0 && stats->linsolve_used == 2) return LQP_RETRY_LU;
     if (fail_index >= 0) {
@@ -548,10 +554,11 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
 // The batch stops as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
 // infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']:
 // P.eps_dinf > 0) | the L1 step (lqp_boxqp_forward_l1: P.l1, whose area shares its storage with the snapshots; the batch stops as one)
-// | the soft band's step (lqp_boxqp_forward_soft: P.l1 == 2, its area at the same place)
-enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT };
+// | the soft band's step (lqp_boxqp_forward_soft: P.l1 == 2, its area at the same place) | the log barrier's step (lqp_boxqp_forward_log:
+// P.l1 == 3, the same place again)
+enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT, FORM_LOG };
 inline LoopForm loop_form(const int l1, const bool each, const bool snapshots, const bool dual) {
-    return l1 == 2 ? FORM_SOFT : l1 ? FORM_L1 : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
+    return l1 == 3 ? FORM_LOG : l1 == 2 ? FORM_SOFT : l1 ? FORM_L1 : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
 }
 inline bool form_each(const LoopForm form) { return form == FORM_EACH || form == FORM_DETECT || form == FORM_CERTIFY; }
 inline bool form_snapshots(const LoopForm form) { return form == FORM_DETECT || form == FORM_CERTIFY; }
@@ -563,6 +570,7 @@ template <typename F> auto by_form(const LoopForm form, F f) -> decltype(f(FormA
         case FORM_CERTIFY: return f(FormCertify());
         case FORM_L1:      return f(FormL1());
         case FORM_SOFT:    return f(FormSoft());
+        case FORM_LOG:     return f(FormLog());
         default:           return f(FormAll());
     }
 }
@@ -577,8 +585,9 @@ template <typename T> struct FwdLayout {
     void* l1_area;                  // [B][l1_stride]: ws, cs, t of lqp_boxqp_forward_l1, BEHIND `bytes` too (the same start: never together with the snapshots)
     size_t l1_bytes;                // ... and the size that holds them
     size_t soft_bytes;              // ... and with [B][soft_stride] there: wls, wus, los, his, tl, tu of lqp_boxqp_forward_soft (the same start)
+    size_t log_bytes;               // ... and with [B][log_stride] there: ws, t of lqp_boxqp_forward_log (the same start)
     size_t bytes_for(const LoopForm form) const {      // the workspace a solve of this form needs
-        return form == FORM_SOFT ? soft_bytes : form == FORM_L1 ? l1_bytes : form == FORM_CERTIFY ? certify_bytes : form == FORM_DETECT ? detect_bytes : bytes;
+        return form == FORM_LOG ? log_bytes : form == FORM_SOFT ? soft_bytes : form == FORM_L1 ? l1_bytes : form == FORM_CERTIFY ? certify_bytes : form == FORM_DETECT ? detect_bytes : bytes;
     }
 };
 // the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
@@ -642,6 +651,9 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     c.off = L.bytes;
     c.take<T>((size_t)B * soft_stride(n));
     L.soft_bytes = c.off + kAlign;
+    c.off = L.bytes;
+    c.take<T>((size_t)B * log_stride(n));
+    L.log_bytes = c.off + kAlign;
     return L;
 }
 
@@ -663,7 +675,7 @@ enum LoopKind {
 inline bool family_has_form(const LoopKind kind, const LoopForm form) {
     switch (kind) {
         case LOOP_ONE: case LOOP_SMALL: case LOOP_SPLIT: return true;      // (the split loop's FormEach serves FormDetect and FormCertify)
-        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1 || form == FORM_SOFT;
+        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1 || form == FORM_SOFT || form == FORM_LOG;
         default: return form == FORM_ALL;                                  // (the dense tiers)
     }
 }
@@ -707,12 +719,14 @@ template <typename T> LoopPair<T> loop_kernels(const LoopForm form, const bool r
     });
 }
 inline LoopFn<float> np2_kernel(const LoopForm form) {
-    return form == FORM_SOFT ? k_admm_loop_np2<FormSoft> : form == FORM_L1 ? k_admm_loop_np2<FormL1> : k_admm_loop_np2<FormAll>;
+    return form == FORM_LOG ? k_admm_loop_np2<FormLog> : form == FORM_SOFT ? k_admm_loop_np2<FormSoft> : form == FORM_L1 ? k_admm_loop_np2<FormL1> : k_admm_loop_np2<FormAll>;
 }
 // the extra arguments of lqp_boxqp_forward_l1
 struct L1Args { const void *w, *c; void *side, *u_box; };
 // ... and of lqp_boxqp_forward_soft
 struct SoftArgs { const void *wl, *wu, *lo, *hi; void *zone, *u_box; };
+// ... and of lqp_boxqp_forward_log
+struct LogArgs { const void* w; void *u_box, *curv; };
 
 constexpr int kMaxChecksPerLaunch = kRing / 4;
 
@@ -739,6 +753,7 @@ template <typename T> struct FwdPlan {
     LoopFn<float> np2_fn = nullptr;     // LOOP_NP2
     L1Args l1a = {nullptr, nullptr, nullptr, nullptr};      // FORM_L1: what k_l1_setup reads, k_fwd_epilogue_l1 (the epilogue of that form) writes
     SoftArgs sfa = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // FORM_SOFT: the same for k_soft_setup and k_fwd_epilogue_soft
+    LogArgs lga = {nullptr, nullptr, nullptr};      // FORM_LOG: the same for k_log_setup and k_fwd_epilogue_log
     int kind_wg = 1;                    // workgroups per problem of the hot launch
     int densew_tpr = 0;
     bool loop_split_seg = false;        // mode 1: k_admm_loop_split per check segment, its pairs taking turns on the chip
@@ -1057,7 +1072,8 @@ template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl*
 template <typename T> int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
     const L1Args l1a = plan.l1a;
     const SoftArgs sfa = plan.sfa;
-    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0; plan.l1a = l1a; plan.sfa = sfa;
+    const LogArgs lga = plan.lga;
+    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0; plan.l1a = l1a; plan.sfa = sfa; plan.lga = lga;
     // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
     // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
     plan.form = loop_form(P);
@@ -1176,6 +1192,11 @@ int enqueue_prologue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pl
     if (plan.form == FORM_SOFT) {    // wls, wus, los, his: at the same place
         ProfScope ps(st, PC_SETUP);
         hipLaunchKernelGGL(k_soft_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.sfa.wl, (const T*)plan.sfa.wu, (const T*)plan.sfa.lo, (const T*)plan.sfa.hi);
+        ++n_launch;
+    }
+    if (plan.form == FORM_LOG) {     // ws: at the same place
+        ProfScope ps(st, PC_SETUP);
+        hipLaunchKernelGGL(k_log_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.lga.w);
         ++n_launch;
     }
     return LQP_OK;
@@ -1329,6 +1350,7 @@ Attempt run_planned(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         ProfScope ps(st, PC_EPILOGUE);
         if (plan.form == FORM_L1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
           else if (plan.form == FORM_SOFT) hipLaunchKernelGGL(k_fwd_epilogue_soft<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.sfa.zone, (T*)plan.sfa.u_box);
+          else if (plan.form == FORM_LOG) hipLaunchKernelGGL(k_fwd_epilogue_log<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.lga.curv, (T*)plan.lga.u_box);
           else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
         ++n_launch;
     }
@@ -1443,6 +1465,7 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         { ProfScope ps(st, PC_EPILOGUE);
           if (plan.form == FORM_L1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
           else if (plan.form == FORM_SOFT) hipLaunchKernelGGL(k_fwd_epilogue_soft<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.sfa.zone, (T*)plan.sfa.u_box);
+          else if (plan.form == FORM_LOG) hipLaunchKernelGGL(k_fwd_epilogue_log<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.lga.curv, (T*)plan.lga.u_box);
           else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P); }
         ++n_launch;
         // (with a host report the epilogue has left status and info words in pinned host memory: one wait, no copies)
@@ -1498,13 +1521,13 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         chunk_cap = std::min(chunk_cap * 2, 64);
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
-    if (plan.form == FORM_L1 || plan.form == FORM_SOFT) {
-        // a weight that is negative or not finite (k_l1_setup / k_soft_setup mark the problem's flag word; the epilogue has reported it)
+    if (plan.form == FORM_L1 || plan.form == FORM_SOFT || plan.form == FORM_LOG) {
+        // a weight that is negative or not finite (k_l1_setup / k_soft_setup / k_log_setup mark the problem's flag word; the epilogue has reported it)
         std::vector<int> fl(B);
         if (P.host_report) for (int i = 0; i < B; ++i) fl[i] = ((const volatile int*)P.host_report)[ST_WORDS + B + i];
         else { HIP_OK(hipMemcpyAsync(fl.data(), P.bflags, sizeof(int) * B, hipMemcpyDeviceToHost, st)); HIP_OK(hipStreamSynchronize(st)); }
         for (int i = 0; i < B; ++i)
-            if (fl[i] & (RP_L1_INPUT | RP_SOFT_INPUT)) {
+            if (fl[i] & (RP_L1_INPUT | RP_SOFT_INPUT | RP_LOG_INPUT)) {
                 if (stats) { memset(stats, 0, sizeof(*stats)); stats->fail_index = i; }
                 return LQP_ERR_INVALID;
             }
@@ -1531,15 +1554,17 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
                  int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const L1Args* l1 = nullptr,
-                 const SoftArgs* soft = nullptr) {
-    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; l1: lqp_boxqp_forward_l1; soft: lqp_boxqp_forward_soft)
+                 const SoftArgs* soft = nullptr, const LogArgs* lg = nullptr) {
+    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; l1: lqp_boxqp_forward_l1; soft: lqp_boxqp_forward_soft;
+    //  lg: lqp_boxqp_forward_log)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    const LoopForm asked = loop_form(soft ? 2 : l1 ? 1 : 0, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
+    const LoopForm asked = loop_form(lg ? 3 : soft ? 2 : l1 ? 1 : 0, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
     if (ws_bytes < L.bytes_for(asked)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
         if (asked == FORM_L1) { P.l1 = 1; P.l1v = (T*)L.l1_area; }
         if (asked == FORM_SOFT) { P.l1 = 2; P.l1v = (T*)L.l1_area; }      // (the same start, soft_stride per problem)
+        if (asked == FORM_LOG) { P.l1 = 3; P.l1v = (T*)L.l1_area; }       // (the same start, log_stride per problem)
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
         P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in; P.beta_in = (const T*)ctl->beta_in;
         P.x = (T*)x; P.z = (T*)z; P.u = (T*)u; P.lams = (T*)lams; P.nus = (T*)nus; P.rho_out = (T*)rho_out;
@@ -1580,6 +1605,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         FwdPlan<T> plan;
         if (l1) plan.l1a = *l1;
         if (soft) plan.sfa = *soft;
+        if (lg) plan.lga = *lg;
         int rc = plan_forward(P, ctl, retry, k, d, plan);
         if (rc) return rc;
         int n_launch = 0;
@@ -1633,6 +1659,7 @@ struct BwdCall {
     int dtype = LQP_F32, B = 0, n = 0, m = 0;
     const void *g = nullptr, *x = nullptr, *u = nullptr, *lams = nullptr, *nus = nullptr, *Q = nullptr, *A = nullptr, *lb = nullptr,
                *ub = nullptr, *rho_in = nullptr;
+    const void* curv = nullptr;         // lqp_boxqp_backward_fp_curv: BwdParams::curv, or null
     int rho_mode = 1; double rho_value = 1.0;
     void *dQ = nullptr, *dp = nullptr, *dA = nullptr, *db = nullptr, *dlb = nullptr, *dub = nullptr;
     int32_t* fail_index = nullptr;      // null: the call neither waits nor repeats anything
@@ -1828,7 +1855,7 @@ int backward_impl(const BwdCall& c) {
     if (c.ws_bytes < carve_backward<T>(c.ws, c.B, c.n, c.m, P0)) return LQP_ERR_WORKSPACE;
     P0.g = (const T*)c.g; P0.x = (const T*)c.x; P0.u = (const T*)c.u; P0.lams = (const T*)c.lams; P0.nus = (const T*)c.nus;
     P0.Q = (const T*)c.Q; P0.A = (const T*)c.A; P0.lb = (const T*)c.lb; P0.ub = (const T*)c.ub; P0.rho_in = (const T*)c.rho_in;
-    P0.rho_value = (T)c.rho_value; P0.rho_mode = c.rho_mode;
+    P0.rho_value = (T)c.rho_value; P0.rho_mode = c.rho_mode; P0.curv = (const T*)c.curv;
     P0.dQ = (T*)c.dQ; P0.dp = (T*)c.dp; P0.dA = (T*)c.dA; P0.db = (T*)c.db; P0.dlb = (T*)c.dlb; P0.dub = (T*)c.dub;
     P0.dbg = g_lu_dbg;
     SoloScope one_wg_lu;
@@ -2304,7 +2331,7 @@ static int forward_entry(void* stream, int dtype, int B, int n, int m, const voi
                          const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
                          void* workspace, size_t workspace_bytes, const double eps_prim_inf, const double eps_dual_inf,
-                         const L1Args* l1 = nullptr, const SoftArgs* soft = nullptr) {
+                         const L1Args* l1 = nullptr, const SoftArgs* soft = nullptr, const LogArgs* lg = nullptr) {
     if (bad_dims(dtype, B, n, m) || !Q || !p || !lb || !ub || !ctrl || !x || !z || !u || !lams || !rho_out || !workspace)
         return LQP_ERR_INVALID;
     if (m > 0 && (!A || !b || !nus)) return LQP_ERR_INVALID;
@@ -2319,7 +2346,7 @@ static int forward_entry(void* stream, int dtype, int B, int n, int m, const voi
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)
     return by_dtype(dtype, [&](auto t) {
-        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf, l1, soft);
+        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf, l1, soft, lg);
     });
 }
 
@@ -2439,6 +2466,54 @@ int lqp_boxqp_soft_finish_grads(void* stream, int dtype, int B, int n, const voi
         typedef decltype(t) T;
         hipLaunchKernelGGL(k_soft_finish_grads<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)zone,
                            (const T*)u_box, (const T*)dp, (const T*)dlb_e, (const T*)dub_e, total, (T*)dlb, (T*)dub, (T*)dwl, (T*)dwu, (T*)dlo, (T*)dhi);
+        return 0;
+    });
+    return last_error();
+}
+
+size_t lqp_boxqp_forward_log_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_LOG); });
+}
+
+int lqp_boxqp_forward_log(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                          const void* b, const void* lb, const void* ub, const void* w, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* u_box, void* curv,
+                          lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
+    // refused before anything is touched, as lqp_boxqp_forward_soft does: a null pointer, the per-problem stop (no log instance of its
+    // kernels), a check hook, the factor kept for the unroll sweep, and the rho = 0 one-shot -- this solve always iterates too
+    if (!w || !u_box || !curv) return LQP_ERR_INVALID;
+    if (!ctrl || (ctrl->reserved2 & (8 | 1)) || ctrl->check_hook) return LQP_ERR_INVALID;
+    if (ctrl->rho_mode == 1 && !(ctrl->rho_value > 0.0)) return LQP_ERR_INVALID;
+    const LogArgs lg = {w, u_box, curv};
+    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
+                         workspace_bytes, 0.0, 0.0, nullptr, nullptr, &lg);
+}
+
+// the two element-wise kernels around lqp_boxqp_backward_fp_curv in the backward of lqp_boxqp_forward_log (csrc/lqp_boxqp.hpp)
+int lqp_boxqp_log_effective_duals(void* stream, int dtype, int B, int n, const void* u_box, int rho_mode, double rho_value,
+                                  const void* rho_in, void* u_e, void* lams_e) {
+    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
+    if (!u_box || !u_e || !lams_e || (rho_mode != 1 && rho_mode != 2) || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
+    const size_t total = (size_t)B * n;
+    by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_log_effective_duals<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)u_box,
+                           rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)u_e, (T*)lams_e);
+        return 0;
+    });
+    return last_error();
+}
+
+int lqp_boxqp_log_finish_grads(void* stream, int dtype, int B, int n, const void* dp, const void* z, const void* w, void* dw) {
+    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
+    if (!dp || !z || !w) return LQP_ERR_INVALID;
+    if (!dw) return LQP_OK;
+    const size_t total = (size_t)B * n;
+    by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_log_finish_grads<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dp,
+                           (const T*)z, (const T*)w, total, (T*)dw);
         return 0;
     });
     return last_error();
@@ -2710,6 +2785,26 @@ int lqp_boxqp_backward_fp(void* stream, int dtype, int B, int n, int m, const vo
     c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m;
     c.ws = workspace; c.ws_bytes = workspace_bytes; c.linsolve = linsolve; c.host_report = host_report;
     c.g = dl_dz; c.x = x; c.u = u; c.lams = lams; c.nus = nus; c.Q = Q; c.A = A; c.lb = lb; c.ub = ub;
+    c.rho_mode = rho_mode; c.rho_value = rho_value; c.rho_in = rho_in;
+    c.dQ = dQ; c.dp = dp; c.dA = dA; c.db = db; c.dlb = dlb; c.dub = dub; c.fail_index = fail_index;
+    return backward_call(c);
+}
+
+int lqp_boxqp_backward_fp_curv(void* stream, int dtype, int B, int n, int m, const void* dl_dz, const void* x, const void* u,
+                               const void* lams, const void* nus, const void* Q, const void* A, const void* lb, const void* ub,
+                               const void* curv, int rho_mode, double rho_value, const void* rho_in, void* dQ, void* dp, void* dA,
+                               void* db, void* dlb, void* dub, int32_t* fail_index, void* workspace, size_t workspace_bytes,
+                               int linsolve, void* host_report) {
+    if (bad_dims(dtype, B, n, m) || !dl_dz || !x || !u || !lams || !Q || !lb || !ub || !workspace) return LQP_ERR_INVALID;
+    if (m > 0 && (!A || !nus)) return LQP_ERR_INVALID;
+    if (rho_mode != 1 && rho_mode != 2) return LQP_ERR_INVALID;
+    if (rho_mode == 2 && !rho_in) return LQP_ERR_INVALID;
+    if (linsolve & LQP_BWD_PREFACTORED) return LQP_ERR_INVALID;      // (no prefactor phase carries the diagonal)
+    if (n + m > max_rows(dtype)) return LQP_ERR_UNSUPPORTED;
+    BwdCall c;
+    c.st = (hipStream_t)stream; c.dtype = dtype; c.B = B; c.n = n; c.m = m;
+    c.ws = workspace; c.ws_bytes = workspace_bytes; c.linsolve = linsolve; c.host_report = host_report;
+    c.g = dl_dz; c.x = x; c.u = u; c.lams = lams; c.nus = nus; c.Q = Q; c.A = A; c.lb = lb; c.ub = ub; c.curv = curv;
     c.rho_mode = rho_mode; c.rho_value = rho_value; c.rho_in = rho_in;
     c.dQ = dQ; c.dp = dp; c.dA = dA; c.db = db; c.dlb = dlb; c.dub = dub; c.fail_index = fail_index;
     return backward_call(c);

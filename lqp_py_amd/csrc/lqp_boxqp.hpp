@@ -29,7 +29,8 @@ enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
        RP_INFEAS = 1 << 16,       // control['infeasible']: the problem was flagged primal infeasible (each_stop)
        RP_UNBOUNDED = 1 << 17,    // control['unbounded']: the problem was flagged dual infeasible (each_stop)
        RP_L1_INPUT = 1 << 18,     // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_l1_setup); its outputs are NaN
-       RP_SOFT_INPUT = 1 << 19 }; // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_soft_setup); its outputs are NaN
+       RP_SOFT_INPUT = 1 << 19,   // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_soft_setup); its outputs are NaN
+       RP_LOG_INPUT = 1 << 20 };  // lqp_boxqp_forward_log: a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (k_log_setup); its outputs are NaN
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -113,6 +114,7 @@ template <typename T> struct FwdParams {
     int relax;                // 1: alpha != 1
     int l1;                   // 1: lqp_boxqp_forward_l1 -- the objective carries sum_i w_i |x_i - c_i| and `snap` is the L1 area (in the alignment gap in front of the pointer: no offset moves)
                               // 2: lqp_boxqp_forward_soft -- it carries sum_i wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ and `l1v` is the soft area (soft_stride, SoftView)
+                              // 3: lqp_boxqp_forward_log -- it carries -sum_i w_i log(x_i) and `l1v` is the barrier's area (log_stride, LogView)
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
     union {
     T* snap;                 // B * snap_stride: control['infeasible'] (stop = 'each' only) -- the certificate's snapshots, or null = no detection
@@ -137,6 +139,13 @@ template <typename T> struct SoftView {
         const int s = round_up(n, 8);
         wls = base; wus = wls + s; los = wus + s; his = los + s; tl = his + s; tu = tl + s;
     }
+};
+// the log barrier (lqp_boxqp_forward_log), at the same place: B * log_stride(n), per problem [ws = w | t = ws / rho of the running segment]
+// (in the scaled space x = D xs the term is -w log(xs) plus a constant: the weight takes no D); k_log_setup writes ws
+__host__ __device__ inline size_t log_stride(int n) { return (size_t)2 * round_up(n, 8); }
+template <typename T> struct LogView {
+    T *ws, *t;
+    __device__ LogView(T* base, int n) { ws = base; t = ws + round_up(n, 8); }
 };
 // control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
 // number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split, FormEach:
@@ -1367,7 +1376,18 @@ template <typename T> __device__ __forceinline__ T soft_prox(const T v, const T 
     const T dh = v - his, dl = v - los;
     return dh > tu ? v - tu : (dl < -tl ? v + tl : tmin(tmax(v, los), his));
 }
-template <typename T, bool L1 = false, bool SOFT = false>
+// Log barrier (lqp_boxqp_forward_log): the prox of -w log(.) with t = w / rho is the positive root of S^2 - v S - t = 0.  With
+// s = sqrt(v^2 + 4 t): 0.5 (v + s) for v >= 0 and 2 t / (s - v) for v < 0 -- the form without cancellation (0.5 (v + s) loses 5 % at
+// v = -50, t = 1e-3 in float32).  t == 0 returns v itself, by a branch: the plain step's bits.  At the returned iterate: u_box is the
+// box's share of the dual, (us + t / zs) / D where the clamp moved S and exactly 0 elsewhere (S - clamp(S) is NOT the multiplier
+// here: the barrier's own force t / zs acts on a clamped element too); curv = w / z^2 (unscaled z) on the free barrier elements,
+// the diagonal of the term's Hessian for the backward, 0 elsewhere.  The outputs take the L1 pair's place.
+template <typename T> __device__ __forceinline__ T log_prox(const T v, const T t) {
+    if (t == T(0)) return v;
+    const T s = tsqrt(v * v + T(4) * t);
+    return v >= T(0) ? T(0.5) * (v + s) : (T(2) * t) / (s - v);
+}
+template <typename T, bool L1 = false, bool SOFT = false, bool LOG = false>
 __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T* __restrict__ l1_side = nullptr, T* __restrict__ l1_ubox = nullptr) {
     const int n = P.n, m = P.m, tid = threadIdx.x, nt = blockDim.x;
     VecView<T> V(P.vecs + (size_t)b * P.vstride, n, m);
@@ -1380,6 +1400,7 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T
     bool bad = info_b != 0 || notspd != 0 || tmo != 0;
     if constexpr (L1) bad = bad || (P.bflags[b] & RP_L1_INPUT) != 0;
     if constexpr (SOFT) bad = bad || (P.bflags[b] & RP_SOFT_INPUT) != 0;
+    if constexpr (LOG) bad = bad || (P.bflags[b] & RP_LOG_INPUT) != 0;
     const T poison = bad ? T(__builtin_nanf("")) : T(0);
     for (int i = tid; i < n; i += nt) {
         const T d = V.D[i];
@@ -1405,6 +1426,17 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T
             const T zone = (v - his > tu) ? T(2) : (v - los < -tl) ? T(-2) : (v >= his && tu > T(0)) ? T(1) : (v <= los && tl > T(0)) ? T(-1) : T(0);
             const T ubx = (S - tmin(tmax(S, V.lbs[i]), V.ubs[i])) / d + poison;
             l1_side[(size_t)b * n + i] = zone + poison;
+            l1_ubox[(size_t)b * n + i] = ubx;
+            y = ubx * rho;
+        }
+        if constexpr (LOG) {
+            const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
+            const T zs = V.z[i], us = V.u[i], wi = W.ws[i], t = wi / rho;
+            const T S = log_prox(zs + us, t);
+            const bool held = S != tmin(tmax(S, V.lbs[i]), V.ubs[i]);
+            const T ubx = (held ? (t == T(0) ? us : us + t / zs) / d : T(0)) + poison;
+            const T zu = d * zs;
+            l1_side[(size_t)b * n + i] = ((wi > T(0) && !held) ? wi / (zu * zu) : T(0)) + poison;      // (curv)
             l1_ubox[(size_t)b * n + i] = ubx;
             y = ubx * rho;
         }
@@ -1495,12 +1527,14 @@ __device__ __forceinline__ AdmmStep<T> admm_step_tag(const FwdParams<T>& P, cons
 //   dual:   ... and the dual certificate beside it (control['unbounded'])
 //   l1:     lqp_boxqp_forward_l1 -- the element-wise step with the L1 term; the batch stops as one
 //   soft:   lqp_boxqp_forward_soft -- the element-wise step with the soft band (admm_step_soft_as); the batch stops as one
-struct FormAll     { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = false; };
-struct FormEach    { static constexpr bool each = true,  detect = false, dual = false, l1 = false, soft = false; };
-struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false, l1 = false, soft = false; };
-struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true,  l1 = false, soft = false; };
-struct FormL1      { static constexpr bool each = false, detect = false, dual = false, l1 = true,  soft = false; };
-struct FormSoft    { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = true; };
+//   barrier: lqp_boxqp_forward_log -- the element-wise step with the log barrier (admm_step_log_as); the batch stops as one
+struct FormAll     { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = false, barrier = false; };
+struct FormEach    { static constexpr bool each = true,  detect = false, dual = false, l1 = false, soft = false, barrier = false; };
+struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false, l1 = false, soft = false, barrier = false; };
+struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true,  l1 = false, soft = false, barrier = false; };
+struct FormL1      { static constexpr bool each = false, detect = false, dual = false, l1 = true,  soft = false, barrier = false; };
+struct FormSoft    { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = true, barrier = false; };
+struct FormLog     { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = false, barrier = true; };
 // what a thread of the streaming loop keeps of the L1 data (nothing at all in an instance without the L1 step)
 template <typename T, bool ON> struct L1Own {};
 template <typename T> struct L1Own<T, true> { T t0 = T(0), c0 = T(0); const T *t = nullptr, *cs = nullptr; };
@@ -1512,6 +1546,13 @@ template <typename T> struct SoftOwn<T, true> {
     __device__ __forceinline__ T prox(const T v, const int i, const int tid) const {
         return i == tid ? soft_prox(v, tl0, tu0, lo0, hi0) : soft_prox(v, tl[i], tu[i], los[i], his[i]);
     }
+};
+// ... and of the log barrier: the threshold t = ws / rho of its first element in a register, those of further elements in the workspace
+template <typename T, bool ON> struct LogOwn {};
+template <typename T> struct LogOwn<T, true> {
+    T t0 = T(0);
+    const T* t = nullptr;
+    __device__ __forceinline__ T prox(const T v, const int i, const int tid) const { return log_prox(v, i == tid ? t0 : t[i]); }
 };
 template <bool RELAX, typename T>
 __device__ __forceinline__ AdmmStep<T> admm_step_l1_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
@@ -1556,6 +1597,29 @@ __device__ __forceinline__ AdmmStep<T> admm_step_soft_tag(const FwdParams<T>& P,
         return admm_step_soft_as<false>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
     } else {
         return admm_step_soft_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
+    }
+}
+// The step with the log barrier -w log(x) (lqp_boxqp_forward_log): log_prox with t = ws / rho in the scaled space, then the clamp; r, s,
+// u are the lines of admm_step_as.  A zero weight returns v itself: the plain step's bits.
+template <bool RELAX, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_log_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                        const T rho, const T t) {
+    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
+    const T zn = tmin(tmax(log_prox(xh + ui, t), lb), ub);
+    const T r = xi - zn;
+    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
+}
+template <typename TAG, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_log_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                         const T rho, const T t) {
+    if constexpr (TAG::kind == 2) {
+        if (P.relax) {
+            asm volatile("");
+            return admm_step_log_as<true>(P, xi, zp, ui, lb, ub, rho, t);
+        }
+        return admm_step_log_as<false>(P, xi, zp, ui, lb, ub, rho, t);
+    } else {
+        return admm_step_log_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, t);
     }
 }
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
@@ -1837,13 +1901,14 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
     loop_event_count<T, EACH>(P, b, seg0);
     return rho_;
 }
-// FORM (FormAll ... FormSoft), read as EACH, DETECT, DUAL, L1 and SOFT below:
+// FORM (FormAll ... FormLog), read as EACH, DETECT, DUAL, L1, SOFT and LOG below:
 // DETECT (control['infeasible']): the certificate at every check (infeas_view ...), instances of their own: inside the one body
 // its registers cost the plain EACH kernels 3 % of their time
 // DUAL (control['unbounded']): the dual certificate too, instances of their own again (FormCertify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
 // L1: the element-wise step, see admm_step_l1_as -- lqp_boxqp_forward_l1's kernels are instances of their own
 // SOFT: the same for the soft band, see admm_step_soft_as -- lqp_boxqp_forward_soft's instances
+// LOG: the same for the log barrier, see admm_step_log_as -- lqp_boxqp_forward_log's instances
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
@@ -1860,7 +1925,7 @@ __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int 
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
-    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1, SOFT = FORM::soft;      // (static: never a lambda's capture)
+    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1, SOFT = FORM::soft, LOG = FORM::barrier;      // (static: never a lambda's capture)
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
     int b = blockIdx.x, part_id = 0;
@@ -2024,6 +2089,14 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         if (tid < n) { sfo.tl0 = W.wls[tid] / rho; sfo.tu0 = W.wus[tid] / rho; sfo.lo0 = W.los[tid]; sfo.hi0 = W.his[tid]; }
         sfo.tl = W.tl; sfo.tu = W.tu; sfo.los = W.los; sfo.his = W.his;
     }
+    // LOG: the same with one threshold per element
+    LogOwn<T, LOG> lgo;
+    if constexpr (LOG) {
+        const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
+        for (int i = tid + NT; i < n; i += NT) W.t[i] = W.ws[i] / rho;
+        if (tid < n) lgo.t0 = W.ws[tid] / rho;
+        lgo.t = W.t;
+    }
     if constexpr (SYM) {
         for (int i = tid; i < Nps; i += NT) cvl[i] = (i < n && m > 0) ? V.cv[i] : T(0);
         if constexpr (NP == 2) {       // (every slot / column sum of the range is written by every product; zeroed once all the same)
@@ -2137,6 +2210,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     T zn = xh + ui;
                     if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
                     if constexpr (SOFT) zn = sfo.prox(zn, i, tid);
+                    if constexpr (LOG) zn = lgo.prox(zn, i, tid);
                     zn = tmin(tmax(zn, lb[i]), ub[i]);     // (:273-276; an infinite bound is a no-op)
                     const T r = xi - zn;
                     const T s = rho * (zn - zp);
@@ -2185,6 +2259,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 T zn = xh + ui;
                 if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
                 if constexpr (SOFT) zn = sfo.prox(zn, i, tid);
+                if constexpr (LOG) zn = lgo.prox(zn, i, tid);
                 zn = tmin(tmax(zn, lb[i]), ub[i]);
                 const T r = xi - zn;
                 const T s = rho * (zn - zp);
@@ -2308,7 +2383,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
     __syncthreads();
   }
 }
-// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft
+// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft, FormLog
 template <typename FORM>
 __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                         const int prev_slot, const int persistent) {
@@ -2318,7 +2393,7 @@ __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P
 
 // The one-workgroup loop in every form.  persistent & 4 (continuation launches, FormAll): this is the forward's LAST launch -- it ends
 // with the epilogue (fwd_finish).  No other form ever is the last launch: under stop = 'each' the workgroups leave at different times,
-// and the L1 and soft epilogues take two more outputs (k_fwd_epilogue_l1, k_fwd_epilogue_soft) -- a launch of its own for all.
+// and the L1, soft and log epilogues take two more outputs (k_fwd_epilogue_l1, k_fwd_epilogue_soft, k_fwd_epilogue_log) -- a launch of its own for all.
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, typename FORM>
 __global__ __launch_bounds__(NT) void k_admm_loop(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
                                                   const int prev_slot, const int persistent) {
@@ -2452,6 +2527,10 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_fwd_epilogue_soft(const FwdParams<T> P, T* __restrict__ zone, T* __restrict__ u_box) {
     fwd_finish<T, false, true>(P, blockIdx.x, zone, u_box);
 }
+template <typename T>
+__global__ __launch_bounds__(256) void k_fwd_epilogue_log(const FwdParams<T> P, T* __restrict__ curv, T* __restrict__ u_box) {
+    fwd_finish<T, false, false, true>(P, blockIdx.x, curv, u_box);
+}
 // lqp_boxqp_forward_l1, behind the prologue (the scaling vector exists whichever kernel made it): ws = D w, cs = c / D next to
 // lbs / ubs' problem, and the input checks that need the data -- a weight that is negative or not finite, or a rho of the problem
 // (a per-problem rho_in among them) that is not positive and finite: t = ws / rho would be no threshold -- mark the problem
@@ -2496,6 +2575,25 @@ __global__ __launch_bounds__(256) void k_soft_setup(const FwdParams<T> P, const 
     if (__syncthreads_or(bad ? 1 : 0) && tid == 0) P.bflags[b] |= RP_SOFT_INPUT;
 }
 
+// lqp_boxqp_forward_log, at the same place: ws = w (no D: see LogView), and the input checks that need the data -- a weight that is
+// negative or not finite, a barrier element whose upper bound is not positive (the domain is empty), or a rho of the problem that is
+// not positive and finite -- mark the problem (RP_LOG_INPUT: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
+template <typename T>
+__global__ __launch_bounds__(256) void k_log_setup(const FwdParams<T> P, const T* __restrict__ w) {
+    const int b = blockIdx.x, n = P.n, tid = threadIdx.x;
+    const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
+    const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
+    bool bad = !(rho > T(0) && rho < T(INFINITY));
+    for (int i = tid; i < n; i += 256) {
+        const size_t g = (size_t)b * n + i;
+        const T wi = w[g];
+        bad |= !(wi >= T(0) && wi < T(INFINITY));      // (NaN fails the first comparison)
+        bad |= wi > T(0) && !(P.ub[g] > T(0));
+        W.ws[i] = wi;
+    }
+    if (__syncthreads_or(bad ? 1 : 0) && tid == 0) P.bflags[b] |= RP_LOG_INPUT;
+}
+
 // ---------------------------------------------------------------------------
 // fixed-point backward (solve_box_qp_admm_torch.py:349-432)
 // ---------------------------------------------------------------------------
@@ -2530,6 +2628,10 @@ template <typename T> struct BwdParams {
                                //    w = lam_lo / s_lo + lam_hi / s_hi (both clamped at 1e-8, :450-452): every variable is "free",
                                //    w takes the place of the 1e-8 regulariser, and the epilogue forms dlb / dub from dlam
     int piv_cols;              // 1: the look-ahead Cholesky's last pivot block stops behind the last free variable (LQP_PIV_COLS)
+    const T* curv;             // B * n or null (lqp_boxqp_backward_fp_curv): a non-negative diagonal h added to the 1e-8 of every FREE variable --
+                               //    the system is [[Q_FF + diag(h_F), A_F^T], [A_F, 0]] (+1e-8 I), the Hessian of a smooth separable term of the
+                               //    objective (the log barrier: w / x^2); the builds, the Cholesky form's equilibration and the refinement's
+                               //    residual read it; null = the expressions as they were; never together with kkt
 };
 
 // diagonal weight of the KKT-system backward for variable i (see BwdParams::kkt)
@@ -2557,6 +2659,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build(const BwdParams<T> P) {
     const T* A = P.A ? P.A + (size_t)b * m * n : nullptr;
     T* M = P.M + (size_t)b * Np * Np;
     T* rhs = P.rhs + (size_t)b * Np;
+    const T* cv = P.curv ? P.curv + (size_t)b * n : nullptr;
     if (tid == 0) P.info[b] = 0;
     const bool qvec = (n % 4 == 0) && ((((uintptr_t)Q) % sizeof(V4<T>)) == 0);
 #pragma unroll 2
@@ -2571,7 +2674,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build(const BwdParams<T> P) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     T val = keep * v.v[e];
-                    if (j + e == i) val = (val + rho * (T(1) - keep)) + T(1e-8);
+                    if (j + e == i) val = (val + rho * (T(1) - keep)) + (cv ? T(1e-8) + keep * cv[i] : T(1e-8));
                     v.v[e] = val;
                 }
                 *(V4<T>*)(mr + j) = v;
@@ -2579,7 +2682,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build(const BwdParams<T> P) {
         } else {
             for (int j = lane; j < n; j += 64) {
                 T val = keep * qr[j];
-                if (j == i) val = (val + rho * (T(1) - keep)) + T(1e-8);
+                if (j == i) val = (val + rho * (T(1) - keep)) + (cv ? T(1e-8) + keep * cv[i] : T(1e-8));
                 mr[j] = val;
             }
         }
@@ -2656,7 +2759,8 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build_reduced(const BwdParams<T>
         const int i0 = fl[a0], i1 = fl[a1];
         const T* q0 = Q + (size_t)i0 * n;
         const T* q1 = Q + (size_t)i1 * n;
-        const T dg0 = P.kkt ? kkt_weight(P, b, i0) : T(1e-8), dg1 = P.kkt ? kkt_weight(P, b, i1) : T(1e-8);
+        const T dg0 = P.kkt ? kkt_weight(P, b, i0) : P.curv ? T(1e-8) + P.curv[(size_t)b * n + i0] : T(1e-8);
+        const T dg1 = P.kkt ? kkt_weight(P, b, i1) : P.curv ? T(1e-8) + P.curv[(size_t)b * n + i1] : T(1e-8);
         for (int c0 = 0; c0 < nf; c0 += 64 * GQ) {
             T v0[GQ], v1[GQ];
 #pragma unroll
@@ -2726,13 +2830,15 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build_chol(const BwdParams<float
     float* AF = P.M + (size_t)b * Np * Np;
     float* rhs = P.rhs + (size_t)b * Np;
     if (tid == 0 && blockIdx.y == 0) P.info[b] = 0;
-    float* wl = (float*)(wtot + LQP_NW + 8);          // KKT-system backward: the diagonal weights (n floats)
+    float* wl = (float*)(wtot + LQP_NW + 8);          // KKT-system backward / a caller's curvature: the diagonal weights (n floats)
+    const bool dwt = P.kkt || P.curv;                 // (the diagonal comes from wl, not the constant)
     bool keep = false;
     if (tid < n) {
         if (P.kkt) { keep = true; wl[tid] = kkt_weight(P, b, tid); }
         else {
             const float sxu = x[tid] + u[tid];
             keep = !(sxu > ub[tid] || sxu < lb[tid]);
+            if (P.curv) wl[tid] = 1e-8f + P.curv[(size_t)b * n + tid];
         }
     }
     const unsigned long long bal = __ballot(keep);
@@ -2759,7 +2865,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build_chol(const BwdParams<float
     float* const sl = wl + round_up(n, 8);
     for (int a = tid; a < Npm; a += LQP_NT) {
         float sv = 1.f;
-        if (P.bsc && a < nf) sv = bwd_equil_scale(Q[(size_t)fl[a] * n + fl[a]] + (P.kkt ? wl[fl[a]] : 1e-8f));
+        if (P.bsc && a < nf) sv = bwd_equil_scale(Q[(size_t)fl[a] * n + fl[a]] + (dwt ? wl[fl[a]] : 1e-8f));
         sl[a] = sv;
         if (P.bsc && blockIdx.y == 0) P.bsc[(size_t)b * Np + a] = sv;
     }
@@ -2784,7 +2890,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_build_chol(const BwdParams<float
         for (int e = 0; e < 4; ++e) {
             const int c = j * 64 + c4 + e;
             float val = (a == c) ? 1.f : 0.f;
-            if (rok && c < nf) val = ((q4[e] + (a == c ? (P.kkt ? wl[fl[a]] : 1e-8f) : 0.f)) * sl[a]) * sl[c];
+            if (rok && c < nf) val = ((q4[e] + (a == c ? (dwt ? wl[fl[a]] : 1e-8f) : 0.f)) * sl[a]) * sl[c];
             v.v[e] = val;
         }
         *(V4<float>*)(Ls + (size_t)t * LQP_BLK + tid * 4) = v;
@@ -3033,7 +3139,7 @@ __global__ __launch_bounds__(LQP_NT) void k_bwd_residual(const BwdParams<T> P) {
             double res;
             if (a < nf) {
                 const int i = fl[a];
-                res = -(double)g[i] - mine - 1e-8 * (double)d[a];
+                res = -(double)g[i] - mine - (P.curv ? (double)(T(1e-8) + P.curv[(size_t)b * n + i]) : 1e-8) * (double)d[a];
                 for (int q = 0; q < m; ++q) res -= (double)A[(size_t)q * n + i] * (double)dn[q];
             } else {
                 res = -mine - 1e-8 * (double)dn[a - nf];
@@ -3351,6 +3457,31 @@ __global__ __launch_bounds__(256) void k_soft_finish_grads(const T* __restrict__
     if (dhi) dhi[i] = Kh ? gl + gu : T(0);
     if (dwu) dwu[i] = zn == T(2) ? g : T(0);
     if (dwl) dwl[i] = zn == T(-2) ? -g : T(0);
+}
+
+// backward of lqp_boxqp_forward_log: the fixed-point backward runs on the box's share of the dual (u_e = u_box: the clamped set is
+// where it is not zero, whatever the barrier adds to u) with curv on the diagonal of the free-set block (lqp_boxqp_backward_fp_curv);
+// lams_e is built from u_e as the forward builds lams
+template <typename T>
+__global__ __launch_bounds__(256) void k_log_effective_duals(const T* __restrict__ ubox, const T* __restrict__ rho_in, const T rho_value,
+                                                             const int n, const size_t total, T* __restrict__ u_e, T* __restrict__ lams_e) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / n, e = i - b * n;
+    const T ue = ubox[i];
+    u_e[i] = ue;
+    const T y = (rho_in ? rho_in[b] : rho_value) * ue;
+    lams_e[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
+    lams_e[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+}
+// ... and dw from dp: the term's gradient is -w_i / x_i, so dw_i = -dp_i / z_i where w_i > 0, else 0 (at w_i = 0 the one-sided
+// derivative is not defined when x_i <= 0: the convention of the header)
+template <typename T>
+__global__ __launch_bounds__(256) void k_log_finish_grads(const T* __restrict__ dp, const T* __restrict__ z, const T* __restrict__ w,
+                                                          const size_t total, T* __restrict__ dw) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    if (dw) dw[i] = w[i] > T(0) ? -dp[i] / z[i] : T(0);
 }
 
 template <int LQP_ANY = 0>

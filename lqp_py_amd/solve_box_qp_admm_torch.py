@@ -654,6 +654,10 @@ def _forward_decide(out, att, owner, look):
         # lqp_boxqp_forward_soft alone: its input checks made on the device
         return _Verdict(error=ValueError("lqp_py_amd: wl and wu must be finite and >= 0, lo <= hi without NaN, and rho positive and finite "
                                          f"(batch index {stats.fail_index})"))
+    if st == 1 and getattr(out, 'log', False):
+        # lqp_boxqp_forward_log alone: its input checks made on the device
+        return _Verdict(error=ValueError("lqp_py_amd: w must be finite and >= 0, ub > 0 wherever w > 0, and rho positive and finite "
+                                         f"(batch index {stats.fail_index})"))
     try:
         _lib.check(st, "torch_solve_box_qp")
     except RuntimeError as exc:
@@ -667,13 +671,14 @@ def _forward_decide(out, att, owner, look):
     return _Verdict(next=att._replace(bounds=(bool(stats.any_lb), bool(stats.any_ub)), one_call=False), release='tail', remember=seen)
 
 
-def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, l1=None, soft=None):
+def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, l1=None, soft=None, log=None):
     """One trip through the library on `att` (a _Try): settle the assumption, fetch the control struct, allocate, launch, make
     the views and run the caller's window while the GPU works, wait.  -> _Outcome, for _forward_decide to read.  What stands
     between entry and the first kernel launch is the forward time of a step that starts from an idle queue (experiment_1's
     protocol): errors of EARLIER calls are polled after this one is enqueued, the outputs are one allocation.
     l1 = (w, c): lqp_boxqp_forward_l1 (lqp_py_amd/solve_box_qp_l1.py, which has refused what that entry point cannot run).
-    soft = (wl, wu, lo, hi): lqp_boxqp_forward_soft (lqp_py_amd/solve_box_qp_soft.py), the same way; its "zone" takes side's place."""
+    soft = (wl, wu, lo, hi): lqp_boxqp_forward_soft (lqp_py_amd/solve_box_qp_soft.py), the same way; its "zone" takes side's place.
+    log = (w,): lqp_boxqp_forward_log (lqp_py_amd/solve_box_qp_log.py), the same way; its "curv" takes side's place."""
     Q, p, A, b, lb, ub = qp
     control, bounds, one_call = att
     lib, dev = _lib.load(), p.device
@@ -707,10 +712,11 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
     # hold x and Qs x too
     detect = each and r['infeasible'] is not None
     certify = each and r['unbounded'] is not None
-    ws_key = (dt, B, n, m, 'soft') if soft is not None else (dt, B, n, m, detect, certify) if l1 is None else (dt, B, n, m, 'l1')
+    ws_key = (dt, B, n, m, 'log') if log is not None else (dt, B, n, m, 'soft') if soft is not None else (dt, B, n, m, detect, certify) if l1 is None else (dt, B, n, m, 'l1')
     nbytes = _ws_bytes.get(ws_key)
     if nbytes is None:
-        size_of = (lib.lqp_boxqp_forward_soft_workspace_bytes if soft is not None else
+        size_of = (lib.lqp_boxqp_forward_log_workspace_bytes if log is not None else
+                   lib.lqp_boxqp_forward_soft_workspace_bytes if soft is not None else
                    lib.lqp_boxqp_forward_l1_workspace_bytes if l1 is not None else
                    lib.lqp_boxqp_forward_certify_workspace_bytes if certify else
                    lib.lqp_boxqp_forward_detect_workspace_bytes if detect else lib.lqp_boxqp_forward_workspace_bytes)
@@ -734,8 +740,14 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
         sc = tuple(_lib.norm(t, p.dtype) for t in soft)
         side, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
         soft_args = args[:11] + tuple(_lib.ptr(t) for t in sc) + args[11:19] + (_lib.ptr(side), _lib.ptr(u_box)) + args[19:]
+    if log is not None:
+        wc = _lib.norm(log[0], p.dtype)
+        side, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
+        log_args = args[:11] + (_lib.ptr(wc),) + args[11:19] + (_lib.ptr(u_box), _lib.ptr(side)) + args[19:]
     with _lib.on_device(dev):
-        if soft is not None:
+        if log is not None:
+            st = lib.lqp_boxqp_forward_log(*log_args)
+        elif soft is not None:
             st = lib.lqp_boxqp_forward_soft(*soft_args)
         elif l1 is not None:
             st = lib.lqp_boxqp_forward_l1(*l1_args)
@@ -765,7 +777,7 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
     return _Outcome(status=st, split_wait=split_wait, stats=stats, hook_error=hook_error, any_bound=any_bound, known=known,
                     report=report, ws=ws, stream=stream, dims=(dt, B, n, m), r=r, rho=rho, rho_mode=ctl.rho_mode,
                     x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out, iters=iters, pstatus=pstatus, l1=l1 is not None, side=side,
-                    u_box=u_box, soft=soft is not None)
+                    u_box=u_box, soft=soft is not None, log=log is not None)
 
 
 def _print_check_trace(out, dev):
@@ -800,7 +812,7 @@ def _solution(out, like, residuals):
     rho_ret = out.rho if as_given else out.rho_out.view(B, 1, 1)     # (un-synchronised calls cannot know whether rho was adapted: tensor)
     sol = {"x": out.x, "z": out.z, "u": out.u, "lams": out.lams, "nus": out.nus, "rho": rho_ret, "iter": int(stats.iters)}
     if getattr(out, 'side', None) is not None:      # lqp_boxqp_forward_l1: which side of c every element rests on, the box's share of u
-        sol["zone" if getattr(out, 'soft', False) else "side"], sol["u_box"] = out.side, out.u_box
+        sol["curv" if getattr(out, 'log', False) else "zone" if getattr(out, 'soft', False) else "side"], sol["u_box"] = out.side, out.u_box
     if out.iters is not None:            # control['stop'] = 'each': every problem's own count; "iter" is the largest
         sol["iters"] = out.iters
         sol["status"] = out.pstatus      # (B,) int32: 0 optimal, 1 ended at max_iters, 2 primal infeasible (control['infeasible']), 3 dual infeasible (control['unbounded'])
@@ -818,7 +830,7 @@ def _solution(out, like, residuals):
 
 def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residuals=False, check_hook=None, mutate=False,
                    holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False, raise_infeasible=False,
-                   raise_unbounded=False, l1=None, soft=None):
+                   raise_unbounded=False, l1=None, soft=None, log=None):
     """bounds: (any_lb, any_ub) when the caller KNOWS them (a shard of a larger batch with host-side flags); None: found
     on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
     nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound).
@@ -833,7 +845,7 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
     owner = control.get('_owner') or control          # (lqp_py_amd.dist hands the layer a copy of the caller's dict)
     att, dev = _Try(control, bounds, one_call), p.device
     while True:
-        out = _forward_attempt((Q, p, A, b, lb, ub), att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, l1=l1, soft=soft)
+        out = _forward_attempt((Q, p, A, b, lb, ub), att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, l1=l1, soft=soft, log=log)
         v = _forward_decide(out, att, owner, lambda: _finite_bounds(lb, ub))
         if v.release == 'tail':
             try:
@@ -1007,8 +1019,9 @@ def _fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, rho, want, sync=True, li
                      late_dQ=(B, n) if late_dQ else None, pref_reported=pref_reported)
 
 
-def _fp_backward_run(prep, dl_dz):
-    _lib.require_gpu(dl_dz)
+def _fp_backward_run(prep, dl_dz, curv=None):
+    """curv: a (B,n,1) non-negative diagonal for the free-set block (lqp_boxqp_backward_fp_curv; never on a prefactored `prep`)"""
+    _lib.require_gpu(dl_dz, curv)
     gc = _lib.norm(dl_dz, prep['dty'])
     dev, report, B, sync, linsolve = prep['dev'], prep['report'], prep['B'], prep['sync'], prep['linsolve']
     if prep['pref'] is not None and prep['pref'] == _lib.workspace_uses(dev, "bwd", prep['stream']):
@@ -1026,10 +1039,14 @@ def _fp_backward_run(prep, dl_dz):
         prep['grads'] = (dQ,) + tuple(prep['grads'][1:])
         tail = tail[:_TAIL_DQ] + (_lib.ptr(dQ),) + tail[_TAIL_DQ + 1:]
     prep['ran'] = True                                                 # (the report buffer is this run's to hand back from here on)
-    _backward_call(prep['lib'].lqp_boxqp_backward_fp, (*prep['head'], _lib.ptr(gc), *tail, linsolve, prep['rep']),
+    entry = prep['lib'].lqp_boxqp_backward_fp
+    if curv is not None:
+        cc = _lib.norm(curv, prep['dty'])
+        entry, tail = prep['lib'].lqp_boxqp_backward_fp_curv, tail[:8] + (_lib.ptr(cc),) + tail[8:]      # (behind ub)
+    _backward_call(entry, (*prep['head'], _lib.ptr(gc), *tail, linsolve, prep['rep']),
                    "torch_solve_box_qp_grad", prep['fail'], report, dev, B, sync)
     return prep['grads']
 
 
-def _fp_backward(dl_dz, x, u, lams, nus, Q, A, lb, ub, rho, want, sync=True, linsolve=1):
-    return _fp_backward_run(_fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, rho, want, sync=sync, linsolve=linsolve), dl_dz)
+def _fp_backward(dl_dz, x, u, lams, nus, Q, A, lb, ub, rho, want, sync=True, linsolve=1, curv=None):
+    return _fp_backward_run(_fp_backward_prepare(x, u, lams, nus, Q, A, lb, ub, rho, want, sync=sync, linsolve=linsolve), dl_dz, curv=curv)

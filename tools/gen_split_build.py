@@ -43,6 +43,13 @@ GROUPS = [
     ("loop_soft_tail", loop("k_admm_loop", "Soft", r"\w+, \w+, true,")),
     ("loop_soft_hot", loop("k_admm_loop", "Soft")),
     ("soft", lambda n: loop("k_admm_loop_np2", "Soft")(n) or loop("k_admm_loop_small", "Soft")(n) or re.search(r"k_fwd_epilogue_soft<|k_soft_", n)),
+    # ... and with the log barrier's step (lqp_boxqp_forward_log)
+    ("split_log_c", loop("k_admm_loop_split", "Log", r"(3|4), 512, false, 2,")),
+    ("split_log_a", loop("k_admm_loop_split", "Log", r"(5|6|7), 512, false, 2,")),
+    ("split_log_b", loop("k_admm_loop_split", "Log")),
+    ("loop_log_tail", loop("k_admm_loop", "Log", r"\w+, \w+, true,")),
+    ("loop_log_hot", loop("k_admm_loop", "Log")),
+    ("log", lambda n: loop("k_admm_loop_np2", "Log")(n) or loop("k_admm_loop_small", "Log")(n) or re.search(r"k_fwd_epilogue_log<|k_log_", n)),
     ("bwd_f", lambda n: re.search(r"k_bwd_chol_solve<\d, true>", n)),
     ("resident_f", lambda n: re.search(r"k_spd_resident<8, 2, true>", n)),
     ("resident_g", lambda n: re.search(r"k_spd_resident<(5|6|7), 2, true>", n)),
@@ -79,9 +86,10 @@ FPF, BPF = "lqp::FwdParams<float>", "lqp::BwdParams<float>"
 KS_NP = [(3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4)]      # Ks, workgroups per problem (four: Ks = 7, 8 only)
 # The forms of the loop kernels (the tags of lqp_boxqp.hpp), the last template argument of every instance: the batch stops as one |
 # control['stop'] = 'each' | ... with the infeasibility certificate (control['infeasible']) | ... and the dual certificate beside it
-# (control['unbounded']) | lqp_boxqp_forward_l1: the L1 step | lqp_boxqp_forward_soft: the soft band's step
-ALL, EACH, DETECT, CERTIFY, L1, SOFT = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify", "L1", "Soft"))
-FORMS = (ALL, EACH, DETECT, CERTIFY, L1, SOFT)
+# (control['unbounded']) | lqp_boxqp_forward_l1: the L1 step | lqp_boxqp_forward_soft: the soft band's step | lqp_boxqp_forward_log: the
+# log barrier's step
+ALL, EACH, DETECT, CERTIFY, L1, SOFT, LOG = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify", "L1", "Soft", "Log"))
+FORMS = (ALL, EACH, DETECT, CERTIFY, L1, SOFT, LOG)
 SPLIT = [(ks, 512, False, np_) for ks, np_ in KS_NP]
 # the one-workgroup loop, hot and continuation: LU f64 | LU f32 | LU f32 resident | symmetric
 LOOP = [(t, res, tail, 1024, sym) for tail in (False, True)
@@ -93,9 +101,9 @@ WIDE_SIG = LU_SIG + ", int const*, int*, unsigned long, unsigned int, int, unsig
 KERNELS = [
     # the ADMM loops (lqp_boxqp.hpp, lqp_loop_split.hpp, lqp_loop_small.hpp, lqp_dense.hpp)
     ("k_admm_loop", LOOP_SIG, in_forms(LOOP, FORMS) + [("float", True, False, 512, False, ALL), ("float", True, False, 512, True, ALL)]),
-    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH, L1, SOFT)) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
+    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH, L1, SOFT, LOG)) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
     ("k_admm_loop_small", FPF + ", int, int, int", in_forms([()], FORMS)),
-    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL, L1, SOFT))),
+    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL, L1, SOFT, LOG))),
     ("k_admm_loop_dense", FP + ", int, int, int", BOTH),
     ("k_admm_loop_dense_w", FP + ", int, int, int, int", BOTH),
     # the symmetric x-update (lqp_spd.hpp)
@@ -134,6 +142,10 @@ KERNELS = [
     ("k_soft_setup", FP + ", {0} const*, {0} const*, {0} const*, {0} const*", BOTH),
     ("k_soft_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_soft_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*, {0}*, {0}*, {0}*", BOTH),
+    ("k_fwd_epilogue_log", FP + ", {0}*, {0}*", BOTH),
+    ("k_log_setup", FP + ", {0} const*", BOTH),
+    ("k_log_effective_duals", "{0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*", BOTH),
+    ("k_log_finish_grads", "{0} const*, {0} const*, {0} const*, unsigned long, {0}*", BOTH),
     ("k_rho_update", FP + ", int, int", BOTH),
     ("k_snap_init", "{0}*, unsigned long, int", BOTH),
     ("k_check_done", "int*, unsigned int const*, int, int", ZERO),
