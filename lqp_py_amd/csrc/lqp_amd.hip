@@ -499,6 +499,11 @@ inline void solve_stats(lqp_boxqp_stats* stats, const volatile int* rv, const in
     stats->any_lb = rv[ST_ANY_LB]; stats->any_ub = rv[ST_ANY_UB];
 }
 inline bool flags_timeout_loop(const int* rep) { return ((const volatile int*)rep)[ST_TIMEOUT] != 0; }
+// the run-time twins of the Term traits (lqp_boxqp.hpp), by Term*::kind
+constexpr int kTerms = 4;
+constexpr int kTermSlots[kTerms] = {TermNone::slots, TermL1::slots, TermSoft::slots, TermLog::slots};
+constexpr int kTermInputs[kTerms] = {TermNone::n_in, TermL1::n_in, TermSoft::n_in, TermLog::n_in};
+constexpr int kTermFlag[kTerms] ={TermNone::input_flag, TermL1::input_flag, TermSoft::input_flag, TermLog::input_flag};
 int collect_report(hipStream_t st, const int* rep, const bool polled, const int B, const int max_iters, const int check,
                    lqp_boxqp_stats* stats) {
     if (polled) {
@@ -513,24 +518,14 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
         lu_timeout = lu_timeout || rv[ST_WORDS + i] == -7;          // (a multi-workgroup LU never met its partner)
         flags_or |= rv[ST_WORDS + B + i];
     }
-    if (flags_or & RP_L1_INPUT) {
-        // lqp_boxqp_forward_l1: a weight that is negative or not finite, a rho that is not positive (k_l1_setup).  First: what such
-        // data do to a factorisation (a negative rho leaves the symmetric x-update, a NaN makes a zero pivot) is no finding of its own
+    for (int k = 1; k < kTerms; ++k) {
+        if (!(flags_or & kTermFlag[k])) continue;
+        // a solve with a separable term: what k_term_setup flags (a weight that is negative or not finite, a rho that is not positive ...).
+        // First: what such data do to a factorisation (a negative rho leaves the symmetric x-update, a NaN makes a zero pivot) is no
+        // finding of its own
         memset(stats, 0, sizeof(*stats));
         stats->fail_index = -1;
-        for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & RP_L1_INPUT) stats->fail_index = i;
-        return LQP_ERR_INVALID;
-    }
-    if (flags_or & RP_SOFT_INPUT) {      // lqp_boxqp_forward_soft: the same for what k_soft_setup flags
-        memset(stats, 0, sizeof(*stats));
-        stats->fail_index = -1;
-        for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & RP_SOFT_INPUT) stats->fail_index = i;
-        return LQP_ERR_INVALID;
-    }
-    if (flags_or & RP_LOG_INPUT) {       // lqp_boxqp_forward_log: the same for what k_log_setup flags
-        memset(stats, 0, sizeof(*stats));
-        stats->fail_index = -1;
-        for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & RP_LOG_INPUT) stats->fail_index = i;
+        for (int i = 0; i < B && stats->fail_index < 0; ++i) if (rv[ST_WORDS + B + i] & kTermFlag[k]) stats->fail_index = i;
         return LQP_ERR_INVALID;
     }
     if (lu_timeout && stats->linsolve_used != 2) return LQP_ERR_TIMEOUT;
@@ -553,16 +548,16 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
 // has an instance per form it supports (family_has_form), and nothing but its selector below chooses one.
 // The batch stops as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
 // infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']:
-// P.eps_dinf > 0) | the L1 step (lqp_boxqp_forward_l1: P.l1, whose area shares its storage with the snapshots; the batch stops as one)
-// | the soft band's step (lqp_boxqp_forward_soft: P.l1 == 2, its area at the same place) | the log barrier's step (lqp_boxqp_forward_log:
-// P.l1 == 3, the same place again)
+// P.eps_dinf > 0) | the step with a separable term, one form per term (lqp_boxqp_forward_l1 / _soft / _log: P.term, whose area shares its
+// storage with the snapshots; the batch stops as one)
 enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT, FORM_LOG };
-inline LoopForm loop_form(const int l1, const bool each, const bool snapshots, const bool dual) {
-    return l1 == 3 ? FORM_LOG : l1 == 2 ? FORM_SOFT : l1 ? FORM_L1 : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
+inline int form_term(const LoopForm form) { return form >= FORM_L1 ? form - FORM_L1 + 1 : 0; }      // (Term*::kind of the form, 0: none)
+inline LoopForm loop_form(const int term, const bool each, const bool snapshots, const bool dual) {
+    return term ? (LoopForm)(FORM_L1 + term - 1) : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
 }
 inline bool form_each(const LoopForm form) { return form == FORM_EACH || form == FORM_DETECT || form == FORM_CERTIFY; }
 inline bool form_snapshots(const LoopForm form) { return form == FORM_DETECT || form == FORM_CERTIFY; }
-template <typename T> LoopForm loop_form(const FwdParams<T>& P) { return loop_form(P.l1, P.pstat != nullptr, P.snap != nullptr, P.eps_dinf > 0); }
+template <typename T> LoopForm loop_form(const FwdParams<T>& P) { return loop_form(P.term, P.pstat != nullptr, P.snap != nullptr, P.eps_dinf > 0); }
 template <typename F> auto by_form(const LoopForm form, F f) -> decltype(f(FormAll())) {
     switch (form) {
         case FORM_EACH:    return f(FormEach());
@@ -582,12 +577,10 @@ template <typename T> struct FwdLayout {
     void* snap_area;                // [B][snap_stride]: the infeasibility certificate's snapshots, BEHIND `bytes` (lqp_boxqp_forward_detect alone)
     size_t detect_bytes;            // ... and the size that holds them
     size_t certify_bytes;           // ... and with the dual certificate's x and Qs x in every slot (lqp_boxqp_forward_certify; the same start)
-    void* l1_area;                  // [B][l1_stride]: ws, cs, t of lqp_boxqp_forward_l1, BEHIND `bytes` too (the same start: never together with the snapshots)
-    size_t l1_bytes;                // ... and the size that holds them
-    size_t soft_bytes;              // ... and with [B][soft_stride] there: wls, wus, los, his, tl, tu of lqp_boxqp_forward_soft (the same start)
-    size_t log_bytes;               // ... and with [B][log_stride] there: ws, t of lqp_boxqp_forward_log (the same start)
+    void* term_area;                // [B][term_stride<TERM>]: the area of a separable term, BEHIND `bytes` too (the same start: never together with the snapshots)
+    size_t term_bytes[kTerms];      // ... and the size that holds it, by Term*::kind
     size_t bytes_for(const LoopForm form) const {      // the workspace a solve of this form needs
-        return form == FORM_LOG ? log_bytes : form == FORM_SOFT ? soft_bytes : form == FORM_L1 ? l1_bytes : form == FORM_CERTIFY ? certify_bytes : form == FORM_DETECT ? detect_bytes : bytes;
+        return form_term(form) ? term_bytes[form_term(form)] : form == FORM_CERTIFY ? certify_bytes : form == FORM_DETECT ? detect_bytes : bytes;
     }
 };
 // the workspaces whose last forward ran with ctrl.reserved2 bit 3: lqp_boxqp_problem_iters is valid for these alone.  Host state keyed
@@ -646,14 +639,12 @@ FwdLayout<T> carve_forward(void* ws, int B, int n, int m) {
     c.take<T>((size_t)B * snap_stride(n, m, true));
     L.certify_bytes = c.off + kAlign;
     c.off = L.bytes;
-    L.l1_area = c.take<T>((size_t)B * l1_stride(n));
-    L.l1_bytes = c.off + kAlign;
-    c.off = L.bytes;
-    c.take<T>((size_t)B * soft_stride(n));
-    L.soft_bytes = c.off + kAlign;
-    c.off = L.bytes;
-    c.take<T>((size_t)B * log_stride(n));
-    L.log_bytes = c.off + kAlign;
+    L.term_bytes[0] = L.bytes;      // (TermNone: no area)
+    for (int k = 1; k < kTerms; ++k) {      // (every term's area at the same start)
+        c.off = L.bytes;
+        L.term_area = c.take<T>((size_t)B * kTermSlots[k] * round_up(n, 8));
+        L.term_bytes[k] = c.off + kAlign;
+    }
     return L;
 }
 
@@ -718,15 +709,16 @@ template <typename T> LoopPair<T> loop_kernels(const LoopForm form, const bool r
         return {k_admm_loop<T, false, false, 1024, false, FORM>, k_admm_loop<T, false, true, 1024, false, FORM>};
     });
 }
+// the streaming loop on two workgroups per problem: no instance for a per-problem form -- null, never another form's kernel; its one
+// caller asks family_has_form(LOOP_NP2, form) first
 inline LoopFn<float> np2_kernel(const LoopForm form) {
-    return form == FORM_LOG ? k_admm_loop_np2<FormLog> : form == FORM_SOFT ? k_admm_loop_np2<FormSoft> : form == FORM_L1 ? k_admm_loop_np2<FormL1> : k_admm_loop_np2<FormAll>;
+    return by_form(form, [](auto f) -> LoopFn<float> {
+        if constexpr (decltype(f)::each) return nullptr;
+        else return k_admm_loop_np2<decltype(f)>;
+    });
 }
-// the extra arguments of lqp_boxqp_forward_l1
-struct L1Args { const void *w, *c; void *side, *u_box; };
-// ... and of lqp_boxqp_forward_soft
-struct SoftArgs { const void *wl, *wu, *lo, *hi; void *zone, *u_box; };
-// ... and of lqp_boxqp_forward_log
-struct LogArgs { const void* w; void *u_box, *curv; };
+// the extra arguments of lqp_boxqp_forward_l1 / _soft / _log: the term (Term*::kind), its input vectors, its two outputs
+struct TermArgs { int kind = 0; const void* in[4] = {nullptr, nullptr, nullptr, nullptr}; void* aux = nullptr; void* u_box = nullptr; };
 
 constexpr int kMaxChecksPerLaunch = kRing / 4;
 
@@ -751,9 +743,7 @@ template <typename T> struct FwdPlan {
     int kind_lds = 0;                   // LDS of LOOP_SMALL / LOOP_DENSE / LOOP_DENSE_W
     SplitFn small_fn = nullptr;         // LOOP_SMALL
     LoopFn<float> np2_fn = nullptr;     // LOOP_NP2
-    L1Args l1a = {nullptr, nullptr, nullptr, nullptr};      // FORM_L1: what k_l1_setup reads, k_fwd_epilogue_l1 (the epilogue of that form) writes
-    SoftArgs sfa = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // FORM_SOFT: the same for k_soft_setup and k_fwd_epilogue_soft
-    LogArgs lga = {nullptr, nullptr, nullptr};      // FORM_LOG: the same for k_log_setup and k_fwd_epilogue_log
+    TermArgs term;                      // a form with a term: what k_term_setup reads and k_fwd_epilogue<T, TERM> (the epilogue of that form) writes
     int kind_wg = 1;                    // workgroups per problem of the hot launch
     int densew_tpr = 0;
     bool loop_split_seg = false;        // mode 1: k_admm_loop_split per check segment, its pairs taking turns on the chip
@@ -1070,10 +1060,8 @@ template <typename T> void plan_scheduler(FwdParams<T>& P, const lqp_boxqp_ctrl*
 //                 CUs -- another stream, another process, RCCL): nothing shared this time -- one workgroup per matrix in every
 //                 factorisation, host-launched check segments instead of the persistent loop with its grid barrier
 template <typename T> int plan_forward(FwdParams<T>& P, const lqp_boxqp_ctrl* ctl, const int retry, const Knobs& k, const Device& d, FwdPlan<T>& plan) {
-    const L1Args l1a = plan.l1a;
-    const SoftArgs sfa = plan.sfa;
-    const LogArgs lga = plan.lga;
-    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0; plan.l1a = l1a; plan.sfa = sfa; plan.lga = lga;
+    const TermArgs term = plan.term;
+    plan = FwdPlan<T>(); plan.retry = retry; plan.solo = (retry & 4) != 0; plan.term = term;
     // control['stop'] = 'each': the loop kernels with a per-problem form -- the one-workgroup loop (every size, dtype and m), the small
     // loop and the split loop on two / four workgroups per problem; no other hot kernel, no hot_past, no hot rounds, no 512-thread build
     plan.form = loop_form(P);
@@ -1157,6 +1145,15 @@ int enqueue_factor(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan
     return r2;
 }
 
+// the epilogue as a launch of its own: the plain one, or the one of the form's term with its two outputs
+template <typename T>
+void launch_epilogue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& plan) {
+    by_form(plan.form, [&](auto f) {
+        using TERM = typename decltype(f)::term;
+        if constexpr (TERM::kind != 0) hipLaunchKernelGGL((k_fwd_epilogue<T, TERM>), dim3(P.B), dim3(256), 0, st, P, (T*)plan.term.aux, (T*)plan.term.u_box);
+        else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(P.B), dim3(256), 0, st, P);
+    });
+}
 // everything in front of the loop: the pass over Q (k_spd_prep), setup (its workgroup 0 zeroes status + counter ring), the first
 // factorisation, and for the dense tiers X = M^-1
 template <typename T>
@@ -1184,21 +1181,16 @@ int enqueue_prologue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pl
         if (rc) return rc;
         ++n_launch;
     }
-    if (plan.form == FORM_L1) {      // ws, cs: behind whoever wrote the scaling vector (the setup kernel, or the resident sweep it defers to)
-        ProfScope ps(st, PC_SETUP);
-        hipLaunchKernelGGL(k_l1_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.l1a.w, (const T*)plan.l1a.c);
-        ++n_launch;
-    }
-    if (plan.form == FORM_SOFT) {    // wls, wus, los, his: at the same place
-        ProfScope ps(st, PC_SETUP);
-        hipLaunchKernelGGL(k_soft_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.sfa.wl, (const T*)plan.sfa.wu, (const T*)plan.sfa.lo, (const T*)plan.sfa.hi);
-        ++n_launch;
-    }
-    if (plan.form == FORM_LOG) {     // ws: at the same place
-        ProfScope ps(st, PC_SETUP);
-        hipLaunchKernelGGL(k_log_setup<T>, dim3(B), dim3(256), 0, st, P, (const T*)plan.lga.w);
-        ++n_launch;
-    }
+    by_form(plan.form, [&](auto f) {      // the term's scaled inputs: behind whoever wrote the scaling vector (the setup kernel, or the resident sweep it defers to)
+        using TERM = typename decltype(f)::term;
+        if constexpr (TERM::kind != 0) {
+            ProfScope ps(st, PC_SETUP);
+            TermIn<T> in;
+            for (int k = 0; k < 4; ++k) in.p[k] = (const T*)plan.term.in[k];
+            hipLaunchKernelGGL((k_term_setup<T, TERM>), dim3(P.B), dim3(256), 0, st, P, in);
+            ++n_launch;
+        }
+    });
     return LQP_OK;
 }
 
@@ -1348,10 +1340,7 @@ Attempt run_planned(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
     }
     if (!epilogue_done) {
         ProfScope ps(st, PC_EPILOGUE);
-        if (plan.form == FORM_L1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
-          else if (plan.form == FORM_SOFT) hipLaunchKernelGGL(k_fwd_epilogue_soft<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.sfa.zone, (T*)plan.sfa.u_box);
-          else if (plan.form == FORM_LOG) hipLaunchKernelGGL(k_fwd_epilogue_log<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.lga.curv, (T*)plan.lga.u_box);
-          else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P);
+        launch_epilogue(st, P, plan);
         ++n_launch;
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
@@ -1463,10 +1452,7 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         // the epilogue only reads state: run it now so that the common case (converged in this chunk)
         // pays no host round trip between the loop and its outputs; a later chunk simply re-runs it
         { ProfScope ps(st, PC_EPILOGUE);
-          if (plan.form == FORM_L1) hipLaunchKernelGGL(k_fwd_epilogue_l1<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.l1a.side, (T*)plan.l1a.u_box);
-          else if (plan.form == FORM_SOFT) hipLaunchKernelGGL(k_fwd_epilogue_soft<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.sfa.zone, (T*)plan.sfa.u_box);
-          else if (plan.form == FORM_LOG) hipLaunchKernelGGL(k_fwd_epilogue_log<T>, dim3(B), dim3(256), 0, st, P, (T*)plan.lga.curv, (T*)plan.lga.u_box);
-          else hipLaunchKernelGGL(k_fwd_epilogue<T>, dim3(B), dim3(256), 0, st, P); }
+          launch_epilogue(st, P, plan); }
         ++n_launch;
         // (with a host report the epilogue has left status and info words in pinned host memory: one wait, no copies)
         if (!P.host_report) HIP_OK(hipMemcpyAsync(h_status, P.status, sizeof(h_status), hipMemcpyDeviceToHost, st));
@@ -1521,13 +1507,13 @@ Attempt run_chunked(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pla
         chunk_cap = std::min(chunk_cap * 2, 64);
     }
     if (hipGetLastError() != hipSuccess) return LQP_ERR_HIP;
-    if (plan.form == FORM_L1 || plan.form == FORM_SOFT || plan.form == FORM_LOG) {
-        // a weight that is negative or not finite (k_l1_setup / k_soft_setup / k_log_setup mark the problem's flag word; the epilogue has reported it)
+    if (form_term(plan.form)) {
+        // a weight that is negative or not finite (k_term_setup marks the problem's flag word; the epilogue has reported it)
         std::vector<int> fl(B);
         if (P.host_report) for (int i = 0; i < B; ++i) fl[i] = ((const volatile int*)P.host_report)[ST_WORDS + B + i];
         else { HIP_OK(hipMemcpyAsync(fl.data(), P.bflags, sizeof(int) * B, hipMemcpyDeviceToHost, st)); HIP_OK(hipStreamSynchronize(st)); }
         for (int i = 0; i < B; ++i)
-            if (fl[i] & (RP_L1_INPUT | RP_SOFT_INPUT | RP_LOG_INPUT)) {
+            if (fl[i] & kTermFlag[form_term(plan.form)]) {
                 if (stats) { memset(stats, 0, sizeof(*stats)); stats->fail_index = i; }
                 return LQP_ERR_INVALID;
             }
@@ -1553,18 +1539,14 @@ template <typename T>
 int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void* p, const void* A, const void* b,
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
-                 int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const L1Args* l1 = nullptr,
-                 const SoftArgs* soft = nullptr, const LogArgs* lg = nullptr) {
-    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; l1: lqp_boxqp_forward_l1; soft: lqp_boxqp_forward_soft;
-    //  lg: lqp_boxqp_forward_log)
+                 int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const TermArgs* term = nullptr) {
+    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; term: lqp_boxqp_forward_l1 / _soft / _log)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
-    const LoopForm asked = loop_form(lg ? 3 : soft ? 2 : l1 ? 1 : 0, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
+    const LoopForm asked = loop_form(term ? term->kind : 0, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
     if (ws_bytes < L.bytes_for(asked)) return LQP_ERR_WORKSPACE;
     {
         FwdParams<T>& P = L.P;
-        if (asked == FORM_L1) { P.l1 = 1; P.l1v = (T*)L.l1_area; }
-        if (asked == FORM_SOFT) { P.l1 = 2; P.l1v = (T*)L.l1_area; }      // (the same start, soft_stride per problem)
-        if (asked == FORM_LOG) { P.l1 = 3; P.l1v = (T*)L.l1_area; }       // (the same start, log_stride per problem)
+        if (term) { P.term = term->kind; P.termv = (T*)L.term_area; }
         P.Q = (const T*)Q; P.p = (const T*)p; P.A = (const T*)A; P.b = (const T*)b;
         P.lb = (const T*)lb; P.ub = (const T*)ub; P.rho_in = (const T*)rho_in; P.beta_in = (const T*)ctl->beta_in;
         P.x = (T*)x; P.z = (T*)z; P.u = (T*)u; P.lams = (T*)lams; P.nus = (T*)nus; P.rho_out = (T*)rho_out;
@@ -1603,9 +1585,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
         if (retry & 4) one_wg_lu.enter();
         FwdParams<T> P = L.P;
         FwdPlan<T> plan;
-        if (l1) plan.l1a = *l1;
-        if (soft) plan.sfa = *soft;
-        if (lg) plan.lga = *lg;
+        if (term) plan.term = *term;
         int rc = plan_forward(P, ctl, retry, k, d, plan);
         if (rc) return rc;
         int n_launch = 0;
@@ -2176,6 +2156,19 @@ bool bad_dims(int dtype, int B, int n, int m) {
 
 }  // namespace
 
+// ---- the element-wise kernels around lqp_boxqp_backward_fp (log: lqp_boxqp_backward_fp_curv) in the backwards of those solves
+//      (csrc/lqp_boxqp.hpp): dtype, dims and the pointers that must be there; one thread per element of [B][n] ----
+inline bool elementwise_ok(int dtype, int B, int n, std::initializer_list<const void*> required) {
+    bool ok = (dtype == LQP_F32 || dtype == LQP_F64) && B >= 1 && n >= 1;
+    for (const void* q : required) ok = ok && q != nullptr;
+    return ok;
+}
+template <typename F> int elementwise(void* stream, int dtype, int B, int n, F launch) {
+    const size_t total = (size_t)B * n;
+    by_dtype(dtype, [&](auto t) { launch(t, dim3((unsigned int)((total + 255) / 256)), (hipStream_t)stream, total); return 0; });
+    return last_error();
+}
+
 extern "C" {
 
 int lqp_abi_version(void) { return LQP_ABI_VERSION; }
@@ -2331,7 +2324,7 @@ static int forward_entry(void* stream, int dtype, int B, int n, int m, const voi
                          const void* b, const void* lb, const void* ub, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
                          void* workspace, size_t workspace_bytes, const double eps_prim_inf, const double eps_dual_inf,
-                         const L1Args* l1 = nullptr, const SoftArgs* soft = nullptr, const LogArgs* lg = nullptr) {
+                         const TermArgs* term = nullptr) {
     if (bad_dims(dtype, B, n, m) || !Q || !p || !lb || !ub || !ctrl || !x || !z || !u || !lams || !rho_out || !workspace)
         return LQP_ERR_INVALID;
     if (m > 0 && (!A || !b || !nus)) return LQP_ERR_INVALID;
@@ -2346,7 +2339,7 @@ static int forward_entry(void* stream, int dtype, int B, int n, int m, const voi
     hipStream_t st = (hipStream_t)stream;
     const int retry0 = (ctrl->reserved2 & 2) ? 4 : 0;      // (bit 1: the caller has seen a shared schedule time out -- nothing shared)
     return by_dtype(dtype, [&](auto t) {
-        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf, l1, soft, lg);
+        return forward_impl<decltype(t)>(st, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes, retry0, eps_prim_inf, eps_dual_inf, term);
     });
 }
 
@@ -2370,153 +2363,119 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const
                          workspace_bytes, eps_prim_inf, 0.0);
 }
 
+// ---- the solves with a separable term: lqp_boxqp_forward_l1 / _soft / _log ----
 size_t lqp_boxqp_forward_l1_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_L1); });
+}
+size_t lqp_boxqp_forward_soft_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_SOFT); });
+}
+size_t lqp_boxqp_forward_log_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_LOG); });
+}
+
+// Refused before anything is touched: a null pointer of the term's own, the per-problem stop (no instance of its kernels with a term), a
+// check hook, the factor kept for the unroll sweep (its tape replays the plain step), and the rho = 0 one-shot -- a solve with a term
+// always iterates, whatever the bounds: all of them infinite is an ordinary case here
+static int term_entry(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                      const void* b, const void* lb, const void* ub, const TermArgs& term, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                      void* x, void* z, void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats,
+                      void* workspace, size_t workspace_bytes) {
+    for (int k = 0; k < kTermInputs[term.kind]; ++k) if (!term.in[k]) return LQP_ERR_INVALID;
+    if (!term.aux || !term.u_box) return LQP_ERR_INVALID;
+    if (!ctrl || (ctrl->reserved2 & (8 | 1)) || ctrl->check_hook) return LQP_ERR_INVALID;
+    if (ctrl->rho_mode == 1 && !(ctrl->rho_value > 0.0)) return LQP_ERR_INVALID;
+    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
+                         workspace_bytes, 0.0, 0.0, &term);
 }
 
 int lqp_boxqp_forward_l1(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
                          const void* b, const void* lb, const void* ub, const void* w, const void* c, const lqp_boxqp_ctrl* ctrl,
                          const void* rho_in, void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* side, void* u_box,
                          lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
-    // refused before anything is touched: a null pointer, the per-problem stop (no L1 instance of its kernels), a check hook, the
-    // factor kept for the unroll sweep (its tape replays the plain step), and the rho = 0 one-shot -- the L1 solve always iterates,
-    // whatever the bounds: all of them infinite is an ordinary case here
-    if (!w || !c || !side || !u_box) return LQP_ERR_INVALID;
-    if (!ctrl || (ctrl->reserved2 & (8 | 1)) || ctrl->check_hook) return LQP_ERR_INVALID;
-    if (ctrl->rho_mode == 1 && !(ctrl->rho_value > 0.0)) return LQP_ERR_INVALID;
-    const L1Args l1 = {w, c, side, u_box};
-    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
-                         workspace_bytes, 0.0, 0.0, &l1);
-}
-
-// the two element-wise kernels around lqp_boxqp_backward_fp in the backward of lqp_boxqp_forward_l1 (csrc/lqp_boxqp.hpp)
-int lqp_boxqp_l1_effective_box(void* stream, int dtype, int B, int n, const void* side, const void* u, const void* u_box,
-                               const void* lb, const void* ub, const void* c, int rho_mode, double rho_value, const void* rho_in,
-                               void* lb_e, void* ub_e, void* u_e, void* lams_e) {
-    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
-    if (!side || !u || !u_box || !lb || !ub || !c || !lb_e || !ub_e || !u_e || !lams_e || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
-    const size_t total = (size_t)B * n;
-    by_dtype(dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_l1_effective_box<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)side,
-                           (const T*)u, (const T*)u_box, (const T*)lb, (const T*)ub, (const T*)c, rho_mode == 2 ? (const T*)rho_in : nullptr,
-                           (T)rho_value, n, total, (T*)lb_e, (T*)ub_e, (T*)u_e, (T*)lams_e);
-        return 0;
-    });
-    return last_error();
-}
-
-int lqp_boxqp_l1_finish_grads(void* stream, int dtype, int B, int n, const void* side, const void* dp, const void* dlb_e,
-                              const void* dub_e, void* dlb, void* dub, void* dc, void* dw) {
-    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
-    if (!side || !dp || !dlb_e || !dub_e) return LQP_ERR_INVALID;
-    const size_t total = (size_t)B * n;
-    by_dtype(dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_l1_finish_grads<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)side,
-                           (const T*)dp, (const T*)dlb_e, (const T*)dub_e, total, (T*)dlb, (T*)dub, (T*)dc, (T*)dw);
-        return 0;
-    });
-    return last_error();
-}
-
-size_t lqp_boxqp_forward_soft_workspace_bytes(int dtype, int B, int n, int m) {
-    if (bad_dims(dtype, B, n, m)) return 0;
-    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_SOFT); });
+    const TermArgs term = {TermL1::kind, {w, c, nullptr, nullptr}, side, u_box};
+    return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
 }
 
 int lqp_boxqp_forward_soft(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
                            const void* b, const void* lb, const void* ub, const void* wl, const void* wu, const void* lo, const void* hi,
                            const lqp_boxqp_ctrl* ctrl, const void* rho_in, void* x, void* z, void* u, void* lams, void* nus, void* rho_out,
                            void* zone, void* u_box, lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
-    // refused before anything is touched, as lqp_boxqp_forward_l1 does: a null pointer, the per-problem stop (no soft instance of its
-    // kernels), a check hook, the factor kept for the unroll sweep, and the rho = 0 one-shot -- this solve always iterates too
-    if (!wl || !wu || !lo || !hi || !zone || !u_box) return LQP_ERR_INVALID;
-    if (!ctrl || (ctrl->reserved2 & (8 | 1)) || ctrl->check_hook) return LQP_ERR_INVALID;
-    if (ctrl->rho_mode == 1 && !(ctrl->rho_value > 0.0)) return LQP_ERR_INVALID;
-    const SoftArgs soft = {wl, wu, lo, hi, zone, u_box};
-    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
-                         workspace_bytes, 0.0, 0.0, nullptr, &soft);
-}
-
-// the two element-wise kernels around lqp_boxqp_backward_fp in the backward of lqp_boxqp_forward_soft (csrc/lqp_boxqp.hpp)
-int lqp_boxqp_soft_effective_box(void* stream, int dtype, int B, int n, const void* zone, const void* u, const void* u_box,
-                                 const void* lb, const void* ub, const void* lo, const void* hi, int rho_mode, double rho_value,
-                                 const void* rho_in, void* lb_e, void* ub_e, void* u_e, void* lams_e) {
-    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
-    if (!zone || !u || !u_box || !lb || !ub || !lo || !hi || !lb_e || !ub_e || !u_e || !lams_e || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
-    const size_t total = (size_t)B * n;
-    by_dtype(dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_soft_effective_box<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)zone,
-                           (const T*)u, (const T*)u_box, (const T*)lb, (const T*)ub, (const T*)lo, (const T*)hi,
-                           rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)lb_e, (T*)ub_e, (T*)u_e, (T*)lams_e);
-        return 0;
-    });
-    return last_error();
-}
-
-int lqp_boxqp_soft_finish_grads(void* stream, int dtype, int B, int n, const void* zone, const void* u_box, const void* dp, const void* dlb_e,
-                                const void* dub_e, void* dlb, void* dub, void* dwl, void* dwu, void* dlo, void* dhi) {
-    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
-    if (!zone || !u_box || !dp || !dlb_e || !dub_e) return LQP_ERR_INVALID;
-    const size_t total = (size_t)B * n;
-    by_dtype(dtype, [&](auto t) {
-        typedef decltype(t) T;
-        hipLaunchKernelGGL(k_soft_finish_grads<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)zone,
-                           (const T*)u_box, (const T*)dp, (const T*)dlb_e, (const T*)dub_e, total, (T*)dlb, (T*)dub, (T*)dwl, (T*)dwu, (T*)dlo, (T*)dhi);
-        return 0;
-    });
-    return last_error();
-}
-
-size_t lqp_boxqp_forward_log_workspace_bytes(int dtype, int B, int n, int m) {
-    if (bad_dims(dtype, B, n, m)) return 0;
-    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_LOG); });
+    const TermArgs term = {TermSoft::kind, {wl, wu, lo, hi}, zone, u_box};
+    return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
 }
 
 int lqp_boxqp_forward_log(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
                           const void* b, const void* lb, const void* ub, const void* w, const lqp_boxqp_ctrl* ctrl, const void* rho_in,
                           void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* u_box, void* curv,
                           lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
-    // refused before anything is touched, as lqp_boxqp_forward_soft does: a null pointer, the per-problem stop (no log instance of its
-    // kernels), a check hook, the factor kept for the unroll sweep, and the rho = 0 one-shot -- this solve always iterates too
-    if (!w || !u_box || !curv) return LQP_ERR_INVALID;
-    if (!ctrl || (ctrl->reserved2 & (8 | 1)) || ctrl->check_hook) return LQP_ERR_INVALID;
-    if (ctrl->rho_mode == 1 && !(ctrl->rho_value > 0.0)) return LQP_ERR_INVALID;
-    const LogArgs lg = {w, u_box, curv};
-    return forward_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace,
-                         workspace_bytes, 0.0, 0.0, nullptr, nullptr, &lg);
+    const TermArgs term = {TermLog::kind, {w, nullptr, nullptr, nullptr}, curv, u_box};
+    return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
 }
 
-// the two element-wise kernels around lqp_boxqp_backward_fp_curv in the backward of lqp_boxqp_forward_log (csrc/lqp_boxqp.hpp)
+int lqp_boxqp_l1_effective_box(void* stream, int dtype, int B, int n, const void* side, const void* u, const void* u_box,
+                               const void* lb, const void* ub, const void* c, int rho_mode, double rho_value, const void* rho_in,
+                               void* lb_e, void* ub_e, void* u_e, void* lams_e) {
+    if (!elementwise_ok(dtype, B, n, {side, u, u_box, lb, ub, c, lb_e, ub_e, u_e, lams_e}) || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_l1_effective_box<T>, grid, dim3(256), 0, st, (const T*)side, (const T*)u, (const T*)u_box, (const T*)lb, (const T*)ub,
+                           (const T*)c, rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)lb_e, (T*)ub_e, (T*)u_e, (T*)lams_e);
+    });
+}
+
+int lqp_boxqp_l1_finish_grads(void* stream, int dtype, int B, int n, const void* side, const void* dp, const void* dlb_e,
+                              const void* dub_e, void* dlb, void* dub, void* dc, void* dw) {
+    if (!elementwise_ok(dtype, B, n, {side, dp, dlb_e, dub_e})) return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_l1_finish_grads<T>, grid, dim3(256), 0, st, (const T*)side, (const T*)dp, (const T*)dlb_e, (const T*)dub_e, total,
+                           (T*)dlb, (T*)dub, (T*)dc, (T*)dw);
+    });
+}
+
+int lqp_boxqp_soft_effective_box(void* stream, int dtype, int B, int n, const void* zone, const void* u, const void* u_box,
+                                 const void* lb, const void* ub, const void* lo, const void* hi, int rho_mode, double rho_value,
+                                 const void* rho_in, void* lb_e, void* ub_e, void* u_e, void* lams_e) {
+    if (!elementwise_ok(dtype, B, n, {zone, u, u_box, lb, ub, lo, hi, lb_e, ub_e, u_e, lams_e}) || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_soft_effective_box<T>, grid, dim3(256), 0, st, (const T*)zone, (const T*)u, (const T*)u_box, (const T*)lb, (const T*)ub,
+                           (const T*)lo, (const T*)hi, rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)lb_e, (T*)ub_e,
+                           (T*)u_e, (T*)lams_e);
+    });
+}
+
+int lqp_boxqp_soft_finish_grads(void* stream, int dtype, int B, int n, const void* zone, const void* u_box, const void* dp, const void* dlb_e,
+                                const void* dub_e, void* dlb, void* dub, void* dwl, void* dwu, void* dlo, void* dhi) {
+    if (!elementwise_ok(dtype, B, n, {zone, u_box, dp, dlb_e, dub_e})) return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_soft_finish_grads<T>, grid, dim3(256), 0, st, (const T*)zone, (const T*)u_box, (const T*)dp, (const T*)dlb_e,
+                           (const T*)dub_e, total, (T*)dlb, (T*)dub, (T*)dwl, (T*)dwu, (T*)dlo, (T*)dhi);
+    });
+}
+
 int lqp_boxqp_log_effective_duals(void* stream, int dtype, int B, int n, const void* u_box, int rho_mode, double rho_value,
                                   const void* rho_in, void* u_e, void* lams_e) {
-    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
-    if (!u_box || !u_e || !lams_e || (rho_mode != 1 && rho_mode != 2) || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
-    const size_t total = (size_t)B * n;
-    by_dtype(dtype, [&](auto t) {
+    if (!elementwise_ok(dtype, B, n, {u_box, u_e, lams_e}) || (rho_mode != 1 && rho_mode != 2) || (rho_mode == 2 && !rho_in)) return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
         typedef decltype(t) T;
-        hipLaunchKernelGGL(k_log_effective_duals<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)u_box,
-                           rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)u_e, (T*)lams_e);
-        return 0;
+        hipLaunchKernelGGL(k_log_effective_duals<T>, grid, dim3(256), 0, st, (const T*)u_box, rho_mode == 2 ? (const T*)rho_in : nullptr,
+                           (T)rho_value, n, total, (T*)u_e, (T*)lams_e);
     });
-    return last_error();
 }
 
 int lqp_boxqp_log_finish_grads(void* stream, int dtype, int B, int n, const void* dp, const void* z, const void* w, void* dw) {
-    if ((dtype != LQP_F32 && dtype != LQP_F64) || B < 1 || n < 1) return LQP_ERR_INVALID;
-    if (!dp || !z || !w) return LQP_ERR_INVALID;
+    if (!elementwise_ok(dtype, B, n, {dp, z, w})) return LQP_ERR_INVALID;
     if (!dw) return LQP_OK;
-    const size_t total = (size_t)B * n;
-    by_dtype(dtype, [&](auto t) {
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
         typedef decltype(t) T;
-        hipLaunchKernelGGL(k_log_finish_grads<T>, dim3((unsigned int)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dp,
-                           (const T*)z, (const T*)w, total, (T*)dw);
-        return 0;
+        hipLaunchKernelGGL(k_log_finish_grads<T>, grid, dim3(256), 0, st, (const T*)dp, (const T*)z, (const T*)w, total, (T*)dw);
     });
-    return last_error();
 }
 
 size_t lqp_boxqp_forward_certify_workspace_bytes(int dtype, int B, int n, int m) {

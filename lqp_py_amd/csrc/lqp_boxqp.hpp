@@ -28,9 +28,9 @@ enum { PS_DONE = 0, PS_FINAL = 1, PS_RESUME = 2, PS_NFACTOR = 3, PS_WORDS = 4 };
 enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
        RP_INFEAS = 1 << 16,       // control['infeasible']: the problem was flagged primal infeasible (each_stop)
        RP_UNBOUNDED = 1 << 17,    // control['unbounded']: the problem was flagged dual infeasible (each_stop)
-       RP_L1_INPUT = 1 << 18,     // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_l1_setup); its outputs are NaN
-       RP_SOFT_INPUT = 1 << 19,   // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_soft_setup); its outputs are NaN
-       RP_LOG_INPUT = 1 << 20 };  // lqp_boxqp_forward_log: a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (k_log_setup); its outputs are NaN
+       RP_L1_INPUT = 1 << 18,     // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_term_setup); its outputs are NaN
+       RP_SOFT_INPUT = 1 << 19,   // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_term_setup); its outputs are NaN
+       RP_LOG_INPUT = 1 << 20 };  // lqp_boxqp_forward_log: a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (k_term_setup); its outputs are NaN
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -112,40 +112,17 @@ template <typename T> struct FwdParams {
     T eps_abs, eps_rel, rho_value, rho_min, rho_max, ar_tol, ar_inv_tol, ar_thr, beta_value;
     T alpha, alpha_c;         // over-relaxation factor (control['alpha']; 1 = the reference's plain step) and 1 - alpha, see admm_relax
     int relax;                // 1: alpha != 1
-    int l1;                   // 1: lqp_boxqp_forward_l1 -- the objective carries sum_i w_i |x_i - c_i| and `snap` is the L1 area (in the alignment gap in front of the pointer: no offset moves)
-                              // 2: lqp_boxqp_forward_soft -- it carries sum_i wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ and `l1v` is the soft area (soft_stride, SoftView)
-                              // 3: lqp_boxqp_forward_log -- it carries -sum_i w_i log(x_i) and `l1v` is the barrier's area (log_stride, LogView)
+    int term;                 // the separable term of the objective, Term*::kind below: 0 none | 1 lqp_boxqp_forward_l1: sum_i w_i |x_i - c_i|
+                              // | 2 lqp_boxqp_forward_soft: sum_i wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ | 3 lqp_boxqp_forward_log: -sum_i w_i log(x_i)
+                              // (in the alignment gap in front of the pointer: no offset moves)
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
     union {
     T* snap;                 // B * snap_stride: control['infeasible'] (stop = 'each' only) -- the certificate's snapshots, or null = no detection
-    T* l1v;                  // l1 (never together with the snapshots, and at their place in the workspace): B * l1_stride(n), per problem
-    };                       //   [ws = D w | cs = c / D | t = ws / rho of the running segment]; k_l1_setup writes ws, cs
+    T* termv;                // term != 0 (never together with the snapshots, and at their place in the workspace): the term's area,
+    };                       //   B * term_stride<TERM>(n), per problem the slots its trait names; k_term_setup writes the scaled inputs
     size_t snap_stride;
     T eps_pinf;              // control['eps_prim_inf']; 0: the primal certificate is off (lqp_boxqp_forward_certify with the dual one alone)
     T eps_dinf;              // control['eps_dual_inf']; 0: no dual certificate (control['unbounded'] absent) -- the slots then end behind nu
-};
-__host__ __device__ inline size_t l1_stride(int n) { return (size_t)3 * round_up(n, 8); }
-// the scaled L1 data of problem b
-template <typename T> struct L1View {
-    T *ws, *cs, *t;
-    __device__ L1View(T* base, int n) { ws = base; cs = ws + round_up(n, 8); t = cs + round_up(n, 8); }
-};
-// the soft band (lqp_boxqp_forward_soft), at the place of the L1 area: B * soft_stride(n), per problem
-// [wls = D wl | wus = D wu | los = lo / D | his = hi / D | tl = wls / rho | tu = wus / rho of the running segment]; k_soft_setup writes the first four
-__host__ __device__ inline size_t soft_stride(int n) { return (size_t)6 * round_up(n, 8); }
-template <typename T> struct SoftView {
-    T *wls, *wus, *los, *his, *tl, *tu;
-    __device__ SoftView(T* base, int n) {
-        const int s = round_up(n, 8);
-        wls = base; wus = wls + s; los = wus + s; his = los + s; tl = his + s; tu = tl + s;
-    }
-};
-// the log barrier (lqp_boxqp_forward_log), at the same place: B * log_stride(n), per problem [ws = w | t = ws / rho of the running segment]
-// (in the scaled space x = D xs the term is -w log(xs) plus a constant: the weight takes no D); k_log_setup writes ws
-__host__ __device__ inline size_t log_stride(int n) { return (size_t)2 * round_up(n, 8); }
-template <typename T> struct LogView {
-    T *ws, *t;
-    __device__ LogView(T* base, int n) { ws = base; t = ws + round_up(n, 8); }
 };
 // control['infeasible']: the snapshot of problem b -- (y, g, nu) of its last check, see infeas_view.  TWO slots by the parity of the check's
 // number (it / check_solved): a check reads the other slot and writes its own, so the workgroups of a shared problem (k_admm_loop_split, FormEach:
@@ -1361,34 +1338,209 @@ __host__ __device__ inline int sym_resident_lds_blocks(int n, int m, int Ks, int
 // block -- no device-to-host copy behind the solve (a 1.4 us blit kernel + a boundary).  Words other workgroups of the SAME
 // launch may still write (ST_NOTSPD, ST_TIMEOUT of an in-kernel refactorisation) are therefore also kept per problem
 // (RP_NOTSPD / RP_TIMEOUT in the writer's own flag word).
-// L1 (lqp_boxqp_forward_l1): the soft threshold once more at the returned iterate, in the scaled space where the kink is exact
-// (z == cs by assignment): v = z + u, S = l1_shrink(v, ws / rho, cs).  side = sign(S - cs), 0 exactly on the kink set (the threshold
-// branch was taken and t > 0); u_box = (S - clamp(S)) / D -- S - z with the clamp taken again, so that it is exactly zero unless
-// the element is clamped (the stored z is the clamp of the last iteration's v, one rounding away from this one) -- the box's share
-// of the dual, and lams are built from it; the rest of u is the L1 term's multiplier.
+// With a separable term (fwd_finish<T, TERM>): the term's finish_elem at the returned iterate, its two outputs, and lams from u_box.
+//
+// ---------------------------------------------------------------------------
+// The separable terms of the objective: sum_i f_i(x_i) beside the box, one trait each.  ADMM sees a term in ONE place, the z-update:
+// z = clamp(prox_{f / rho}(x + u)) -- so a trait holds the element-wise prox and what surrounds it, and nothing else in the library
+// knows a term: the scaled inputs k_term_setup leaves in the term's area of the workspace (FwdParams::termv: `slots` vectors of
+// round_up(n, 8) per problem, the inputs first, then the thresholds = weights / rho that the streaming loop keeps for a launch), what
+// a thread of a loop kernel holds per element (Regs), and what the epilogue reports for the backward (finish_elem: aux, u_box).
+//   kind        FwdParams::term
+//   input_flag  the bit of the problem's flag word that says "bad input" (setup_elem's verdict, OR-ed over the problem)
+//   n_in        input vectors ([B][n] each, TermIn), slots: vectors of the area
+//   Regs<T>     load: from the area with the rho of this launch (a division per element and launch, none per iteration); prox: the prox
+//               at t = weight / rho, in the scaled space
+//   View<T>     a pointer per vector of a problem's area -- the ONE place that states the area's layout; keep(i, rho) stores an element's
+//               thresholds there (the streaming loop, TermOwn)
+//   prox_at     (Regs) the prox of the thread's first element (registers) or of a further one (through the view)
+//   setup_elem  one element of k_term_setup: scales the inputs into the area; true = this element's input is no input
+//   finish_elem one element of the epilogue, in the scaled space where the kinks are exact
+// Every prox returns v itself at a zero weight, by a branch: the plain step's bits.  A compile-time choice (Form*::term), never a flag.
+// ---------------------------------------------------------------------------
+template <typename T> struct TermIn { const T* p[4]; };
+template <typename T> struct TermOut { T aux, u_box; };
+template <typename TERM> __host__ __device__ inline size_t term_stride(int n) { return (size_t)TERM::slots * round_up(n, 8); }
+struct TermNone {
+    static constexpr int kind = 0, input_flag = 0, n_in = 0, slots = 0;
+    template <typename T> struct Regs {
+        __device__ __forceinline__ T prox(const T v) const { return v; }
+    };
+};
+// L1 (lqp_boxqp_forward_l1), w |x - c|: soft-threshold around cs.  Area: [ws = D w | cs = c / D | t = ws / rho]
 template <typename T> __device__ __forceinline__ T l1_shrink(const T v, const T t, const T c) {
     const T d = v - c;
     return d > t ? v - t : (d < -t ? v + t : c);
 }
-// Soft band (lqp_boxqp_forward_soft): the same with soft_prox; zone = +-2 on the sloped pieces, +-1 on the kinks hi / lo (only where the
-// weight of that side is positive: with none the kink is no kink), 0 inside the band; u_box as above.  The outputs take the L1 pair's place.
+struct TermL1 {
+    static constexpr int kind = 1, input_flag = RP_L1_INPUT, n_in = 2, slots = 3;
+    enum { WS, CS, TH };
+    template <typename T> struct View {
+        T *ws = nullptr, *cs = nullptr, *t = nullptr;
+        View() = default;
+        __device__ __forceinline__ View(T* a, const int n) { ws = a + WS * round_up(n, 8); cs = a + CS * round_up(n, 8); t = a + TH * round_up(n, 8); }
+        __device__ __forceinline__ void keep(const int i, const T rho) const { t[i] = ws[i] / rho; }
+    };
+    template <typename T> struct Regs {
+        T t = T(0), c = T(0);
+        __device__ __forceinline__ void load(const T* a, const int n, const int i, const T rho) { const View<const T> W(a, n); t = W.ws[i] / rho; c = W.cs[i]; }
+        __device__ __forceinline__ T prox(const T v) const { return l1_shrink(v, t, c); }
+        __device__ __forceinline__ T prox_at(const T v, const bool first, const View<T> W, const int i) const {
+            return l1_shrink(v, first ? t : W.t[i], first ? c : W.cs[i]);
+        }
+    };
+    // a weight that is negative or not finite: t = ws / rho would be no threshold
+    template <typename T>
+    static __device__ __forceinline__ bool setup_elem(T* a, const int n, const int i, const TermIn<T>& in, const size_t g, const T* D, const T*) {
+        const View<T> W(a, n);
+        const T wi = in.p[0][g], di = D[i];
+        W.ws[i] = di * wi;
+        W.cs[i] = in.p[1][g] / di;
+        return !(wi >= T(0) && wi < T(INFINITY));            // (NaN fails the first comparison)
+    }
+    // The soft threshold once more at the returned iterate, in the scaled space where the kink is exact (z == cs by assignment):
+    // v = z + u, S = l1_shrink(v, ws / rho, cs).  side = sign(S - cs), 0 exactly on the kink set (the threshold branch was taken and
+    // t > 0); u_box = (S - clamp(S)) / D -- S - z with the clamp taken again, so that it is exactly zero unless the element is clamped
+    // (the stored z is the clamp of the last iteration's v, one rounding away from this one) -- the box's share of the dual, and lams
+    // are built from it; the rest of u is the L1 term's multiplier.
+    template <typename T>
+    static __device__ __forceinline__ TermOut<T> finish_elem(const T* a, const int n, const int i, const T zs, const T us, const T lbs,
+                                                             const T ubs, const T d, const T rho, const T poison) {
+        const View<const T> W(a, n);
+        const T v = zs + us, t = W.ws[i] / rho, cs = W.cs[i], dd = v - cs;
+        const bool kink = t > T(0) && !(dd > t) && !(dd < -t);
+        const T S = l1_shrink(v, t, cs);
+        const T ubx = (S - tmin(tmax(S, lbs), ubs)) / d + poison;      // (S - z with z = clamp(S): exactly zero off the bounds)
+        return {(kink ? T(0) : (dd < T(0) ? T(-1) : T(1))) + poison, ubx};
+    }
+};
+// Soft band (lqp_boxqp_forward_soft), wl (lo - x)_+ + wu (x - hi)_+: two thresholds tl = wls / rho, tu = wus / rho, two kinks
+// los <= his; los == his with tl == tu is l1_shrink, bit for bit.  Area: [wls = D wl | wus = D wu | los = lo / D | his = hi / D | tl | tu]
 template <typename T> __device__ __forceinline__ T soft_prox(const T v, const T tl, const T tu, const T los, const T his) {
     const T dh = v - his, dl = v - los;
     return dh > tu ? v - tu : (dl < -tl ? v + tl : tmin(tmax(v, los), his));
 }
-// Log barrier (lqp_boxqp_forward_log): the prox of -w log(.) with t = w / rho is the positive root of S^2 - v S - t = 0.  With
+struct TermSoft {
+    static constexpr int kind = 2, input_flag = RP_SOFT_INPUT, n_in = 4, slots = 6;
+    enum { WLS, WUS, LOS, HIS, TL, TU };
+    template <typename T> struct View {
+        T *wls = nullptr, *wus = nullptr, *los = nullptr, *his = nullptr, *tl = nullptr, *tu = nullptr;
+        View() = default;
+        __device__ __forceinline__ View(T* a, const int n) {
+            const int s = round_up(n, 8);
+            wls = a + WLS * s; wus = a + WUS * s; los = a + LOS * s; his = a + HIS * s; tl = a + TL * s; tu = a + TU * s;
+        }
+        __device__ __forceinline__ void keep(const int i, const T rho) const { tl[i] = wls[i] / rho; tu[i] = wus[i] / rho; }
+    };
+    template <typename T> struct Regs {
+        T tl = T(0), tu = T(0), lo = T(0), hi = T(0);
+        __device__ __forceinline__ void load(const T* a, const int n, const int i, const T rho) {
+            const View<const T> W(a, n);
+            tl = W.wls[i] / rho; tu = W.wus[i] / rho; lo = W.los[i]; hi = W.his[i];
+        }
+        __device__ __forceinline__ T prox(const T v) const { return soft_prox(v, tl, tu, lo, hi); }
+        __device__ __forceinline__ T prox_at(const T v, const bool first, const View<T> W, const int i) const {
+            return first ? soft_prox(v, tl, tu, lo, hi) : soft_prox(v, W.tl[i], W.tu[i], W.los[i], W.his[i]);
+        }
+    };
+    // a weight that is negative or not finite, lo > hi, a NaN in lo or hi (an infinite kink stays infinite)
+    template <typename T>
+    static __device__ __forceinline__ bool setup_elem(T* a, const int n, const int i, const TermIn<T>& in, const size_t g, const T* D, const T*) {
+        const View<T> W(a, n);
+        const T wli = in.p[0][g], wui = in.p[1][g], loi = in.p[2][g], hii = in.p[3][g], di = D[i];
+        bool bad = !(wli >= T(0) && wli < T(INFINITY)) || !(wui >= T(0) && wui < T(INFINITY));      // (NaN fails the first comparison)
+        bad |= !(loi <= hii);                                  // (lo > hi, or a NaN in either)
+        W.wls[i] = di * wli;
+        W.wus[i] = di * wui;
+        W.los[i] = loi / di;
+        W.his[i] = hii / di;
+        return bad;
+    }
+    // The same with soft_prox; zone = +-2 on the sloped pieces, +-1 on the kinks hi / lo (only where the weight of that side is
+    // positive: with none the kink is no kink), 0 inside the band; u_box as for L1.
+    template <typename T>
+    static __device__ __forceinline__ TermOut<T> finish_elem(const T* a, const int n, const int i, const T zs, const T us, const T lbs,
+                                                             const T ubs, const T d, const T rho, const T poison) {
+        const View<const T> W(a, n);
+        const T v = zs + us, tl = W.wls[i] / rho, tu = W.wus[i] / rho, los = W.los[i], his = W.his[i];
+        const T S = soft_prox(v, tl, tu, los, his);
+        const T zone = (v - his > tu) ? T(2) : (v - los < -tl) ? T(-2) : (v >= his && tu > T(0)) ? T(1) : (v <= los && tl > T(0)) ? T(-1) : T(0);
+        const T ubx = (S - tmin(tmax(S, lbs), ubs)) / d + poison;
+        return {zone + poison, ubx};
+    }
+};
+// Log barrier (lqp_boxqp_forward_log), -w log(x): the prox with t = w / rho is the positive root of S^2 - v S - t = 0.  With
 // s = sqrt(v^2 + 4 t): 0.5 (v + s) for v >= 0 and 2 t / (s - v) for v < 0 -- the form without cancellation (0.5 (v + s) loses 5 % at
-// v = -50, t = 1e-3 in float32).  t == 0 returns v itself, by a branch: the plain step's bits.  At the returned iterate: u_box is the
-// box's share of the dual, (us + t / zs) / D where the clamp moved S and exactly 0 elsewhere (S - clamp(S) is NOT the multiplier
-// here: the barrier's own force t / zs acts on a clamped element too); curv = w / z^2 (unscaled z) on the free barrier elements,
-// the diagonal of the term's Hessian for the backward, 0 elsewhere.  The outputs take the L1 pair's place.
+// v = -50, t = 1e-3 in float32).  Area: [ws = w | t = ws / rho] (in the scaled space x = D xs the term is -w log(xs) plus a constant:
+// the weight takes no D)
 template <typename T> __device__ __forceinline__ T log_prox(const T v, const T t) {
     if (t == T(0)) return v;
     const T s = tsqrt(v * v + T(4) * t);
     return v >= T(0) ? T(0.5) * (v + s) : (T(2) * t) / (s - v);
 }
-template <typename T, bool L1 = false, bool SOFT = false, bool LOG = false>
-__device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T* __restrict__ l1_side = nullptr, T* __restrict__ l1_ubox = nullptr) {
+struct TermLog {
+    static constexpr int kind = 3, input_flag = RP_LOG_INPUT, n_in = 1, slots = 2;
+    enum { WS, TH };
+    template <typename T> struct View {
+        T *ws = nullptr, *t = nullptr;
+        View() = default;
+        __device__ __forceinline__ View(T* a, const int n) { ws = a + WS * round_up(n, 8); t = a + TH * round_up(n, 8); }
+        __device__ __forceinline__ void keep(const int i, const T rho) const { t[i] = ws[i] / rho; }
+    };
+    template <typename T> struct Regs {
+        T t = T(0);
+        __device__ __forceinline__ void load(const T* a, const int n, const int i, const T rho) { t = View<const T>(a, n).ws[i] / rho; }
+        __device__ __forceinline__ T prox(const T v) const { return log_prox(v, t); }
+        __device__ __forceinline__ T prox_at(const T v, const bool first, const View<T> W, const int i) const { return log_prox(v, first ? t : W.t[i]); }
+    };
+    // a weight that is negative or not finite, or a barrier element whose upper bound is not positive (the domain is empty)
+    template <typename T>
+    static __device__ __forceinline__ bool setup_elem(T* a, const int n, const int i, const TermIn<T>& in, const size_t g, const T*, const T* ub) {
+        const T wi = in.p[0][g];
+        View<T>(a, n).ws[i] = wi;
+        return !(wi >= T(0) && wi < T(INFINITY)) || (wi > T(0) && !(ub[g] > T(0)));      // (NaN fails the first comparison)
+    }
+    // At the returned iterate: u_box is the box's share of the dual, (us + t / zs) / D where the clamp moved S and exactly 0 elsewhere
+    // (S - clamp(S) is NOT the multiplier here: the barrier's own force t / zs acts on a clamped element too); curv = w / z^2
+    // (unscaled z) on the free barrier elements, the diagonal of the term's Hessian for the backward, 0 elsewhere.
+    template <typename T>
+    static __device__ __forceinline__ TermOut<T> finish_elem(const T* a, const int n, const int i, const T zs, const T us, const T lbs,
+                                                             const T ubs, const T d, const T rho, const T poison) {
+        const T wi = View<const T>(a, n).ws[i], t = wi / rho;
+        const T S = log_prox(zs + us, t);
+        const bool held = S != tmin(tmax(S, lbs), ubs);
+        const T ubx = (held ? (t == T(0) ? us : us + t / zs) / d : T(0)) + poison;
+        const T zu = d * zs;
+        return {((wi > T(0) && !held) ? wi / (zu * zu) : T(0)) + poison, ubx};      // (curv)
+    }
+};
+// What a thread of the streaming loop, which owns several elements, keeps of a term: its first element in registers; the thresholds
+// of its further elements (n > NT only) come from the area, where prime() stores them itself -- nothing is stored for the first
+// (both workgroups of a shared problem would write the same values).  Nothing at all for TermNone.
+template <typename T, typename TERM> struct TermOwn {
+    typename TERM::template Regs<T> r0;
+    typename TERM::template View<T> W;
+    template <int NT> __device__ __forceinline__ void prime(T* a, const int n, const int tid, const T rho) {
+        W = typename TERM::template View<T>(a, n);
+        for (int i = tid + NT; i < n; i += NT) W.keep(i, rho);
+        if (tid < n) r0.load(a, n, tid, rho);
+    }
+    __device__ __forceinline__ T prox(const T v, const int i, const int tid) const { return r0.prox_at(v, i == tid, W, i); }
+};
+// (an empty specialisation, not dead members: with the members the plain instances of the streaming loop were no longer the
+//  instructions they had been)
+template <typename T> struct TermOwn<T, TermNone> {
+    template <int NT> __device__ __forceinline__ void prime(T*, int, int, T) {}
+    __device__ __forceinline__ T prox(const T v, int, int) const { return v; }
+};
+
+// lams = (max(-y, 0), max(y, 0)) of element e of problem b from y = rho * (the box's share of u) (:316-327)
+template <typename T, typename I> __device__ __forceinline__ void lams_from_y(T* lams, const size_t b, const int n, const I e, const T y) {
+    lams[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
+    lams[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+}
+template <typename T, typename TERM = TermNone>
+__device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T* __restrict__ term_aux = nullptr, T* __restrict__ term_ubox = nullptr) {
     const int n = P.n, m = P.m, tid = threadIdx.x, nt = blockDim.x;
     VecView<T> V(P.vecs + (size_t)b * P.vstride, n, m);
     const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
@@ -1398,9 +1550,7 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T
     const int notspd = __hip_atomic_load(P.status + ST_NOTSPD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int tmo = __hip_atomic_load(P.status + ST_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     bool bad = info_b != 0 || notspd != 0 || tmo != 0;
-    if constexpr (L1) bad = bad || (P.bflags[b] & RP_L1_INPUT) != 0;
-    if constexpr (SOFT) bad = bad || (P.bflags[b] & RP_SOFT_INPUT) != 0;
-    if constexpr (LOG) bad = bad || (P.bflags[b] & RP_LOG_INPUT) != 0;
+    if constexpr (TERM::kind != 0) bad = bad || (P.bflags[b] & TERM::input_flag) != 0;
     const T poison = bad ? T(__builtin_nanf("")) : T(0);
     for (int i = tid; i < n; i += nt) {
         const T d = V.D[i];
@@ -1409,39 +1559,13 @@ __device__ __forceinline__ void fwd_finish(const FwdParams<T>& P, const int b, T
         P.z[(size_t)b * n + i] = zo;
         P.u[(size_t)b * n + i] = uo;
         T y = uo * rho;
-        if constexpr (L1) {
-            const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
-            const T zs = V.z[i], v = zs + V.u[i], t = W.ws[i] / rho, cs = W.cs[i], dd = v - cs;
-            const bool kink = t > T(0) && !(dd > t) && !(dd < -t);
-            const T S = l1_shrink(v, t, cs);
-            const T ubx = (S - tmin(tmax(S, V.lbs[i]), V.ubs[i])) / d + poison;      // (S - z with z = clamp(S): exactly zero off the bounds)
-            l1_side[(size_t)b * n + i] = (kink ? T(0) : (dd < T(0) ? T(-1) : T(1))) + poison;
-            l1_ubox[(size_t)b * n + i] = ubx;
-            y = ubx * rho;
+        if constexpr (TERM::kind != 0) {
+            const TermOut<T> o = TERM::finish_elem(P.termv + (size_t)b * term_stride<TERM>(n), n, i, V.z[i], V.u[i], V.lbs[i], V.ubs[i], d, rho, poison);
+            term_aux[(size_t)b * n + i] = o.aux;
+            term_ubox[(size_t)b * n + i] = o.u_box;
+            y = o.u_box * rho;
         }
-        if constexpr (SOFT) {
-            const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
-            const T v = V.z[i] + V.u[i], tl = W.wls[i] / rho, tu = W.wus[i] / rho, los = W.los[i], his = W.his[i];
-            const T S = soft_prox(v, tl, tu, los, his);
-            const T zone = (v - his > tu) ? T(2) : (v - los < -tl) ? T(-2) : (v >= his && tu > T(0)) ? T(1) : (v <= los && tl > T(0)) ? T(-1) : T(0);
-            const T ubx = (S - tmin(tmax(S, V.lbs[i]), V.ubs[i])) / d + poison;
-            l1_side[(size_t)b * n + i] = zone + poison;
-            l1_ubox[(size_t)b * n + i] = ubx;
-            y = ubx * rho;
-        }
-        if constexpr (LOG) {
-            const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
-            const T zs = V.z[i], us = V.u[i], wi = W.ws[i], t = wi / rho;
-            const T S = log_prox(zs + us, t);
-            const bool held = S != tmin(tmax(S, V.lbs[i]), V.ubs[i]);
-            const T ubx = (held ? (t == T(0) ? us : us + t / zs) / d : T(0)) + poison;
-            const T zu = d * zs;
-            l1_side[(size_t)b * n + i] = ((wi > T(0) && !held) ? wi / (zu * zu) : T(0)) + poison;      // (curv)
-            l1_ubox[(size_t)b * n + i] = ubx;
-            y = ubx * rho;
-        }
-        P.lams[(size_t)b * 2 * n + i] = (-y > T(0)) ? -y : T(0);
-        P.lams[(size_t)b * 2 * n + n + i] = (y > T(0)) ? y : T(0);
+        lams_from_y(P.lams, (size_t)b, n, i, y);
     }
     for (int r = tid; r < m; r += nt) P.nus[(size_t)b * m + r] = V.nu[r] * V.E[r] + poison;
     if (tid == 0) P.rho_out[b] = rho;
@@ -1486,142 +1610,54 @@ __device__ __forceinline__ T admm_relax(const T xi, const T zp, const FwdParams<
 // z-update, residuals and dual of one element (:271-282).  The projection and the dual see xh; the primal residual of the
 // check stays x - z (the unrelaxed x, as in OSQP); at alpha == 1, xh - zn is r
 template <typename T> struct AdmmStep { T zn, r, s, un; };
-template <bool RELAX, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                    const T rho) {
+// With a separable term (TERM, `tr`: the element's thresholds) its prox stands between xh + u and the clamp; TermNone's is v itself
+template <bool RELAX, typename TERM, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_term_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                         const T rho, const typename TERM::template Regs<T> tr) {
     const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
-    T zn = xh + ui;
+    T zn = tr.prox(xh + ui);
     zn = tmin(tmax(zn, lb), ub);                             // (:273-276; an infinite bound is a no-op)
     const T r = xi - zn;
     return {zn, r, rho * (zn - zp), ui + (xh - zn)};
 }
-template <typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                 const T rho) {
-    if (P.relax) {
-        asm volatile("");
-        return admm_step_as<true>(P, xi, zp, ui, lb, ub, rho);
-    }
-    return admm_step_as<false>(P, xi, zp, ui, lb, ub, rho);
-}
 // ... for a kernel that decides on P.relax outside its iteration (k_admm_loop_split: one hot loop per value, so that the plain step's
-// loop is the code it was): the step as a tag -- plain, relaxed, or the run-time branch of admm_step
+// loop is the code it was): the step as a tag -- plain, relaxed, or a run-time branch on the uniform flag (see admm_relax)
 struct RelaxOff { static constexpr int kind = 0; };
 struct RelaxOn { static constexpr int kind = 1; };
 struct RelaxDyn { static constexpr int kind = 2; };
-template <typename TAG, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                     const T rho) {
-    if constexpr (TAG::kind == 2) return admm_step(P, xi, zp, ui, lb, ub, rho);
-    else return admm_step_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho);
+template <typename TAG, typename TERM, typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step_term_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                          const T rho, const typename TERM::template Regs<T> tr) {
+    if constexpr (TAG::kind == 2) {
+        if (P.relax) {
+            asm volatile("");
+            return admm_step_term_as<true, TERM>(P, xi, zp, ui, lb, ub, rho, tr);
+        }
+        return admm_step_term_as<false, TERM>(P, xi, zp, ui, lb, ub, rho, tr);
+    } else {
+        return admm_step_term_as<TAG::kind == 1, TERM>(P, xi, zp, ui, lb, ub, rho, tr);
+    }
 }
-// The step with an L1 term w |x - c| in the objective (lqp_boxqp_forward_l1): the prox of the two separable terms is "soft-threshold
-// around cs, then clamp", t = ws / rho with the rho of this iteration; r, s, u are the lines of admm_step_as.  The branch form of
-// l1_shrink returns v itself at t = 0: w = 0 gives the plain step's bits.  A compile-time choice (Form*::l1 below), never a run-time flag.
-//
-// The FORM of a loop kernel: the five ways a solve runs its loop, one tag each -- every loop family (admm_loop_body, admm_loop_small_body,
+// the plain step of a kernel without forms (lqp_dense.hpp)
+template <typename T>
+__device__ __forceinline__ AdmmStep<T> admm_step(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
+                                                 const T rho) {
+    return admm_step_term_tag<RelaxDyn, TermNone>(P, xi, zp, ui, lb, ub, rho, {});
+}
+// The FORM of a loop kernel: the ways a solve runs its loop, one tag each -- every loop family (admm_loop_body, admm_loop_small_body,
 // admm_loop_split_body) has an instance per form it supports, named by the tag (k_admm_loop<..., lqp::FormEach>), and the host's
 // LoopForm / by_form (lqp_amd.hip) is the run-time twin.  A combination that is no form cannot be written.
 //   each:   control['stop'] = 'each' -- every problem stops and adapts rho as a batch of one
 //   detect: ... with the primal infeasibility certificate at every check (control['infeasible'])
 //   dual:   ... and the dual certificate beside it (control['unbounded'])
-//   l1:     lqp_boxqp_forward_l1 -- the element-wise step with the L1 term; the batch stops as one
-//   soft:   lqp_boxqp_forward_soft -- the element-wise step with the soft band (admm_step_soft_as); the batch stops as one
-//   barrier: lqp_boxqp_forward_log -- the element-wise step with the log barrier (admm_step_log_as); the batch stops as one
-struct FormAll     { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = false, barrier = false; };
-struct FormEach    { static constexpr bool each = true,  detect = false, dual = false, l1 = false, soft = false, barrier = false; };
-struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false, l1 = false, soft = false, barrier = false; };
-struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true,  l1 = false, soft = false, barrier = false; };
-struct FormL1      { static constexpr bool each = false, detect = false, dual = false, l1 = true,  soft = false, barrier = false; };
-struct FormSoft    { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = true, barrier = false; };
-struct FormLog     { static constexpr bool each = false, detect = false, dual = false, l1 = false, soft = false, barrier = true; };
-// what a thread of the streaming loop keeps of the L1 data (nothing at all in an instance without the L1 step)
-template <typename T, bool ON> struct L1Own {};
-template <typename T> struct L1Own<T, true> { T t0 = T(0), c0 = T(0); const T *t = nullptr, *cs = nullptr; };
-// ... and of the soft band: thresholds and kinks of its first element in registers, those of further elements in the workspace
-template <typename T, bool ON> struct SoftOwn {};
-template <typename T> struct SoftOwn<T, true> {
-    T tl0 = T(0), tu0 = T(0), lo0 = T(0), hi0 = T(0);
-    const T *tl = nullptr, *tu = nullptr, *los = nullptr, *his = nullptr;
-    __device__ __forceinline__ T prox(const T v, const int i, const int tid) const {
-        return i == tid ? soft_prox(v, tl0, tu0, lo0, hi0) : soft_prox(v, tl[i], tu[i], los[i], his[i]);
-    }
-};
-// ... and of the log barrier: the threshold t = ws / rho of its first element in a register, those of further elements in the workspace
-template <typename T, bool ON> struct LogOwn {};
-template <typename T> struct LogOwn<T, true> {
-    T t0 = T(0);
-    const T* t = nullptr;
-    __device__ __forceinline__ T prox(const T v, const int i, const int tid) const { return log_prox(v, i == tid ? t0 : t[i]); }
-};
-template <bool RELAX, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_l1_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                       const T rho, const T t, const T cs) {
-    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
-    const T zn = tmin(tmax(l1_shrink(xh + ui, t, cs), lb), ub);
-    const T r = xi - zn;
-    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
-}
-template <typename TAG, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_l1_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                        const T rho, const T t, const T cs) {
-    if constexpr (TAG::kind == 2) {
-        if (P.relax) {
-            asm volatile("");
-            return admm_step_l1_as<true>(P, xi, zp, ui, lb, ub, rho, t, cs);
-        }
-        return admm_step_l1_as<false>(P, xi, zp, ui, lb, ub, rho, t, cs);
-    } else {
-        return admm_step_l1_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, t, cs);
-    }
-}
-// The step with the soft band wl (lo - x)_+ + wu (x - hi)_+ (lqp_boxqp_forward_soft): the prox of the band in the scaled space (soft_prox:
-// two thresholds tl = wls / rho, tu = wus / rho, two kinks los <= his), then the clamp; r, s, u are the lines of admm_step_as.  Zero
-// weights return v itself: the plain step's bits.  los == his with tl == tu is l1_shrink, bit for bit.
-template <bool RELAX, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_soft_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                         const T rho, const T tl, const T tu, const T los, const T his) {
-    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
-    const T zn = tmin(tmax(soft_prox(xh + ui, tl, tu, los, his), lb), ub);
-    const T r = xi - zn;
-    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
-}
-template <typename TAG, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_soft_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                          const T rho, const T tl, const T tu, const T los, const T his) {
-    if constexpr (TAG::kind == 2) {
-        if (P.relax) {
-            asm volatile("");
-            return admm_step_soft_as<true>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
-        }
-        return admm_step_soft_as<false>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
-    } else {
-        return admm_step_soft_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, tl, tu, los, his);
-    }
-}
-// The step with the log barrier -w log(x) (lqp_boxqp_forward_log): log_prox with t = ws / rho in the scaled space, then the clamp; r, s,
-// u are the lines of admm_step_as.  A zero weight returns v itself: the plain step's bits.
-template <bool RELAX, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_log_as(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                        const T rho, const T t) {
-    const T xh = RELAX ? P.alpha * xi + P.alpha_c * zp : xi;
-    const T zn = tmin(tmax(log_prox(xh + ui, t), lb), ub);
-    const T r = xi - zn;
-    return {zn, r, rho * (zn - zp), ui + (xh - zn)};
-}
-template <typename TAG, typename T>
-__device__ __forceinline__ AdmmStep<T> admm_step_log_tag(const FwdParams<T>& P, const T xi, const T zp, const T ui, const T lb, const T ub,
-                                                         const T rho, const T t) {
-    if constexpr (TAG::kind == 2) {
-        if (P.relax) {
-            asm volatile("");
-            return admm_step_log_as<true>(P, xi, zp, ui, lb, ub, rho, t);
-        }
-        return admm_step_log_as<false>(P, xi, zp, ui, lb, ub, rho, t);
-    } else {
-        return admm_step_log_as<TAG::kind == 1>(P, xi, zp, ui, lb, ub, rho, t);
-    }
-}
+//   term:   the separable term whose prox the element-wise step takes (lqp_boxqp_forward_l1 / _soft / _log); the batch stops as one
+struct FormAll     { static constexpr bool each = false, detect = false, dual = false; using term = TermNone; };
+struct FormEach    { static constexpr bool each = true,  detect = false, dual = false; using term = TermNone; };
+struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false; using term = TermNone; };
+struct FormCertify { static constexpr bool each = true,  detect = true,  dual = true;  using term = TermNone; };
+struct FormL1      { static constexpr bool each = false, detect = false, dual = false; using term = TermL1; };
+struct FormSoft    { static constexpr bool each = false, detect = false, dual = false; using term = TermSoft; };
+struct FormLog     { static constexpr bool each = false, detect = false, dual = false; using term = TermLog; };
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
 // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu without touching Q -- it only feeds a tolerance SCALE; the
 // caller forms it from wherever its w, As and nu live.  ACC: the thread owns several elements (fold) or one (assign).
@@ -1906,9 +1942,7 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
 // its registers cost the plain EACH kernels 3 % of their time
 // DUAL (control['unbounded']): the dual certificate too, instances of their own again (FormCertify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
-// L1: the element-wise step, see admm_step_l1_as -- lqp_boxqp_forward_l1's kernels are instances of their own
-// SOFT: the same for the soft band, see admm_step_soft_as -- lqp_boxqp_forward_soft's instances
-// LOG: the same for the log barrier, see admm_step_log_as -- lqp_boxqp_forward_log's instances
+// FORM::term: the separable term of the element-wise step (TermOwn) -- the kernels of lqp_boxqp_forward_l1 / _soft / _log are instances of their own
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
@@ -1925,7 +1959,8 @@ __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int 
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int it0, const int it1, int ctr_base, int prev_slot,
                                                     const int persistent, char* smem) {
-    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1, SOFT = FORM::soft, LOG = FORM::barrier;      // (static: never a lambda's capture)
+    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual;      // (static: never a lambda's capture)
+    using TERM = typename FORM::term;
     static_assert(NP == 1 || (NP == 2 && SYM && RES && !TAIL && NT == 1024 && sizeof(T) == 4), "two workgroups per problem: the hot symmetric loop only");
     static_assert(!EACH || NP == 1, "per-problem stopping on the streaming loop: one workgroup per problem (the split loop has its own EACH form)");
     int b = blockIdx.x, part_id = 0;
@@ -2071,32 +2106,9 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
         z[i] = V.z[i]; u[i] = V.u[i]; ps[i] = V.ps[i]; lb[i] = V.lbs[i]; ub[i] = V.ubs[i]; D[i] = V.D[i];
     }
     for (int r = tid; r < m; r += NT) bs[r] = V.bs[r];
-    // L1: t = ws / rho with this segment's rho (a division per element and rho, none per iteration).  A thread keeps t and cs of
-    // its first element in registers; those of its further elements (n > NT only) come from the workspace, where it stores their t
-    // itself here -- nothing is stored for the first (both workgroups of a shared problem would write the same values)
-    L1Own<T, L1> l1o;
-    if constexpr (L1) {
-        const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
-        for (int i = tid + NT; i < n; i += NT) W.t[i] = W.ws[i] / rho;
-        if (tid < n) { l1o.t0 = W.ws[tid] / rho; l1o.c0 = W.cs[tid]; }
-        l1o.t = W.t; l1o.cs = W.cs;
-    }
-    // SOFT: the same with two thresholds and two kinks per element
-    SoftOwn<T, SOFT> sfo;
-    if constexpr (SOFT) {
-        const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
-        for (int i = tid + NT; i < n; i += NT) { W.tl[i] = W.wls[i] / rho; W.tu[i] = W.wus[i] / rho; }
-        if (tid < n) { sfo.tl0 = W.wls[tid] / rho; sfo.tu0 = W.wus[tid] / rho; sfo.lo0 = W.los[tid]; sfo.hi0 = W.his[tid]; }
-        sfo.tl = W.tl; sfo.tu = W.tu; sfo.los = W.los; sfo.his = W.his;
-    }
-    // LOG: the same with one threshold per element
-    LogOwn<T, LOG> lgo;
-    if constexpr (LOG) {
-        const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
-        for (int i = tid + NT; i < n; i += NT) W.t[i] = W.ws[i] / rho;
-        if (tid < n) lgo.t0 = W.ws[tid] / rho;
-        lgo.t = W.t;
-    }
+    // the term's thresholds = weights / rho with this segment's rho (a division per element and rho, none per iteration)
+    TermOwn<T, TERM> own;
+    if constexpr (TERM::kind != 0) own.template prime<NT>(P.termv + (size_t)b * term_stride<TERM>(n), n, tid, rho);
     if constexpr (SYM) {
         for (int i = tid; i < Nps; i += NT) cvl[i] = (i < n && m > 0) ? V.cv[i] : T(0);
         if constexpr (NP == 2) {       // (every slot / column sum of the range is written by every product; zeroed once all the same)
@@ -2208,9 +2220,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                     const T ui = u[i];
                     const T xh = admm_relax(xi, zp, P);      // (the lines of admm_step)
                     T zn = xh + ui;
-                    if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
-                    if constexpr (SOFT) zn = sfo.prox(zn, i, tid);
-                    if constexpr (LOG) zn = lgo.prox(zn, i, tid);
+                    if constexpr (TERM::kind != 0) zn = own.prox(zn, i, tid);
                     zn = tmin(tmax(zn, lb[i]), ub[i]);     // (:273-276; an infinite bound is a no-op)
                     const T r = xi - zn;
                     const T s = rho * (zn - zp);
@@ -2257,9 +2267,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
                 const T ui = u[i];
                 const T xh = admm_relax(xi, zp, P);          // (the lines of admm_step)
                 T zn = xh + ui;
-                if constexpr (L1) zn = l1_shrink(zn, i == tid ? l1o.t0 : l1o.t[i], i == tid ? l1o.c0 : l1o.cs[i]);
-                if constexpr (SOFT) zn = sfo.prox(zn, i, tid);
-                if constexpr (LOG) zn = lgo.prox(zn, i, tid);
+                if constexpr (TERM::kind != 0) zn = own.prox(zn, i, tid);
                 zn = tmin(tmax(zn, lb[i]), ub[i]);
                 const T r = xi - zn;
                 const T s = rho * (zn - zp);
@@ -2393,7 +2401,7 @@ __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P
 
 // The one-workgroup loop in every form.  persistent & 4 (continuation launches, FormAll): this is the forward's LAST launch -- it ends
 // with the epilogue (fwd_finish).  No other form ever is the last launch: under stop = 'each' the workgroups leave at different times,
-// and the L1, soft and log epilogues take two more outputs (k_fwd_epilogue_l1, k_fwd_epilogue_soft, k_fwd_epilogue_log) -- a launch of its own for all.
+// and a term's epilogue takes two more outputs (k_fwd_epilogue<T, TERM>) -- a launch of its own for all.
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, typename FORM>
 __global__ __launch_bounds__(NT) void k_admm_loop(const FwdParams<T> P, const int it0, const int it1, const int ctr_base,
                                                   const int prev_slot, const int persistent) {
@@ -2519,79 +2527,24 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_fwd_epilogue(const FwdParams<T> P) {
     fwd_finish(P, blockIdx.x);
 }
-template <typename T>
-__global__ __launch_bounds__(256) void k_fwd_epilogue_l1(const FwdParams<T> P, T* __restrict__ side, T* __restrict__ u_box) {
-    fwd_finish<T, true>(P, blockIdx.x, side, u_box);
+// ... of a solve with a separable term: the term's two outputs beside (an overload: the plain kernel keeps its name)
+template <typename T, typename TERM>
+__global__ __launch_bounds__(256) void k_fwd_epilogue(const FwdParams<T> P, T* __restrict__ aux, T* __restrict__ u_box) {
+    fwd_finish<T, TERM>(P, blockIdx.x, aux, u_box);
 }
-template <typename T>
-__global__ __launch_bounds__(256) void k_fwd_epilogue_soft(const FwdParams<T> P, T* __restrict__ zone, T* __restrict__ u_box) {
-    fwd_finish<T, false, true>(P, blockIdx.x, zone, u_box);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void k_fwd_epilogue_log(const FwdParams<T> P, T* __restrict__ curv, T* __restrict__ u_box) {
-    fwd_finish<T, false, false, true>(P, blockIdx.x, curv, u_box);
-}
-// lqp_boxqp_forward_l1, behind the prologue (the scaling vector exists whichever kernel made it): ws = D w, cs = c / D next to
-// lbs / ubs' problem, and the input checks that need the data -- a weight that is negative or not finite, or a rho of the problem
-// (a per-problem rho_in among them) that is not positive and finite: t = ws / rho would be no threshold -- mark the problem
-// (RP_L1_INPUT: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
-template <typename T>
-__global__ __launch_bounds__(256) void k_l1_setup(const FwdParams<T> P, const T* __restrict__ w, const T* __restrict__ c) {
+// A solve with a separable term, behind the prologue (the scaling vector exists whichever kernel made it): the term's scaled inputs
+// into its area, next to lbs / ubs' problem, and the input checks that need the data -- what the term's setup_elem refuses, or a rho
+// of the problem (a per-problem rho_in among them) that is not positive and finite: weight / rho would be no threshold -- mark the
+// problem (TERM::input_flag: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
+template <typename T, typename TERM>
+__global__ __launch_bounds__(256) void k_term_setup(const FwdParams<T> P, const TermIn<T> in) {
     const int b = blockIdx.x, n = P.n, tid = threadIdx.x;
     VecView<T> V(P.vecs + (size_t)b * P.vstride, n, P.m);
-    const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
-    const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
-    bool badw = !(rho > T(0) && rho < T(INFINITY));
-    for (int i = tid; i < n; i += 256) {
-        const T wi = w[(size_t)b * n + i], di = V.D[i];
-        badw |= !(wi >= T(0) && wi < T(INFINITY));            // (NaN fails the first comparison)
-        W.ws[i] = di * wi;
-        W.cs[i] = c[(size_t)b * n + i] / di;
-    }
-    if (__syncthreads_or(badw ? 1 : 0) && tid == 0) P.bflags[b] |= RP_L1_INPUT;
-}
-
-// lqp_boxqp_forward_soft, at the same place: wls = D wl, wus = D wu, los = lo / D, his = hi / D (an infinite kink stays infinite), and the
-// input checks that need the data -- a weight that is negative or not finite, lo > hi, a NaN in lo or hi, or a rho of the problem that
-// is not positive and finite -- mark the problem (RP_SOFT_INPUT: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
-template <typename T>
-__global__ __launch_bounds__(256) void k_soft_setup(const FwdParams<T> P, const T* __restrict__ wl, const T* __restrict__ wu,
-                                                    const T* __restrict__ lo, const T* __restrict__ hi) {
-    const int b = blockIdx.x, n = P.n, tid = threadIdx.x;
-    VecView<T> V(P.vecs + (size_t)b * P.vstride, n, P.m);
-    const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
+    T* const area = P.termv + (size_t)b * term_stride<TERM>(n);
     const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
     bool bad = !(rho > T(0) && rho < T(INFINITY));
-    for (int i = tid; i < n; i += 256) {
-        const size_t g = (size_t)b * n + i;
-        const T wli = wl[g], wui = wu[g], loi = lo[g], hii = hi[g], di = V.D[i];
-        bad |= !(wli >= T(0) && wli < T(INFINITY)) || !(wui >= T(0) && wui < T(INFINITY));      // (NaN fails the first comparison)
-        bad |= !(loi <= hii);                                  // (lo > hi, or a NaN in either)
-        W.wls[i] = di * wli;
-        W.wus[i] = di * wui;
-        W.los[i] = loi / di;
-        W.his[i] = hii / di;
-    }
-    if (__syncthreads_or(bad ? 1 : 0) && tid == 0) P.bflags[b] |= RP_SOFT_INPUT;
-}
-
-// lqp_boxqp_forward_log, at the same place: ws = w (no D: see LogView), and the input checks that need the data -- a weight that is
-// negative or not finite, a barrier element whose upper bound is not positive (the domain is empty), or a rho of the problem that is
-// not positive and finite -- mark the problem (RP_LOG_INPUT: NaN outputs, LQP_ERR_INVALID from whoever reads the report)
-template <typename T>
-__global__ __launch_bounds__(256) void k_log_setup(const FwdParams<T> P, const T* __restrict__ w) {
-    const int b = blockIdx.x, n = P.n, tid = threadIdx.x;
-    const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
-    const T rho = P.scal[(size_t)b * SC_WORDS + SC_RHO];
-    bool bad = !(rho > T(0) && rho < T(INFINITY));
-    for (int i = tid; i < n; i += 256) {
-        const size_t g = (size_t)b * n + i;
-        const T wi = w[g];
-        bad |= !(wi >= T(0) && wi < T(INFINITY));      // (NaN fails the first comparison)
-        bad |= wi > T(0) && !(P.ub[g] > T(0));
-        W.ws[i] = wi;
-    }
-    if (__syncthreads_or(bad ? 1 : 0) && tid == 0) P.bflags[b] |= RP_LOG_INPUT;
+    for (int i = tid; i < n; i += 256) bad |= TERM::setup_elem(area, n, i, in, (size_t)b * n + i, V.D, P.ub);
+    if (__syncthreads_or(bad ? 1 : 0) && tid == 0) P.bflags[b] |= TERM::input_flag;
 }
 
 // ---------------------------------------------------------------------------
@@ -3395,9 +3348,7 @@ __global__ __launch_bounds__(256) void k_l1_effective_box(const T* __restrict__ 
     lb_e[i] = K ? c[i] : lb[i];
     ub_e[i] = K ? c[i] : ub[i];
     u_e[i] = ue;
-    const T y = (rho_in ? rho_in[b] : rho_value) * ue;
-    lams_e[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
-    lams_e[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+    lams_from_y(lams_e, b, n, e, (rho_in ? rho_in[b] : rho_value) * ue);
 }
 // ... and what the effective box's gradients mean for the eight inputs: on K both bounds were c (dc = dlb_e + dub_e, nothing for
 // lb and ub), elsewhere they were the bounds; dw = side * dp.  Outputs may be null; dlb / dub may be dlb_e / dub_e themselves.
@@ -3435,9 +3386,7 @@ __global__ __launch_bounds__(256) void k_soft_effective_box(const T* __restrict_
     lb_e[i] = K ? kv : lb[i];
     ub_e[i] = K ? kv : ub[i];
     u_e[i] = ue;
-    const T y = (rho_in ? rho_in[b] : rho_value) * ue;
-    lams_e[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
-    lams_e[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+    lams_from_y(lams_e, b, n, e, (rho_in ? rho_in[b] : rho_value) * ue);
 }
 // ... and the ten inputs' gradients from the effective box's: on a kink both bounds were the kink (its gradient dlb_e + dub_e, nothing
 // for lb and ub); dwu = dp on zone == +2, dwl = -dp on zone == -2.  Outputs may be null; dlb / dub may be dlb_e / dub_e themselves.
@@ -3470,9 +3419,7 @@ __global__ __launch_bounds__(256) void k_log_effective_duals(const T* __restrict
     const size_t b = i / n, e = i - b * n;
     const T ue = ubox[i];
     u_e[i] = ue;
-    const T y = (rho_in ? rho_in[b] : rho_value) * ue;
-    lams_e[b * 2 * n + e] = (-y > T(0)) ? -y : T(0);
-    lams_e[b * 2 * n + n + e] = (y > T(0)) ? y : T(0);
+    lams_from_y(lams_e, b, n, e, (rho_in ? rho_in[b] : rho_value) * ue);
 }
 // ... and dw from dp: the term's gradient is -w_i / x_i, so dw_i = -dp_i / z_i where w_i > 0, else 0 (at w_i = 0 the one-sided
 // derivative is not defined when x_i <= 0: the convention of the header)

@@ -15,18 +15,17 @@ namespace lqp {
 // LDS: w[128] | y[128] | nus[m] | red[4 * 8 + 8]
 // ---------------------------------------------------------------------------
 __host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 + (m > 0 ? m : 1) + 4 * 8 + 8 + 8) * 4; }
-// FORM (FormAll ... FormLog), read as EACH, DETECT, DUAL, L1, SOFT and LOG below:
+// FORM (FormAll ... FormLog), read as EACH, DETECT, DUAL and TERM below:
 // EACH (control['stop'] = 'each'): the problem's own verdict ends its workgroup; no arrival word, no grid_wait
 // DETECT (control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
 // check iterations, and the certificate's registers in it cost the plain EACH kernel 12 % of its time
 // DUAL (control['unbounded']): the dual certificate too
-// L1 (lqp_boxqp_forward_l1): the element-wise step with the L1 term; keeps t = ws / rho and cs beside lb / ub
-// SOFT (lqp_boxqp_forward_soft): the element-wise step with the soft band; keeps tl, tu, los, his beside lb / ub
-// LOG (lqp_boxqp_forward_log): the element-wise step with the log barrier; keeps t = ws / rho beside lb / ub
+// FORM::term (lqp_boxqp_forward_l1 / _soft / _log): the element-wise step with the separable term; keeps its thresholds beside lb / ub
 template <typename FORM>
 __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                      char* smem) {
-    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual, L1 = FORM::l1, SOFT = FORM::soft, LOG = FORM::barrier;      // (static: never a lambda's capture)
+    static constexpr bool EACH = FORM::each, DETECT = FORM::detect, DUAL = FORM::dual;      // (static: never a lambda's capture)
+    using TERM = typename FORM::term;
     typedef float T;
     constexpr int NT = 256;
     const int b = blockIdx.x, n = P.n, m = P.m, Ks = P.Ks;
@@ -79,21 +78,8 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
     T zi = live ? V.z[e] : T(0), ui = live ? V.u[e] : T(0);
     const T psi = live ? V.ps[e] : T(0), lbi = live ? V.lbs[e] : T(0), ubi = live ? V.ubs[e] : T(0);
     const T di = live ? V.D[e] : T(1), cvi = (live && m > 0) ? V.cv[e] : T(0);
-    T l1t = T(0), l1c = T(0);           // (L1; rho is this launch's: an adaptive-rho event ends it)
-    if constexpr (L1) {
-        const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
-        if (live) { l1t = W.ws[e] / rho; l1c = W.cs[e]; }
-    }
-    T sftl = T(0), sftu = T(0), sflo = T(0), sfhi = T(0);           // (SOFT)
-    if constexpr (SOFT) {
-        const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
-        if (live) { sftl = W.wls[e] / rho; sftu = W.wus[e] / rho; sflo = W.los[e]; sfhi = W.his[e]; }
-    }
-    T lgt = T(0);           // (LOG)
-    if constexpr (LOG) {
-        const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
-        if (live) lgt = W.ws[e] / rho;
-    }
+    typename TERM::template Regs<T> tr;           // (the term's thresholds; rho is this launch's: an adaptive-rho event ends it)
+    if constexpr (TERM::kind != 0) { if (live) tr.load(P.termv + (size_t)b * term_stride<TERM>(n), n, e, rho); }
     T xi = T(0);
     if (tid < 128) { wv[tid] = live ? -psi + rho * (zi - ui) : T(0); }
     __syncthreads();
@@ -134,11 +120,7 @@ __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, c
         if (live) {
             const T wi = wv[e];
             xi = cvi - yv[e];
-            AdmmStep<T> sp;
-            if constexpr (L1) sp = admm_step_l1_tag<RelaxDyn>(P, xi, zi, ui, lbi, ubi, rho, l1t, l1c);
-            else if constexpr (SOFT) sp = admm_step_soft_tag<RelaxDyn>(P, xi, zi, ui, lbi, ubi, rho, sftl, sftu, sflo, sfhi);
-            else if constexpr (LOG) sp = admm_step_log_tag<RelaxDyn>(P, xi, zi, ui, lbi, ubi, rho, lgt);
-            else sp = admm_step(P, xi, zi, ui, lbi, ubi, rho);
+            const AdmmStep<T> sp = admm_step_term_tag<RelaxDyn, TERM>(P, xi, zi, ui, lbi, ubi, rho, tr);
             zi = sp.zn;
             ui = sp.un;
             if (check) {

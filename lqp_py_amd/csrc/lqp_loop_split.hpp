@@ -44,15 +44,15 @@ template <int NT, int NP = 2> __host__ __device__ inline int split_loop_lds_byte
 // launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop, FormEach ...) takes the problem's own decision.
 // (P by value: a reference to the kernel's parameter block costs the default's instances registers)
 // FORM: FormAll, FormEach (which takes the certificates from P.snap and P.eps_dinf at run time: it serves FormDetect and FormCertify
-// solves too) or FormL1 (lqp_boxqp_forward_l1: the element-wise step of every iteration form below with the L1 term; thread i
-// keeps t = ws_i / rho and cs_i in two registers beside its element -- rho is this launch's, an event that changes it ends the launch)
-// or FormSoft (lqp_boxqp_forward_soft: the same with the soft band's step; four registers, tl, tu, los, his)
-// or FormLog (lqp_boxqp_forward_log: the same with the log barrier's step; one register, t)
+// solves too) or a form with a separable term, FormL1 / FormSoft / FormLog (lqp_boxqp_forward_l1 / _soft / _log: the element-wise step
+// of every iteration form below with the term's prox; thread i keeps the term's Regs of its element, two / four / one registers -- rho
+// is this launch's, an event that changes it ends the launch)
 template <int KS, int NT, bool DBG, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, int it0, const int it1, int ctr_base, char* smem) {
     typedef float T;
     static_assert(!FORM::detect, "the split loop's per-problem form reads the certificates at run time: FormEach is its instance");
-    static constexpr bool EACH = FORM::each, L1 = FORM::l1, SOFT = FORM::soft, LOG = FORM::barrier;      // (static: never a lambda's capture -- a generic lambda would take a plain local by reference)
+    static constexpr bool EACH = FORM::each;      // (static: never a lambda's capture -- a generic lambda would take a plain local by reference)
+    using TERM = typename FORM::term;
     if (P.hot_resume) {            // (a later round of the hot loop: it goes on where the round before stopped)
         const int r = __builtin_amdgcn_readfirstlane(P.status[ST_RESUME]);
         if (r <= 0) return;
@@ -136,23 +136,10 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         yrow[i] = T(0);                                       // rows / columns of the partner stay zero
     }
     for (int r = tid; r < m; r += NT) bs[r] = V.bs[r];
-    T l1t = T(0), l1c = T(0);
-    if constexpr (L1) {
-        static_assert(NT >= KS * LQP_NB, "the L1 step: one element per thread");
-        const L1View<T> W(P.l1v + (size_t)b * l1_stride(n), n);
-        if (tid < n) { l1t = W.ws[tid] / rho; l1c = W.cs[tid]; }
-    }
-    T sftl = T(0), sftu = T(0), sflo = T(0), sfhi = T(0);
-    if constexpr (SOFT) {
-        static_assert(NT >= KS * LQP_NB, "the soft step: one element per thread");
-        const SoftView<T> W(P.l1v + (size_t)b * soft_stride(n), n);
-        if (tid < n) { sftl = W.wls[tid] / rho; sftu = W.wus[tid] / rho; sflo = W.los[tid]; sfhi = W.his[tid]; }
-    }
-    T lgt = T(0);
-    if constexpr (LOG) {
-        static_assert(NT >= KS * LQP_NB, "the log step: one element per thread");
-        const LogView<T> W(P.l1v + (size_t)b * log_stride(n), n);
-        if (tid < n) lgt = W.ws[tid] / rho;
+    typename TERM::template Regs<T> tr;
+    if constexpr (TERM::kind != 0) {
+        static_assert(NT >= KS * LQP_NB, "the step with a term: one element per thread");
+        if (tid < n) tr.load(P.termv + (size_t)b * term_stride<TERM>(n), n, tid, rho);
     }
     for (int i = tid; i < m * Nps; i += NT) { const int q = i / Nps, e = i - q * Nps; Asl[i] = e < n ? V.As[(size_t)q * n + e] : T(0); }
     for (int i = tid; i < NWV * Nps; i += NT) part[i] = T(0);
@@ -419,11 +406,7 @@ __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, i
         if (tid < Nps) {
             const int i = tid;
             xs[i] = xi;
-            AdmmStep<T> sp;
-            if constexpr (L1) sp = admm_step_l1_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho, l1t, l1c);
-            else if constexpr (SOFT) sp = admm_step_soft_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho, sftl, sftu, sflo, sfhi);
-            else if constexpr (LOG) sp = admm_step_log_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho, lgt);
-            else sp = admm_step_tag<decltype(relax_tag)>(P, xi, z[i], u[i], lb[i], ub[i], rho);
+            const AdmmStep<T> sp = admm_step_term_tag<decltype(relax_tag), TERM>(P, xi, z[i], u[i], lb[i], ub[i], rho, tr);
             const T zn = sp.zn, un = sp.un;
             const bool in = i < n;
             if (in) { z[i] = zn; u[i] = un; }

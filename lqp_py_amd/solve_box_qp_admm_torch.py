@@ -647,17 +647,9 @@ def _forward_decide(out, att, owner, look):
         # the reference's torch.linalg.lu_factor raises on an exactly singular KKT matrix (:215)
         return _Verdict(error=RuntimeError(f"lqp_py_amd.torch_solve_box_qp: LU factorisation hit an exactly zero pivot "
                                            f"(batch index {stats.fail_index}); the KKT matrix is singular"))
-    if st == 1 and getattr(out, 'l1', False):
-        # lqp_boxqp_forward_l1 alone: the one input check made on the device (every other cause of this status is refused in Python first)
-        return _Verdict(error=ValueError(f"lqp_py_amd: w must be finite and >= 0, and rho positive and finite (batch index {stats.fail_index})"))
-    if st == 1 and getattr(out, 'soft', False):
-        # lqp_boxqp_forward_soft alone: its input checks made on the device
-        return _Verdict(error=ValueError("lqp_py_amd: wl and wu must be finite and >= 0, lo <= hi without NaN, and rho positive and finite "
-                                         f"(batch index {stats.fail_index})"))
-    if st == 1 and getattr(out, 'log', False):
-        # lqp_boxqp_forward_log alone: its input checks made on the device
-        return _Verdict(error=ValueError("lqp_py_amd: w must be finite and >= 0, ub > 0 wherever w > 0, and rho positive and finite "
-                                         f"(batch index {stats.fail_index})"))
+    if st == 1 and getattr(out, 'term', None) is not None:
+        # a layer with a separable term alone: the input checks made on the device (every other cause of this status is refused in Python first)
+        return _Verdict(error=ValueError(f"lqp_py_amd: {out.term.device_check} (batch index {stats.fail_index})"))
     try:
         _lib.check(st, "torch_solve_box_qp")
     except RuntimeError as exc:
@@ -671,14 +663,13 @@ def _forward_decide(out, att, owner, look):
     return _Verdict(next=att._replace(bounds=(bool(stats.any_lb), bool(stats.any_ub)), one_call=False), release='tail', remember=seen)
 
 
-def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, l1=None, soft=None, log=None):
+def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, term=None):
     """One trip through the library on `att` (a _Try): settle the assumption, fetch the control struct, allocate, launch, make
     the views and run the caller's window while the GPU works, wait.  -> _Outcome, for _forward_decide to read.  What stands
     between entry and the first kernel launch is the forward time of a step that starts from an idle queue (experiment_1's
     protocol): errors of EARLIER calls are polled after this one is enqueued, the outputs are one allocation.
-    l1 = (w, c): lqp_boxqp_forward_l1 (lqp_py_amd/solve_box_qp_l1.py, which has refused what that entry point cannot run).
-    soft = (wl, wu, lo, hi): lqp_boxqp_forward_soft (lqp_py_amd/solve_box_qp_soft.py), the same way; its "zone" takes side's place.
-    log = (w,): lqp_boxqp_forward_log (lqp_py_amd/solve_box_qp_log.py), the same way; its "curv" takes side's place."""
+    term = (record, tensors): a layer with a separable term (lqp_py_amd/_terms.py, whose check_term has refused what those entry points
+    cannot run) -- the record's entry point, with the term's inputs behind ub and its two outputs behind rho_out."""
     Q, p, A, b, lb, ub = qp
     control, bounds, one_call = att
     lib, dev = _lib.load(), p.device
@@ -712,12 +703,11 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
     # hold x and Qs x too
     detect = each and r['infeasible'] is not None
     certify = each and r['unbounded'] is not None
-    ws_key = (dt, B, n, m, 'log') if log is not None else (dt, B, n, m, 'soft') if soft is not None else (dt, B, n, m, detect, certify) if l1 is None else (dt, B, n, m, 'l1')
+    rec, term_in = term if term is not None else (None, ())
+    ws_key = (dt, B, n, m, detect, certify) if rec is None else (dt, B, n, m, rec.entry)
     nbytes = _ws_bytes.get(ws_key)
     if nbytes is None:
-        size_of = (lib.lqp_boxqp_forward_log_workspace_bytes if log is not None else
-                   lib.lqp_boxqp_forward_soft_workspace_bytes if soft is not None else
-                   lib.lqp_boxqp_forward_l1_workspace_bytes if l1 is not None else
+        size_of = (getattr(lib, rec.size_of) if rec is not None else
                    lib.lqp_boxqp_forward_certify_workspace_bytes if certify else
                    lib.lqp_boxqp_forward_detect_workspace_bytes if detect else lib.lqp_boxqp_forward_workspace_bytes)
         nbytes = _ws_bytes[ws_key] = size_of(dt, B, n, m)
@@ -731,26 +721,15 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
             _lib.ptr(Qc), _lib.ptr(pc), _lib.ptr(Ac), _lib.ptr(bc), _lib.ptr(lbc), _lib.ptr(ubc),
             ctypes.byref(ctl), _lib.ptr(rho_tensor), *addresses,
             ctypes.byref(stats), _lib.ptr(ws), ws.numel())
-    side = u_box = None
-    if l1 is not None:
-        wc, cc = (_lib.norm(t, p.dtype) for t in l1)
-        side, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
-        l1_args = args[:11] + (_lib.ptr(wc), _lib.ptr(cc)) + args[11:19] + (_lib.ptr(side), _lib.ptr(u_box)) + args[19:]
-    if soft is not None:
-        sc = tuple(_lib.norm(t, p.dtype) for t in soft)
-        side, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
-        soft_args = args[:11] + tuple(_lib.ptr(t) for t in sc) + args[11:19] + (_lib.ptr(side), _lib.ptr(u_box)) + args[19:]
-    if log is not None:
-        wc = _lib.norm(log[0], p.dtype)
-        side, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
-        log_args = args[:11] + (_lib.ptr(wc),) + args[11:19] + (_lib.ptr(u_box), _lib.ptr(side)) + args[19:]
+    aux = u_box = None
+    if rec is not None:
+        tc = tuple(_lib.norm(t, p.dtype) for t in term_in)
+        aux, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
+        extra = dict(aux=_lib.ptr(aux), u_box=_lib.ptr(u_box))
+        term_args = args[:11] + tuple(_lib.ptr(t) for t in tc) + args[11:19] + tuple(extra[k] for k in rec.outputs) + args[19:]
     with _lib.on_device(dev):
-        if log is not None:
-            st = lib.lqp_boxqp_forward_log(*log_args)
-        elif soft is not None:
-            st = lib.lqp_boxqp_forward_soft(*soft_args)
-        elif l1 is not None:
-            st = lib.lqp_boxqp_forward_l1(*l1_args)
+        if rec is not None:
+            st = getattr(lib, rec.entry)(*term_args)
         elif certify:
             st = lib.lqp_boxqp_forward_certify(*args, float(r['eps_prim_inf']) if detect else 0.0, float(r['eps_dual_inf']))
         else:
@@ -776,8 +755,7 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
                                           ctypes.c_void_p(report.data_ptr()), ctypes.byref(stats))
     return _Outcome(status=st, split_wait=split_wait, stats=stats, hook_error=hook_error, any_bound=any_bound, known=known,
                     report=report, ws=ws, stream=stream, dims=(dt, B, n, m), r=r, rho=rho, rho_mode=ctl.rho_mode,
-                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out, iters=iters, pstatus=pstatus, l1=l1 is not None, side=side,
-                    u_box=u_box, soft=soft is not None, log=log is not None)
+                    x=x, z=z, u=u, lams=lams, nus=nus, rho_out=rho_out, iters=iters, pstatus=pstatus, term=rec, aux=aux, u_box=u_box)
 
 
 def _print_check_trace(out, dev):
@@ -811,8 +789,8 @@ def _solution(out, like, residuals):
     as_given = out.rho_mode == 1 and not stats.rho_updated and not (stats.mode_used == 3 and r['adaptive_rho'])
     rho_ret = out.rho if as_given else out.rho_out.view(B, 1, 1)     # (un-synchronised calls cannot know whether rho was adapted: tensor)
     sol = {"x": out.x, "z": out.z, "u": out.u, "lams": out.lams, "nus": out.nus, "rho": rho_ret, "iter": int(stats.iters)}
-    if getattr(out, 'side', None) is not None:      # lqp_boxqp_forward_l1: which side of c every element rests on, the box's share of u
-        sol["curv" if getattr(out, 'log', False) else "zone" if getattr(out, 'soft', False) else "side"], sol["u_box"] = out.side, out.u_box
+    if getattr(out, 'term', None) is not None:      # a separable term: where every element rests (side / zone / curv), the box's share of u
+        sol[out.term.aux], sol["u_box"] = out.aux, out.u_box
     if out.iters is not None:            # control['stop'] = 'each': every problem's own count; "iter" is the largest
         sol["iters"] = out.iters
         sol["status"] = out.pstatus      # (B,) int32: 0 optimal, 1 ended at max_iters, 2 primal infeasible (control['infeasible']), 3 dual infeasible (control['unbounded'])
@@ -830,7 +808,7 @@ def _solution(out, like, residuals):
 
 def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residuals=False, check_hook=None, mutate=False,
                    holder=None, private_ws=None, keep_factor=False, while_running=None, one_call=False, raise_infeasible=False,
-                   raise_unbounded=False, l1=None, soft=None, log=None):
+                   raise_unbounded=False, term=None):
     """bounds: (any_lb, any_ub) when the caller KNOWS them (a shard of a larger batch with host-side flags); None: found
     on the device.  mutate: apply the reference layer's dict side effect control['rho'] = 0 (:37-38).  holder: the
     nn.Module on whose behalf the call is made (keys what is remembered between calls, see _assume_any_bound).
@@ -845,7 +823,7 @@ def _forward_solve(Q, p, A, b, lb, ub, control, bounds=None, sync=True, residual
     owner = control.get('_owner') or control          # (lqp_py_amd.dist hands the layer a copy of the caller's dict)
     att, dev = _Try(control, bounds, one_call), p.device
     while True:
-        out = _forward_attempt((Q, p, A, b, lb, ub), att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, l1=l1, soft=soft, log=log)
+        out = _forward_attempt((Q, p, A, b, lb, ub), att, owner, sync, check_hook, holder, private_ws, keep_factor, while_running, term=term)
         v = _forward_decide(out, att, owner, lambda: _finite_bounds(lb, ub))
         if v.release == 'tail':
             try:

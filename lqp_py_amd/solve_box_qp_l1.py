@@ -11,48 +11,17 @@ The solve always takes the loop schedule: bounds that are all infinite are an or
 to, the rho = 0 one-shot is never chosen.  ``alpha``, ``sync=False``, ``linsolve``, ``launch_mode`` and per-problem ``rho`` /
 ``beta`` work as in the plain layer; what does not is refused by ``check_l1``.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 
 from . import _lib
+from . import _terms as _T
 from . import solve_box_qp_admm_torch as _S
-from .utils import get_ncon
 
 
 def check_l1(control, Q=None, p=None, w=None, c=None):
-    """What the L1 layer cannot be combined with, and the shapes and dtypes of w and c.  Raises the package's ValueError at the
-    call, before any launch; the one place that holds these rules (torch_solve_box_qp_l1 and SolveBoxQPL1 both come here)."""
-    if control.get('stop', 'all') != 'all':
-        _S._bad("the L1 layer has no per-problem stop: control['stop'] = 'each' cannot be combined with it")
-    for key in ('infeasible', 'unbounded'):
-        if control.get(key) is not None:
-            _S._bad(f"control['{key}'] cannot be combined with the L1 layer: the certificates belong to the per-problem stop")
-    if control.get('unroll', False):
-        _S._bad("unroll=True cannot be combined with the L1 layer: the tape replays the plain step")
-    if control.get('backward', 'fixed_point') == 'kkt':
-        _S._bad("control['backward'] = 'kkt' cannot be combined with the L1 layer: its backward is the fixed-point form on the effective box")
-    if any(control.get(k) is not None for k in ('_global_bounds', '_bound_flags_dev', '_check_hook', '_owner')) or \
-            control.get('dist_strict_stop', False):
-        _S._bad("the sharded wrapper (lqp_py_amd.dist) does not carry the L1 layer")
-    rho = control.get('rho')
-    if rho is not None and not torch.is_tensor(rho) and not float(rho) > 0.0:
-        _S._bad("control['rho'] must be positive (or None) for the L1 layer: it always iterates")
-    if p is None:
-        return
-    for name, t in (('w', w), ('c', c)):
-        if not torch.is_tensor(t) or tuple(t.shape) != tuple(p.shape):
-            _S._bad(f"{name} must be a tensor of p's shape {tuple(p.shape)}")
-        if t.dtype != p.dtype:
-            _S._bad(f"{name} must have p's dtype {p.dtype}, got {t.dtype}")
-
-
-def _solve(Q, p, A, b, lb, ub, w, c, control, sync=True):
-    check_l1(control, Q, p, w, c)
-    _lib.require_gpu(w, c)
-    # (bounds known = "some bound is finite": the loop schedule whatever the data hold; nothing is assumed, compared or remembered)
-    return _S._forward_solve(Q, p, A, b, lb, ub, control, bounds=(True, True), sync=sync, l1=(w, c))
+    """What the L1 layer cannot be combined with, and the shapes and dtypes of w and c (``_terms.check_term``)."""
+    _T.check_term(_T.L1, control, p, (w, c))
 
 
 def torch_solve_box_qp_l1(Q, p, A, b, lb, ub, w, c, control):
@@ -60,7 +29,7 @@ def torch_solve_box_qp_l1(Q, p, A, b, lb, ub, w, c, control):
       "side"   (B,n,1): +1 / -1 where x_i rests above / below c_i or is pushed there by a bound, 0 exactly on the kink x_i = c_i
       "u_box"  (B,n,1): the box's share of the dual u -- zero unless the element is clamped at a bound;
     "lams" is built from u_box (the rest of u is the L1 term's multiplier, |rho (u - u_box)| <= w)."""
-    return _solve(Q, p, A, b, lb, ub, w, c, control)
+    return _T.solve(_T.L1, (Q, p, A, b, lb, ub), (w, c), control)
 
 
 class SolveBoxQPL1(nn.Module):
@@ -84,35 +53,25 @@ class SolveBoxQPL1Layer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Q, p, A, b, lb, ub, w, c, control):
-        sync = bool(control.get('sync', True))
-        sol = _solve(Q, p, A, b, lb, ub, w, c, control, sync=sync)
-        ctx.rho, ctx.sync = sol['rho'], sync
-        ctx.linsolve = int(sol['_stats']['linsolve_used'])
-        ctx.save_for_backward(sol['x'], sol['u'], sol['u_box'], sol['side'], sol['nus'], Q, A, lb, ub, c)
-        return sol['x']
+        return _T.layer_forward(ctx, _T.L1, (Q, p, A, b, lb, ub), (w, c), control, ('x', 'u', 'u_box', 'side', 'nus'), (Q, A, lb, ub, c))
 
     @staticmethod
     def backward(ctx, dl_dz):
         x, u, u_box, side, nus, Q, A, lb, ub, c = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        lib, B, n = _lib.load(), Q.shape[0], Q.shape[1]
-        dt, dev, dty = _lib.dtype_code(x), x.device, x.dtype
-        stream = ctypes.c_void_p(_lib.current_stream_handle(dev))
-        rho_mode, rho_value, rho_tensor = _S._per_problem_argument('rho', '(B,1,1)', ctx.rho, B, x)
-        lbc, ubc, cc = (_lib.norm(t, dty) for t in (lb, ub, c))
-        lb_e, ub_e, u_e = (torch.empty((B, n, 1), dtype=dty, device=dev) for _ in range(3))
-        lams_e = torch.empty((B, 2 * n, 1), dtype=dty, device=dev)
-        with _lib.on_device(dev):
-            _lib.check(lib.lqp_boxqp_l1_effective_box(stream, dt, B, n, _lib.ptr(side), _lib.ptr(u), _lib.ptr(u_box), _lib.ptr(lbc),
-                                                      _lib.ptr(ubc), _lib.ptr(cc), rho_mode, rho_value, _lib.ptr(rho_tensor),
+        h = _T.backward_prelude(ctx, x, Q, A, box_grads=True)
+        need, lib, B, n = h.need, h.lib, h.B, h.n
+        lbc, ubc, cc = (_lib.norm(t, h.dty) for t in (lb, ub, c))
+        lb_e, ub_e, u_e = (torch.empty((B, n, 1), dtype=h.dty, device=h.dev) for _ in range(3))
+        lams_e = torch.empty((B, 2 * n, 1), dtype=h.dty, device=h.dev)
+        with _lib.on_device(h.dev):
+            _lib.check(lib.lqp_boxqp_l1_effective_box(h.stream, h.dt, B, n, _lib.ptr(side), _lib.ptr(u), _lib.ptr(u_box), _lib.ptr(lbc),
+                                                      _lib.ptr(ubc), _lib.ptr(cc), h.rho_mode, h.rho_value, _lib.ptr(h.rho_tensor),
                                                       _lib.ptr(lb_e), _lib.ptr(ub_e), _lib.ptr(u_e), _lib.ptr(lams_e)), "l1_effective_box")
-        has_eq = get_ncon(A, dim=1) > 0
-        want = dict(dQ=need[0], dp=True, dA=need[2] and has_eq, db=need[3] and has_eq, dlb=True, dub=True)
-        dQ, dp, dA, db, dlb, dub, _ = _S._fp_backward(dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, ctx.rho, want, sync=ctx.sync,
+        dQ, dp, dA, db, dlb, dub, _ = _S._fp_backward(dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, ctx.rho, h.want, sync=ctx.sync,
                                                       linsolve=ctx.linsolve)
         dc = torch.empty_like(dp) if need[7] else None
         dw = torch.empty_like(dp) if need[6] else None
-        with _lib.on_device(dev):
-            _lib.check(lib.lqp_boxqp_l1_finish_grads(stream, dt, B, n, _lib.ptr(side), _lib.ptr(dp), _lib.ptr(dlb), _lib.ptr(dub),
+        with _lib.on_device(h.dev):
+            _lib.check(lib.lqp_boxqp_l1_finish_grads(h.stream, h.dt, B, n, _lib.ptr(side), _lib.ptr(dp), _lib.ptr(dlb), _lib.ptr(dub),
                                                      _lib.ptr(dlb), _lib.ptr(dub), _lib.ptr(dc), _lib.ptr(dw)), "l1_finish_grads")
         return (dQ, dp if need[1] else None, dA, db, dlb if need[4] else None, dub if need[5] else None, dw, dc, None)

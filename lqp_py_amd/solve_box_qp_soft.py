@@ -13,48 +13,17 @@ The solve always takes the loop schedule: bounds that are all infinite are an or
 to, the rho = 0 one-shot is never chosen.  ``alpha``, ``sync=False``, ``linsolve``, ``launch_mode`` and per-problem ``rho`` /
 ``beta`` work as in the plain layer; what does not is refused by ``check_soft``.
 """
-import ctypes
-
 import torch
 import torch.nn as nn
 
 from . import _lib
+from . import _terms as _T
 from . import solve_box_qp_admm_torch as _S
-from .utils import get_ncon
 
 
 def check_soft(control, Q=None, p=None, wl=None, wu=None, lo=None, hi=None):
-    """What the soft-band layer cannot be combined with, and the shapes and dtypes of wl, wu, lo and hi.  Raises the package's
-    ValueError at the call, before any launch; the one place that holds these rules."""
-    if control.get('stop', 'all') != 'all':
-        _S._bad("the soft-band layer has no per-problem stop: control['stop'] = 'each' cannot be combined with it")
-    for key in ('infeasible', 'unbounded'):
-        if control.get(key) is not None:
-            _S._bad(f"control['{key}'] cannot be combined with the soft-band layer: the certificates belong to the per-problem stop")
-    if control.get('unroll', False):
-        _S._bad("unroll=True cannot be combined with the soft-band layer: the tape replays the plain step")
-    if control.get('backward', 'fixed_point') == 'kkt':
-        _S._bad("control['backward'] = 'kkt' cannot be combined with the soft-band layer: its backward is the fixed-point form on the effective box")
-    if any(control.get(k) is not None for k in ('_global_bounds', '_bound_flags_dev', '_check_hook', '_owner')) or \
-            control.get('dist_strict_stop', False):
-        _S._bad("the sharded wrapper (lqp_py_amd.dist) does not carry the soft-band layer")
-    rho = control.get('rho')
-    if rho is not None and not torch.is_tensor(rho) and not float(rho) > 0.0:
-        _S._bad("control['rho'] must be positive (or None) for the soft-band layer: it always iterates")
-    if p is None:
-        return
-    for name, t in (('wl', wl), ('wu', wu), ('lo', lo), ('hi', hi)):
-        if not torch.is_tensor(t) or tuple(t.shape) != tuple(p.shape):
-            _S._bad(f"{name} must be a tensor of p's shape {tuple(p.shape)}")
-        if t.dtype != p.dtype:
-            _S._bad(f"{name} must have p's dtype {p.dtype}, got {t.dtype}")
-
-
-def _solve(Q, p, A, b, lb, ub, wl, wu, lo, hi, control, sync=True):
-    check_soft(control, Q, p, wl, wu, lo, hi)
-    _lib.require_gpu(wl, wu, lo, hi)
-    # (bounds known = "some bound is finite": the loop schedule whatever the data hold; nothing is assumed, compared or remembered)
-    return _S._forward_solve(Q, p, A, b, lb, ub, control, bounds=(True, True), sync=sync, soft=(wl, wu, lo, hi))
+    """What the soft-band layer cannot be combined with, and the shapes and dtypes of wl, wu, lo and hi (``_terms.check_term``)."""
+    _T.check_term(_T.SOFT, control, p, (wl, wu, lo, hi))
 
 
 def torch_solve_box_qp_soft(Q, p, A, b, lb, ub, wl, wu, lo, hi, control):
@@ -63,7 +32,7 @@ def torch_solve_box_qp_soft(Q, p, A, b, lb, ub, wl, wu, lo, hi, control):
                         x_i = hi_i / x_i = lo_i (only where that side's weight is positive), 0 inside the band
       "u_box"  (B,n,1): the box's share of the dual u -- zero unless the element is clamped at a bound;
     "lams" is built from u_box (the rest of u is the band's multiplier, -wl <= rho (u - u_box) <= wu)."""
-    return _solve(Q, p, A, b, lb, ub, wl, wu, lo, hi, control)
+    return _T.solve(_T.SOFT, (Q, p, A, b, lb, ub), (wl, wu, lo, hi), control)
 
 
 class SolveBoxQPSoft(nn.Module):
@@ -88,36 +57,27 @@ class SolveBoxQPSoftLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, Q, p, A, b, lb, ub, wl, wu, lo, hi, control):
-        sync = bool(control.get('sync', True))
-        sol = _solve(Q, p, A, b, lb, ub, wl, wu, lo, hi, control, sync=sync)
-        ctx.rho, ctx.sync = sol['rho'], sync
-        ctx.linsolve = int(sol['_stats']['linsolve_used'])
-        ctx.save_for_backward(sol['x'], sol['u'], sol['u_box'], sol['zone'], sol['nus'], Q, A, lb, ub, lo, hi)
-        return sol['x']
+        return _T.layer_forward(ctx, _T.SOFT, (Q, p, A, b, lb, ub), (wl, wu, lo, hi), control, ('x', 'u', 'u_box', 'zone', 'nus'),
+                                (Q, A, lb, ub, lo, hi))
 
     @staticmethod
     def backward(ctx, dl_dz):
         x, u, u_box, zone, nus, Q, A, lb, ub, lo, hi = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        lib, B, n = _lib.load(), Q.shape[0], Q.shape[1]
-        dt, dev, dty = _lib.dtype_code(x), x.device, x.dtype
-        stream = ctypes.c_void_p(_lib.current_stream_handle(dev))
-        rho_mode, rho_value, rho_tensor = _S._per_problem_argument('rho', '(B,1,1)', ctx.rho, B, x)
-        lbc, ubc, loc, hic = (_lib.norm(t, dty) for t in (lb, ub, lo, hi))
-        lb_e, ub_e, u_e = (torch.empty((B, n, 1), dtype=dty, device=dev) for _ in range(3))
-        lams_e = torch.empty((B, 2 * n, 1), dtype=dty, device=dev)
-        with _lib.on_device(dev):
-            _lib.check(lib.lqp_boxqp_soft_effective_box(stream, dt, B, n, _lib.ptr(zone), _lib.ptr(u), _lib.ptr(u_box), _lib.ptr(lbc),
-                                                        _lib.ptr(ubc), _lib.ptr(loc), _lib.ptr(hic), rho_mode, rho_value,
-                                                        _lib.ptr(rho_tensor), _lib.ptr(lb_e), _lib.ptr(ub_e), _lib.ptr(u_e),
+        h = _T.backward_prelude(ctx, x, Q, A, box_grads=True)
+        need, lib, B, n = h.need, h.lib, h.B, h.n
+        lbc, ubc, loc, hic = (_lib.norm(t, h.dty) for t in (lb, ub, lo, hi))
+        lb_e, ub_e, u_e = (torch.empty((B, n, 1), dtype=h.dty, device=h.dev) for _ in range(3))
+        lams_e = torch.empty((B, 2 * n, 1), dtype=h.dty, device=h.dev)
+        with _lib.on_device(h.dev):
+            _lib.check(lib.lqp_boxqp_soft_effective_box(h.stream, h.dt, B, n, _lib.ptr(zone), _lib.ptr(u), _lib.ptr(u_box), _lib.ptr(lbc),
+                                                        _lib.ptr(ubc), _lib.ptr(loc), _lib.ptr(hic), h.rho_mode, h.rho_value,
+                                                        _lib.ptr(h.rho_tensor), _lib.ptr(lb_e), _lib.ptr(ub_e), _lib.ptr(u_e),
                                                         _lib.ptr(lams_e)), "soft_effective_box")
-        has_eq = get_ncon(A, dim=1) > 0
-        want = dict(dQ=need[0], dp=True, dA=need[2] and has_eq, db=need[3] and has_eq, dlb=True, dub=True)
-        dQ, dp, dA, db, dlb, dub, _ = _S._fp_backward(dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, ctx.rho, want, sync=ctx.sync,
+        dQ, dp, dA, db, dlb, dub, _ = _S._fp_backward(dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, ctx.rho, h.want, sync=ctx.sync,
                                                       linsolve=ctx.linsolve)
         dwl, dwu, dlo, dhi = (torch.empty_like(dp) if need[k] else None for k in (6, 7, 8, 9))
-        with _lib.on_device(dev):
-            _lib.check(lib.lqp_boxqp_soft_finish_grads(stream, dt, B, n, _lib.ptr(zone), _lib.ptr(u_box), _lib.ptr(dp), _lib.ptr(dlb), _lib.ptr(dub),
+        with _lib.on_device(h.dev):
+            _lib.check(lib.lqp_boxqp_soft_finish_grads(h.stream, h.dt, B, n, _lib.ptr(zone), _lib.ptr(u_box), _lib.ptr(dp), _lib.ptr(dlb), _lib.ptr(dub),
                                                        _lib.ptr(dlb), _lib.ptr(dub), _lib.ptr(dwl), _lib.ptr(dwu), _lib.ptr(dlo),
                                                        _lib.ptr(dhi)), "soft_finish_grads")
         return (dQ, dp if need[1] else None, dA, db, dlb if need[4] else None, dub if need[5] else None, dwl, dwu, dlo, dhi, None)

@@ -27,29 +27,24 @@ def loop(kernel, form, args=""):
     return lambda n: re.search(rf"{kernel}<{args}[^>]*lqp::Form{form}>", n)
 
 
+def term_groups(g, tag):
+    """the groups of the instances with a separable term's step (lqp::Form<tag>, lqp::Term<tag>), grouped as their plain twins are"""
+    own = rf"k_(fwd_epilogue|term_setup)<\w+, lqp::Term{tag}>|k_{g}_"
+    return [
+        (f"split_{g}_c", loop("k_admm_loop_split", tag, r"(3|4), 512, false, 2,")),
+        (f"split_{g}_a", loop("k_admm_loop_split", tag, r"(5|6|7), 512, false, 2,")),
+        (f"split_{g}_b", loop("k_admm_loop_split", tag)),
+        (f"loop_{g}_tail", loop("k_admm_loop", tag, r"\w+, \w+, true,")),
+        (f"loop_{g}_hot", loop("k_admm_loop", tag)),
+        (g, lambda n: loop("k_admm_loop_np2", tag)(n) or loop("k_admm_loop_small", tag)(n) or re.search(own, n)),
+    ]
+
+
+# the separable terms (lqp_boxqp_forward_l1 / _soft / _log): (group suffix, tag of lqp::Form* and lqp::Term*).  A new term is one entry here
+# and its backward's element-wise kernels in KERNELS.
+TERMS = [("l1", "L1"), ("soft", "Soft"), ("log", "Log")]
 # group -> predicate on the demangled name; first match wins.  Balanced by measured compile time (seconds at -O3).
-GROUPS = [
-    # the instances with the L1 step (lqp_boxqp_forward_l1), grouped as their plain twins are
-    ("split_l1_c", loop("k_admm_loop_split", "L1", r"(3|4), 512, false, 2,")),
-    ("split_l1_a", loop("k_admm_loop_split", "L1", r"(5|6|7), 512, false, 2,")),
-    ("split_l1_b", loop("k_admm_loop_split", "L1")),
-    ("loop_l1_tail", loop("k_admm_loop", "L1", r"\w+, \w+, true,")),
-    ("loop_l1_hot", loop("k_admm_loop", "L1")),
-    ("l1", lambda n: loop("k_admm_loop_np2", "L1")(n) or loop("k_admm_loop_small", "L1")(n) or re.search(r"k_fwd_epilogue_l1<|k_l1_", n)),
-    # ... and with the soft band's step (lqp_boxqp_forward_soft), the same groups again
-    ("split_soft_c", loop("k_admm_loop_split", "Soft", r"(3|4), 512, false, 2,")),
-    ("split_soft_a", loop("k_admm_loop_split", "Soft", r"(5|6|7), 512, false, 2,")),
-    ("split_soft_b", loop("k_admm_loop_split", "Soft")),
-    ("loop_soft_tail", loop("k_admm_loop", "Soft", r"\w+, \w+, true,")),
-    ("loop_soft_hot", loop("k_admm_loop", "Soft")),
-    ("soft", lambda n: loop("k_admm_loop_np2", "Soft")(n) or loop("k_admm_loop_small", "Soft")(n) or re.search(r"k_fwd_epilogue_soft<|k_soft_", n)),
-    # ... and with the log barrier's step (lqp_boxqp_forward_log)
-    ("split_log_c", loop("k_admm_loop_split", "Log", r"(3|4), 512, false, 2,")),
-    ("split_log_a", loop("k_admm_loop_split", "Log", r"(5|6|7), 512, false, 2,")),
-    ("split_log_b", loop("k_admm_loop_split", "Log")),
-    ("loop_log_tail", loop("k_admm_loop", "Log", r"\w+, \w+, true,")),
-    ("loop_log_hot", loop("k_admm_loop", "Log")),
-    ("log", lambda n: loop("k_admm_loop_np2", "Log")(n) or loop("k_admm_loop_small", "Log")(n) or re.search(r"k_fwd_epilogue_log<|k_log_", n)),
+GROUPS = [grp for g, tag in TERMS for grp in term_groups(g, tag)] + [
     ("bwd_f", lambda n: re.search(r"k_bwd_chol_solve<\d, true>", n)),
     ("resident_f", lambda n: re.search(r"k_spd_resident<8, 2, true>", n)),
     ("resident_g", lambda n: re.search(r"k_spd_resident<(5|6|7), 2, true>", n)),
@@ -86,10 +81,11 @@ FPF, BPF = "lqp::FwdParams<float>", "lqp::BwdParams<float>"
 KS_NP = [(3, 2), (4, 2), (5, 2), (6, 2), (7, 2), (8, 2), (7, 4), (8, 4)]      # Ks, workgroups per problem (four: Ks = 7, 8 only)
 # The forms of the loop kernels (the tags of lqp_boxqp.hpp), the last template argument of every instance: the batch stops as one |
 # control['stop'] = 'each' | ... with the infeasibility certificate (control['infeasible']) | ... and the dual certificate beside it
-# (control['unbounded']) | lqp_boxqp_forward_l1: the L1 step | lqp_boxqp_forward_soft: the soft band's step | lqp_boxqp_forward_log: the
-# log barrier's step
-ALL, EACH, DETECT, CERTIFY, L1, SOFT, LOG = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify", "L1", "Soft", "Log"))
-FORMS = (ALL, EACH, DETECT, CERTIFY, L1, SOFT, LOG)
+# (control['unbounded']) | one per separable term (TERMS): that term's step
+ALL, EACH, DETECT, CERTIFY = ("lqp::Form" + f for f in ("All", "Each", "Detect", "Certify"))
+TERM_FORMS = tuple("lqp::Form" + tag for _, tag in TERMS)
+TERM_TAGS = tuple("lqp::Term" + tag for _, tag in TERMS)
+FORMS = (ALL, EACH, DETECT, CERTIFY) + TERM_FORMS
 SPLIT = [(ks, 512, False, np_) for ks, np_ in KS_NP]
 # the one-workgroup loop, hot and continuation: LU f64 | LU f32 | LU f32 resident | symmetric
 LOOP = [(t, res, tail, 1024, sym) for tail in (False, True)
@@ -101,9 +97,9 @@ WIDE_SIG = LU_SIG + ", int const*, int*, unsigned long, unsigned int, int, unsig
 KERNELS = [
     # the ADMM loops (lqp_boxqp.hpp, lqp_loop_split.hpp, lqp_loop_small.hpp, lqp_dense.hpp)
     ("k_admm_loop", LOOP_SIG, in_forms(LOOP, FORMS) + [("float", True, False, 512, False, ALL), ("float", True, False, 512, True, ALL)]),
-    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH, L1, SOFT, LOG)) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
+    ("k_admm_loop_split", FPF + ", int, int, int", in_forms(SPLIT, (ALL, EACH) + TERM_FORMS) + [(8, 512, True, 2, ALL)]),      # (EACH serves DETECT and CERTIFY)
     ("k_admm_loop_small", FPF + ", int, int, int", in_forms([()], FORMS)),
-    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL, L1, SOFT, LOG))),
+    ("k_admm_loop_np2", FPF + ", int, int, int, int, int", in_forms([()], (ALL,) + TERM_FORMS)),
     ("k_admm_loop_dense", FP + ", int, int, int", BOTH),
     ("k_admm_loop_dense_w", FP + ", int, int, int, int", BOTH),
     # the symmetric x-update (lqp_spd.hpp)
@@ -134,16 +130,13 @@ KERNELS = [
     # forward prologue / epilogue and the copies out of the workspace
     ("k_fwd_setup", FP, BOTH),
     ("k_fwd_epilogue", FP, BOTH),
-    ("k_fwd_epilogue_l1", FP + ", {0}*, {0}*", BOTH),
-    ("k_l1_setup", FP + ", {0} const*, {0} const*", BOTH),
+    ("k_fwd_epilogue", FP + ", {0}*, {0}*", in_forms(BOTH, TERM_TAGS)),
+    ("k_term_setup", FP + ", lqp::TermIn<{0}>", in_forms(BOTH, TERM_TAGS)),
+    # ... and the element-wise kernels of the three backwards, whose sets differ
     ("k_l1_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_l1_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
-    ("k_fwd_epilogue_soft", FP + ", {0}*, {0}*", BOTH),
-    ("k_soft_setup", FP + ", {0} const*, {0} const*, {0} const*, {0} const*", BOTH),
     ("k_soft_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_soft_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*, {0}*, {0}*, {0}*", BOTH),
-    ("k_fwd_epilogue_log", FP + ", {0}*, {0}*", BOTH),
-    ("k_log_setup", FP + ", {0} const*", BOTH),
     ("k_log_effective_duals", "{0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*", BOTH),
     ("k_log_finish_grads", "{0} const*, {0} const*, {0} const*, unsigned long, {0}*", BOTH),
     ("k_rho_update", FP + ", int, int", BOTH),
