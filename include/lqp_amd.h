@@ -545,6 +545,63 @@ int lqp_boxqp_backward_fp_curv(void* stream, int dtype, int B, int n, int m,
 int lqp_boxqp_log_effective_duals(void* stream, int dtype, int B, int n, const void* u_box,
                                   int rho_mode, double rho_value, const void* rho_in, void* u_e, void* lams_e);
 int lqp_boxqp_log_finish_grads(void* stream, int dtype, int B, int n, const void* dp, const void* z, const void* w, void* dw);
+/* ---- a piecewise-linear term in the objective (added within ABI 17: new symbols only, no struct and no signature changed) ---
+ *   min 0.5 x'Qx + p'x + sum_i f_i(x_i)   s.t.  A x = b,  lb <= x <= ub
+ *   f_i(x) = s_i0 x + sum_{k=1..K} (s_ik - s_i,k-1) (x - c_ik)_+ ,   1 <= K <= 3
+ *   slopes s_i0 <= ... <= s_iK, finite;  kinks c_i1 <= ... <= c_iK, no NaN, -inf allowed at the low end and +inf at the high end
+ * (convex, K kinks, K + 1 slopes per element: the L1 term is K = 1 with slopes -w, w; the soft band K = 2 with slopes -wl, 0, wu; both
+ * at once, two-tier trading costs c - delta, c, c + delta, asymmetric buy and sell tiers are K = 3.)
+ * Layout: s is [K + 1][B][n] and c is [K][B][n] -- slope k / kink k of every element as one (B,n,1) vector, the vectors one
+ * behind the other.  The kernels are written for three kinks; K < 3 is padded at the top by this entry (a kink at +inf, the last
+ * slope once more), which does not change any piece number.
+ * lqp_boxqp_forward_pwl is the same implementation once more with another z-update: in the scaled space of the loop the data are
+ * ss_k = D s_k, cs_k = c_k / D, and with v = xh + u (xh as in lqp_boxqp_forward, over-relaxation included), t_k = ss_k / rho (the
+ * rho of this iteration, a true division):
+ *   S = v                                   if every slope is zero (a branch: lqp_boxqp_forward's x, z, u bit for bit)
+ *   for k = K .. 1:  d = v - cs_k;  S = v - t_k if d > t_k;  S = cs_k if d >= t_{k-1}
+ *   S = v - t_0                             otherwise;                                  z = min(max(S, lbs), ubs)
+ * -- these comparisons, from the top: slopes (-w, w) give lqp_boxqp_forward_l1's results and (-wl, 0, wu) lqp_boxqp_forward_soft's,
+ * bit for bit.  x-update, factorisations, stopping rule, rho adaptation: unchanged.  The solve always iterates: bounds that are
+ * all infinite are an ordinary case, the rho = 0 one-shot does not exist here (rho_mode 1 with rho_value <= 0: LQP_ERR_INVALID),
+ * ctrl.any_lb / any_ub are not read.  The same loop kernel families as the other terms have instances with this step.
+ * Two more outputs, (B,n,1) in the solve's dtype, from the scan taken once more at the returned iterate (v = zs + us):
+ *   piece  2 k where the element rests on the slope s_k (d > t_k at kink k, or below every kink: 0), 2 k - 1 exactly on kink k
+ *          (zs == cs_k there) -- only where the kink's jump s_k - s_{k-1} is positive; with none the element belongs to the piece
+ *          below, 2 k - 2
+ *   u_box  (S - clamp(S)) / D, exactly zero unless the element is clamped: the box's share of the dual u; lams is built from it.
+ * Refused with LQP_ERR_INVALID before anything is touched: a null s, c, piece or u_box, K outside 1 .. 3, ctrl.reserved2 bit 3
+ * (per-problem stopping) or bit 0 (the factor kept for the unroll sweep), a check_hook.  A slope that is not finite, slopes or kinks
+ * that decrease, a NaN kink, and a rho of a problem (rho_mode 2: an entry of rho_in) that is not positive and finite, is found on the
+ * device: the problem's outputs are NaN, bit 21 (2097152) of its flag word in ctrl.host_report is set, and a call that waits returns
+ * LQP_ERR_INVALID with stats.fail_index naming it.  lqp_boxqp_forward_pwl_workspace_bytes: the forward's layout, unchanged, and
+ * behind it 11 n values per problem (cs_1..3, ss_0..3, t_0..3), written by kernels of the call before they are read. */
+size_t lqp_boxqp_forward_pwl_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_pwl(void* stream, int dtype, int B, int n, int m,
+                          const void* Q, const void* p, const void* A, const void* b,
+                          const void* lb, const void* ub, const void* s, const void* c, int K,
+                          const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                          void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* piece, void* u_box,
+                          lqp_boxqp_stats* stats,
+                          void* workspace, size_t workspace_bytes);
+/* Its backward: an element on kink k behaves like one whose two bounds are both c_k, a free element on a slope like p_i shifted by
+ * that slope.  An element a hard bound holds (u_box != 0) is an ordinary clamped one, whatever kink lies there.  Two element-wise
+ * kernels around lqp_boxqp_backward_fp, which runs unchanged on (dl_dz, x, u_e, lams_e, nus, Q, A, lb_e, ub_e, rho); c, ds, dc in the
+ * caller's K and the layout above:
+ *   lqp_boxqp_pwl_effective_box    on = (piece odd and u_box == 0), k = (piece + 1) / 2:
+ *                                  lb_e = on ? c_k : lb,  ub_e = on ? c_k : ub,  u_e = on ? u : u_box,
+ *                                  lams_e = [relu(-rho u_e); relu(rho u_e)] (B,2n,1); rho_mode 1 = rho_value, 2 = rho_in (B)
+ *   lqp_boxqp_pwl_finish_grads     dlb = on ? 0 : dlb_e,  dub = on ? 0 : dub_e,  dc_k = (on and piece == 2 k - 1) ? dlb_e + dub_e : 0,
+ *                                  ds_k = (piece == 2 k) ? dp : 0; any of the four outputs may be NULL = skip, dlb / dub may be
+ *                                  dlb_e / dub_e themselves.
+ * dQ, dp, dA, db are lqp_boxqp_backward_fp's.  Enqueued on `stream`, nothing is waited for. */
+int lqp_boxqp_pwl_effective_box(void* stream, int dtype, int B, int n,
+                                const void* piece, const void* u, const void* u_box,
+                                const void* lb, const void* ub, const void* c, int K,
+                                int rho_mode, double rho_value, const void* rho_in,
+                                void* lb_e, void* ub_e, void* u_e, void* lams_e);
+int lqp_boxqp_pwl_finish_grads(void* stream, int dtype, int B, int n,
+                               const void* piece, const void* u_box, const void* dp, const void* dlb_e, const void* dub_e, int K,
+                               void* dlb, void* dub, void* ds, void* dc);
 /* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
  * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
  * optimal, 2 primal infeasible, 3 dual infeasible (lqp_boxqp_forward_certify) -- B int32 on the DEVICE.  Enqueued on `stream`,

@@ -500,10 +500,10 @@ inline void solve_stats(lqp_boxqp_stats* stats, const volatile int* rv, const in
 }
 inline bool flags_timeout_loop(const int* rep) { return ((const volatile int*)rep)[ST_TIMEOUT] != 0; }
 // the run-time twins of the Term traits (lqp_boxqp.hpp), by Term*::kind
-constexpr int kTerms = 4;
-constexpr int kTermSlots[kTerms] = {TermNone::slots, TermL1::slots, TermSoft::slots, TermLog::slots};
-constexpr int kTermInputs[kTerms] = {TermNone::n_in, TermL1::n_in, TermSoft::n_in, TermLog::n_in};
-constexpr int kTermFlag[kTerms] ={TermNone::input_flag, TermL1::input_flag, TermSoft::input_flag, TermLog::input_flag};
+constexpr int kTerms = 5;
+constexpr int kTermSlots[kTerms] = {TermNone::slots, TermL1::slots, TermSoft::slots, TermLog::slots, TermPwl::slots};
+constexpr int kTermInputs[kTerms] = {TermNone::n_in, TermL1::n_in, TermSoft::n_in, TermLog::n_in, TermPwl::n_in};
+constexpr int kTermFlag[kTerms] ={TermNone::input_flag, TermL1::input_flag, TermSoft::input_flag, TermLog::input_flag, TermPwl::input_flag};
 int collect_report(hipStream_t st, const int* rep, const bool polled, const int B, const int max_iters, const int check,
                    lqp_boxqp_stats* stats) {
     if (polled) {
@@ -548,9 +548,9 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
 // has an instance per form it supports (family_has_form), and nothing but its selector below chooses one.
 // The batch stops as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
 // infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']:
-// P.eps_dinf > 0) | the step with a separable term, one form per term (lqp_boxqp_forward_l1 / _soft / _log: P.term, whose area shares its
+// P.eps_dinf > 0) | the step with a separable term, one form per term (lqp_boxqp_forward_l1 / _soft / _log / _pwl: P.term, whose area shares its
 // storage with the snapshots; the batch stops as one)
-enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT, FORM_LOG };
+enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT, FORM_LOG, FORM_PWL };
 inline int form_term(const LoopForm form) { return form >= FORM_L1 ? form - FORM_L1 + 1 : 0; }      // (Term*::kind of the form, 0: none)
 inline LoopForm loop_form(const int term, const bool each, const bool snapshots, const bool dual) {
     return term ? (LoopForm)(FORM_L1 + term - 1) : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
@@ -566,6 +566,7 @@ template <typename F> auto by_form(const LoopForm form, F f) -> decltype(f(FormA
         case FORM_L1:      return f(FormL1());
         case FORM_SOFT:    return f(FormSoft());
         case FORM_LOG:     return f(FormLog());
+        case FORM_PWL:     return f(FormPwl());
         default:           return f(FormAll());
     }
 }
@@ -666,7 +667,7 @@ enum LoopKind {
 inline bool family_has_form(const LoopKind kind, const LoopForm form) {
     switch (kind) {
         case LOOP_ONE: case LOOP_SMALL: case LOOP_SPLIT: return true;      // (the split loop's FormEach serves FormDetect and FormCertify)
-        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1 || form == FORM_SOFT || form == FORM_LOG;
+        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1 || form == FORM_SOFT || form == FORM_LOG || form == FORM_PWL;
         default: return form == FORM_ALL;                                  // (the dense tiers)
     }
 }
@@ -717,8 +718,8 @@ inline LoopFn<float> np2_kernel(const LoopForm form) {
         else return k_admm_loop_np2<decltype(f)>;
     });
 }
-// the extra arguments of lqp_boxqp_forward_l1 / _soft / _log: the term (Term*::kind), its input vectors, its two outputs
-struct TermArgs { int kind = 0; const void* in[4] = {nullptr, nullptr, nullptr, nullptr}; void* aux = nullptr; void* u_box = nullptr; };
+// the extra arguments of lqp_boxqp_forward_l1 / _soft / _log / _pwl: the term (Term*::kind), its input vectors, its two outputs
+struct TermArgs { int kind = 0; const void* in[TERM_IN_MAX] = {}; void* aux = nullptr; void* u_box = nullptr; };
 
 constexpr int kMaxChecksPerLaunch = kRing / 4;
 
@@ -1186,7 +1187,7 @@ int enqueue_prologue(hipStream_t st, const FwdParams<T>& P, const FwdPlan<T>& pl
         if constexpr (TERM::kind != 0) {
             ProfScope ps(st, PC_SETUP);
             TermIn<T> in;
-            for (int k = 0; k < 4; ++k) in.p[k] = (const T*)plan.term.in[k];
+            for (int k = 0; k < TERM_IN_MAX; ++k) in.p[k] = (const T*)plan.term.in[k];
             hipLaunchKernelGGL((k_term_setup<T, TERM>), dim3(P.B), dim3(256), 0, st, P, in);
             ++n_launch;
         }
@@ -1540,7 +1541,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
                  int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const TermArgs* term = nullptr) {
-    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; term: lqp_boxqp_forward_l1 / _soft / _log)
+    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; term: lqp_boxqp_forward_l1 / _soft / _log / _pwl)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
     const LoopForm asked = loop_form(term ? term->kind : 0, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
     if (ws_bytes < L.bytes_for(asked)) return LQP_ERR_WORKSPACE;
@@ -2363,7 +2364,7 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const
                          workspace_bytes, eps_prim_inf, 0.0);
 }
 
-// ---- the solves with a separable term: lqp_boxqp_forward_l1 / _soft / _log ----
+// ---- the solves with a separable term: lqp_boxqp_forward_l1 / _soft / _log / _pwl ----
 size_t lqp_boxqp_forward_l1_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_L1); });
@@ -2375,6 +2376,10 @@ size_t lqp_boxqp_forward_soft_workspace_bytes(int dtype, int B, int n, int m) {
 size_t lqp_boxqp_forward_log_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_LOG); });
+}
+size_t lqp_boxqp_forward_pwl_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_PWL); });
 }
 
 // Refused before anything is touched: a null pointer of the term's own, the per-problem stop (no instance of its kernels with a term), a
@@ -2413,6 +2418,21 @@ int lqp_boxqp_forward_log(void* stream, int dtype, int B, int n, int m, const vo
                           void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* u_box, void* curv,
                           lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
     const TermArgs term = {TermLog::kind, {w, nullptr, nullptr, nullptr}, curv, u_box};
+    return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
+}
+
+// s: [K + 1][B][n], c: [K][B][n], 1 <= K <= PWL_K.  Fewer kinks than the kernels are written for are padded at the top here, by
+// pointers alone: the last slope's vector once more, and no vector (= +inf) for a kink
+int lqp_boxqp_forward_pwl(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                          const void* b, const void* lb, const void* ub, const void* s, const void* c, int K, const lqp_boxqp_ctrl* ctrl,
+                          const void* rho_in, void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* piece, void* u_box,
+                          lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
+    if (bad_dims(dtype, B, n, m) || !s || !c || K < 1 || K > PWL_K) return LQP_ERR_INVALID;
+    const size_t vec = (size_t)B * n * (dtype == LQP_F64 ? 8 : 4);
+    TermArgs term;
+    term.kind = TermPwl::kind; term.aux = piece; term.u_box = u_box;
+    for (int k = 0; k <= PWL_K; ++k) term.in[k] = (const char*)s + (size_t)(k < K ? k : K) * vec;
+    for (int k = 0; k < K; ++k) term.in[PWL_K + 1 + k] = (const char*)c + (size_t)k * vec;
     return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
 }
 
@@ -2456,6 +2476,29 @@ int lqp_boxqp_soft_finish_grads(void* stream, int dtype, int B, int n, const voi
         typedef decltype(t) T;
         hipLaunchKernelGGL(k_soft_finish_grads<T>, grid, dim3(256), 0, st, (const T*)zone, (const T*)u_box, (const T*)dp, (const T*)dlb_e,
                            (const T*)dub_e, total, (T*)dlb, (T*)dub, (T*)dwl, (T*)dwu, (T*)dlo, (T*)dhi);
+    });
+}
+
+int lqp_boxqp_pwl_effective_box(void* stream, int dtype, int B, int n, const void* piece, const void* u, const void* u_box,
+                                const void* lb, const void* ub, const void* c, int K, int rho_mode, double rho_value,
+                                const void* rho_in, void* lb_e, void* ub_e, void* u_e, void* lams_e) {
+    if (!elementwise_ok(dtype, B, n, {piece, u, u_box, lb, ub, c, lb_e, ub_e, u_e, lams_e}) || (rho_mode == 2 && !rho_in) || K < 1 || K > PWL_K)
+        return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_pwl_effective_box<T>, grid, dim3(256), 0, st, (const T*)piece, (const T*)u, (const T*)u_box, (const T*)lb, (const T*)ub,
+                           (const T*)c, K, rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)lb_e, (T*)ub_e, (T*)u_e,
+                           (T*)lams_e);
+    });
+}
+
+int lqp_boxqp_pwl_finish_grads(void* stream, int dtype, int B, int n, const void* piece, const void* u_box, const void* dp, const void* dlb_e,
+                               const void* dub_e, int K, void* dlb, void* dub, void* ds, void* dc) {
+    if (!elementwise_ok(dtype, B, n, {piece, u_box, dp, dlb_e, dub_e}) || K < 1 || K > PWL_K) return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_pwl_finish_grads<T>, grid, dim3(256), 0, st, (const T*)piece, (const T*)u_box, (const T*)dp, (const T*)dlb_e,
+                           (const T*)dub_e, K, total, (T*)dlb, (T*)dub, (T*)ds, (T*)dc);
     });
 }
 

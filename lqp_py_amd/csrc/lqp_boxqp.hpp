@@ -30,7 +30,8 @@ enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
        RP_UNBOUNDED = 1 << 17,    // control['unbounded']: the problem was flagged dual infeasible (each_stop)
        RP_L1_INPUT = 1 << 18,     // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_term_setup); its outputs are NaN
        RP_SOFT_INPUT = 1 << 19,   // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_term_setup); its outputs are NaN
-       RP_LOG_INPUT = 1 << 20 };  // lqp_boxqp_forward_log: a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (k_term_setup); its outputs are NaN
+       RP_LOG_INPUT = 1 << 20,    // lqp_boxqp_forward_log: a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (k_term_setup); its outputs are NaN
+       RP_PWL_INPUT = 1 << 21 };  // lqp_boxqp_forward_pwl: a slope not finite, slopes or kinks that decrease, a NaN kink, or a rho not positive and finite (k_term_setup); its outputs are NaN
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -114,6 +115,7 @@ template <typename T> struct FwdParams {
     int relax;                // 1: alpha != 1
     int term;                 // the separable term of the objective, Term*::kind below: 0 none | 1 lqp_boxqp_forward_l1: sum_i w_i |x_i - c_i|
                               // | 2 lqp_boxqp_forward_soft: sum_i wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ | 3 lqp_boxqp_forward_log: -sum_i w_i log(x_i)
+                              // | 4 lqp_boxqp_forward_pwl: sum_i s_i0 x_i + sum_k (s_ik - s_i,k-1) (x_i - c_ik)_+
                               // (in the alignment gap in front of the pointer: no offset moves)
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
     union {
@@ -1358,7 +1360,8 @@ __host__ __device__ inline int sym_resident_lds_blocks(int n, int m, int Ks, int
 //   finish_elem one element of the epilogue, in the scaled space where the kinks are exact
 // Every prox returns v itself at a zero weight, by a branch: the plain step's bits.  A compile-time choice (Form*::term), never a flag.
 // ---------------------------------------------------------------------------
-template <typename T> struct TermIn { const T* p[4]; };
+constexpr int TERM_IN_MAX = 7;      // (the piecewise-linear term's four slopes and three kinks)
+template <typename T> struct TermIn { const T* p[TERM_IN_MAX]; };
 template <typename T> struct TermOut { T aux, u_box; };
 template <typename TERM> __host__ __device__ inline size_t term_stride(int n) { return (size_t)TERM::slots * round_up(n, 8); }
 struct TermNone {
@@ -1514,6 +1517,110 @@ struct TermLog {
         return {((wi > T(0) && !held) ? wi / (zu * zu) : T(0)) + poison, ubx};      // (curv)
     }
 };
+// Piecewise linear (lqp_boxqp_forward_pwl), f(x) = s_0 x + sum_k (s_k - s_{k-1}) (x - c_k)_+ with PWL_K sorted kinks and PWL_K + 1
+// non-decreasing slopes: L1 (one kink, slopes -w, w), the band (two kinks, slopes -wl, 0, wu), both at once, tiered costs.  Fewer kinks are
+// padded at the top: a kink at +inf and the last slope repeated.  Thresholds t_k = ss_k / rho; the prox scans from the top,
+//   for k = K .. 1:  d = v - cs_k;  d > t_k: v - t_k;  d >= t_{k-1}: cs_k      and v - t_0 below the lowest kink
+// -- these comparisons and no others: at slopes (-w, w, w, w) it is l1_shrink and at (-wl, 0, wu, wu) soft_prox, bit for bit (min_k
+// max(v - t_k, cs_k) is the same number in exact arithmetic only).  Non-decreasing slopes that are zero at both ends are zero throughout:
+// the branch of the plain step's bits looks at two.  Area: [cs_1 .. cs_K | ss_0 .. ss_K | t_0 .. t_K], cs_k = c_k / D, ss_k = D s_k
+constexpr int PWL_K = 3;
+template <typename T, typename TA, typename CA> __device__ __forceinline__ T pwl_prox(const T v, const TA& t, const CA& cs) {
+    if (t[0] == T(0) && t[PWL_K] == T(0)) return v;
+#pragma unroll
+    for (int k = PWL_K; k >= 1; --k) {
+        const T d = v - cs[k - 1];
+        if (d > t[k]) return v - t[k];
+        if (d >= t[k - 1]) return cs[k - 1];
+    }
+    return v - t[0];
+}
+struct TermPwl {
+    static constexpr int K = PWL_K;
+    static_assert(2 * K + 1 <= TERM_IN_MAX, "TermIn holds a pointer per slope and kink");
+    // (n_in: the pointers of TermIn that cannot be null -- the K + 1 slopes and the first kink, then the further kinks, null = +inf)
+    static constexpr int kind = 4, input_flag = RP_PWL_INPUT, n_in = K + 2, slots = 3 * K + 2;
+    enum { CS = 0, SS = K, TH = 2 * K + 1 };
+    template <typename T> struct View {
+        T *cs[K] = {}, *ss[K + 1] = {}, *t[K + 1] = {};
+        View() = default;
+        __device__ __forceinline__ View(T* a, const int n) {
+            const int s = round_up(n, 8);
+#pragma unroll
+            for (int k = 0; k < K; ++k) cs[k] = a + (CS + k) * s;
+#pragma unroll
+            for (int k = 0; k <= K; ++k) { ss[k] = a + (SS + k) * s; t[k] = a + (TH + k) * s; }
+        }
+        __device__ __forceinline__ void keep(const int i, const T rho) const {
+#pragma unroll
+            for (int k = 0; k <= K; ++k) t[k][i] = ss[k][i] / rho;
+        }
+    };
+    template <typename T> struct Regs {
+        T t[K + 1] = {}, c[K] = {};
+        __device__ __forceinline__ void load(const T* a, const int n, const int i, const T rho) {
+            const View<const T> W(a, n);
+#pragma unroll
+            for (int k = 0; k <= K; ++k) t[k] = W.ss[k][i] / rho;
+#pragma unroll
+            for (int k = 0; k < K; ++k) c[k] = W.cs[k][i];
+        }
+        __device__ __forceinline__ T prox(const T v) const { return pwl_prox(v, t, c); }
+        __device__ __forceinline__ T prox_at(const T v, const bool first, const View<T> W, const int i) const {
+            if (first) return pwl_prox(v, t, c);
+            Regs o;
+#pragma unroll
+            for (int k = 0; k <= K; ++k) o.t[k] = W.t[k][i];
+#pragma unroll
+            for (int k = 0; k < K; ++k) o.c[k] = W.cs[k][i];
+            return pwl_prox(v, o.t, o.c);
+        }
+    };
+    // a slope that is not finite, slopes or kinks that decrease, a NaN kink (an infinite kink stays infinite; a null kink vector is +inf)
+    template <typename T>
+    static __device__ __forceinline__ bool setup_elem(T* a, const int n, const int i, const TermIn<T>& in, const size_t g, const T* D, const T*) {
+        const View<T> W(a, n);
+        const T di = D[i];
+        bool bad = false;
+        T prev = T(0);
+#pragma unroll
+        for (int k = 0; k <= K; ++k) {
+            const T sk = in.p[k][g];
+            bad |= !(sk > T(-INFINITY) && sk < T(INFINITY));        // (NaN fails the first comparison)
+            if (k > 0) bad |= !(sk >= prev);
+            prev = sk;
+            W.ss[k][i] = di * sk;
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const T ck = in.p[K + 1 + k] ? in.p[K + 1 + k][g] : T(INFINITY);
+            bad |= k > 0 ? !(ck >= prev) : !(ck == ck);            // (a NaN fails either)
+            prev = ck;
+            W.cs[k][i] = ck / di;
+        }
+        return bad;
+    }
+    // The scan once more at the returned iterate: piece = 2 k on the slope s_k, 2 k - 1 exactly on kink k -- only where its jump is
+    // positive (t_k > t_{k-1}: with none the kink is no kink, and the element belongs to the piece below it, the band's tu > 0 rule);
+    // u_box as for L1.
+    template <typename T>
+    static __device__ __forceinline__ TermOut<T> finish_elem(const T* a, const int n, const int i, const T zs, const T us, const T lbs,
+                                                             const T ubs, const T d, const T rho, const T poison) {
+        Regs<T> r;
+        r.load(a, n, i, rho);
+        const T v = zs + us;
+        const T S = pwl_prox(v, r.t, r.c);
+        int piece = 0;
+#pragma unroll
+        for (int k = K; k >= 1; --k) {
+            const T dd = v - r.c[k - 1];
+            if (dd > r.t[k]) { piece = 2 * k; break; }
+            if (dd >= r.t[k - 1]) { piece = r.t[k] > r.t[k - 1] ? 2 * k - 1 : 2 * k - 2; break; }
+        }
+        const T ubx = (S - tmin(tmax(S, lbs), ubs)) / d + poison;
+        return {T(piece) + poison, ubx};
+    }
+};
 // What a thread of the streaming loop, which owns several elements, keeps of a term: its first element in registers; the thresholds
 // of its further elements (n > NT only) come from the area, where prime() stores them itself -- nothing is stored for the first
 // (both workgroups of a shared problem would write the same values).  Nothing at all for TermNone.
@@ -1650,7 +1757,7 @@ __device__ __forceinline__ AdmmStep<T> admm_step(const FwdParams<T>& P, const T 
 //   each:   control['stop'] = 'each' -- every problem stops and adapts rho as a batch of one
 //   detect: ... with the primal infeasibility certificate at every check (control['infeasible'])
 //   dual:   ... and the dual certificate beside it (control['unbounded'])
-//   term:   the separable term whose prox the element-wise step takes (lqp_boxqp_forward_l1 / _soft / _log); the batch stops as one
+//   term:   the separable term whose prox the element-wise step takes (lqp_boxqp_forward_l1 / _soft / _log / _pwl); the batch stops as one
 struct FormAll     { static constexpr bool each = false, detect = false, dual = false; using term = TermNone; };
 struct FormEach    { static constexpr bool each = true,  detect = false, dual = false; using term = TermNone; };
 struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false; using term = TermNone; };
@@ -1658,6 +1765,7 @@ struct FormCertify { static constexpr bool each = true,  detect = true,  dual = 
 struct FormL1      { static constexpr bool each = false, detect = false, dual = false; using term = TermL1; };
 struct FormSoft    { static constexpr bool each = false, detect = false, dual = false; using term = TermSoft; };
 struct FormLog     { static constexpr bool each = false, detect = false, dual = false; using term = TermLog; };
+struct FormPwl     { static constexpr bool each = false, detect = false, dual = false; using term = TermPwl; };
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
 // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu without touching Q -- it only feeds a tolerance SCALE; the
 // caller forms it from wherever its w, As and nu live.  ACC: the thread owns several elements (fold) or one (assign).
@@ -1942,7 +2050,7 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
 // its registers cost the plain EACH kernels 3 % of their time
 // DUAL (control['unbounded']): the dual certificate too, instances of their own again (FormCertify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
-// FORM::term: the separable term of the element-wise step (TermOwn) -- the kernels of lqp_boxqp_forward_l1 / _soft / _log are instances of their own
+// FORM::term: the separable term of the element-wise step (TermOwn) -- the kernels of lqp_boxqp_forward_l1 / _soft / _log / _pwl are instances of their own
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
@@ -2391,7 +2499,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
     __syncthreads();
   }
 }
-// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft, FormLog
+// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft, FormLog, FormPwl
 template <typename FORM>
 __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                         const int prev_slot, const int persistent) {
@@ -3406,6 +3514,44 @@ __global__ __launch_bounds__(256) void k_soft_finish_grads(const T* __restrict__
     if (dhi) dhi[i] = Kh ? gl + gu : T(0);
     if (dwu) dwu[i] = zn == T(2) ? g : T(0);
     if (dwl) dwl[i] = zn == T(-2) ? -g : T(0);
+}
+
+// backward of lqp_boxqp_forward_pwl, the same recipe with a kink set per kink: K_k = (piece == 2 k - 1) rests on kink k (`c`: [K][B][n], the
+// caller's K <= PWL_K kinks; a padded kink holds nothing: its jump is zero); a free element on a slope (piece == 2 k) is p shifted
+// by s_k.  As for the band, an element a hard bound holds (u_box != 0) is an ordinary clamped one, whatever kink lies there.
+template <typename T>
+__global__ __launch_bounds__(256) void k_pwl_effective_box(const T* __restrict__ piece, const T* __restrict__ u, const T* __restrict__ ubox,
+                                                           const T* __restrict__ lb, const T* __restrict__ ub, const T* __restrict__ c, const int K,
+                                                           const T* __restrict__ rho_in, const T rho_value, const int n, const size_t total,
+                                                           T* __restrict__ lb_e, T* __restrict__ ub_e, T* __restrict__ u_e,
+                                                           T* __restrict__ lams_e) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / n, e = i - b * n;
+    const int pc = (int)piece[i];
+    const bool on = (pc & 1) && pc >= 1 && pc < 2 * K && ubox[i] == T(0);      // (bounded: `piece` is data)
+    const T kv = on ? c[(size_t)(pc >> 1) * total + i] : T(0);
+    const T ue = on ? u[i] : ubox[i];
+    lb_e[i] = on ? kv : lb[i];
+    ub_e[i] = on ? kv : ub[i];
+    u_e[i] = ue;
+    lams_from_y(lams_e, b, n, e, (rho_in ? rho_in[b] : rho_value) * ue);
+}
+// ... and the eight inputs' gradients from the effective box's: on kink k both bounds were c_k (dc_k = dlb_e + dub_e, nothing for lb
+// and ub); ds_k = dp where piece == 2 k.  ds: [K + 1][B][n], dc: [K][B][n], every slot written.  Outputs may be null; dlb / dub
+// may be dlb_e / dub_e themselves.
+template <typename T>
+__global__ __launch_bounds__(256) void k_pwl_finish_grads(const T* __restrict__ piece, const T* __restrict__ ubox, const T* __restrict__ dp, const T* dlb_e,
+                                                          const T* dub_e, const int K, const size_t total, T* dlb, T* dub, T* __restrict__ ds, T* __restrict__ dc) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int pc = (int)piece[i];
+    const bool on = (pc & 1) && ubox[i] == T(0);
+    const T gl = dlb_e[i], gu = dub_e[i], g = dp[i];
+    if (dlb) dlb[i] = on ? T(0) : gl;
+    if (dub) dub[i] = on ? T(0) : gu;
+    if (ds) for (int k = 0; k <= K; ++k) ds[(size_t)k * total + i] = pc == 2 * k ? g : T(0);
+    if (dc) for (int k = 1; k <= K; ++k) dc[(size_t)(k - 1) * total + i] = (on && pc == 2 * k - 1) ? gl + gu : T(0);
 }
 
 // backward of lqp_boxqp_forward_log: the fixed-point backward runs on the box's share of the dual (u_e = u_box: the clamped set is

@@ -723,10 +723,10 @@ def _forward_attempt(qp, att, owner, sync, check_hook, holder, private_ws, keep_
             ctypes.byref(stats), _lib.ptr(ws), ws.numel())
     aux = u_box = None
     if rec is not None:
-        tc = tuple(_lib.norm(t, p.dtype) for t in term_in)
+        tc = tuple(_lib.norm(t, p.dtype) if torch.is_tensor(t) else t for t in term_in)      # (a plain int of the entry point as it is)
         aux, u_box = torch.empty((B, n, 1), dtype=p.dtype, device=dev), torch.empty((B, n, 1), dtype=p.dtype, device=dev)
         extra = dict(aux=_lib.ptr(aux), u_box=_lib.ptr(u_box))
-        term_args = args[:11] + tuple(_lib.ptr(t) for t in tc) + args[11:19] + tuple(extra[k] for k in rec.outputs) + args[19:]
+        term_args = args[:11] + tuple(_lib.ptr(t) if torch.is_tensor(t) else t for t in tc) + args[11:19] + tuple(extra[k] for k in rec.outputs) + args[19:]
     with _lib.on_device(dev):
         if rec is not None:
             st = getattr(lib, rec.entry)(*term_args)
