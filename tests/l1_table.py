@@ -1,8 +1,8 @@
 """The cases of the L1 layer -- min 0.5 x'Qx + p'x + sum_i w_i |x_i - c_i| over {Ax = b, lb <= x <= ub} -- and their truth (no GPU
 needed to import this module).  tests/test_l1_table.py checks them on the CPU, tests/test_gpu_l1.py runs them.
 
-The truth is `solve_l1`: the oracle's iteration (``oracle.solve_box_qp``, the loop the reference-made goldens pin) restated with
-one other z-update, on the oracle's own ``resolve_control``, ``equilibrate`` and ``kkt_matrix``.  In the scaled space of the loop
+The truth is `solve_l1`: the oracle's own iteration (``oracle.solve_box_qp``, the loop the reference-made goldens pin) with `L1Term`
+as its ``term=`` -- the one other z-update -- through the record `TERM` (tests/term_table.py).  In the scaled space of the loop
 (x = D xs) the data are ws = D w, cs = c / D, and with v = xh + u, t = ws / rho (a true division, the rho of this iteration),
 d = v - cs
 
@@ -24,12 +24,10 @@ iteration 100, where t changes with rho.  The two dense-tier rows must land on t
 their signature says one workgroup per problem.  One row above 1024 rows, where a thread of the streaming body owns two elements
 and reads the second one's t back from the workspace.  Three rows more: every bound infinite, w = 0 on half the elements, c on a bound.
 """
-import functools
-import math
-
 import torch
 
 from oracle import boxqp_oracle as O
+import term_table as TT
 import tier_table as T
 
 K_FAR, K_NEAR, K_EVENT = 10, 60, 110
@@ -89,10 +87,7 @@ GRAD_ROWS = {"sweep2_n129_m1": _row("sweep2_n129_m1", K_NEAR, "gradients, split 
 GRADS8 = ("dQ", "dp", "dA", "db", "dlb", "dub", "dw", "dc")
 OUTPUTS = T.OUTPUTS + ("side", "u_box")
 
-# a solve that stops by itself (eps 1e-5, the oracle's generator): (n, B, seed)
-STOP = (100, 4, 0)
-STOP_CONTROL = dict(eps_abs=1e-5, eps_rel=1e-5)
-STOP_ROW = dict(dtype="f32", R=T.R_DEFAULT, F=T.F_DEFAULT)
+STOP, STOP_CONTROL, STOP_ROW = TT.STOP, TT.STOP_CONTROL, TT.STOP_ROW
 
 
 def l1_data(r, i, lb, ub):
@@ -114,115 +109,37 @@ def l1_data(r, i, lb, ub):
     return w, c
 
 
-def l1_inputs(r, B, idx=None):
-    """(Q, p, A, b, lb, ub, w, c) of the batch -- or of the problems `idx` of it -- in the row's dtype"""
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    idx = list(range(B)) if idx is None else list(idx)
-    base = [None if t is None else t.double() for t in T.inputs(dict(r, dtype="f64"), B, idx)]
-    if r.get("l1") == "allinf":
-        base[4] = torch.full_like(base[4], -math.inf)
-        base[5] = torch.full_like(base[5], math.inf)
-    wc = [l1_data(r, i, base[4][k], base[5][k]) for k, i in enumerate(idx)]
-    base += [torch.stack([x[0] for x in wc]), torch.stack([x[1] for x in wc])]
-    return tuple(None if t is None else t.to(dt) for t in base)
-
-
 def shrink(v, t, cs):
     """S of the step, in exactly its branch form"""
     d = v - cs
     return torch.where(d > t, v - t, torch.where(d < -t, v + t, cs + torch.zeros_like(v)))
 
 
-def solve_l1(Q, p, A, b, lb, ub, w, c, control, alpha=1.0, trace=None, at_iter=None):
-    """The oracle's forward (oracle.solve_box_qp: same operations, same order) with the L1 step; returns its dict plus "side", "u_box",
-    and "lams" built from u_box.  at_iter(it, v, t, cs): shown what the step thresholds, in the scaled space."""
-    B, n = Q.shape[0], p.shape[1]
-    m = 0 if A is None else A.shape[1]
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    cr = O.resolve_control(control, n)
-    rho = cr.rho
-    if cr.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, cr.beta, True)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    ws, cs = D * w, c / D
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor = 1
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * cr.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = cr.adaptive_rho
-    xv = None
-    it = 0
-    for it in range(cr.max_iters):
-        if (cr.adaptive_rho and it % cr.adaptive_rho_iter == 0 and 0 < it < cr.adaptive_rho_max_iter and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            if bool((ratio > cr.adaptive_rho_tol).sum() > 0) or bool((ratio < 1 / cr.adaptive_rho_tol).sum() > 0):
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        x = xv[:, :n, :]
-        z_old = z
-        xh = x if alpha == 1.0 else alpha * x + (1 - alpha) * z_old
-        v = xh + u
-        t = ws / rho
-        if at_iter is not None:
-            at_iter(it, v, t, cs)
-        z = torch.minimum(torch.maximum(shrink(v, t, cs), lbs), ubs)
-        r = x - z
-        s = rho * (z - z_old)
-        u = u + (r if alpha == 1.0 else xh - z)
-        if it % cr.check_solved == 0:
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * s)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx_inf = O._inf_norm_cols(torch.matmul(Qs, x) / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = cr.eps_abs + cr.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = cr.eps_abs + cr.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                break
-    # ---- the step once more at the returned iterate, in the scaled space (z == cs by assignment on the kink)
-    v = z + u
-    t = ws / rho + torch.zeros_like(v)
-    d = v - cs
-    kink = (t > 0) & ~(d > t) & ~(d < -t)
-    side = torch.where(kink, torch.zeros_like(v), torch.where(d < 0, -torch.ones_like(v), torch.ones_like(v)))
-    S = shrink(v, t, cs)
-    u_box = (S - torch.minimum(torch.maximum(S, lbs), ubs)) / D      # (S - z with the clamp taken again: exactly zero off the bounds)
-    margin = torch.minimum((d.abs() - t).abs() * D, ((shrink(v, t, cs) - lbs).abs().minimum((shrink(v, t, cs) - ubs).abs())) * D)
-    x, z, u = D * x, D * z, u / D
-    y = u_box * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E if m > 0 else None
-    if trace is not None:
-        trace.update(n_factor=n_factor)
-    # "margin": how far every element is from changing its set -- | |d| - t | and the distance from S to the nearer bound, unscaled
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it, "side": side, "u_box": u_box, "margin": margin,
-            "n_factor": n_factor}
+class L1Term:
+    """w'|x - c| for oracle.solve_box_qp(term=): ws = D w, cs = c / D, t = ws / rho"""
+
+    def __init__(self, w, c):
+        self.w, self.c = w, c
+
+    def scale(self, D):
+        self.ws, self.cs = D * self.w, self.c / D
+
+    def step(self, v, rho):
+        return shrink(v, self.ws / rho, self.cs)
+
+    def finish(self, z, u, rho, lbs, ubs, D):
+        """the step once more at the returned iterate, in the scaled space (z == cs by assignment on the kink)"""
+        cs = self.cs
+        v = z + u
+        t = self.ws / rho + torch.zeros_like(v)
+        d = v - cs
+        kink = (t > 0) & ~(d > t) & ~(d < -t)
+        side = torch.where(kink, torch.zeros_like(v), torch.where(d < 0, -torch.ones_like(v), torch.ones_like(v)))
+        S = shrink(v, t, cs)
+        u_box = (S - torch.minimum(torch.maximum(S, lbs), ubs)) / D      # (S - z with the clamp taken again: exactly zero off the bounds)
+        # "margin": how far every element is from changing its set -- | |d| - t | and the distance from S to the nearer bound, unscaled
+        margin = torch.minimum((d.abs() - t).abs() * D, ((S - lbs).abs().minimum((S - ubs).abs())) * D)
+        return {"side": side, "u_box": u_box, "margin": margin}
 
 
 def sets(sol):
@@ -232,29 +149,8 @@ def sets(sol):
     return kink, ~kink & ~clamped, clamped
 
 
-def truth(r, inp, dtype, w_zero=False):
-    """The truth of row r on `inp` (eight tensors) in `dtype`, pinned to the row's K"""
-    d = [None if t is None else t.to(dtype) for t in inp]
-    if w_zero:
-        d[6] = torch.zeros_like(d[6])
-    return solve_l1(*d, O.make_control(**T.control(r)), alpha=r["alpha"])
-
-
-@functools.lru_cache(maxsize=None)
-def row_truth(key, cus, table="ROWS"):
-    """-> (idx, t32 or None, t64) of a row at `cus` compute units: the problems `tier_table.sample` picks, computed once and shared"""
-    r = globals()[table][key]
-    B = T.batch(r, cus)
-    idx = T.sample(B)
-    sub = l1_inputs(r, B, idx)
-    t64 = truth(r, sub, torch.float64)
-    t32 = truth(r, sub, torch.float32) if r["dtype"] == "f32" else None
-    return idx, t32, t64
-
-
 def grad_recipe(cot, sol, Q, A, lb, ub, c):
     """The eight gradients of `cot` at the solution `sol` of solve_l1: the effective box into the oracle's fixed-point backward"""
-    n = Q.shape[1]
     K = sol["side"] == 0
     lb_e, ub_e = torch.where(K, c, lb), torch.where(K, c, ub)
     u_e = torch.where(K, sol["u"], sol["u_box"])
@@ -266,16 +162,6 @@ def grad_recipe(cot, sol, Q, A, lb, ub, c):
                 dw=sol["side"] * dp, dc=torch.where(K, dlb_e + dub_e, zero))
 
 
-def truth_grads(r, inp, sol, cot, dtype):
-    Q, _, A, _, lb, ub, _, c = [None if t is None else t.to(dtype) for t in inp]
-    return grad_recipe(cot.to(dtype), sol, Q, A, lb, ub, c)
-
-
-def cot_of(r, B, dtype):
-    g = torch.Generator().manual_seed(T.seed_of(r) + 1)
-    return torch.randn(B, r["n"], 1, generator=g, dtype=torch.float64).to(dtype)
-
-
 def stop_inputs(dtype):
     n, B, seed = STOP
     qp = O.create_qp_data(n, B, seed=seed, dtype=torch.float64)
@@ -285,13 +171,11 @@ def stop_inputs(dtype):
     return tuple(None if t is None else t.to(dtype) for t in qp + (w, c))
 
 
-@functools.lru_cache(maxsize=None)
-def stop_truth(dtype):
-    """The truth of a solve that stops by itself"""
-    return solve_l1(*stop_inputs(dtype), O.make_control(**STOP_CONTROL))
-
-
-def excused(t64, bar_z):
-    """bool (B, n, 1): elements whose `side` may differ from the float64 truth's -- their | |d| - t | or the distance from S to a
-    bound, in that truth, is below the bar for z"""
-    return t64["margin"] < bar_z
+# (the step that ignores w is the term at w = 0)
+TERM = TT.Table(name="l1", weights=1, aux="side", grads=GRADS8, term=L1Term,
+                others={"plain": (lambda w, c: L1Term(torch.zeros_like(w), c), ())}, far_keys=("x", "z", "u"), data=l1_data,
+                stop_inputs=stop_inputs, label=lambda sol: sol["side"].double(), what="side", grad_recipe=grad_recipe,
+                recipe_data=(1,), tables={"ROWS": ROWS, "GRAD_ROWS": GRAD_ROWS})
+solve_l1, l1_inputs, truth = TERM.solve, TERM.inputs, TERM.truth
+row_truth, truth_grads, stop_truth = TERM.row_truth, TERM.truth_grads, TERM.stop_truth
+cot_of, excused = TT.cot_of, TT.excused

@@ -1,9 +1,9 @@
 """The cases of the log-barrier layer -- min 0.5 x'Qx + p'x - sum_i w_i log(x_i) over {Ax = b, lb <= x <= ub}, w >= 0 -- and their
 truth (no GPU needed to import this module).  tests/test_log_table.py checks them on the CPU, tests/test_gpu_log.py runs them.
 
-The truth is `solve_log`: the oracle's iteration restated with one other z-update, on the oracle's own ``resolve_control``,
-``equilibrate`` and ``kkt_matrix``, exactly as ``l1_table.solve_l1`` and ``soft_table.solve_soft`` are.  In the scaled space of the
-loop (x = D xs) the barrier is -w_i log(xs_i) plus a constant, so ws = w (``equilibrate`` scales Q, p by D and the equality rows by
+The truth is `solve_log`: the oracle's own iteration (``oracle.solve_box_qp``) with `LogTerm` as its ``term=`` -- the one other
+z-update -- through the record `TERM` (tests/term_table.py), exactly as ``l1_table.solve_l1`` and ``soft_table.solve_soft`` are.  In
+the scaled space of the loop (x = D xs) the barrier is -w_i log(xs_i) plus a constant, so ws = w (the equilibration scales Q, p by D and the equality rows by
 E; the objective has no scalar scale).  With v = xh + u, t = ws / rho (a true division, the rho of this iteration) and
 s = sqrt(v v + 4 t)
 
@@ -28,13 +28,11 @@ inside the margin, and the plain step's iterate misses the bar for z by at least
 three).  In the plain kind every third element has w = 0; an element whose upper bound is not positive (a few of the tier rows'
 lb == ub elements) has w = 0 too: with w > 0 its domain would be empty and the solve refuses it.
 """
-import functools
-import math
-
 import torch
 
 from oracle import boxqp_oracle as O
 import l1_table as LT
+import term_table as TT
 import tier_table as T
 
 K_FAR, K_NEAR, K_EVENT = LT.K_FAR, LT.K_NEAR, LT.K_EVENT
@@ -115,20 +113,6 @@ def log_data(r, i, lb, ub):
     return w, lb
 
 
-def log_inputs(r, B, idx=None):
-    """(Q, p, A, b, lb, ub, w) of the batch -- or of the problems `idx` of it -- in the row's dtype"""
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    idx = list(range(B)) if idx is None else list(idx)
-    base = [None if t is None else t.double() for t in T.inputs(dict(r, dtype="f64"), B, idx)]
-    if r.get("log") == "allinf":
-        base[4] = torch.full_like(base[4], -math.inf)
-        base[5] = torch.full_like(base[5], math.inf)
-    wd = [log_data(r, i, base[4][k], base[5][k]) for k, i in enumerate(idx)]
-    base[4] = torch.stack([x[1] for x in wd])
-    base.append(torch.stack([x[0] for x in wd]))
-    return tuple(None if t is None else t.to(dt) for t in base)      # (rounding to float32 is monotone: 0 < lb <= ub stays)
-
-
 def prox(v, t):
     """S of the step, in exactly its branch form"""
     s = torch.sqrt(v * v + 4 * t)
@@ -136,125 +120,45 @@ def prox(v, t):
     return torch.where(t == 0, v, torch.where(v >= 0, 0.5 * (v + s), (2 * t) / safe))
 
 
-def solve_log(Q, p, A, b, lb, ub, w, control, alpha=1.0, trace=None, step="log", at_iter=None):
-    """The oracle's forward (oracle.solve_box_qp: same operations, same order) with the barrier's step; returns its dict plus
-    "u_box", "curv", and "lams" built from u_box.  step = "plain": the iterate of a kernel that ignores the barrier -- what the rows
-    must be far from.  at_iter(it, v, t): shown what the step sees, in the scaled space."""
-    B, n = Q.shape[0], p.shape[1]
-    m = 0 if A is None else A.shape[1]
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    cr = O.resolve_control(control, n)
-    rho = cr.rho
-    if cr.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, cr.beta, True)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    ws = w
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor = 1
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * cr.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = cr.adaptive_rho
-    xv = None
-    it = 0
-    for it in range(cr.max_iters):
-        if (cr.adaptive_rho and it % cr.adaptive_rho_iter == 0 and 0 < it < cr.adaptive_rho_max_iter and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            if bool((ratio > cr.adaptive_rho_tol).sum() > 0) or bool((ratio < 1 / cr.adaptive_rho_tol).sum() > 0):
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        x = xv[:, :n, :]
-        z_old = z
-        xh = x if alpha == 1.0 else alpha * x + (1 - alpha) * z_old
-        v = xh + u
-        t = ws / rho
-        if at_iter is not None:
-            at_iter(it, v, t)
-        S = prox(v, t) if step == "log" else v
-        z = torch.minimum(torch.maximum(S, lbs), ubs)
-        r = x - z
-        s = rho * (z - z_old)
-        u = u + (r if alpha == 1.0 else xh - z)
-        if it % cr.check_solved == 0:
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * s)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx_inf = O._inf_norm_cols(torch.matmul(Qs, x) / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = cr.eps_abs + cr.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = cr.eps_abs + cr.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                break
-    # ---- the step once more at the returned iterate, in the scaled space
-    v = z + u
-    t = ws / rho + torch.zeros_like(v)
-    S = prox(v, t) if step == "log" else v
-    held = S != torch.minimum(torch.maximum(S, lbs), ubs)
-    zsafe = torch.where(t == 0, torch.ones_like(z), z)
-    u_box = torch.where(held, (u + t / zsafe) / D, torch.zeros_like(v))
-    zu = D * z
-    curv = torch.where((ws > 0) & ~held, ws / (zu * zu), torch.zeros_like(v))
-    # "margin": how far every element is from changing its set -- the distance from S to the nearer bound, unscaled
-    margin = (S - lbs).abs().minimum((S - ubs).abs()) * D
-    x, z, u = D * x, D * z, u / D
-    y = u_box * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E if m > 0 else None
-    if trace is not None:
-        trace.update(n_factor=n_factor)
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it, "u_box": u_box, "curv": curv, "margin": margin,
-            "n_factor": n_factor}
+class LogTerm:
+    """-w' log x for oracle.solve_box_qp(term=): the barrier is -w_i log(xs_i) plus a constant in the scaled space, so ws = w"""
+
+    def __init__(self, w):
+        self.w = w
+
+    def scale(self, D):
+        pass
+
+    def step(self, v, rho):
+        return prox(v, self.w / rho)
+
+    def finish(self, z, u, rho, lbs, ubs, D):
+        """the step once more at the returned iterate, in the scaled space"""
+        ws = self.w
+        v = z + u
+        t = ws / rho + torch.zeros_like(v)
+        S = self.step(v, rho)
+        held = S != torch.minimum(torch.maximum(S, lbs), ubs)
+        zsafe = torch.where(t == 0, torch.ones_like(z), z)
+        u_box = torch.where(held, (u + t / zsafe) / D, torch.zeros_like(v))
+        zu = D * z
+        curv = torch.where((ws > 0) & ~held, ws / (zu * zu), torch.zeros_like(v))
+        # "margin": how far every element is from changing its set -- the distance from S to the nearer bound, unscaled
+        margin = (S - lbs).abs().minimum((S - ubs).abs()) * D
+        return {"u_box": u_box, "curv": curv, "margin": margin}
+
+
+class LogPlain(LogTerm):
+    """the iterate of a kernel that ignores the barrier"""
+
+    def step(self, v, rho):
+        return v
 
 
 def sets(sol, w):
     """-> {barrier_free, barrier_clamped, zero_free, zero_clamped}: bool (B, n, 1) each, a partition"""
     clamped, bar = sol["u_box"] != 0, w > 0
     return {"barrier_free": bar & ~clamped, "barrier_clamped": bar & clamped, "zero_free": ~bar & ~clamped, "zero_clamped": ~bar & clamped}
-
-
-def truth(r, inp, dtype, step="log", w_zero=False):
-    """The truth of row r on `inp` (seven tensors) in `dtype`, pinned to the row's K"""
-    d = [None if t is None else t.to(dtype) for t in inp]
-    if w_zero:
-        d[6] = torch.zeros_like(d[6])
-    return solve_log(*d, O.make_control(**T.control(r)), alpha=r["alpha"], step=step)
-
-
-@functools.lru_cache(maxsize=None)
-def row_truth(key, cus, table="ROWS"):
-    """-> (idx, t32 or None, t64) of a row at `cus` compute units: the problems `tier_table.sample` picks, computed once and shared"""
-    r = globals()[table][key]
-    B = T.batch(r, cus)
-    idx = T.sample(B)
-    sub = log_inputs(r, B, idx)
-    t64 = truth(r, sub, torch.float64)
-    t32 = truth(r, sub, torch.float32) if r["dtype"] == "f32" else None
-    return idx, t32, t64
 
 
 def grad_recipe(cot, sol, Q, A, lb, ub, w):
@@ -268,14 +172,6 @@ def grad_recipe(cot, sol, Q, A, lb, ub, w):
     return dict(dQ=dQ, dp=dp, dA=dA, db=db, dlb=dlb, dub=dub, dw=torch.where(w > 0, -dp / zsafe, torch.zeros_like(dp)))
 
 
-def truth_grads(r, inp, sol, cot, dtype):
-    Q, _, A, _, lb, ub, w = [None if t is None else t.to(dtype) for t in inp]
-    return grad_recipe(cot.to(dtype), sol, Q, A, lb, ub, w)
-
-
-cot_of = LT.cot_of
-
-
 def stop_inputs(dtype):
     n, B, seed = STOP
     qp = O.create_qp_data(n, B, seed=seed, dtype=torch.float64)
@@ -286,13 +182,16 @@ def stop_inputs(dtype):
     return tuple(None if t is None else t.to(dtype) for t in qp + (w,))
 
 
-@functools.lru_cache(maxsize=None)
-def stop_truth(dtype):
-    """The truth of a solve that stops by itself"""
-    return solve_log(*stop_inputs(dtype), O.make_control(**STOP_CONTROL))
+class LogTable(TT.Table):
+    def inputs(self, r, B, idx=None):
+        """(Q, p, A, b, lb, ub, w): the lower bounds are log_data's (the kind "poslb" moves them; 0 < lb <= ub stays in float32)"""
+        *qp, w, lb = super().inputs(r, B, idx)
+        return (*qp[:4], lb, qp[5], w)
 
 
-def excused(t64, bar_z):
-    """bool (B, n, 1): elements whose membership of the clamped set may differ from the float64 truth's -- in that truth their S sits
-    within the bar for z of a bound"""
-    return t64["margin"] < bar_z
+TERM = LogTable(name="log", weights=1, aux="curv", grads=GRADS7, term=LogTerm, others={"plain": (LogPlain, ())},
+                far_keys=("z",), data=log_data, stop_inputs=stop_inputs, label=lambda sol: sol["u_box"] != 0, what="clamped set",
+                grad_recipe=grad_recipe, recipe_data=(0,), tables={"ROWS": ROWS, "GRAD_ROWS": GRAD_ROWS}, share=SHARE, empty=EMPTY)
+solve_log, log_inputs, truth = TERM.solve, TERM.inputs, TERM.truth
+row_truth, truth_grads, stop_truth = TERM.row_truth, TERM.truth_grads, TERM.stop_truth
+cot_of, excused = TT.cot_of, TT.excused

@@ -2,8 +2,9 @@
 f_i(x) = s_i0 x + sum_k (s_ik - s_i,k-1) (x - c_ik)_+, K <= 3 sorted kinks and K + 1 non-decreasing slopes per element -- and their truth
 (no GPU needed to import this module).  tests/test_pwl_table.py checks them on the CPU, tests/test_gpu_pwl.py runs them.
 
-The truth is `solve_pwl`: the oracle's iteration restated with one other z-update, on the oracle's own ``resolve_control``,
-``equilibrate`` and ``kkt_matrix``, exactly as ``l1_table.solve_l1`` and ``soft_table.solve_soft`` are.  In the scaled space of the loop
+The truth is `solve_pwl`: the oracle's own iteration (``oracle.solve_box_qp``) with `PwlTerm` as its ``term=`` -- the one other
+z-update -- through the record `TERM` (tests/term_table.py), exactly as ``l1_table.solve_l1`` and ``soft_table.solve_soft`` are.  In the
+scaled space of the loop
 (x = D xs) the data are ss_k = D s_k, cs_k = c_k / D, and with v = xh + u, t_k = ss_k / rho (true divisions, the rho of this iteration)
 the step scans the kinks from the top, in exactly this compare form:
 
@@ -33,6 +34,7 @@ import torch
 from oracle import boxqp_oracle as O
 import l1_table as LT
 import soft_table as ST
+import term_table as TT
 import tier_table as T
 
 K_FAR, K_NEAR, K_EVENT = LT.K_FAR, LT.K_NEAR, LT.K_EVENT
@@ -99,19 +101,6 @@ def pwl_data(r, i, lb, ub):
     return torch.cat((-(w0 + wl), -w0, w1, w1 + wu), 1), torch.cat((lo, c, hi), 1)
 
 
-def pwl_inputs(r, B, idx=None):
-    """(Q, p, A, b, lb, ub, s, c) of the batch -- or of the problems `idx` of it -- in the row's dtype"""
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    idx = list(range(B)) if idx is None else list(idx)
-    base = [None if t is None else t.double() for t in T.inputs(dict(r, dtype="f64"), B, idx)]
-    if r.get("pwl") == "allinf":
-        base[4] = torch.full_like(base[4], -math.inf)
-        base[5] = torch.full_like(base[5], math.inf)
-    sc = [pwl_data(r, i, base[4][k], base[5][k]) for k, i in enumerate(idx)]
-    base += [torch.stack([x[j] for x in sc]) for j in range(2)]
-    return tuple(None if t is None else t.to(dt) for t in base)      # (rounding to float32 is monotone: sorted stays sorted)
-
-
 def pad(s, c, K=PWL_K):
     """The same term with K kinks: kinks at +inf and the last slope repeated, at the top"""
     k = c.shape[2]
@@ -142,103 +131,48 @@ def piece_of(v, t, cs):
     return out
 
 
-def solve_pwl(Q, p, A, b, lb, ub, s, c, control, alpha=1.0, trace=None, step="pwl"):
-    """The oracle's forward (oracle.solve_box_qp: same operations, same order) with the piecewise-linear step; returns its dict plus
-    "piece", "u_box", and "lams" built from u_box.  step = "plain" / "band": the iterate of a kernel that ignores the term / the middle
-    kink (the outer kinks with the outer slopes and 0 between them) -- what the rows must be far from."""
-    B, n = Q.shape[0], p.shape[1]
-    m = 0 if A is None else A.shape[1]
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    cr = O.resolve_control(control, n)
-    rho = cr.rho
-    if cr.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, cr.beta, True)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    ss, cs = [D * sk for sk in _cols(s)], [ck / D for ck in _cols(c)]
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor = 1
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * cr.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = cr.adaptive_rho
-    xv = None
-    it = 0
-    for it in range(cr.max_iters):
-        if (cr.adaptive_rho and it % cr.adaptive_rho_iter == 0 and 0 < it < cr.adaptive_rho_max_iter and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            if bool((ratio > cr.adaptive_rho_tol).sum() > 0) or bool((ratio < 1 / cr.adaptive_rho_tol).sum() > 0):
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        x = xv[:, :n, :]
-        z_old = z
-        xh = x if alpha == 1.0 else alpha * x + (1 - alpha) * z_old
-        v = xh + u
-        if step == "pwl":
-            S = prox(v, [sk / rho for sk in ss], cs)
-        elif step == "band":
-            S = prox(v, [ss[0] / rho, 0 * ss[0] / rho, ss[-1] / rho], [cs[0], cs[-1]])
-        else:
-            S = v
-        z = torch.minimum(torch.maximum(S, lbs), ubs)
-        r = x - z
-        sres = rho * (z - z_old)
-        u = u + (r if alpha == 1.0 else xh - z)
-        if it % cr.check_solved == 0:
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * sres)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx_inf = O._inf_norm_cols(torch.matmul(Qs, x) / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = cr.eps_abs + cr.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = cr.eps_abs + cr.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                break
-    # ---- the scan once more at the returned iterate, in the scaled space (z == cs_k by assignment on a kink)
-    v = z + u
-    t = [sk / rho + torch.zeros_like(v) for sk in ss]
-    piece = piece_of(v, t, cs)
-    S = prox(v, t, cs)
-    u_box = (S - torch.minimum(torch.maximum(S, lbs), ubs)) / D      # (S - z with the clamp taken again: exactly zero off the bounds)
-    # "margin": how far every element is from changing its set -- the two comparisons at every kink and the distance from S to the
-    # nearer bound, unscaled (a comparison with an infinite kink is infinitely far)
-    margin = (S - lbs).abs().minimum((S - ubs).abs())
-    for k in range(1, len(t)):
-        d = v - cs[k - 1]
-        margin = torch.minimum(margin, torch.minimum((d - t[k]).abs(), (d - t[k - 1]).abs()))
-    margin = margin * D
-    x, z, u = D * x, D * z, u / D
-    y = u_box * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E if m > 0 else None
-    if trace is not None:
-        trace.update(n_factor=n_factor)
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it, "piece": piece, "u_box": u_box, "margin": margin,
-            "n_factor": n_factor}
+class PwlTerm:
+    """sum_i f_i(x_i) for oracle.solve_box_qp(term=): ss_k = D s_k, cs_k = c_k / D, t_k = ss_k / rho"""
+
+    def __init__(self, s, c):
+        self.s, self.c = s, c
+
+    def scale(self, D):
+        self.ss, self.cs = [D * sk for sk in _cols(self.s)], [ck / D for ck in _cols(self.c)]
+
+    def step(self, v, rho):
+        return prox(v, [sk / rho for sk in self.ss], self.cs)
+
+    def finish(self, z, u, rho, lbs, ubs, D):
+        """the scan once more at the returned iterate, in the scaled space (z == cs_k by assignment on a kink)"""
+        cs = self.cs
+        v = z + u
+        t = [sk / rho + torch.zeros_like(v) for sk in self.ss]
+        piece = piece_of(v, t, cs)
+        S = prox(v, t, cs)
+        u_box = (S - torch.minimum(torch.maximum(S, lbs), ubs)) / D      # (S - z with the clamp taken again: exactly zero off the bounds)
+        # "margin": how far every element is from changing its set -- the two comparisons at every kink and the distance from S to the
+        # nearer bound, unscaled (a comparison with an infinite kink is infinitely far)
+        margin = (S - lbs).abs().minimum((S - ubs).abs())
+        for k in range(1, len(t)):
+            d = v - cs[k - 1]
+            margin = torch.minimum(margin, torch.minimum((d - t[k]).abs(), (d - t[k - 1]).abs()))
+        return {"piece": piece, "u_box": u_box, "margin": margin * D}
+
+
+class PwlPlain(PwlTerm):
+    """the iterate of a kernel that ignores the term (the classification behind the loop is the term's all the same)"""
+
+    def step(self, v, rho):
+        return v
+
+
+class PwlAsBand(PwlTerm):
+    """the iterate of a kernel that ignores the middle kink: the outer kinks with the outer slopes and 0 between them"""
+
+    def step(self, v, rho):
+        ss, cs = self.ss, self.cs
+        return prox(v, [ss[0] / rho, 0 * ss[0] / rho, ss[-1] / rho], [cs[0], cs[-1]])
 
 
 def sets(sol):
@@ -247,24 +181,6 @@ def sets(sol):
     out = {f"p{k}": (sol["piece"] == k) & ~clamped for k in PIECES}
     out["clamped"] = clamped
     return out
-
-
-def truth(r, inp, dtype, step="pwl"):
-    """The truth of row r on `inp` (eight tensors) in `dtype`, pinned to the row's K"""
-    d = [None if t is None else t.to(dtype) for t in inp]
-    return solve_pwl(*d, O.make_control(**T.control(r)), alpha=r["alpha"], step=step)
-
-
-@functools.lru_cache(maxsize=None)
-def row_truth(key, cus, table="ROWS"):
-    """-> (idx, t32 or None, t64) of a row at `cus` compute units: the problems `tier_table.sample` picks, computed once and shared"""
-    r = globals()[table][key]
-    B = T.batch(r, cus)
-    idx = T.sample(B)
-    sub = pwl_inputs(r, B, idx)
-    t64 = truth(r, sub, torch.float64)
-    t32 = truth(r, sub, torch.float32) if r["dtype"] == "f32" else None
-    return idx, t32, t64
 
 
 def grad_recipe(cot, sol, Q, A, lb, ub, c):
@@ -285,14 +201,6 @@ def grad_recipe(cot, sol, Q, A, lb, ub, c):
                 dc=torch.cat([torch.where(on & (piece == 2 * k - 1), dlb_e + dub_e, zero) for k in range(1, K + 1)], 2))
 
 
-def truth_grads(r, inp, sol, cot, dtype):
-    d = [None if t is None else t.to(dtype) for t in inp]
-    return grad_recipe(cot.to(dtype), sol, d[0], d[2], d[4], d[5], d[7])
-
-
-cot_of = LT.cot_of
-
-
 def stop_inputs(dtype):
     n, B, seed = STOP
     qp = ST.stop_inputs(torch.float64)
@@ -304,13 +212,11 @@ def stop_inputs(dtype):
     return tuple(None if t is None else t.to(dtype) for t in qp[:6] + (s, k))
 
 
-@functools.lru_cache(maxsize=None)
-def stop_truth(dtype):
-    """The truth of a solve that stops by itself"""
-    return solve_pwl(*stop_inputs(dtype), O.make_control(**STOP_CONTROL))
-
-
-def excused(t64, bar_z):
-    """bool (B, n, 1): elements whose `piece` may differ from the float64 truth's -- in that truth they sit within the bar for z of a
-    comparison of the scan or of a bound"""
-    return t64["margin"] < bar_z
+# the steps the rows must be far from: l1eq has no outer kinks and bandeq IS the band
+TERM = TT.Table(name="pwl", weights=1, aux="piece", grads=GRADS8, term=PwlTerm,
+                others={"plain": (PwlPlain, ()), "band": (PwlAsBand, ("l1eq", "bandeq"))}, far_keys=("z",), data=pwl_data,
+                stop_inputs=stop_inputs, label=lambda sol: sol["piece"].double(), what="piece", grad_recipe=grad_recipe,
+                recipe_data=(1,), tables={"ROWS": ROWS, "GRAD_ROWS": GRAD_ROWS}, share=SHARE, empty=EMPTY, pooled_below=129)
+solve_pwl, pwl_inputs, truth = TERM.solve, TERM.inputs, TERM.truth
+row_truth, truth_grads, stop_truth = TERM.row_truth, TERM.truth_grads, TERM.stop_truth
+cot_of, excused = TT.cot_of, TT.excused

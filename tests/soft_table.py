@@ -2,8 +2,8 @@
 -- and their truth (no GPU needed to import this module).  tests/test_soft_table.py checks them on the CPU, tests/test_gpu_soft.py
 runs them.
 
-The truth is `solve_soft`: the oracle's iteration restated with one other z-update, on the oracle's own ``resolve_control``,
-``equilibrate`` and ``kkt_matrix``, exactly as ``l1_table.solve_l1`` is.  In the scaled space of the loop (x = D xs) the data are
+The truth is `solve_soft`: the oracle's own iteration (``oracle.solve_box_qp``) with `SoftTerm` as its ``term=`` -- the one other
+z-update -- through the record `TERM` (tests/term_table.py), exactly as ``l1_table.solve_l1`` is.  In the scaled space of the loop (x = D xs) the data are
 wls = D wl, wus = D wu, los = lo / D, his = hi / D, and with v = xh + u, tl = wls / rho, tu = wus / rho (true divisions, the rho
 of this iteration), dh = v - his, dl = v - los
 
@@ -23,13 +23,13 @@ The pinned rows are l1_table's tier rows (``tier_table`` records, the same K, al
 and five kinds more: lo = hi with wl = wu (the L1 term), lo = -inf everywhere (a hinge), zero weights on half the elements, a
 kink on a hard bound, every hard bound infinite.
 """
-import functools
 import math
 
 import torch
 
 from oracle import boxqp_oracle as O
 import l1_table as LT
+import term_table as TT
 import tier_table as T
 
 K_FAR, K_NEAR, K_EVENT = LT.K_FAR, LT.K_NEAR, LT.K_EVENT
@@ -110,127 +110,61 @@ def soft_data(r, i, lb, ub):
     return wl, wu, lo, hi
 
 
-def soft_inputs(r, B, idx=None):
-    """(Q, p, A, b, lb, ub, wl, wu, lo, hi) of the batch -- or of the problems `idx` of it -- in the row's dtype"""
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    idx = list(range(B)) if idx is None else list(idx)
-    base = [None if t is None else t.double() for t in T.inputs(dict(r, dtype="f64"), B, idx)]
-    if r.get("soft") == "allinf":
-        base[4] = torch.full_like(base[4], -math.inf)
-        base[5] = torch.full_like(base[5], math.inf)
-    sd = [soft_data(r, i, base[4][k], base[5][k]) for k, i in enumerate(idx)]
-    base += [torch.stack([x[j] for x in sd]) for j in range(4)]
-    return tuple(None if t is None else t.to(dt) for t in base)      # (rounding to float32 is monotone: lo <= hi stays, lo == hi too)
-
-
 def prox(v, tl, tu, los, his):
     """S of the step, in exactly its branch form"""
     dh, dl = v - his, v - los
     return torch.where(dh > tu, v - tu, torch.where(dl < -tl, v + tl, torch.minimum(torch.maximum(v, los), his)))
 
 
-def solve_soft(Q, p, A, b, lb, ub, wl, wu, lo, hi, control, alpha=1.0, trace=None, step="soft"):
-    """The oracle's forward (oracle.solve_box_qp: same operations, same order) with the soft band's step; returns its dict plus
-    "zone", "u_box", and "lams" built from u_box.  step = "plain" / "l1": the iterate of a kernel that ignores the band / takes it for
-    an L1 term around its middle -- what the rows must be far from."""
-    B, n = Q.shape[0], p.shape[1]
-    m = 0 if A is None else A.shape[1]
-    dt = p.dtype
-    p_inf = O._inf_norm_cols(p)
-    cr = O.resolve_control(control, n)
-    rho = cr.rho
-    if cr.scale:
-        sp = O.equilibrate(Q, p, A, b, lb, ub, cr.beta, True)
-    else:
-        sp = O.ScaledProblem(Q, p, A, b, lb, ub, 1.0, 1.0)
-    Qs, ps, As, bs, lbs, ubs, D, E = sp.Q, sp.p, sp.A, sp.b, sp.lb, sp.ub, sp.D, sp.E
-    wls, wus, los, his = D * wl, D * wu, lo / D, hi / D
-    if step == "l1":
-        l1w, l1c = D * ((wl + wu) / 2), ((lo + hi) / 2) / D
-    if rho is None:
-        rho = torch.linalg.matrix_norm(Qs, keepdim=True) / n ** 0.5
-        rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-    eye = torch.eye(n, dtype=dt).unsqueeze(0)
-    M = Qs + rho * eye
-    if m > 0:
-        M = O.kkt_matrix(M, As, torch.zeros(B, m, m, dtype=dt))
-    LU, piv = torch.linalg.lu_factor(M)
-    n_factor = 1
-    x = torch.zeros(B, n, 1, dtype=dt)
-    z = torch.zeros(B, n, 1, dtype=dt)
-    u = torch.zeros(B, n, 1, dtype=dt)
-    tiny = torch.ones(1) * O.TINY
-    thr = torch.ones(1) * cr.adaptive_rho_threshold
-    r_inf = s_inf = pri_scale = dua_scale = None
-    wants_rho = cr.adaptive_rho
-    xv = None
-    it = 0
-    for it in range(cr.max_iters):
-        if (cr.adaptive_rho and it % cr.adaptive_rho_iter == 0 and 0 < it < cr.adaptive_rho_max_iter and bool(torch.any(wants_rho))):
-            ratio = (torch.clamp(r_inf / pri_scale, min=O.TINY) / torch.clamp(s_inf / dua_scale, min=O.TINY)) ** 0.5
-            if bool((ratio > cr.adaptive_rho_tol).sum() > 0) or bool((ratio < 1 / cr.adaptive_rho_tol).sum() > 0):
-                rho = rho * torch.logical_not(wants_rho) + (rho * ratio) * wants_rho
-                rho = torch.clamp(rho, min=cr.rho_min, max=cr.rho_max)
-                M[:, :n, :n] = Qs + rho * eye
-                LU, piv = torch.linalg.lu_factor(M)
-                n_factor += 1
-        rhs = -ps + rho * (z - u)
-        if m > 0:
-            rhs = torch.cat((rhs, bs), 1)
-        xv = torch.linalg.lu_solve(LU, piv, rhs)
-        x = xv[:, :n, :]
-        z_old = z
-        xh = x if alpha == 1.0 else alpha * x + (1 - alpha) * z_old
-        v = xh + u
-        if step == "soft":
-            S = prox(v, wls / rho, wus / rho, los, his)
-        elif step == "l1":
-            S = LT.shrink(v, l1w / rho, l1c)
-        else:
-            S = v
-        z = torch.minimum(torch.maximum(S, lbs), ubs)
-        r = x - z
-        s = rho * (z - z_old)
-        u = u + (r if alpha == 1.0 else xh - z)
-        if it % cr.check_solved == 0:
-            r_inf = O._inf_norm_cols(D * r)
-            s_inf = O._inf_norm_cols(D * s)
-            x_inf = O._inf_norm_cols(D * x)
-            z_inf = O._inf_norm_cols(D * z)
-            y_inf = O._inf_norm_cols(rho * D * u)
-            qx_inf = O._inf_norm_cols(torch.matmul(Qs, x) / D)
-            pri_scale = torch.maximum(torch.maximum(x_inf, z_inf), tiny)
-            tol_p = cr.eps_abs + cr.eps_rel * pri_scale
-            dua_scale = torch.maximum(torch.maximum(torch.maximum(y_inf, qx_inf), p_inf), tiny)
-            tol_d = cr.eps_abs + cr.eps_rel * dua_scale
-            solved = torch.logical_and(r_inf < tol_p, s_inf < tol_d)
-            wants_rho = torch.logical_or(r_inf > torch.maximum(tol_p, thr), s_inf > torch.maximum(tol_d, thr))
-            if torch.all(solved).item():
-                break
-    # ---- the step once more at the returned iterate, in the scaled space (z == his / los by assignment on a kink)
-    v = z + u
-    tl, tu = wls / rho + torch.zeros_like(v), wus / rho + torch.zeros_like(v)
-    dh, dl = v - his, v - los
-    one = torch.ones_like(v)
-    zone = torch.where(dh > tu, 2 * one, torch.where(dl < -tl, -2 * one, torch.where((v >= his) & (tu > 0), one,
-                       torch.where((v <= los) & (tl > 0), -one, 0 * one))))
-    S = prox(v, tl, tu, los, his)
-    u_box = (S - torch.minimum(torch.maximum(S, lbs), ubs)) / D      # (S - z with the clamp taken again: exactly zero off the bounds)
-    # "margin": how far every element is from changing its set -- the four comparisons of the zone and the distance from S to the
-    # nearer bound, unscaled (a comparison with an infinite kink is infinitely far)
-    inf = torch.full_like(v, math.inf)
-    margin = torch.minimum((dh - tu).abs(), (dl + tl).abs())
-    margin = torch.minimum(margin, torch.where(tu > 0, dh.abs(), inf))
-    margin = torch.minimum(margin, torch.where(tl > 0, dl.abs(), inf))
-    margin = torch.minimum(margin, (S - lbs).abs().minimum((S - ubs).abs())) * D
-    x, z, u = D * x, D * z, u / D
-    y = u_box * rho
-    lams = torch.cat((torch.relu(-y), torch.relu(y)), 1)
-    nus = xv[:, -m:, :] * E if m > 0 else None
-    if trace is not None:
-        trace.update(n_factor=n_factor)
-    return {"x": x, "z": z, "u": u, "lams": lams, "nus": nus, "rho": rho, "iter": it, "zone": zone, "u_box": u_box, "margin": margin,
-            "n_factor": n_factor}
+class SoftTerm:
+    """wl (lo - x)+ + wu (x - hi)+ for oracle.solve_box_qp(term=): wls = D wl, wus = D wu, los = lo / D, his = hi / D"""
+
+    def __init__(self, wl, wu, lo, hi):
+        self.wl, self.wu, self.lo, self.hi = wl, wu, lo, hi
+
+    def scale(self, D):
+        self.wls, self.wus, self.los, self.his = D * self.wl, D * self.wu, self.lo / D, self.hi / D
+
+    def step(self, v, rho):
+        return prox(v, self.wls / rho, self.wus / rho, self.los, self.his)
+
+    def finish(self, z, u, rho, lbs, ubs, D):
+        """the step once more at the returned iterate, in the scaled space (z == his / los by assignment on a kink)"""
+        los, his = self.los, self.his
+        v = z + u
+        tl, tu = self.wls / rho + torch.zeros_like(v), self.wus / rho + torch.zeros_like(v)
+        dh, dl = v - his, v - los
+        one = torch.ones_like(v)
+        zone = torch.where(dh > tu, 2 * one, torch.where(dl < -tl, -2 * one, torch.where((v >= his) & (tu > 0), one,
+                           torch.where((v <= los) & (tl > 0), -one, 0 * one))))
+        S = prox(v, tl, tu, los, his)
+        u_box = (S - torch.minimum(torch.maximum(S, lbs), ubs)) / D      # (S - z with the clamp taken again: exactly zero off the bounds)
+        # "margin": how far every element is from changing its set -- the four comparisons of the zone and the distance from S to the
+        # nearer bound, unscaled (a comparison with an infinite kink is infinitely far)
+        inf = torch.full_like(v, math.inf)
+        margin = torch.minimum((dh - tu).abs(), (dl + tl).abs())
+        margin = torch.minimum(margin, torch.where(tu > 0, dh.abs(), inf))
+        margin = torch.minimum(margin, torch.where(tl > 0, dl.abs(), inf))
+        margin = torch.minimum(margin, (S - lbs).abs().minimum((S - ubs).abs())) * D
+        return {"zone": zone, "u_box": u_box, "margin": margin}
+
+
+class SoftPlain(SoftTerm):
+    """the iterate of a kernel that ignores the band (the classification behind the loop is the band's all the same)"""
+
+    def step(self, v, rho):
+        return v
+
+
+class SoftAsL1(SoftTerm):
+    """the iterate of a kernel that takes the band for an L1 term around its middle"""
+
+    def scale(self, D):
+        super().scale(D)
+        self.l1w, self.l1c = D * ((self.wl + self.wu) / 2), ((self.lo + self.hi) / 2) / D
+
+    def step(self, v, rho):
+        return LT.shrink(v, self.l1w / rho, self.l1c)
 
 
 def sets(sol):
@@ -239,26 +173,6 @@ def sets(sol):
     out = {f"z{k}": (sol["zone"] == k) & ~clamped for k in ZONES}
     out["clamped"] = clamped
     return out
-
-
-def truth(r, inp, dtype, step="soft", w_zero=False):
-    """The truth of row r on `inp` (ten tensors) in `dtype`, pinned to the row's K"""
-    d = [None if t is None else t.to(dtype) for t in inp]
-    if w_zero:
-        d[6], d[7] = torch.zeros_like(d[6]), torch.zeros_like(d[7])
-    return solve_soft(*d, O.make_control(**T.control(r)), alpha=r["alpha"], step=step)
-
-
-@functools.lru_cache(maxsize=None)
-def row_truth(key, cus, table="ROWS"):
-    """-> (idx, t32 or None, t64) of a row at `cus` compute units: the problems `tier_table.sample` picks, computed once and shared"""
-    r = globals()[table][key]
-    B = T.batch(r, cus)
-    idx = T.sample(B)
-    sub = soft_inputs(r, B, idx)
-    t64 = truth(r, sub, torch.float64)
-    t32 = truth(r, sub, torch.float32) if r["dtype"] == "f32" else None
-    return idx, t32, t64
 
 
 def grad_recipe(cot, sol, Q, A, lb, ub, lo, hi):
@@ -279,14 +193,6 @@ def grad_recipe(cot, sol, Q, A, lb, ub, lo, hi):
                 dlo=torch.where(Kl, dlb_e + dub_e, zero), dhi=torch.where(Kh, dlb_e + dub_e, zero))
 
 
-def truth_grads(r, inp, sol, cot, dtype):
-    d = [None if t is None else t.to(dtype) for t in inp]
-    return grad_recipe(cot.to(dtype), sol, d[0], d[2], d[4], d[5], d[8], d[9])
-
-
-cot_of = LT.cot_of
-
-
 def stop_inputs(dtype):
     n, B, seed = STOP
     qp = LT.stop_inputs(torch.float64)
@@ -298,13 +204,11 @@ def stop_inputs(dtype):
     return tuple(None if t is None else t.to(dtype) for t in qp[:6] + (wl, wu, lo, hi))
 
 
-@functools.lru_cache(maxsize=None)
-def stop_truth(dtype):
-    """The truth of a solve that stops by itself"""
-    return solve_soft(*stop_inputs(dtype), O.make_control(**STOP_CONTROL))
-
-
-def excused(t64, bar_z):
-    """bool (B, n, 1): elements whose `zone` may differ from the float64 truth's -- in that truth they sit within the bar for z of a
-    comparison of the zone or of a bound"""
-    return t64["margin"] < bar_z
+# the steps the rows must be far from: l1eq IS the L1 iterate and onesided has no middle
+TERM = TT.Table(name="soft", weights=2, aux="zone", grads=GRADS10, term=SoftTerm,
+                others={"plain": (SoftPlain, ()), "l1": (SoftAsL1, ("l1eq", "onesided"))}, far_keys=("z",), data=soft_data,
+                stop_inputs=stop_inputs, label=lambda sol: sol["zone"].double(), what="zone", grad_recipe=grad_recipe,
+                recipe_data=(2, 3), tables={"ROWS": ROWS, "GRAD_ROWS": GRAD_ROWS}, share=SHARE, empty=EMPTY, pooled_below=129)
+solve_soft, soft_inputs, truth = TERM.solve, TERM.inputs, TERM.truth
+row_truth, truth_grads, stop_truth = TERM.row_truth, TERM.truth_grads, TERM.stop_truth
+cot_of, excused = TT.cot_of, TT.excused

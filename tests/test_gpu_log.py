@@ -17,193 +17,54 @@ import torch
 import lqp_py_amd as L
 from lqp_py_amd import _lib
 import lqp_py_amd.solve_box_qp_admm_torch as SB
-from oracle import boxqp_oracle as O
 import fp_table as FT
 import log_table as G
+import term_checks as C
+from term_checks import _control, _pick, _report, dev, cus          # (the fixtures, by name)
 import tier_table as T
 
 pytestmark = pytest.mark.gpu
-HIP_KEYS = ("linsolve", "launch_mode")
-VALUES = tuple(k for k in G.OUTPUTS if k != "curv")
-
-
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    _lib.load()
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def cus(dev):
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _control(r, **extra):
-    c = O.make_control(**T.control(r), **{k: r["ctl"][k] for k in HIP_KEYS if k in r["ctl"]}, **extra)
-    if r.get("alpha", 1.0) != 1.0:
-        c["alpha"] = r["alpha"]
-    return c
-
-
-def _pick(v, idx):
-    if torch.is_tensor(v) and v.dim() > 0:
-        return v[torch.tensor(idx).to(v.device)].detach().cpu()
-    return v
-
-
-def _report(what, res):
-    for k, rec in res.items():
-        print(what, k, "err %.3e" % rec["err"], "bar %.3e" % rec["bar"], "ratio", rec.get("ratio"))
-
-
-def _set_check(what, u_box, t64, bar_z):
-    """-> list of failures: the clamped set against the float64 truth's, exact outside the margin, at most 1 % of a problem inside it"""
-    bad = []
-    diff = (u_box != 0) != (t64["u_box"] != 0)
-    ok = G.excused(t64, bar_z)
-    n = u_box.shape[1]
-    for b in range(u_box.shape[0]):
-        nd, nbad = int(diff[b].sum()), int((diff[b] & ~ok[b]).sum())
-        print(what, "problem", b, "clamped set differs on", nd, "of", n, "outside the margin:", nbad)
-        if nbad or nd > 0.01 * n:
-            bad.append(("clamped set", b, nd, nbad))
-    return bad
+LAYER = (G.TERM, L.torch_solve_box_qp_log, L.SolveBoxQPLog)
 
 
 @pytest.mark.parametrize("key", list(G.ROWS))
 def test_row_against_the_truth(dev, cus, monkeypatch, key):
-    r = G.ROWS[key]
-    B = T.batch(r, cus)
-    args = [None if t is None else t.to(dev) for t in G.log_inputs(r, B)]
-    for k, v in r["env"].items():
-        monkeypatch.setenv(k, v)
-    ctl = _control(r)
-    before = dict(ctl)
-    sol = L.torch_solve_box_qp_log(*args, ctl)
-    st, bad = sol["_stats"], []
-    if ctl != before:
-        bad.append(("control mutated", {k: (before.get(k), ctl.get(k)) for k in set(ctl) | set(before) if before.get(k) != ctl.get(k)}))
-    if r["ctl"].get("sync", True) is False:
-        # the module's un-synchronised path: the same schedule, enqueued whole; nothing reports back but the device's status block
-        x = L.SolveBoxQPLog(control=_control(r, sync=False))(*args)
-        mst = SB.last_forward_status(dev)
-        L.synchronize()
-        if mst["iters"] != r["K"] or not torch.equal(x, sol["x"]):
-            bad.append(("sync=False", mst["iters"], bool(torch.equal(x, sol["x"]))))
-    idx, t32, t64 = G.row_truth(key, cus)
-    if sol["iter"] != r["K"]:
-        bad.append(("iter", sol["iter"], r["K"]))
-    print(key, "stats", {k: st[k] for k in ("linsolve_used", "loop_workgroups", "factor_launches", "mode_used", "loop_kind", "n_factor")})
-    bad += [("sig", k, st[k], v) for k, v in r["sig"].items() if st[k] != v]
-    if st["n_factor"] != t64["n_factor"] or (t32 is not None and t32["n_factor"] != t64["n_factor"]):
-        bad.append(("n_factor", st["n_factor"], t64["n_factor"]))
-    res = T.compare(r, {k: _pick(sol[k], idx) for k in VALUES}, t32, t64, keys=VALUES)
+    args, got, idx, t32, t64, res = C.row_against_the_truth(LAYER, dev, cus, monkeypatch, key)
     # curv: the elements inside the margin take the float64 truth's value on both sides (see the module's docstring)
     ex = G.excused(t64, res["z"]["bar"])
     c64 = t64["curv"]
-    chip = torch.where(ex, c64, _pick(sol["curv"], idx).double())
+    chip = torch.where(ex, c64, got["curv"].double())
     c32 = None if t32 is None else dict(t32, curv=torch.where(ex, c64, t32["curv"].double()))
-    res.update(T.compare(r, {"curv": chip}, c32, t64, keys=("curv",)))
-    _report(key, res)
-    bad += [("value", k, rec) for k, rec in res.items() if not rec["ok"]]
-    bad += _set_check(key, _pick(sol["u_box"], idx), t64, res["z"]["bar"])
-    w = _pick(args[6], idx)
-    if not bool((_pick(sol["z"], idx)[w > 0] > 0).all()):
-        bad.append(("z > 0 on the barrier elements",))
-    assert not bad, (key, bad)
+    rec = T.compare(G.ROWS[key], {"curv": chip}, c32, t64, keys=("curv",))
+    _report(key, rec)
+    assert rec["curv"]["ok"], (key, rec)
+    assert bool((got["z"][_pick(args[6], idx) > 0] > 0).all()), (key, "z > 0 on the barrier elements")
 
 
 @pytest.mark.parametrize("name", G.SAME_BITS)
 def test_zero_weights_are_the_plain_forward_bit_for_bit(dev, cus, monkeypatch, name):
-    r = dict(T.ROW_BY_NAME[name], log="plain", l1="plain", alpha=1.0)
-    B = T.batch(r, cus)
-    args = [None if t is None else t.to(dev) for t in G.log_inputs(r, B)]
-    for k, v in r["env"].items():
-        monkeypatch.setenv(k, v)
-    plain = L.torch_solve_box_qp(*args[:6], _control(r))
-    zero = L.torch_solve_box_qp_log(*args[:6], torch.zeros_like(args[6]), _control(r))
-    assert plain["iter"] == zero["iter"] == r["K"]
-    assert all(zero["_stats"][k] == v for k, v in r["sig"].items() if k != "n_factor"), zero["_stats"]
-    assert torch.equal(plain["x"], zero["x"])
-    assert torch.equal(plain["z"], zero["z"]) and torch.equal(plain["u"], zero["u"])
+    zero = C.zero_term_is_the_plain_forward(LAYER, dev, cus, monkeypatch, name)
     assert not bool(zero["curv"].any()) and bool(torch.isfinite(zero["u_box"]).all())
 
 
 @pytest.mark.parametrize("name", list(G.GRAD_ROWS))
 def test_all_seven_gradients_through_the_module(dev, cus, monkeypatch, name):
-    r = G.GRAD_ROWS[name]
-    B = T.batch(r, cus)
-    args = [None if t is None else t.to(dev) for t in G.log_inputs(r, B)]
-    for k, v in r["env"].items():
-        monkeypatch.setenv(k, v)
-    leaves = [None if t is None else t.clone().requires_grad_(True) for t in args]
-    cot = G.cot_of(r, B, args[1].dtype)
-    x = L.SolveBoxQPLog(control=_control(r))(*leaves)
-    mst = SB.last_forward_status(dev)
-    x.backward(cot.to(dev))
-    torch.cuda.synchronize()
-    assert mst["iters"] == r["K"] and all(mst[{"loop_workgroups": "loop_workgroups_per_qp"}.get(k, k)] == v for k, v in r["sig"].items()
-                                          if k != "factor_launches"), mst
-    idx, t32, t64 = G.row_truth(name, cus, "GRAD_ROWS")
-    sub = G.log_inputs(r, B, idx)
-    g64 = G.truth_grads(r, sub, t64, cot[idx], torch.float64)
-    g32 = G.truth_grads(r, sub, t32, cot[idx], torch.float32) if t32 is not None else None
-    order = dict(zip(G.GRADS7, leaves))
-    assert all(t.grad is not None for t in order.values() if t is not None)
-    res = T.compare(r, {k: _pick(t.grad, idx) for k, t in order.items() if t is not None}, g32, g64, keys=G.GRADS7)
-    res.update(T.compare(r, {"x": _pick(x, idx)}, t32, t64, keys=("x",)))
-    _report(name, res)
-    assert set(res) == set(G.GRADS7) | {"x"}
+    res, _, g64, t64, sub, cot = C.gradients_through_the_module(LAYER, dev, cus, monkeypatch, name)
     assert float(g64["dw"].abs().max()) > 0 and float(t64["curv"].max()) > 0          # (the new gradient and the curvature are not trivially zero)
     # ... and the curvature matters: the recipe without it is far outside the bar for dp
-    flat = G.grad_recipe(cot[idx].double(), dict(t64, curv=torch.zeros_like(t64["curv"])), *[None if sub[k] is None else sub[k].double() for k in (0, 2, 4, 5, 6)])
+    flat = G.grad_recipe(cot.double(), dict(t64, curv=torch.zeros_like(t64["curv"])), *[None if sub[k] is None else sub[k].double() for k in (0, 2, 4, 5, 6)])
     assert float((flat["dp"] - g64["dp"]).abs().max()) > 100 * res["dp"]["bar"]
-    bad = [(k, rec) for k, rec in res.items() if not rec["ok"]]
-    assert not bad, (name, bad)
 
 
 def test_a_solve_that_stops_by_itself_takes_the_truths_iterations(dev):
-    args = [t.to(dev) for t in G.stop_inputs(torch.float32)]
-    sol = L.torch_solve_box_qp_log(*args, O.make_control(**G.STOP_CONTROL))
-    t32, t64 = G.stop_truth(torch.float32), G.stop_truth(torch.float64)
-    print("stop", sol["iter"], t32["iter"], t64["iter"])
-    assert sol["iter"] == t64["iter"] == t32["iter"]
-    res = T.compare(G.STOP_ROW, {"x": sol["x"].cpu()}, t32, t64, keys=("x",))
-    _report("stop", res)
-    assert res["x"]["ok"], res
+    C.stopped_solve_takes_the_truths_iterations(LAYER, dev)
 
 
 def test_no_result_depends_on_what_the_new_memory_held(dev, cus, monkeypatch):
     """In the manner of tests/mem_table.py, on tests/memharness.py: every workspace (the two new regions behind the forward's layout
     among them), output and temporary of a forward and a backward through the module is a guarded buffer filled with 0x00, then with
     0xFF -- the same bits come back, no guard is touched."""
-    import memharness as H
-    r = G.ROWS["wide_n1025_f32-K10"]          # (n > 1024: the one shape class at which the t region is read)
-    B = T.batch(r, cus)
-    args = [None if t is None else t.to(dev) for t in G.log_inputs(r, B)]
-    lib = _lib.load()
-    dt = _lib.dtype_code(args[1])
-    assert lib.lqp_boxqp_forward_log_workspace_bytes(dt, B, r["n"], r["m"]) > lib.lqp_boxqp_forward_workspace_bytes(dt, B, r["n"], r["m"])
-    outs = []
-    for fill in (0x00, 0xFF):
-        H.release(_lib)
-        with H.controlled_memory(monkeypatch, fill):
-            sol = L.torch_solve_box_qp_log(*args, _control(r))
-            leaves = [None if t is None else t.clone().requires_grad_(True) for t in args]
-            x = L.SolveBoxQPLog(control=_control(r))(*leaves)
-            x.backward(G.cot_of(r, B, x.dtype).to(dev))
-            torch.cuda.synchronize()
-            got = {k: sol[k].clone() for k in ("x", "z", "u", "lams", "u_box", "curv")}          # (m = 0 at this shape: no nus)
-            got.update({"x_module": x.detach().clone()}, **{"d" + str(k): t.grad.clone() for k, t in enumerate(leaves) if t is not None})
-            assert sol["iter"] == r["K"]
-        assert H.check_guards() == [] and H.check_inputs_untouched() == []
-        outs.append(got)
-    H.release(_lib)
-    assert len(outs[0]) == 6 + 1 + sum(t is not None for t in args)
-    for k in outs[0]:
-        assert H.same_bits(outs[0][k], outs[1][k]), k
-    assert bool(torch.isfinite(outs[1]["curv"]).all()) and bool(torch.isfinite(outs[1]["u_box"]).all())
+    C.no_result_depends_on_what_the_new_memory_held(LAYER, dev, cus, monkeypatch, "lqp_boxqp_forward_workspace_bytes")
 
 
 MESSAGE = r"w must be finite and >= 0, ub > 0 wherever w > 0, and rho positive and finite \(batch index %d\)"

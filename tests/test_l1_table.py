@@ -15,9 +15,10 @@ from lqp_py_amd import _lib
 from lqp_py_amd import solve_box_qp_l1 as S1
 from oracle import boxqp_oracle as O
 import l1_table as LT
+import term_checks as C
 import tier_table as T
 
-CUS = 256          # the compute units of an MI355X: the batch sizes the GPU test will see
+CUS = C.CUS
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -95,71 +96,30 @@ def test_the_gradient_recipe_matches_central_differences():
     kink, free, clamped = LT.sets(sol)
     assert int(kink.sum()) >= 1 and int(free.sum()) >= 1 and int(clamped.sum()) >= 1, (kink.sum(), free.sum(), clamped.sum())
     assert float(sol["margin"].min()) > 1e-3          # (no element near a change of set: the differences below stay on one piece)
-    got = LT.grad_recipe(cot, sol, Q, A, lb, ub, c)
-    h = 1e-6
-    for name, k in zip(LT.GRADS8, (0, 1, 2, 3, 4, 5, 6, 7)):
-        t = args[k]
-        fd = torch.zeros_like(t)
-        flat, out = t.reshape(-1), fd.reshape(-1)
-        for e in range(flat.numel()):
-            vals = []
-            for sgn in (1, -1):
-                tt = flat.clone()
-                tt[e] += sgn * h
-                a2 = list(args)
-                a2[k] = tt.reshape(t.shape)
-                if k == 0:      # (dQ is the gradient with respect to a symmetric perturbation: the reference's (dv x' + x dv') / 2)
-                    a2[0] = 0.5 * (a2[0] + a2[0].transpose(1, 2))
-                vals.append(float((cot * LT.solve_l1(*a2, ctl)["x"]).sum()))
-            out[e] = (vals[0] - vals[1]) / (2 * h)
-        ref = got[name]
-        err = float((fd - ref).abs().max())
-        print(name, "max |fd - recipe| %.2e" % err, "scale %.2e" % float(ref.abs().max()))
-        assert err < 2e-5 * max(1.0, float(ref.abs().max())), (name, err)
+    C.central_differences(LT.TERM, args, cot, ctl, sol)
 
 
 @pytest.mark.parametrize("key", list(LT.ROWS))
 def test_every_row_holds_the_three_sets_and_needs_w(key):
-    r = LT.ROWS[key]
-    idx, t32, t64 = LT.row_truth(key, CUS)
+    # (the unthresholded iterates, w = 0, are the other step here: a kernel that ignores w cannot pass)
+    r, idx, t32, t64, sub = C.row_needs_the_step(LT.TERM, key)
     n = r["n"]
-    assert t64["iter"] == r["K"]
     for b, (k, f, c) in enumerate(zip(*LT.sets(t64))):
         sizes = (int(k.sum()), int(f.sum()), int(c.sum()))
         need = (n / 10, n / 10, 0 if r["l1"] == "allinf" else n / 10)      # (no bound, nothing clamped)
         assert all(s >= q for s, q in zip(sizes, need)), (key, b, sizes)
     if r["l1"] == "halfw":
-        assert float(LT.l1_inputs(r, T.batch(r, CUS), idx)[6][:, 0::2].abs().max()) == 0.0
+        assert float(sub[6][:, 0::2].abs().max()) == 0.0
     if r["l1"] == "cbound":
-        inp = LT.l1_inputs(r, T.batch(r, CUS), idx)
-        assert int(((inp[7] == inp[4]) | (inp[7] == inp[5])).sum()) >= len(idx) * n // 5
-    # the unthresholded iterates (w = 0) are at least 100 bars away: a kernel that ignores w cannot pass
-    sub = LT.l1_inputs(r, T.batch(r, CUS), idx)
-    plain = LT.truth(r, sub, torch.float32 if r["dtype"] == "f32" else torch.float64, w_zero=True)
-    res = T.compare(r, {k: plain[k] for k in ("x", "z", "u")}, t32, t64, keys=("x", "z", "u"))
-    for k, rec in res.items():
-        assert rec["err"] >= 100 * rec["bar"], (key, k, rec)
-    # `side` of the float32 truth against the float64 truth: exact outside the margin, under the 1 % cap inside it
-    if t32 is not None:
-        zbar = T.compare(r, {"z": t32["z"]}, t32, t64, keys=("z",))["z"]["bar"]
-        diff = t32["side"].double() != t64["side"]
-        assert not bool((diff & ~LT.excused(t64, zbar)).any()), key
-        assert all(int(d.sum()) <= 0.01 * n for d in diff), key
-        assert t32["n_factor"] == t64["n_factor"]
-    if key.startswith(LT.EVENT_ROW):
-        assert t64["n_factor"] == 2           # (the event at iteration 100 fires: t = ws / rho changes with it)
+        assert int(((sub[7] == sub[4]) | (sub[7] == sub[5])).sum()) >= len(idx) * n // 5
 
 
 @pytest.mark.parametrize("name", list(LT.GRAD_ROWS))
 def test_gradient_rows_have_the_same_sets_in_both_precisions(name):
-    idx, t32, t64 = LT.row_truth(name, CUS, "GRAD_ROWS")
-    if t32 is None:
-        t32 = LT.truth(LT.GRAD_ROWS[name], LT.l1_inputs(LT.GRAD_ROWS[name], T.batch(LT.GRAD_ROWS[name], CUS), idx), torch.float32)
+    r, idx, t32, t64, sub = C.gradient_row_in_both_precisions(LT.TERM, name)
     for a, b in zip(LT.sets(t32), LT.sets(t64)):
         assert torch.equal(a, b), name
     # ... and the backward's own active set (x + u_e against the effective box) too
-    r = LT.GRAD_ROWS[name]
-    sub = LT.l1_inputs(r, T.batch(r, CUS), idx)
     act = []
     for sol, dt in ((t32, torch.float32), (t64, torch.float64)):
         lb, ub, c = (sub[k].to(dt) for k in (4, 5, 7))
@@ -170,10 +130,7 @@ def test_gradient_rows_have_the_same_sets_in_both_precisions(name):
 
 
 def test_the_stopped_solve_stops_at_one_count():
-    t32, t64 = LT.stop_truth(torch.float32), LT.stop_truth(torch.float64)
-    assert t32["iter"] == t64["iter"] and 0 < t64["iter"] < 9999
-    plain = O.solve_box_qp(*LT.stop_inputs(torch.float64)[:6], O.make_control(**LT.STOP_CONTROL))
-    assert float((plain["x"] - t64["x"]).abs().max()) > 1e-2
+    C.stopped_solve_stops_at_one_count(LT.TERM)
 
 
 def test_refusals():

@@ -17,9 +17,10 @@ from lqp_py_amd import _lib
 from lqp_py_amd import solve_box_qp_log as SL
 from oracle import boxqp_oracle as O
 import log_table as G
+import term_checks as C
 import tier_table as T
 
-CUS = 256          # the compute units of an MI355X: the batch sizes the GPU test will see
+CUS = C.CUS
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -108,31 +109,8 @@ def test_the_gradient_recipe_matches_central_differences():
     print(sizes)
     assert all(v >= 1 for v in sizes.values()), sizes
     assert float(sol["margin"].min()) > 1e-3          # (no element near a change of set: the differences below stay on one piece)
-    got = G.grad_recipe(cot, sol, args[0], args[2], args[4], args[5], args[6])
-    h = 1e-6
-    for k, name in enumerate(G.GRADS7):
-        t = args[k]
-        fd = torch.zeros_like(t)
-        flat, out = t.reshape(-1), fd.reshape(-1)
-        for e in range(flat.numel()):
-            if name == "dw" and float(flat[e]) == 0.0:
-                continue
-            vals = []
-            for sgn in (1, -1):
-                tt = flat.clone()
-                tt[e] += sgn * h
-                a2 = list(args)
-                a2[k] = tt.reshape(t.shape)
-                if k == 0:      # (dQ is the gradient with respect to a symmetric perturbation: the reference's (dv x' + x dv') / 2)
-                    a2[0] = 0.5 * (a2[0] + a2[0].transpose(1, 2))
-                vals.append(float((cot * G.solve_log(*a2, ctl)["x"]).sum()))
-            out[e] = (vals[0] - vals[1]) / (2 * h)
-        ref = got[name]
-        err = float((fd - ref).abs().max())
-        print(name, "max |fd - recipe| %.2e" % err, "scale %.2e" % float(ref.abs().max()))
-        assert err < 2e-5 * max(1.0, float(ref.abs().max())), (name, err)
-        if name == "dw":
-            assert float(ref.abs().max()) > 1e-3 and float(ref[args[6] == 0].abs().max()) == 0.0
+    ref = C.central_differences(G.TERM, args, cot, ctl, sol, leave_out={"dw": args[6] == 0})["dw"]
+    assert float(ref.abs().max()) > 1e-3 and float(ref[args[6] == 0].abs().max()) == 0.0
 
 
 def test_the_branch_form_of_the_step_holds_its_precision_in_float32():
@@ -156,20 +134,12 @@ def test_the_branch_form_of_the_step_holds_its_precision_in_float32():
 
 @pytest.mark.parametrize("key", list(G.ROWS))
 def test_every_row_holds_its_sets_and_needs_the_step(key):
-    r = G.ROWS[key]
-    idx, t32, t64 = G.row_truth(key, CUS)
+    # (the plain iterate is at least 100 bars away in z: a kernel without the step cannot pass)
+    r, idx, t32, t64, sub = C.row_needs_the_step(G.TERM, key)
     n, kind = r["n"], r["log"]
-    assert t64["iter"] == r["K"]
-    sub = G.log_inputs(r, T.batch(r, CUS), idx)
     w = sub[6].double()
     assert bool((w >= 0).all()) and bool((sub[5][w > 0] > 0).all())
-    s = G.sets(t64, w)
-    for k in G.SETS:
-        sizes = [int(v.sum()) for v in s[k]]
-        if k in G.EMPTY.get(kind, ()):
-            assert sum(sizes) == 0, (key, k)
-        else:
-            assert all(q >= G.SHARE * n for q in sizes), (key, k, sizes)
+    C.row_holds_its_sets(G.TERM, key, r, G.sets(t64, w), len(idx))
     assert float(t64["z"][w > 0].min()) > 0
     if kind == "halfw":
         assert float(w[:, 0::2].abs().max()) == 0.0
@@ -182,35 +152,18 @@ def test_every_row_holds_its_sets_and_needs_the_step(key):
     if kind == "tiny":
         shares = []
 
-        def at_iter(it, v, t):
-            bar = t > 0
-            shares.append(float((((v < 0) & bar).sum(dim=(1, 2)).double() / bar.sum(dim=(1, 2)).double()).min()))
-        G.solve_log(*[None if a is None else a.double() for a in sub], O.make_control(**T.control(r)), alpha=r["alpha"], at_iter=at_iter)
+        class Watched(G.LogTerm):
+            def step(self, v, rho):
+                bar = self.w > 0
+                shares.append(float((((v < 0) & bar).sum(dim=(1, 2)).double() / bar.sum(dim=(1, 2)).double()).min()))
+                return super().step(v, rho)
+        G.solve_log(*[None if a is None else a.double() for a in sub], O.make_control(**T.control(r)), alpha=r["alpha"], step=Watched)
         assert max(shares) >= G.SHARE, max(shares)
-    # the plain iterate is at least 100 bars away in z: a kernel without the step cannot pass
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    other = G.truth(r, sub, dt, step="plain")
-    rec = T.compare(r, {"z": other["z"]}, t32, t64, keys=("z",))["z"]
-    assert rec["err"] >= 100 * rec["bar"], (key, rec)
-    # the clamped set of the float32 truth against the float64 truth's: exact outside the margin, under the 1 % cap inside it
-    if t32 is not None:
-        zbar = T.compare(r, {"z": t32["z"]}, t32, t64, keys=("z",))["z"]["bar"]
-        diff = (t32["u_box"] != 0) != (t64["u_box"] != 0)
-        assert not bool((diff & ~G.excused(t64, zbar)).any()), key
-        assert all(int(d.sum()) <= 0.01 * n for d in diff), key
-        assert t32["n_factor"] == t64["n_factor"]
-    if key.startswith(G.EVENT_ROW):
-        assert t64["n_factor"] == 2           # (the event at iteration 100 fires: t changes with rho)
 
 
 @pytest.mark.parametrize("name", list(G.GRAD_ROWS))
 def test_gradient_rows_have_the_same_sets_in_both_precisions(name):
-    r = G.GRAD_ROWS[name]
-    idx, t32, t64 = G.row_truth(name, CUS, "GRAD_ROWS")
-    sub = G.log_inputs(r, T.batch(r, CUS), idx)
-    if t32 is None:
-        t32 = G.truth(r, sub, torch.float32)
-    assert torch.equal(t32["u_box"] != 0, t64["u_box"] != 0), name
+    r, idx, t32, t64, sub = C.gradient_row_in_both_precisions(G.TERM, name)
     assert torch.equal(t32["curv"] != 0, t64["curv"] != 0), name
     # ... and the backward's own active set (x + u_e against the box) too
     act = []
@@ -224,10 +177,7 @@ def test_gradient_rows_have_the_same_sets_in_both_precisions(name):
 
 
 def test_the_stopped_solve_stops_at_one_count():
-    t32, t64 = G.stop_truth(torch.float32), G.stop_truth(torch.float64)
-    assert t32["iter"] == t64["iter"] and 0 < t64["iter"] < 9999
-    plain = O.solve_box_qp(*G.stop_inputs(torch.float64)[:6], O.make_control(**G.STOP_CONTROL))
-    assert float((plain["x"] - t64["x"]).abs().max()) > 1e-2
+    C.stopped_solve_stops_at_one_count(G.TERM)
 
 
 def test_refusals():

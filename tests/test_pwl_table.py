@@ -19,9 +19,10 @@ from oracle import boxqp_oracle as O
 import l1_table as LT
 import pwl_table as PT
 import soft_table as ST
+import term_checks as C
 import tier_table as T
 
-CUS = 256          # the compute units of an MI355X: the batch sizes the GPU test will see
+CUS = C.CUS
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -199,51 +200,19 @@ def test_the_gradient_recipe_matches_central_differences():
     assert sizes["clamped"] >= 1 and sum(sizes[f"p{k}"] > 0 for k in (1, 3, 5)) >= 2 and sum(sizes[f"p{k}"] > 0 for k in (0, 2, 4, 6)) >= 3, sizes
     assert float(sol["margin"].min()) > 1e-3          # (no element near a change of set: the differences below stay on one piece)
     assert float((args[7][:, :, 1:] - args[7][:, :, :-1]).min()) > 0.04
-    got = PT.grad_recipe(cot, sol, args[0], args[2], args[4], args[5], args[7])
-    h = 1e-6
-    for k, name in enumerate(PT.GRADS8):
-        t = args[k]
-        fd = torch.zeros_like(t)
-        flat, out = t.reshape(-1), fd.reshape(-1)
-        for e in range(flat.numel()):
-            vals = []
-            for sgn in (1, -1):
-                tt = flat.clone()
-                tt[e] += sgn * h
-                a2 = list(args)
-                a2[k] = tt.reshape(t.shape)
-                if k == 0:      # (dQ is the gradient with respect to a symmetric perturbation: the reference's (dv x' + x dv') / 2)
-                    a2[0] = 0.5 * (a2[0] + a2[0].transpose(1, 2))
-                vals.append(float((cot * PT.solve_pwl(*a2, ctl)["x"]).sum()))
-            out[e] = (vals[0] - vals[1]) / (2 * h)
-        ref = got[name]
-        err = float((fd - ref).abs().max())
-        print(name, "max |fd - recipe| %.2e" % err, "scale %.2e" % float(ref.abs().max()))
-        assert err < 2e-5 * max(1.0, float(ref.abs().max())), (name, err)
-        if name in ("ds", "dc"):
-            assert float(ref.abs().max()) > 1e-3, name          # (the new gradients are not trivially zero here)
+    got = C.central_differences(PT.TERM, args, cot, ctl, sol)
+    for name in ("ds", "dc"):
+        assert float(got[name].abs().max()) > 1e-3, name          # (the new gradients are not trivially zero here)
 
 
 @pytest.mark.parametrize("key", list(PT.ROWS))
 def test_every_row_holds_the_eight_sets_and_needs_the_step(key):
-    r = PT.ROWS[key]
-    idx, t32, t64 = PT.row_truth(key, CUS)
+    # the plain iterate and the band's iterate on (lo, hi) alone are at least 100 bars away in z: a kernel without the step, or one
+    # that ignores the middle kink, cannot pass (l1eq has no outer kinks and bandeq IS the band: the plain iterate alone there); the
+    # seven pieces (unclamped) and the clamped set
+    r, idx, t32, t64, sub = C.row_needs_the_step(PT.TERM, key)
+    C.row_holds_its_sets(PT.TERM, key, r, PT.sets(t64), len(idx))
     n, kind = r["n"], r["pwl"]
-    assert t64["iter"] == r["K"]
-    # the seven pieces (unclamped) and the clamped set: SHARE of every sampled problem at n >= 129, of the row's sampled problems
-    # together at n = 31 (a single problem of 31 elements can have an empty piece); not the sets the kind empties by construction
-    s = PT.sets(t64)
-    asked = [k for k in s if k not in PT.EMPTY.get(kind, ())]
-    for k in PT.EMPTY.get(kind, ()):
-        assert int(s[k].sum()) == 0, (key, k)
-    if n >= 129:
-        for k in asked:
-            sizes = [int(v.sum()) for v in s[k]]
-            assert all(q >= PT.SHARE * n for q in sizes), (key, k, sizes)
-    else:
-        for k in asked:
-            assert int(s[k].sum()) >= PT.SHARE * n * len(idx), (key, k, int(s[k].sum()))
-    sub = PT.pwl_inputs(r, T.batch(r, CUS), idx)
     sl, cn = sub[6], sub[7]
     assert bool((sl[:, :, 1:] >= sl[:, :, :-1]).all()) and bool((cn[:, :, 1:] >= cn[:, :, :-1]).all())
     assert cn.shape[2] == {"l1eq": 1, "bandeq": 2}.get(kind, 3) and sl.shape[2] == cn.shape[2] + 1
@@ -256,33 +225,11 @@ def test_every_row_holds_the_eight_sets_and_needs_the_step(key):
         assert int(((cn[:, :, 2:3] == sub[5]) | (cn[:, :, 0:1] == sub[4])).sum()) >= len(idx) * n // 5
     if kind == "allinf":
         assert bool(torch.isinf(sub[4]).all()) and bool(torch.isinf(sub[5]).all())
-    # the plain iterate and the band's iterate on (lo, hi) alone are at least 100 bars away in z: a kernel without the step, or one
-    # that ignores the middle kink, cannot pass (l1eq has no outer kinks and bandeq IS the band: the plain iterate alone there)
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    for step in ("plain",) + (() if kind in ("l1eq", "bandeq") else ("band",)):
-        other = PT.truth(r, sub, dt, step=step)
-        rec = T.compare(r, {"z": other["z"]}, t32, t64, keys=("z",))["z"]
-        assert rec["err"] >= 100 * rec["bar"], (key, step, rec)
-    # `piece` of the float32 truth against the float64 truth: exact outside the margin, under the 1 % cap inside it
-    if t32 is not None:
-        zbar = T.compare(r, {"z": t32["z"]}, t32, t64, keys=("z",))["z"]["bar"]
-        diff = t32["piece"].double() != t64["piece"]
-        assert not bool((diff & ~PT.excused(t64, zbar)).any()), key
-        assert all(int(d.sum()) <= 0.01 * n for d in diff), key
-        assert t32["n_factor"] == t64["n_factor"]
-    if key.startswith(PT.EVENT_ROW):
-        assert t64["n_factor"] == 2           # (the event at iteration 100 fires: the t_k change with rho)
 
 
 @pytest.mark.parametrize("name", list(PT.GRAD_ROWS))
 def test_gradient_rows_have_the_same_pieces_in_both_precisions(name):
-    r = PT.GRAD_ROWS[name]
-    idx, t32, t64 = PT.row_truth(name, CUS, "GRAD_ROWS")
-    sub = PT.pwl_inputs(r, T.batch(r, CUS), idx)
-    if t32 is None:
-        t32 = PT.truth(r, sub, torch.float32)
-    assert torch.equal(t32["piece"].double(), t64["piece"]), name
-    assert torch.equal(t32["u_box"] != 0, t64["u_box"] != 0), name
+    r, idx, t32, t64, sub = C.gradient_row_in_both_precisions(PT.TERM, name)
     g64 = PT.truth_grads(r, sub, t64, PT.cot_of(r, T.batch(r, CUS), torch.float64)[idx], torch.float64)
     for k in range(4):
         assert float(g64["ds"][:, :, k].abs().max()) > 0, k          # (not trivially zero, in every slot)
@@ -291,10 +238,7 @@ def test_gradient_rows_have_the_same_pieces_in_both_precisions(name):
 
 
 def test_the_stopped_solve_stops_at_one_count():
-    t32, t64 = PT.stop_truth(torch.float32), PT.stop_truth(torch.float64)
-    assert t32["iter"] == t64["iter"] and 0 < t64["iter"] < 9999
-    plain = O.solve_box_qp(*PT.stop_inputs(torch.float64)[:6], O.make_control(**PT.STOP_CONTROL))
-    assert float((plain["x"] - t64["x"]).abs().max()) > 1e-2
+    C.stopped_solve_stops_at_one_count(PT.TERM)
 
 
 def test_refusals():

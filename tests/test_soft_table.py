@@ -17,9 +17,10 @@ from lqp_py_amd import solve_box_qp_soft as SS
 from oracle import boxqp_oracle as O
 import l1_table as LT
 import soft_table as ST
+import term_checks as C
 import tier_table as T
 
-CUS = 256          # the compute units of an MI355X: the batch sizes the GPU test will see
+CUS = C.CUS
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -120,51 +121,18 @@ def test_the_gradient_recipe_matches_central_differences():
     sizes = {k: int(v.sum()) for k, v in ST.sets(sol).items()}
     assert all(v >= 1 for v in sizes.values()), sizes
     assert float(sol["margin"].min()) > 1e-3          # (no element near a change of set: the differences below stay on one piece)
-    got = ST.grad_recipe(cot, sol, args[0], args[2], args[4], args[5], args[8], args[9])
-    h = 1e-6
-    for k, name in enumerate(ST.GRADS10):
-        t = args[k]
-        fd = torch.zeros_like(t)
-        flat, out = t.reshape(-1), fd.reshape(-1)
-        for e in range(flat.numel()):
-            vals = []
-            for sgn in (1, -1):
-                tt = flat.clone()
-                tt[e] += sgn * h
-                a2 = list(args)
-                a2[k] = tt.reshape(t.shape)
-                if k == 0:      # (dQ is the gradient with respect to a symmetric perturbation: the reference's (dv x' + x dv') / 2)
-                    a2[0] = 0.5 * (a2[0] + a2[0].transpose(1, 2))
-                vals.append(float((cot * ST.solve_soft(*a2, ctl)["x"]).sum()))
-            out[e] = (vals[0] - vals[1]) / (2 * h)
-        ref = got[name]
-        err = float((fd - ref).abs().max())
-        print(name, "max |fd - recipe| %.2e" % err, "scale %.2e" % float(ref.abs().max()))
-        assert err < 2e-5 * max(1.0, float(ref.abs().max())), (name, err)
-        if name in ("dwl", "dwu", "dlo", "dhi"):
-            assert float(ref.abs().max()) > 1e-3, name          # (the new gradients are not trivially zero here)
+    got = C.central_differences(ST.TERM, args, cot, ctl, sol)
+    for name in ("dwl", "dwu", "dlo", "dhi"):
+        assert float(got[name].abs().max()) > 1e-3, name          # (the new gradients are not trivially zero here)
 
 
 @pytest.mark.parametrize("key", list(ST.ROWS))
 def test_every_row_holds_the_six_sets_and_needs_the_step(key):
-    r = ST.ROWS[key]
-    idx, t32, t64 = ST.row_truth(key, CUS)
+    # the plain iterate and the L1 iterate (c = (lo + hi) / 2, w = (wl + wu) / 2) are at least 100 bars away in z (l1eq IS the L1
+    # iterate and onesided has no middle: the plain iterate alone there); the five zones (unclamped) and the clamped set
+    r, idx, t32, t64, sub = C.row_needs_the_step(ST.TERM, key)
+    C.row_holds_its_sets(ST.TERM, key, r, ST.sets(t64), len(idx))
     n, kind = r["n"], r["soft"]
-    assert t64["iter"] == r["K"]
-    # the five zones (unclamped) and the clamped set: SHARE of every sampled problem at n >= 129, of the row's sampled problems
-    # together at n = 31 (a single problem of 31 elements can have an empty zone); not the sets the kind empties by construction
-    s = ST.sets(t64)
-    asked = [k for k in s if k not in ST.EMPTY.get(kind, ())]
-    for k in ST.EMPTY.get(kind, ()):
-        assert int(s[k].sum()) == 0, (key, k)
-    if n >= 129:
-        for k in asked:
-            sizes = [int(v.sum()) for v in s[k]]
-            assert all(q >= ST.SHARE * n for q in sizes), (key, k, sizes)
-    else:
-        for k in asked:
-            assert int(s[k].sum()) >= ST.SHARE * n * len(idx), (key, k, int(s[k].sum()))
-    sub = ST.soft_inputs(r, T.batch(r, CUS), idx)
     assert bool((sub[8] <= sub[9]).all())
     if kind == "l1eq":
         assert torch.equal(sub[8], sub[9]) and torch.equal(sub[6], sub[7])
@@ -176,33 +144,11 @@ def test_every_row_holds_the_six_sets_and_needs_the_step(key):
         assert int(((sub[9] == sub[5]) | (sub[8] == sub[4])).sum()) >= len(idx) * n // 5
     if kind == "allinf":
         assert bool(torch.isinf(sub[4]).all()) and bool(torch.isinf(sub[5]).all())
-    # the plain iterate and the L1 iterate (c = (lo + hi) / 2, w = (wl + wu) / 2) are at least 100 bars away in z: a kernel without
-    # the step cannot pass (l1eq IS the L1 iterate and onesided has no middle: the plain iterate alone there)
-    dt = torch.float32 if r["dtype"] == "f32" else torch.float64
-    for step in ("plain",) + (() if kind in ("l1eq", "onesided") else ("l1",)):
-        other = ST.truth(r, sub, dt, step=step)
-        rec = T.compare(r, {"z": other["z"]}, t32, t64, keys=("z",))["z"]
-        assert rec["err"] >= 100 * rec["bar"], (key, step, rec)
-    # `zone` of the float32 truth against the float64 truth: exact outside the margin, under the 1 % cap inside it
-    if t32 is not None:
-        zbar = T.compare(r, {"z": t32["z"]}, t32, t64, keys=("z",))["z"]["bar"]
-        diff = t32["zone"].double() != t64["zone"]
-        assert not bool((diff & ~ST.excused(t64, zbar)).any()), key
-        assert all(int(d.sum()) <= 0.01 * n for d in diff), key
-        assert t32["n_factor"] == t64["n_factor"]
-    if key.startswith(ST.EVENT_ROW):
-        assert t64["n_factor"] == 2           # (the event at iteration 100 fires: tl, tu change with rho)
 
 
 @pytest.mark.parametrize("name", list(ST.GRAD_ROWS))
 def test_gradient_rows_have_the_same_zones_in_both_precisions(name):
-    r = ST.GRAD_ROWS[name]
-    idx, t32, t64 = ST.row_truth(name, CUS, "GRAD_ROWS")
-    sub = ST.soft_inputs(r, T.batch(r, CUS), idx)
-    if t32 is None:
-        t32 = ST.truth(r, sub, torch.float32)
-    assert torch.equal(t32["zone"].double(), t64["zone"]), name
-    assert torch.equal(t32["u_box"] != 0, t64["u_box"] != 0), name
+    r, idx, t32, t64, sub = C.gradient_row_in_both_precisions(ST.TERM, name)
     # ... and the backward's own active set (x + u_e against the effective box) too
     act = []
     for sol, dt in ((t32, torch.float32), (t64, torch.float64)):
@@ -215,10 +161,7 @@ def test_gradient_rows_have_the_same_zones_in_both_precisions(name):
 
 
 def test_the_stopped_solve_stops_at_one_count():
-    t32, t64 = ST.stop_truth(torch.float32), ST.stop_truth(torch.float64)
-    assert t32["iter"] == t64["iter"] and 0 < t64["iter"] < 9999
-    plain = O.solve_box_qp(*ST.stop_inputs(torch.float64)[:6], O.make_control(**ST.STOP_CONTROL))
-    assert float((plain["x"] - t64["x"]).abs().max()) > 1e-2
+    C.stopped_solve_stops_at_one_count(ST.TERM)
 
 
 def test_refusals():
