@@ -602,6 +602,57 @@ int lqp_boxqp_pwl_effective_box(void* stream, int dtype, int B, int n,
 int lqp_boxqp_pwl_finish_grads(void* stream, int dtype, int B, int n,
                                const void* piece, const void* u_box, const void* dp, const void* dlb_e, const void* dub_e, int K,
                                void* dlb, void* dub, void* ds, void* dc);
+/* ---- a Huber term in the objective (added within ABI 17: new symbols only, no struct and no signature changed) --------------
+ *   min 0.5 x'Qx + p'x + sum_i w_i H_{delta_i}(x_i - c_i)   s.t.  A x = b,  lb <= x <= ub
+ *   H_delta(d) = 0.5 d^2 for |d| <= delta,  delta |d| - 0.5 delta^2 beyond;   w, c, delta (B,n,1) like p
+ * (robust tracking / regression: Q = X'X with bounded coefficients, outliers taken linearly; a trade cost that is quadratic for
+ * small trades and linear for large ones).  A pure quadratic can be folded into Q and p by the caller; this cannot, because where
+ * the curvature acts depends on the solution.  lqp_boxqp_forward_huber is the same implementation once more with another
+ * z-update.  In the scaled space of the loop (x = D xs): ws = D^2 w, cs = c / D, ds = delta / D; with v = xh + u (xh as in
+ * lqp_boxqp_forward, over-relaxation included), d = v - cs, t = ws / rho (the rho of the launch, a true division) and, once per
+ * element and launch, q = t ds, lim = ds + q, sh = t / (1 + t):
+ *   S = v           if t == 0     (a branch: w = 0 returns lqp_boxqp_forward's x, z, u bit for bit)
+ *   S = v - q       if d >  lim
+ *   S = v + q       if d < -lim
+ *   S = v - sh d    otherwise
+ *   z = min(max(S, lbs), ubs)
+ * delta = +inf is allowed (lim = q = +inf: the quadratic branch always, a weighted least-squares term); delta = 0 is no term.
+ * x-update, factorisations, stopping rule, rho adaptation: unchanged.  The solve always iterates, as with the other terms: the
+ * rho = 0 one-shot does not exist here (rho_mode 1 with rho_value <= 0: LQP_ERR_INVALID), ctrl.any_lb / any_ub are not read.  The
+ * same loop kernel families as the other terms have instances with this step; the dense LU tiers' problems run the streaming
+ * loop's LU branch.
+ * Two more outputs, (B,n,1) in the solve's dtype, from the step's comparisons once more at the returned iterate (v = zs + us):
+ *   zone   +1 / -1 on the upper / lower linear piece, 0 on the quadratic zone and wherever w = 0
+ *   u_box  the box's share of the dual u: (us - t clip(zs - cs, -ds, ds)) / D on an element where S != clamp(S); exactly zero
+ *          everywhere else.  As for the log barrier, (S - zs) / D is NOT the bound's multiplier: the term pushes on a clamped
+ *          element too.  lams = [relu(-rho u_box); relu(rho u_box)].
+ * Refused with LQP_ERR_INVALID before anything is touched: a null w, c, delta, zone or u_box, ctrl.reserved2 bit 3 (per-problem
+ * stopping) or bit 0 (the factor kept for the unroll sweep), a check_hook; a workspace that is too short: LQP_ERR_WORKSPACE.
+ * A weight that is negative or not finite, a delta that is negative or NaN, a c that is not finite, and a rho of a problem
+ * (rho_mode 2: an entry of rho_in) that is not positive and finite, is found on the device: the problem's outputs are NaN,
+ * bit 22 (4194304) of its flag word in ctrl.host_report is set, and a call that waits returns LQP_ERR_INVALID with
+ * stats.fail_index naming it.
+ * lqp_boxqp_forward_huber_workspace_bytes: the forward's layout, unchanged, and behind it 6 n values per problem (ws, cs, ds,
+ * q, lim, sh), written by kernels of the call before they are read. */
+size_t lqp_boxqp_forward_huber_workspace_bytes(int dtype, int B, int n, int m);
+int lqp_boxqp_forward_huber(void* stream, int dtype, int B, int n, int m,
+                            const void* Q, const void* p, const void* A, const void* b,
+                            const void* lb, const void* ub, const void* w, const void* c, const void* delta,
+                            const lqp_boxqp_ctrl* ctrl, const void* rho_in,
+                            void* x, void* z, void* u, void* lams, void* nus, void* rho_out, void* zone, void* u_box,
+                            lqp_boxqp_stats* stats,
+                            void* workspace, size_t workspace_bytes);
+/* The backward of lqp_boxqp_forward_huber: the term is C1, so it has no kink sets -- lqp_boxqp_backward_fp_curv on
+ * (dl_dz, x, u_e, lams_e, nus, Q, A, lb, ub, curv, rho) with the true lb, ub, between two element-wise kernels:
+ *   lqp_boxqp_huber_effective_duals  u_e = u_box,  lams_e = [relu(-rho u_e); relu(rho u_e)] (B,2n,1),  curv = w where
+ *                                    zone == 0, w > 0 and u_box == 0, else 0; rho_mode 1 = rho_value, 2 = rho_in (B)
+ *   lqp_boxqp_huber_finish_grads     dw = dp clip(z - c, -delta, delta),  dc = -w dp on zone 0, else 0,  ddelta = w zone dp;
+ *                                    each of the three may be NULL.
+ * dQ, dp, dA, db, dlb, dub are the backward's own.  All (B,n,1) in `dtype`; enqueued on `stream`, nothing is waited for. */
+int lqp_boxqp_huber_effective_duals(void* stream, int dtype, int B, int n, const void* u_box, const void* zone, const void* w,
+                                    int rho_mode, double rho_value, const void* rho_in, void* u_e, void* lams_e, void* curv);
+int lqp_boxqp_huber_finish_grads(void* stream, int dtype, int B, int n, const void* dp, const void* z, const void* zone,
+                                 const void* w, const void* c, const void* delta, void* dw, void* dc, void* ddelta);
 /* How every problem of the LAST forward on `workspace` ended, which must have run with ctrl.reserved2 bit 3, detection or not
  * (LQP_ERR_INVALID otherwise, as lqp_boxqp_problem_iters): status_out[b] = 0 optimal, 1 it ended at max_iters without being
  * optimal, 2 primal infeasible, 3 dual infeasible (lqp_boxqp_forward_certify) -- B int32 on the DEVICE.  Enqueued on `stream`,

@@ -12,7 +12,7 @@ import sys
 
 _ALIASED = ("solve_box_qp_admm_torch", "lu_layer", "solve_qp_eqcon_torch", "solve_qp_uncon_torch", "control", "utils",
             "solve_box_qp_admm", "solve_qp_uncon", "optnet", "solve_box_qp_l1", "solve_box_qp_soft", "solve_box_qp_log",
-            "solve_box_qp_pwl")
+            "solve_box_qp_pwl", "solve_box_qp_huber")
 
 for _name in _ALIASED:
     _mod = importlib.import_module("lqp_py_amd." + _name)

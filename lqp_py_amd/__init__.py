@@ -10,6 +10,7 @@ from .solve_box_qp_l1 import SolveBoxQPL1, SolveBoxQPL1Layer, torch_solve_box_qp
 from .solve_box_qp_soft import SolveBoxQPSoft, SolveBoxQPSoftLayer, torch_solve_box_qp_soft
 from .solve_box_qp_log import SolveBoxQPLog, SolveBoxQPLogLayer, torch_solve_box_qp_log
 from .solve_box_qp_pwl import SolveBoxQPPwl, SolveBoxQPPwlLayer, torch_solve_box_qp_pwl
+from .solve_box_qp_huber import SolveBoxQPHuber, SolveBoxQPHuberLayer, torch_solve_box_qp_huber
 from ._lib import InfeasibleQPError, UnboundedQPError
 from .lu_layer import TorchLU, TorchLULayer
 from .solve_qp_eqcon_torch import torch_solve_qp_eqcon, torch_solve_qp_eqcon_grad
@@ -45,4 +46,5 @@ __all__ = [
     "SolveBoxQPSoft", "SolveBoxQPSoftLayer", "torch_solve_box_qp_soft",
     "SolveBoxQPLog", "SolveBoxQPLogLayer", "torch_solve_box_qp_log",
     "SolveBoxQPPwl", "SolveBoxQPPwlLayer", "torch_solve_box_qp_pwl",
+    "SolveBoxQPHuber", "SolveBoxQPHuberLayer", "torch_solve_box_qp_huber",
 ]

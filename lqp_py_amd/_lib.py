@@ -100,6 +100,11 @@ SYMBOLS = {
                               [ctypes.POINTER(BoxQPCtrl)] + [_P] * 9 + [ctypes.POINTER(BoxQPStats), _P, c_size_t]),
     "lqp_boxqp_pwl_effective_box": (c_int, [_P, c_int, c_int, c_int] + [_P] * 6 + [c_int, c_int, c_double, _P] + [_P] * 4),
     "lqp_boxqp_pwl_finish_grads": (c_int, [_P, c_int, c_int, c_int] + [_P] * 5 + [c_int] + [_P] * 4),
+    "lqp_boxqp_forward_huber_workspace_bytes": (c_size_t, [c_int] * 4),       # (added within ABI 17)
+    "lqp_boxqp_forward_huber": (c_int, [_P, c_int, c_int, c_int, c_int] + [_P] * 9 +
+                                [ctypes.POINTER(BoxQPCtrl)] + [_P] * 9 + [ctypes.POINTER(BoxQPStats), _P, c_size_t]),
+    "lqp_boxqp_huber_effective_duals": (c_int, [_P, c_int, c_int, c_int] + [_P] * 3 + [c_int, c_double, _P] + [_P] * 3),
+    "lqp_boxqp_huber_finish_grads": (c_int, [_P, c_int, c_int, c_int] + [_P] * 9),
     "lqp_boxqp_problem_status": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "lqp_boxqp_forward_finish": (c_int, [_P, c_int, c_int, c_int, _P, ctypes.POINTER(BoxQPStats)]),
     "lqp_boxqp_forward_layout": (c_int, [c_int] * 4 + [ctypes.POINTER(c_size_t)] * 4),
@@ -154,7 +159,7 @@ def build_library(force=False, verbose=False):
 
     Default: the split build -- the host translation unit (csrc/lqp_amd.hip with `extern template` declarations of every
     kernel instance, csrc/split/lqp_extern.inc) and one translation unit per group of kernel instances
-    (csrc/split/lqp_tu_*.hip: 51 units, 277 instances), compiled in parallel and linked; same headers and flags, hence
+    (csrc/split/lqp_tu_*.hip: 57 units, 303 instances), compiled in parallel and linked; same headers and flags, hence
     the same code per kernel as the single-source build (LQP_UNITY_BUILD=1: one hipcc command, ~3.5 minutes of serial
     code generation).  The lists are written by tools/gen_split_build.py from the manifest of kernel instances in it."""
     split_dir = os.path.join(CSRC, "split")
@@ -339,6 +344,7 @@ RP_L1_INPUT = 1 << 18        # a weight of the problem is negative or not finite
 RP_SOFT_INPUT = 1 << 19      # a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (lqp_boxqp_forward_soft)
 RP_LOG_INPUT = 1 << 20       # a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (lqp_boxqp_forward_log)
 RP_PWL_INPUT = 1 << 21       # a slope not finite, slopes or kinks that decrease, a NaN kink, or a rho not positive and finite (lqp_boxqp_forward_pwl)
+RP_HUBER_INPUT = 1 << 22     # a weight negative or not finite, a delta negative or NaN, a c not finite, or a rho not positive and finite (lqp_boxqp_forward_huber)
 
 
 class CertifiedQPError(RuntimeError):
@@ -466,6 +472,10 @@ def poll_errors(block=False):
         if flags & RP_PWL_INPUT:
             raise RuntimeError(f"lqp_py_amd.{p.what} (reported late: the call did not synchronise): s must be finite and non-decreasing, c "
                                f"non-decreasing without NaN, and rho positive and finite (batch index {int((flags_each & RP_PWL_INPUT).nonzero()[0][0])}); "
+                               "the outputs are NaN")
+        if flags & RP_HUBER_INPUT:
+            raise RuntimeError(f"lqp_py_amd.{p.what} (reported late: the call did not synchronise): w must be finite and >= 0, delta >= 0 "
+                               f"without NaN, c finite, and rho positive and finite (batch index {int((flags_each & RP_HUBER_INPUT).nonzero()[0][0])}); "
                                "the outputs are NaN")
         if p.raise_infeasible and (flags & RP_INFEAS):
             raise InfeasibleQPError(p.what, (flags_each & RP_INFEAS).nonzero()[0].tolist())

@@ -1,4 +1,4 @@
-"""The separable terms a box-QP layer can carry in its objective (solve_box_qp_l1 / _soft / _log / _pwl): one record per term, and what the
+"""The separable terms a box-QP layer can carry in its objective (solve_box_qp_l1 / _soft / _log / _pwl / _huber): one record per term, and what the
 layers share -- the rules of what a term cannot be combined with, the forward solve, the body of ``Function.forward`` and the
 prelude of ``Function.backward``.  What is a term's own stays in its module: the docstrings, the two element-wise kernels around the
 fixed-point backward, and the gradients it returns.  The device-side twin is the Term trait of csrc/lqp_boxqp.hpp.
@@ -43,6 +43,9 @@ def _pwl_shapes(p, tensors):
 PWL = Term("piecewise-linear", ("s", "c"), "piece", "lqp_boxqp_forward_pwl", "lqp_boxqp_forward_pwl_workspace_bytes", ("aux", "u_box"),
            "s must be finite and non-decreasing, c non-decreasing without NaN, and rho positive and finite",
            "its backward is the fixed-point form on the effective box", _pwl_shapes)
+HUBER = Term("Huber", ("w", "c", "delta"), "zone", "lqp_boxqp_forward_huber", "lqp_boxqp_forward_huber_workspace_bytes", ("aux", "u_box"),
+             "w must be finite and >= 0, delta >= 0 without NaN, c finite, and rho positive and finite",
+             "its backward is the fixed-point form with the term's curvature on the quadratic zone")
 
 
 def check_term(term, control, p=None, tensors=()):

@@ -500,10 +500,10 @@ inline void solve_stats(lqp_boxqp_stats* stats, const volatile int* rv, const in
 }
 inline bool flags_timeout_loop(const int* rep) { return ((const volatile int*)rep)[ST_TIMEOUT] != 0; }
 // the run-time twins of the Term traits (lqp_boxqp.hpp), by Term*::kind
-constexpr int kTerms = 5;
-constexpr int kTermSlots[kTerms] = {TermNone::slots, TermL1::slots, TermSoft::slots, TermLog::slots, TermPwl::slots};
-constexpr int kTermInputs[kTerms] = {TermNone::n_in, TermL1::n_in, TermSoft::n_in, TermLog::n_in, TermPwl::n_in};
-constexpr int kTermFlag[kTerms] ={TermNone::input_flag, TermL1::input_flag, TermSoft::input_flag, TermLog::input_flag, TermPwl::input_flag};
+constexpr int kTerms = 6;
+constexpr int kTermSlots[kTerms] = {TermNone::slots, TermL1::slots, TermSoft::slots, TermLog::slots, TermPwl::slots, TermHuber::slots};
+constexpr int kTermInputs[kTerms] = {TermNone::n_in, TermL1::n_in, TermSoft::n_in, TermLog::n_in, TermPwl::n_in, TermHuber::n_in};
+constexpr int kTermFlag[kTerms] ={TermNone::input_flag, TermL1::input_flag, TermSoft::input_flag, TermLog::input_flag, TermPwl::input_flag, TermHuber::input_flag};
 int collect_report(hipStream_t st, const int* rep, const bool polled, const int B, const int max_iters, const int check,
                    lqp_boxqp_stats* stats) {
     if (polled) {
@@ -548,9 +548,9 @@ int collect_report(hipStream_t st, const int* rep, const bool polled, const int 
 // has an instance per form it supports (family_has_form), and nothing but its selector below chooses one.
 // The batch stops as one | control['stop'] = 'each': every problem stops and adapts rho as a batch of one (P.pstat) | ... with the primal
 // infeasibility certificate in its check (control['infeasible']: P.snap) | ... and the dual one beside it (control['unbounded']:
-// P.eps_dinf > 0) | the step with a separable term, one form per term (lqp_boxqp_forward_l1 / _soft / _log / _pwl: P.term, whose area shares its
+// P.eps_dinf > 0) | the step with a separable term, one form per term (lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber: P.term, whose area shares its
 // storage with the snapshots; the batch stops as one)
-enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT, FORM_LOG, FORM_PWL };
+enum LoopForm { FORM_ALL, FORM_EACH, FORM_DETECT, FORM_CERTIFY, FORM_L1, FORM_SOFT, FORM_LOG, FORM_PWL, FORM_HUBER };
 inline int form_term(const LoopForm form) { return form >= FORM_L1 ? form - FORM_L1 + 1 : 0; }      // (Term*::kind of the form, 0: none)
 inline LoopForm loop_form(const int term, const bool each, const bool snapshots, const bool dual) {
     return term ? (LoopForm)(FORM_L1 + term - 1) : !each ? FORM_ALL : !snapshots ? FORM_EACH : dual ? FORM_CERTIFY : FORM_DETECT;
@@ -567,6 +567,7 @@ template <typename F> auto by_form(const LoopForm form, F f) -> decltype(f(FormA
         case FORM_SOFT:    return f(FormSoft());
         case FORM_LOG:     return f(FormLog());
         case FORM_PWL:     return f(FormPwl());
+        case FORM_HUBER:   return f(FormHuber());
         default:           return f(FormAll());
     }
 }
@@ -667,7 +668,7 @@ enum LoopKind {
 inline bool family_has_form(const LoopKind kind, const LoopForm form) {
     switch (kind) {
         case LOOP_ONE: case LOOP_SMALL: case LOOP_SPLIT: return true;      // (the split loop's FormEach serves FormDetect and FormCertify)
-        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1 || form == FORM_SOFT || form == FORM_LOG || form == FORM_PWL;
+        case LOOP_NP2: return form == FORM_ALL || form == FORM_L1 || form == FORM_SOFT || form == FORM_LOG || form == FORM_PWL || form == FORM_HUBER;
         default: return form == FORM_ALL;                                  // (the dense tiers)
     }
 }
@@ -718,7 +719,7 @@ inline LoopFn<float> np2_kernel(const LoopForm form) {
         else return k_admm_loop_np2<decltype(f)>;
     });
 }
-// the extra arguments of lqp_boxqp_forward_l1 / _soft / _log / _pwl: the term (Term*::kind), its input vectors, its two outputs
+// the extra arguments of lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber: the term (Term*::kind), its input vectors, its two outputs
 struct TermArgs { int kind = 0; const void* in[TERM_IN_MAX] = {}; void* aux = nullptr; void* u_box = nullptr; };
 
 constexpr int kMaxChecksPerLaunch = kRing / 4;
@@ -1541,7 +1542,7 @@ int forward_impl(hipStream_t st, int B, int n, int m, const void* Q, const void*
                  const void* lb, const void* ub, const lqp_boxqp_ctrl* ctl, const void* rho_in, void* x, void* z,
                  void* u, void* lams, void* nus, void* rho_out, lqp_boxqp_stats* stats, void* ws, size_t ws_bytes,
                  int retry = 0, const double eps_prim_inf = 0.0, const double eps_dual_inf = 0.0, const TermArgs* term = nullptr) {
-    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; term: lqp_boxqp_forward_l1 / _soft / _log / _pwl)
+    // (eps_prim_inf > 0: lqp_boxqp_forward_detect; either > 0: lqp_boxqp_forward_certify; term: lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber)
     FwdLayout<T> L = carve_forward<T>(ws, B, n, m);
     const LoopForm asked = loop_form(term ? term->kind : 0, (ctl->reserved2 & 8) != 0, eps_prim_inf > 0.0 || eps_dual_inf > 0.0, eps_dual_inf > 0.0);
     if (ws_bytes < L.bytes_for(asked)) return LQP_ERR_WORKSPACE;
@@ -2364,7 +2365,7 @@ int lqp_boxqp_forward_detect(void* stream, int dtype, int B, int n, int m, const
                          workspace_bytes, eps_prim_inf, 0.0);
 }
 
-// ---- the solves with a separable term: lqp_boxqp_forward_l1 / _soft / _log / _pwl ----
+// ---- the solves with a separable term: lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber ----
 size_t lqp_boxqp_forward_l1_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_L1); });
@@ -2380,6 +2381,10 @@ size_t lqp_boxqp_forward_log_workspace_bytes(int dtype, int B, int n, int m) {
 size_t lqp_boxqp_forward_pwl_workspace_bytes(int dtype, int B, int n, int m) {
     if (bad_dims(dtype, B, n, m)) return 0;
     return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_PWL); });
+}
+size_t lqp_boxqp_forward_huber_workspace_bytes(int dtype, int B, int n, int m) {
+    if (bad_dims(dtype, B, n, m)) return 0;
+    return by_dtype(dtype, [&](auto t) { return carve_forward<decltype(t)>(nullptr, B, n, m).bytes_for(FORM_HUBER); });
 }
 
 // Refused before anything is touched: a null pointer of the term's own, the per-problem stop (no instance of its kernels with a term), a
@@ -2433,6 +2438,14 @@ int lqp_boxqp_forward_pwl(void* stream, int dtype, int B, int n, int m, const vo
     term.kind = TermPwl::kind; term.aux = piece; term.u_box = u_box;
     for (int k = 0; k <= PWL_K; ++k) term.in[k] = (const char*)s + (size_t)(k < K ? k : K) * vec;
     for (int k = 0; k < K; ++k) term.in[PWL_K + 1 + k] = (const char*)c + (size_t)k * vec;
+    return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
+}
+
+int lqp_boxqp_forward_huber(void* stream, int dtype, int B, int n, int m, const void* Q, const void* p, const void* A,
+                            const void* b, const void* lb, const void* ub, const void* w, const void* c, const void* delta,
+                            const lqp_boxqp_ctrl* ctrl, const void* rho_in, void* x, void* z, void* u, void* lams, void* nus, void* rho_out,
+                            void* zone, void* u_box, lqp_boxqp_stats* stats, void* workspace, size_t workspace_bytes) {
+    const TermArgs term = {TermHuber::kind, {w, c, delta, nullptr}, zone, u_box};
     return term_entry(stream, dtype, B, n, m, Q, p, A, b, lb, ub, term, ctrl, rho_in, x, z, u, lams, nus, rho_out, stats, workspace, workspace_bytes);
 }
 
@@ -2518,6 +2531,28 @@ int lqp_boxqp_log_finish_grads(void* stream, int dtype, int B, int n, const void
     return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
         typedef decltype(t) T;
         hipLaunchKernelGGL(k_log_finish_grads<T>, grid, dim3(256), 0, st, (const T*)dp, (const T*)z, (const T*)w, total, (T*)dw);
+    });
+}
+
+int lqp_boxqp_huber_effective_duals(void* stream, int dtype, int B, int n, const void* u_box, const void* zone, const void* w,
+                                    int rho_mode, double rho_value, const void* rho_in, void* u_e, void* lams_e, void* curv) {
+    if (!elementwise_ok(dtype, B, n, {u_box, zone, w, u_e, lams_e, curv}) || (rho_mode != 1 && rho_mode != 2) || (rho_mode == 2 && !rho_in))
+        return LQP_ERR_INVALID;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_huber_effective_duals<T>, grid, dim3(256), 0, st, (const T*)u_box, (const T*)zone, (const T*)w,
+                           rho_mode == 2 ? (const T*)rho_in : nullptr, (T)rho_value, n, total, (T*)u_e, (T*)lams_e, (T*)curv);
+    });
+}
+
+int lqp_boxqp_huber_finish_grads(void* stream, int dtype, int B, int n, const void* dp, const void* z, const void* zone, const void* w,
+                                 const void* c, const void* delta, void* dw, void* dc, void* ddelta) {
+    if (!elementwise_ok(dtype, B, n, {dp, z, zone, w, c, delta})) return LQP_ERR_INVALID;
+    if (!dw && !dc && !ddelta) return LQP_OK;
+    return elementwise(stream, dtype, B, n, [&](auto t, dim3 grid, hipStream_t st, size_t total) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL(k_huber_finish_grads<T>, grid, dim3(256), 0, st, (const T*)dp, (const T*)z, (const T*)zone, (const T*)w, (const T*)c,
+                           (const T*)delta, total, (T*)dw, (T*)dc, (T*)ddelta);
     });
 }
 

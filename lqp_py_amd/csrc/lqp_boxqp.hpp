@@ -31,7 +31,8 @@ enum { RP_LB = 1, RP_UB = 2, RP_TIMEOUT = 4, RP_NOTSPD = 8,
        RP_L1_INPUT = 1 << 18,     // lqp_boxqp_forward_l1: a weight of the problem is negative or not finite, or its rho not positive (k_term_setup); its outputs are NaN
        RP_SOFT_INPUT = 1 << 19,   // lqp_boxqp_forward_soft: a weight negative or not finite, lo > hi, a NaN in lo or hi, or a rho not positive and finite (k_term_setup); its outputs are NaN
        RP_LOG_INPUT = 1 << 20,    // lqp_boxqp_forward_log: a weight negative or not finite, w_i > 0 with ub_i <= 0, or a rho not positive and finite (k_term_setup); its outputs are NaN
-       RP_PWL_INPUT = 1 << 21 };  // lqp_boxqp_forward_pwl: a slope not finite, slopes or kinks that decrease, a NaN kink, or a rho not positive and finite (k_term_setup); its outputs are NaN
+       RP_PWL_INPUT = 1 << 21,    // lqp_boxqp_forward_pwl: a slope not finite, slopes or kinks that decrease, a NaN kink, or a rho not positive and finite (k_term_setup); its outputs are NaN
+       RP_HUBER_INPUT = 1 << 22 };  // lqp_boxqp_forward_huber: a weight negative or not finite, a delta negative or NaN, a centre not finite, or a rho not positive and finite (k_term_setup); its outputs are NaN
 // per-check counters (uint32 x 4): not-optimal, arrivals, wants-rho, ratio-trigger
 // (NOTOPT and ARRIVE share one aligned 64-bit word: the two-workgroup loop adds to and reads both with ONE atomic)
 enum { CT_NOTOPT = 0, CT_ARRIVE = 1, CT_WANTS = 2, CT_TRIG = 3, CT_WORDS = 4 };
@@ -116,6 +117,7 @@ template <typename T> struct FwdParams {
     int term;                 // the separable term of the objective, Term*::kind below: 0 none | 1 lqp_boxqp_forward_l1: sum_i w_i |x_i - c_i|
                               // | 2 lqp_boxqp_forward_soft: sum_i wl_i (lo_i - x_i)_+ + wu_i (x_i - hi_i)_+ | 3 lqp_boxqp_forward_log: -sum_i w_i log(x_i)
                               // | 4 lqp_boxqp_forward_pwl: sum_i s_i0 x_i + sum_k (s_ik - s_i,k-1) (x_i - c_ik)_+
+                              // | 5 lqp_boxqp_forward_huber: sum_i w_i H_delta_i(x_i - c_i)
                               // (in the alignment gap in front of the pointer: no offset moves)
     int* pstat;              // B * PS_WORDS: control['stop'] = 'each' (every problem stops and adapts rho as a batch of one), or null
     union {
@@ -1621,6 +1623,72 @@ struct TermPwl {
         return {T(piece) + poison, ubx};
     }
 };
+// Huber (lqp_boxqp_forward_huber), w H_delta(x - c) with H_delta(d) = 0.5 d^2 for |d| <= delta and delta |d| - 0.5 delta^2 beyond: the
+// first term with zones AND curvature.  In the scaled space ws = D^2 w, cs = c / D, ds = delta / D.  With t = ws / rho the prox is
+// v - t / (1 + t) (v - cs) where that lands inside the quadratic zone, |v - cs| <= ds (1 + t), and v -+ t ds beyond.  Per element and
+// launch: q = t ds, lim = ds + q, sh = t / (1 + t); an iteration holds two compares and one multiply-subtract.  sh == 0 exactly where
+// t == 0 (t >= 0), so the branch of the plain step's bits needs no register for t -- and it comes first: delta = +inf (lim = q = +inf, the
+// quadratic branch always: a weighted least-squares term) makes q = 0 * inf a NaN at t == 0.  delta = 0 is no term (q = 0).
+// Area: [ws | cs | ds | q | lim | sh]
+template <typename T> __device__ __forceinline__ T huber_prox(const T v, const T c, const T q, const T lim, const T sh) {
+    if (sh == T(0)) return v;
+    const T d = v - c;
+    return d > lim ? v - q : (d < -lim ? v + q : v - sh * d);
+}
+struct TermHuber {
+    static constexpr int kind = 5, input_flag = RP_HUBER_INPUT, n_in = 3, slots = 6;
+    enum { WS, CS, DS, QS, LIM, SH };
+    template <typename T> struct View {
+        T *ws = nullptr, *cs = nullptr, *ds = nullptr, *q = nullptr, *lim = nullptr, *sh = nullptr;
+        View() = default;
+        __device__ __forceinline__ View(T* a, const int n) {
+            const int s = round_up(n, 8);
+            ws = a + WS * s; cs = a + CS * s; ds = a + DS * s; q = a + QS * s; lim = a + LIM * s; sh = a + SH * s;
+        }
+        __device__ __forceinline__ void keep(const int i, const T rho) const {
+            const T t = ws[i] / rho, qi = t * ds[i];
+            q[i] = qi; lim[i] = ds[i] + qi; sh[i] = t / (T(1) + t);
+        }
+    };
+    template <typename T> struct Regs {
+        T c = T(0), q = T(0), lim = T(0), sh = T(0);
+        __device__ __forceinline__ void load(const T* a, const int n, const int i, const T rho) {
+            const View<const T> W(a, n);
+            const T t = W.ws[i] / rho, dsi = W.ds[i];
+            c = W.cs[i]; q = t * dsi; lim = dsi + q; sh = t / (T(1) + t);
+        }
+        __device__ __forceinline__ T prox(const T v) const { return huber_prox(v, c, q, lim, sh); }
+        __device__ __forceinline__ T prox_at(const T v, const bool first, const View<T> W, const int i) const {
+            return first ? huber_prox(v, c, q, lim, sh) : huber_prox(v, W.cs[i], W.q[i], W.lim[i], W.sh[i]);
+        }
+    };
+    // a weight that is negative or not finite, a delta that is negative or NaN (+inf is the pure quadratic), a centre that is not finite
+    template <typename T>
+    static __device__ __forceinline__ bool setup_elem(T* a, const int n, const int i, const TermIn<T>& in, const size_t g, const T* D, const T*) {
+        const View<T> W(a, n);
+        const T wi = in.p[0][g], ci = in.p[1][g], dli = in.p[2][g], di = D[i];
+        W.ws[i] = di * (di * wi);
+        W.cs[i] = ci / di;
+        W.ds[i] = dli / di;
+        return !(wi >= T(0) && wi < T(INFINITY)) || !(dli >= T(0)) || !(ci > T(-INFINITY) && ci < T(INFINITY));      // (NaN fails the first comparison of each)
+    }
+    // The step's comparisons once more at the returned iterate (v = zs + us): zone = +-1 on the linear pieces, 0 on the quadratic zone
+    // and wherever w = 0.  u_box as for the log barrier: the term's own force t clip(zs - cs, -ds, ds) acts on a clamped element too, so
+    // the box's share of the dual is (us - that) / D where the clamp moved S, and exactly 0 elsewhere.
+    template <typename T>
+    static __device__ __forceinline__ TermOut<T> finish_elem(const T* a, const int n, const int i, const T zs, const T us, const T lbs,
+                                                             const T ubs, const T d, const T rho, const T poison) {
+        Regs<T> r;
+        r.load(a, n, i, rho);
+        const View<const T> W(a, n);
+        const T v = zs + us, dd = v - r.c, t = W.ws[i] / rho, dsi = W.ds[i];
+        const T S = huber_prox(v, r.c, r.q, r.lim, r.sh);
+        const T zone = t == T(0) ? T(0) : dd > r.lim ? T(1) : dd < -r.lim ? T(-1) : T(0);
+        const bool held = S != tmin(tmax(S, lbs), ubs);
+        const T ubx = (held ? (t == T(0) ? us : us - t * tmin(tmax(zs - r.c, -dsi), dsi)) / d : T(0)) + poison;
+        return {zone + poison, ubx};
+    }
+};
 // What a thread of the streaming loop, which owns several elements, keeps of a term: its first element in registers; the thresholds
 // of its further elements (n > NT only) come from the area, where prime() stores them itself -- nothing is stored for the first
 // (both workgroups of a shared problem would write the same values).  Nothing at all for TermNone.
@@ -1757,7 +1825,7 @@ __device__ __forceinline__ AdmmStep<T> admm_step(const FwdParams<T>& P, const T 
 //   each:   control['stop'] = 'each' -- every problem stops and adapts rho as a batch of one
 //   detect: ... with the primal infeasibility certificate at every check (control['infeasible'])
 //   dual:   ... and the dual certificate beside it (control['unbounded'])
-//   term:   the separable term whose prox the element-wise step takes (lqp_boxqp_forward_l1 / _soft / _log / _pwl); the batch stops as one
+//   term:   the separable term whose prox the element-wise step takes (lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber); the batch stops as one
 struct FormAll     { static constexpr bool each = false, detect = false, dual = false; using term = TermNone; };
 struct FormEach    { static constexpr bool each = true,  detect = false, dual = false; using term = TermNone; };
 struct FormDetect  { static constexpr bool each = true,  detect = true,  dual = false; using term = TermNone; };
@@ -1766,6 +1834,7 @@ struct FormL1      { static constexpr bool each = false, detect = false, dual = 
 struct FormSoft    { static constexpr bool each = false, detect = false, dual = false; using term = TermSoft; };
 struct FormLog     { static constexpr bool each = false, detect = false, dual = false; using term = TermLog; };
 struct FormPwl     { static constexpr bool each = false, detect = false, dual = false; using term = TermPwl; };
+struct FormHuber   { static constexpr bool each = false, detect = false, dual = false; using term = TermHuber; };
 // ... and its terms of the six inf-norms of a check (:285-299).  qx = (Qs x)_i: the x-update solved (Qs + rho I) x + As^T nu = w
 // exactly (to the solve's rounding), so Qs x = w - rho x - As^T nu without touching Q -- it only feeds a tolerance SCALE; the
 // caller forms it from wherever its w, As and nu live.  ACC: the thread owns several elements (fold) or one (assign).
@@ -2050,7 +2119,7 @@ __device__ __forceinline__ T loop_event_rho(const FwdParams<T>& P, T* scal, cons
 // its registers cost the plain EACH kernels 3 % of their time
 // DUAL (control['unbounded']): the dual certificate too, instances of their own again (FormCertify): under a
 // run-time flag its registers cost the primal-only DETECT kernels 3 % (6 % in the small loop) of their time
-// FORM::term: the separable term of the element-wise step (TermOwn) -- the kernels of lqp_boxqp_forward_l1 / _soft / _log / _pwl are instances of their own
+// FORM::term: the separable term of the element-wise step (TermOwn) -- the kernels of lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber are instances of their own
 template <typename T, bool RES, bool TAIL, int NT, bool SYM, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_body(const FwdParams<T>& P, const int it0, const int it1,
                                                const int ctr_base,       // counter slot of check it0 / check
@@ -2499,7 +2568,7 @@ __device__ __forceinline__ void admm_loop_body_from(const FwdParams<T>& P, int i
     __syncthreads();
   }
 }
-// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft, FormLog, FormPwl
+// the first launch of the symmetric path above 512 rows on TWO workgroups per problem (admm_loop_body_from, NP == 2): FormAll, FormL1, FormSoft, FormLog, FormPwl, FormHuber
 template <typename FORM>
 __global__ __launch_bounds__(1024) void k_admm_loop_np2(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                         const int prev_slot, const int persistent) {
@@ -3575,6 +3644,35 @@ __global__ __launch_bounds__(256) void k_log_finish_grads(const T* __restrict__ 
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     if (dw) dw[i] = w[i] > T(0) ? -dp[i] / z[i] : T(0);
+}
+
+// backward of lqp_boxqp_forward_huber: the log barrier's recipe (u_e = u_box, lams_e from it, the true box) with the term's own
+// curvature, which is data of the zones: curv = w on the free elements of the quadratic zone (zone == 0, w > 0, u_box == 0), 0 on the
+// linear pieces -- a constant force, p shifted by +-w delta -- and on a clamped element
+template <typename T>
+__global__ __launch_bounds__(256) void k_huber_effective_duals(const T* __restrict__ ubox, const T* __restrict__ zone, const T* __restrict__ w,
+                                                               const T* __restrict__ rho_in, const T rho_value, const int n, const size_t total,
+                                                               T* __restrict__ u_e, T* __restrict__ lams_e, T* __restrict__ curv) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const size_t b = i / n, e = i - b * n;
+    const T ue = ubox[i], wi = w[i];
+    u_e[i] = ue;
+    curv[i] = (zone[i] == T(0) && wi > T(0) && ue == T(0)) ? wi : T(0);
+    lams_from_y(lams_e, b, n, e, (rho_in ? rho_in[b] : rho_value) * ue);
+}
+// ... and the term's three gradients from dp: the term's force on x is g = w clip(z - c, -delta, delta), so dw = dp clip(z - c, -delta,
+// delta), dc = -w dp on the quadratic zone (0 on the linear pieces: g does not see c there) and ddelta = w zone dp.  Outputs may be null.
+template <typename T>
+__global__ __launch_bounds__(256) void k_huber_finish_grads(const T* __restrict__ dp, const T* __restrict__ z, const T* __restrict__ zone,
+                                                            const T* __restrict__ w, const T* __restrict__ c, const T* __restrict__ delta,
+                                                            const size_t total, T* __restrict__ dw, T* __restrict__ dc, T* __restrict__ ddelta) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const T g = dp[i], zn = zone[i], wi = w[i], dl = delta[i];
+    if (dw) dw[i] = g * tmin(tmax(z[i] - c[i], -dl), dl);
+    if (dc) dc[i] = zn == T(0) ? -wi * g : T(0);
+    if (ddelta) ddelta[i] = wi * zn * g;
 }
 
 template <int LQP_ANY = 0>

@@ -20,7 +20,7 @@ __host__ __device__ inline int small_loop_lds_bytes(int m) { return (128 + 128 +
 // DETECT (control['infeasible']): the certificate at every check, an instance of its own -- the loop has ONE body for hot and
 // check iterations, and the certificate's registers in it cost the plain EACH kernel 12 % of its time
 // DUAL (control['unbounded']): the dual certificate too
-// FORM::term (lqp_boxqp_forward_l1 / _soft / _log / _pwl): the element-wise step with the separable term; keeps its thresholds beside lb / ub
+// FORM::term (lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber): the element-wise step with the separable term; keeps its thresholds beside lb / ub
 template <typename FORM>
 __device__ __forceinline__ void admm_loop_small_body(const FwdParams<float> P, const int it0, const int it1, const int ctr_base,
                                                      char* smem) {

@@ -44,8 +44,8 @@ template <int NT, int NP = 2> __host__ __device__ inline int split_loop_lds_byte
 // launch ends at the first possible rho event (no hot_past): the continuation kernel (k_admm_loop, FormEach ...) takes the problem's own decision.
 // (P by value: a reference to the kernel's parameter block costs the default's instances registers)
 // FORM: FormAll, FormEach (which takes the certificates from P.snap and P.eps_dinf at run time: it serves FormDetect and FormCertify
-// solves too) or a form with a separable term, FormL1 / FormSoft / FormLog / FormPwl (lqp_boxqp_forward_l1 / _soft / _log / _pwl: the element-wise step
-// of every iteration form below with the term's prox; thread i keeps the term's Regs of its element, two / four / one / seven registers -- rho
+// solves too) or a form with a separable term, FormL1 / FormSoft / FormLog / FormPwl / FormHuber (lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber: the element-wise step
+// of every iteration form below with the term's prox; thread i keeps the term's Regs of its element, two / four / one / seven / four registers -- rho
 // is this launch's, an event that changes it ends the launch)
 template <int KS, int NT, bool DBG, int NP, typename FORM>
 __device__ __forceinline__ void admm_loop_split_body(const FwdParams<float> P, int it0, const int it1, int ctr_base, char* smem) {

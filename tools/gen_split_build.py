@@ -40,9 +40,9 @@ def term_groups(g, tag):
     ]
 
 
-# the separable terms (lqp_boxqp_forward_l1 / _soft / _log / _pwl): (group suffix, tag of lqp::Form* and lqp::Term*).  A new term is one entry here
+# the separable terms (lqp_boxqp_forward_l1 / _soft / _log / _pwl / _huber): (group suffix, tag of lqp::Form* and lqp::Term*).  A new term is one entry here
 # and its backward's element-wise kernels in KERNELS.
-TERMS = [("l1", "L1"), ("soft", "Soft"), ("log", "Log"), ("pwl", "Pwl")]
+TERMS = [("l1", "L1"), ("soft", "Soft"), ("log", "Log"), ("pwl", "Pwl"), ("huber", "Huber")]
 # group -> predicate on the demangled name; first match wins.  Balanced by measured compile time (seconds at -O3).
 GROUPS = [grp for g, tag in TERMS for grp in term_groups(g, tag)] + [
     ("bwd_f", lambda n: re.search(r"k_bwd_chol_solve<\d, true>", n)),
@@ -141,6 +141,8 @@ KERNELS = [
     ("k_log_finish_grads", "{0} const*, {0} const*, {0} const*, unsigned long, {0}*", BOTH),
     ("k_pwl_effective_box", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, int, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
     ("k_pwl_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, int, unsigned long, {0}*, {0}*, {0}*, {0}*", BOTH),
+    ("k_huber_effective_duals", "{0} const*, {0} const*, {0} const*, {0} const*, {0}, int, unsigned long, {0}*, {0}*, {0}*", BOTH),
+    ("k_huber_finish_grads", "{0} const*, {0} const*, {0} const*, {0} const*, {0} const*, {0} const*, unsigned long, {0}*, {0}*, {0}*", BOTH),
     ("k_rho_update", FP + ", int, int", BOTH),
     ("k_snap_init", "{0}*, unsigned long, int", BOTH),
     ("k_check_done", "int*, unsigned int const*, int, int", ZERO),
